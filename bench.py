@@ -106,7 +106,53 @@ def parse_args():
                          "the generator's own torch packer (same ends; outside the timed region either way)")
     ap.add_argument("--exchange-only", action="store_true")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default: nccl with GPUs, gloo without)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy, float64: scan results, barcode "
+                         "windows and barcode results of every read, or of a fixed seeded sample of %d reads when there are more" % DUMP_SAMPLE_READS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+# --dump-outputs: reads of a step written at most (24 float64 columns, 48 MiB), and the seed of the sample when a step has more
+DUMP_SAMPLE_READS = 1 << 18
+DUMP_SEED = 20240607
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_rows(n):
+    """the reads --dump-outputs writes, ascending: all n of them, or a fixed seeded sample when n > DUMP_SAMPLE_READS"""
+    if n <= DUMP_SAMPLE_READS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE_READS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, rows, scan_rows, win_rows, out_rows, extra=None):
+    """write the step's results at `rows` (read indices) as float64 arrays, one per field of the C structs: scan_<field> (scan_result),
+    window_<field> (bc_window; the 64-bit bases as two 32-bit halves so that float64 holds them exactly), bc_<field> (bc_result) and
+    read_index; `extra`: further named arrays of the step.  *_rows: the device tensors of the step gathered at `rows`."""
+    lib = graft.load_package().lib
+    cols = {"read_index": np.asarray(rows, dtype=np.float64)}
+    for prefix, t, dt in (("scan", scan_rows, lib.SCAN_RESULT_DTYPE), ("window", win_rows, lib.BC_WINDOW_DTYPE), ("bc", out_rows, lib.BC_RESULT_DTYPE)):
+        a = t.cpu().numpy().view(dt).reshape(-1)
+        assert a.size == len(rows), (prefix, a.size, len(rows))
+        for f in dt.names:
+            if f == "reserved":
+                continue
+            if a[f].dtype == np.uint64:
+                cols[f"{prefix}_{f}_lo"] = (a[f] & np.uint64(0xFFFFFFFF)).astype(np.float64)
+                cols[f"{prefix}_{f}_hi"] = (a[f] >> np.uint64(32)).astype(np.float64)
+            else:
+                cols[f"{prefix}_{f}"] = a[f].astype(np.float64)
+    for name, v in (extra or {}).items():
+        cols[name] = np.asarray(v, dtype=np.float64)
+    total = sum(v.nbytes for v in cols.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte bound")
+    os.makedirs(path, exist_ok=True)
+    for name, v in cols.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def free_port():
@@ -790,8 +836,13 @@ def config2(args, dist, rank, local_rank, world, dev):
     out = torch.zeros((Bmax, 4), dtype=torch.int32, device=dev)
     hist = torch.zeros(keys.size, dtype=torch.int32, device=dev)
     state = {}
+    dump = None
+    if args.dump_outputs and rank == 0:
+        # the pass-2 buffers are reused batch by batch: the last timed step gathers the sampled reads of each batch as it goes
+        rows = dump_rows(n)
+        dump = {"rows": rows, "idx": [torch.from_numpy(rows[(rows >= b0) & (rows < b0 + B)] - b0).to(dev) for b0 in range(0, n, B)]}
 
-    def step(timed):
+    def step(timed, keep=None):
         hist.zero_()
         for m, ends, lens, qt, qs in batches:
             ctx1.scan_device(ends, lens, m, cfg_p1, scan, win, qt, qs)
@@ -799,13 +850,18 @@ def config2(args, dist, rank, local_rank, world, dev):
         k, c, r = distributed.pass1_finalize(hist, keys, record_count=(n + 9_999) // 10_000)
         ctx2.set_barcode_set(k, mode=0)
         n_assigned, ms_bc2, ms_scan = 0, 0.0, 0.0
-        for m, ends, lens, qt, qs in batches:
+        for j, (m, ends, lens, qt, qs) in enumerate(batches):
             ctx2.scan_device(ends, lens, m, cfg_p2, scan, win)
             ctx2.bc_match_device(win, out, m, max_ed=2, five_prime=False)
             if timed:
                 ms_scan += ctx2.kernel_ms(ctx2.K_SCAN)
                 ms_bc2 += ctx2.kernel_ms(ctx2.K_BC_MATCH)
+            if keep is not None:
+                for name, t in (("scan", scan), ("win", win), ("out", out)):
+                    keep.setdefault(name, []).append(t.index_select(0, keep["idx"][j]))
             n_assigned += int(((out[:m, 2] & 0xFF) == 1).sum().item())
+        if keep is not None:
+            keep.update(used_keys=k, used_counts=c, used_ranks=r)
         state.update(used=int(k.size), assigned=n_assigned, ms_bc2=ms_bc2, ms_scan=ms_scan)
 
     def barrier():
@@ -819,8 +875,8 @@ def config2(args, dist, rank, local_rank, world, dev):
     ctx2.set_timing(True)
     t0 = time.perf_counter()
     bc2_ms = []
-    for _ in range(args.steps):
-        step(True)
+    for s in range(args.steps):
+        step(True, keep=dump if s == args.steps - 1 else None)
         bc2_ms.append(state["ms_bc2"])
     barrier()
     elapsed = time.perf_counter() - t0
@@ -831,6 +887,9 @@ def config2(args, dist, rank, local_rank, world, dev):
         dist.destroy_process_group()
     if rank != 0:
         return
+    if dump is not None:
+        dump_outputs(args.dump_outputs, dump["rows"], torch.cat(dump["scan"]), torch.cat(dump["win"]), torch.cat(dump["out"]),
+                     extra={"used_keys": dump["used_keys"], "used_counts": dump["used_counts"], "used_ranks": dump["used_ranks"]})
     k_bc2 = float(np.mean(bc2_ms))
     rf = roofline_entry("k_bc_match_ed2", "k_bc_match_ed2", k_bc2, ALG_BYTES_PER_READ_BC2, n, pmc_table())
     rf.update({"bound": "instruction issue (round 6: seven waves per SIMD; VALU + SALU fill the SIMD cycles, `valu_issue` has the vector share; `frac` is the counter "
@@ -910,6 +969,10 @@ def config4(args, dist, rank, local_rank, world, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ctx.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        rows = dump_rows(n)
+        idx = torch.from_numpy(rows).to(dev)
+        dump_outputs(args.dump_outputs, rows, scan_out.index_select(0, idx), win.index_select(0, idx), out.index_select(0, idx))
     found = (out[:, 2] & 0xFF) == 1
     n_found = int(found.sum().item())
     acc = float(((out[:, 0].to(torch.int64) & 0xFFFFFFFF)[found] == truth[found]).float().mean().item())
@@ -1080,6 +1143,7 @@ def main():
         t1 = time.perf_counter()
         scan_ms = [a0.elapsed_time(a1) for a0, a1, _, _ in marks]
         match_ms = [b0.elapsed_time(b1) for _, _, b0, b1 in marks]
+        win = wins[(args.steps - 1) & 1]             # the window buffer of the last step
     else:
         ctx.set_timing(True)
         t0 = time.perf_counter()
@@ -1098,6 +1162,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ctx.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        rows = dump_rows(n)
+        idx = torch.from_numpy(rows).to(dev)
+        dump_outputs(args.dump_outputs, rows, scan_out.index_select(0, idx), win.index_select(0, idx), out.index_select(0, idx))
 
     found = (out[:n, 2] & 0xFF) == 1
     n_found = int(found.sum().item())

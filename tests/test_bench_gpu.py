@@ -64,6 +64,45 @@ def test_bench_overlap_gives_the_same_assignments():
     assert b["steps"] == 5 and b["value"] > 0 and len(b["roofline"]["kernels_ms"]) == 2
 
 
+def _dump(path):
+    import numpy as np
+
+    return {n[:-4]: np.load(os.path.join(path, n)) for n in sorted(os.listdir(path))}
+
+
+def test_bench_dump_outputs_repeat_and_follow_the_last_step(tmp_path):
+    """--dump-outputs: the same arguments give the same arrays run after run, the two-stream pipeline (--overlap: the last step's window
+    buffer alternates) gives the plain run's arrays, a step larger than the sample gives the fixed sample, within the 64 MiB bound"""
+    import numpy as np
+
+    common = ("--reads", "300000", "--whitelist", "400000", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--e2e-reads", "0", "--two-pass-reads", "0",
+              "--umi-molecules", "0", "--h2h-reads", "0", "--f2f-reads", "0")
+    a = _run(*common, "--dump-outputs", str(tmp_path / "a"))
+    _run(*common, "--dump-outputs", str(tmp_path / "b"))
+    c = _run(*common, "--overlap", "--dump-outputs", str(tmp_path / "c"))
+    da, db, dc = _dump(tmp_path / "a"), _dump(tmp_path / "b"), _dump(tmp_path / "c")
+    assert a["steps"] == c["steps"] == 4 and set(da) == set(db) == set(dc)
+    for name in da:
+        assert da[name].dtype == np.float64 and np.array_equal(da[name], db[name]) and np.array_equal(da[name], dc[name]), name
+    assert sum(v.nbytes for v in da.values()) <= 64 << 20
+    rows = da["read_index"]
+    assert rows.size == 1 << 18 and (np.diff(rows) > 0).all() and rows[-1] < 300_000
+    assert abs((da["bc_found"] == 1).mean() - a["config"]["bc_assigned_frac"]) < 0.01
+    assert abs((da["scan_found"] == 1).mean() - a["config"]["adapter_found_frac"]) < 0.01
+
+
+def test_bench_config2_dump_outputs_hold_every_batch(tmp_path):
+    """--config 2 reuses its result buffers batch by batch: the dump of the last step holds the reads of every batch and the used list"""
+    import numpy as np
+
+    d = _run("--config", "2", "--reads", "200000", "--batch", "70000", "--whitelist", "400000", "--steps", "2", "--warmup", "1",
+             "--dump-outputs", str(tmp_path))
+    a = _dump(tmp_path)
+    assert np.array_equal(a["read_index"], np.arange(200_000)) and a["used_keys"].size == d["config"]["used_list"]
+    assert int((a["bc_found"] == 1).sum()) == round(d["config"]["bc_assigned_frac"] * 200_000)
+    assert (a["scan_found"][:70_000] == 1).mean() > 0.5 and (a["scan_found"][140_000:] == 1).mean() > 0.5
+
+
 def test_bench_config2_small():
     d = _run("--config", "2", "--reads", "400000", "--batch", "200000", "--whitelist", "400000", "--steps", "2", "--warmup", "1")
     _common(d, 2)

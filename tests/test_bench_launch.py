@@ -56,3 +56,39 @@ def test_strong_scaling_split_sums_to_the_one_rank_run():
     assert one["used_list"] == two["used_list"] == three["used_list"] > 100
     assert one["used_list_digest"] == two["used_list_digest"] == three["used_list_digest"]
     assert two["same_used_list_on_all_ranks"] is True and three["same_used_list_on_all_ranks"] is True
+
+
+def test_dump_outputs_sample_and_layout(tmp_path):
+    """--dump-outputs without a GPU: the sampled reads are fixed, ascending and distinct (all reads up to the sample size); one float64 array
+    per field of the three result structs, the 64-bit window bases split exactly into halves, within the 64 MiB bound at the full sample"""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(graft.ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert (bench.dump_rows(5) == np.arange(5)).all()
+    rows = bench.dump_rows(10_000_000)
+    assert rows.size == bench.DUMP_SAMPLE_READS and (np.diff(rows) > 0).all() and 0 <= rows[0] and rows[-1] < 10_000_000
+    assert (rows == bench.dump_rows(10_000_000)).all()
+    k = bench.DUMP_SAMPLE_READS
+    g = torch.Generator().manual_seed(3)
+    scan = torch.randint(-2 ** 31, 2 ** 31 - 1, (k, 8), dtype=torch.int32, generator=g)
+    win = torch.randint(-2 ** 62, 2 ** 62, (k, 2), dtype=torch.int64, generator=g)
+    out = torch.randint(-2 ** 31, 2 ** 31 - 1, (k, 4), dtype=torch.int32, generator=g)
+    bench.dump_outputs(str(tmp_path), rows, scan, win, out, extra={"used_keys": np.arange(7, dtype=np.uint64)})
+    lib = graft.load_package().lib
+    want = {"read_index.npy", "used_keys.npy", "window_bases_lo.npy", "window_bases_hi.npy"}
+    want |= {f"scan_{f}.npy" for f in lib.SCAN_RESULT_DTYPE.names if f != "reserved"}
+    want |= {f"window_{f}.npy" for f in lib.BC_WINDOW_DTYPE.names if f != "bases"} | {f"bc_{f}.npy" for f in lib.BC_RESULT_DTYPE.names}
+    assert set(os.listdir(tmp_path)) == want
+    a = {n[:-4]: np.load(os.path.join(tmp_path, n)) for n in want}
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    w = win.numpy().view(lib.BC_WINDOW_DTYPE).reshape(-1)
+    assert ((a["window_bases_hi"].astype(np.uint64) << np.uint64(32)) | a["window_bases_lo"].astype(np.uint64) == w["bases"]).all()
+    s = scan.numpy().view(lib.SCAN_RESULT_DTYPE).reshape(-1)
+    assert (a["scan_adapter_end"] == s["adapter_end"]).all() and (a["scan_flags"] == s["flags"]).all() and (a["read_index"] == rows).all()
+    r = out.numpy().view(lib.BC_RESULT_DTYPE).reshape(-1)
+    assert (a["bc_bc"] == r["bc"]).all() and (a["bc_found"] == r["found"]).all()

@@ -2,12 +2,14 @@
 library, the finalize folds, mergeBCsED, the UMI stage's values), what it still refuses BY NAME because it is compiled in, and the reference's
 output-file naming with the duplicate check (FastqWriterThreadPool$FastQoneFileThread.init L242-250)."""
 import importlib
+import os
 import re
 
 import numpy as np
 import pytest
 
-SHIPPED = "/root/reference/Jar/config.xml"
+# the reference's Jar/config.xml as it ships (a data file, stored unchanged)
+SHIPPED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_config.xml")
 
 
 @pytest.fixture(scope="module")
@@ -39,11 +41,7 @@ def test_shipped_defaults_are_the_knob_defaults(cli, lib):
 
 
 def test_the_reference_shipped_file_parses_to_the_defaults(cli, lib):
-    """(build container only: the reference's own Jar/config.xml) every element of the shipped file is accepted and changes nothing"""
-    import os
-
-    if not os.path.isfile(SHIPPED):
-        pytest.skip("the reference checkout is not here")
+    """the reference's own Jar/config.xml (tests/golden/reference_config.xml): every element of the shipped file is accepted and changes nothing"""
     knobs = cli.read_config(SHIPPED)
     assert cli.run_knobs_from(knobs, SHIPPED) is None
     assert cli.host_knobs_from(knobs, cli.HOST_KNOBS_SCAN) == dict(min_count_fold=10, cells_fold_below_max=500)
@@ -54,7 +52,7 @@ def test_the_reference_shipped_file_parses_to_the_defaults(cli, lib):
 
 
 def test_run_time_knobs_reach_the_library_structure(cli, lib, tmp_path):
-    """the README's printed defaults (QV 10, fold 20: /root/reference/README.md:480-489) and the other knob groups: file -> smi_run_knobs / call arguments"""
+    """the README's printed defaults (QV 10, fold 20: the reference's README.md:480-489) and the other knob groups: file -> smi_run_knobs / call arguments"""
     path = _config(tmp_path, "<readscanner><minReadLength>150</minReadLength><minMeanBCqv>10</minMeanBCqv><minMeanReadqv>10</minMeanReadqv><minAdapter3pMatches>6</minAdapter3pMatches>"
                              "<minCountFold>20</minCountFold><cellsWithReadsnFoldBelowMaxToKeep>200</cellsWithReadsnFoldBelowMaxToKeep><mergeBCsED>2</mergeBCsED></readscanner>"
                              "<polyAT><internalpATlength>12</internalpATlength><internalFractionATInPolyAT>0.8</internalFractionATInPolyAT></polyAT>"

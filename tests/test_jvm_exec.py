@@ -1,12 +1,9 @@
 """tools/jvm_exec.py (the bytecode interpreter behind tests/golden/ref_exec_*.json) checked against answers that do NOT come from this
-repository: (1) third-party pure-Java methods from jars the reference ships, executed by the interpreter, against PUBLISHED test vectors
-(CRC-32C: RFC 3720 B.4; MurmurHash3 x86_32: the SMHasher / reference-implementation vectors; xxHash32: the xxHash specification;
-Levenshtein: the textbook pairs; greatest common divisors); (2) single instructions assembled into a class file by this test, against the
-Java Virtual Machine Specification's own statements about them (shift-count masking, float-to-integer saturation, NaN compares, the signs
-of idiv / irem, narrowing conversions, long compare, integer overflow wrap).  It does not make the runtime a JVM; it removes the doubt that
-interpreter and oracle share one author's misreading of these rules."""
+repository: single instructions assembled into a class file by this test, against the Java Virtual Machine Specification's own statements
+about them (shift-count masking, float-to-integer saturation, NaN compares, the signs of idiv / irem, narrowing conversions, long compare,
+integer overflow wrap).  It does not make the runtime a JVM; it removes the doubt that interpreter and oracle share one author's misreading
+of these rules."""
 import io
-import math
 import os
 import struct
 import sys
@@ -16,71 +13,18 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-LIBDIR = "/root/reference/Jar/lib"
-pytestmark = pytest.mark.skipif(not os.path.isdir(LIBDIR), reason="the reference jars exist only in the build container")
 
 
-def _jvm(extra_zip=None):
+def _jvm(extra_zip):
+    """the interpreter with no jars but the class file(s) in `extra_zip`"""
     import jvm_exec
 
-    jars = [os.path.join(LIBDIR, j) for j in ("commons-codec-1.17.0.jar", "commons-lang3-3.17.0.jar", "commons-math3-3.6.1.jar")]
-    j = jvm_exec.JVM(jars)
-    # the JDK intrinsics the library methods below call (plain bit operations, as the JDK API documents them)
-    rot = lambda v, n, bits: ((v << (n % bits)) | ((v & (2 ** bits - 1)) >> (bits - n % bits))) & (2 ** bits - 1)  # noqa: E731
-    j.natives.setdefault("java/lang/Integer.rotateLeft:(II)I", lambda jv, v, n: jvm_exec.i32(rot(v & 0xFFFFFFFF, n & 31, 32) if n & 31 else v))
-    j.natives.setdefault("java/lang/Long.rotateLeft:(JI)J", lambda jv, v, n: jvm_exec.i64(rot(v & (2 ** 64 - 1), n & 63, 64) if n & 63 else v))
-    ntz = lambda v, bits: bits if v == 0 else (v & -v).bit_length() - 1  # noqa: E731
-    j.natives.setdefault("java/lang/Integer.numberOfTrailingZeros:(I)I", lambda jv, v: ntz(v & 0xFFFFFFFF, 32))
-    j.natives.setdefault("java/lang/Long.numberOfTrailingZeros:(J)I", lambda jv, v: ntz(v & (2 ** 64 - 1), 64))
-    if extra_zip is not None:
-        z = zipfile.ZipFile(io.BytesIO(extra_zip))
-        j.zips.append(z)
-        for n in z.namelist():
-            j.index.setdefault(n[:-6], z)
-    return j, jvm_exec
-
-
-def _bytes(jx, data):
-    return jx.JArray("B", [b - 256 if b > 127 else b for b in data])
-
-
-def test_crc32c_rfc3720_vectors():
-    j, jx = _jvm()
-    cases = [(bytes(32), 0x8A9136AA), (b"\xff" * 32, 0x62A8AB43), (bytes(range(32)), 0x46DD794E), (bytes(range(31, -1, -1)), 0x113FDB5C),
-             (b"123456789", 0xE3069283)]
-    for data, want in cases:
-        o = j.new("org/apache/commons/codec/digest/PureJavaCrc32C")
-        j.call_virtual(o, "update", "([BII)V", _bytes(jx, data), 0, len(data))
-        assert j.call_virtual(o, "getValue", "()J") & 0xFFFFFFFF == want
-
-
-def test_murmur3_x86_32_published_vectors():
-    j, jx = _jvm()
-    cases = [(b"", 0, 0x00000000), (b"", 1, 0x514E28B7), (b"", 0xFFFFFFFF, 0x81F16F39), (b"\xff\xff\xff\xff", 0, 0x76293B50),
-             (b"\x21\x43\x65\x87", 0, 0xF55B516B), (b"\x21\x43\x65\x87", 0x5082EDEE, 0x2362F9DE), (b"\x21\x43\x65", 0, 0x7E4A8634),
-             (b"\x21\x43", 0, 0xA0F7B07A), (b"\x21", 0, 0x72661CF4), (b"\0\0\0\0", 0, 0x2362F9DE), (b"abc", 0, 0xB3DD93FA),
-             (b"Hello, world!", 1234, 0xFAF6CDB3), (b"The quick brown fox jumps over the lazy dog", 0x9747B28C, 0x2FA826CD)]
-    for data, seed, want in cases:
-        got = j.call_static("org/apache/commons/codec/digest/MurmurHash3", "hash32x86", "([BIII)I", _bytes(jx, data), 0, len(data), jx.i32(seed))
-        assert got & 0xFFFFFFFF == want, (data, seed)
-
-
-def test_xxhash32_specification_vectors():
-    j, jx = _jvm()
-    for data, want in ((b"", 0x02CC5D05), (b"a", 0x550D7456), (b"abc", 0x32D153FF), (b"Nobody inspects the spammish repetition", 0xE2293B2F)):
-        o = j.new("org/apache/commons/codec/digest/XXHash32")
-        j.call_virtual(o, "update", "([BII)V", _bytes(jx, data), 0, len(data))
-        assert j.call_virtual(o, "getValue", "()J") & 0xFFFFFFFF == want, data
-
-
-def test_levenshtein_and_gcd():
-    j, jx = _jvm()
-    for a, b, want in (("kitten", "sitting", 3), ("flaw", "lawn", 2), ("", "abc", 3), ("intention", "execution", 5), ("same", "same", 0)):
-        o = j.call_static("org/apache/commons/lang3/StringUtils", "getLevenshteinDistance", "(Ljava/lang/CharSequence;Ljava/lang/CharSequence;)I", a, b)
-        assert o == want
-    for num, den, want in ((1071, 462, (51, 22)), (-6, 8, (-3, 4)), (2 ** 30, 2 ** 20 * 3, (1024, 3)), (0, 7, (0, 1))):
-        fr = j.call_static("org/apache/commons/lang3/math/Fraction", "getReducedFraction", "(II)Lorg/apache/commons/lang3/math/Fraction;", num, den)
-        assert (fr.f["numerator"], fr.f["denominator"]) == want
+    j = jvm_exec.JVM([])
+    z = zipfile.ZipFile(io.BytesIO(extra_zip))
+    j.zips.append(z)
+    for n in z.namelist():
+        j.index.setdefault(n[:-6], z)
+    return j
 
 
 # ---- single instructions, assembled here ---------------------------------------------------------------------------------------------
@@ -133,7 +77,7 @@ def ops():
     buf = io.BytesIO()
     with zipfile.ZipFile(buf, "w") as z:
         z.writestr("t/Ops.class", _class_file("t/Ops", OPS))
-    j, jx = _jvm(buf.getvalue())
+    j = _jvm(buf.getvalue())
     desc = {n: d for n, d, *_ in OPS}
     return lambda name, *a: j.call_static("t/Ops", name, desc[name], *a)
 

@@ -990,6 +990,45 @@ int smi_gene_counts_info(const smi_gene_counts *gc, int64_t *records_with_gene, 
 int smi_gene_counts_tsv(const smi_gene_counts *gc, int bc_length, char *out, size_t cap, size_t *n_out);
 int smi_umi_depths_tsv(const smi_gene_counts *gc, char *out, size_t cap, size_t *n_out);
 
+/* ---- tagbamwithread (K-TAG, smi_tagbam.hip) -----------------------------------------------------------------------------------------------
+ * Replaces TagWithReadSequenceMain.doJob (FJ!com/rw/tagbamwithread/TagWithReadSequenceMain.java:L85-116) with ReadNameChrHashMap
+ * (L85-106) and SplitFastqByChromosome.split (L45-92): the per-chromosome temporary FASTQs and HashMaps only save memory, every lookup gives
+ * what one map gives whose key is getReadName().split(" ")[0] (the header line without '@' up to its first SPACE; a tab stays in the key) and
+ * in which a name that occurs twice keeps its LAST record.
+ * smi_tagbam_create: the uncompressed FASTQ text goes to the device and stays there (K-FQ indexes it; SMI_FQ_* in *errors and the call fails,
+ * as FastqReader throws -- nothing is repaired); a text that does not fit in device memory fails with the sizes before any kernel runs.
+ * Per BAM record, in file order (smi_tagbam_segment): reference index -1 (getReferenceName() "*") -> dropped and counted in *n_unmapped;
+ * name not in the FASTQ -> dropped, its index in `missing` (the caller prints "ERROR: Did not find read for  SAM record, name: ..."), the
+ * run goes on; otherwise written with setAttribute(read_tag, bases) and, with with_qv, setAttribute(qv_tag, qualities), both Z strings
+ * verbatim from the FASTQ text.  Everything in front of the attributes is copied, block_size recomputed, and the attribute list is the one
+ * htsjdk writes (ordered by binary tag, a repeated tag keeping its last value, integers in the smallest type, H as B:c; at most
+ * SMI_TAGBAM_MAX_ATTRS per record, more fail the call).
+ * bam[0 .. n_bam): inflated BAM bytes holding the n records indexed by recs (smi_bam_index_records).  out: the records as written, back to
+ * back, each with its block_size word; *n_out = their size.  out == NULL -> sizes only (SMI_OK); cap < *n_out -> returns 1 and writes
+ * nothing.  Either way the segment stays on the device, and the next call with the same bam / n_bam / recs / n only writes it: the caller
+ * must not change those buffers in between.  missing: n entries.  All work runs on the context's stream; the calls are synchronous. */
+#define SMI_TAGBAM_MAX_ATTRS 64
+#define SMI_TAG_BAD_AUX 1u          /* a malformed attribute or one of an unknown type */
+#define SMI_TAG_BAD_HEX 2u          /* an H attribute that is not an even number of hex digits */
+#define SMI_TAG_TOO_MANY_ATTRS 4u   /* more than SMI_TAGBAM_MAX_ATTRS attributes */
+#define SMI_TAG_OVERFLOW 8u         /* internal: a record would not fit in the output buffer (never written) */
+#define SMI_TAGBAM_STAGES 5         /* smi_tagbam_stage_ms: key, build (last create), probe, size, assemble (last segment) */
+typedef struct {
+    char read_tag[4];   /* -r / --readTag: two characters + NUL ("read tag must be two characters", L54-61) */
+    char qv_tag[4];     /* -q / --qvTag ("QV tag must be two characters") */
+    int32_t with_qv;    /* -q given */
+    int32_t hash_bits;  /* TEST ONLY: the name hash cut to its low hash_bits bits (forces collisions through the byte compare); 0 = all 64 */
+} smi_tagbam_config;
+typedef struct smi_tagbam smi_tagbam;
+int smi_tagbam_default_config(smi_tagbam_config *cfg);
+int smi_tagbam_create(smi_ctx *ctx, const uint8_t *fastq_text, size_t n_bytes, const smi_tagbam_config *cfg, smi_tagbam **out, uint32_t *errors);
+int smi_tagbam_free(smi_tagbam *h);
+int smi_tagbam_records(const smi_tagbam *h, size_t *n_records);
+int smi_tagbam_segment(smi_tagbam *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n, uint8_t *out, size_t cap,
+                       size_t *n_out, int32_t *missing, int32_t *n_missing, int32_t *n_unmapped);
+/* device time in ms of the stages of the last create / segment (HIP events on the context's stream) */
+int smi_tagbam_stage_ms(const smi_tagbam *h, float *ms);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

@@ -3,13 +3,15 @@
     java -jar [-Xmx..] NanoporeBC_UMI_finder-2.1.jar scanfastq  -d <dir[,dir..]> -o <dir> --bcEditDistance k [--compress] [--ncpu N] [-h] [-y] [-a file]
                                                                 [-g usedBarcodes] [-n] [-v regex] [-k skip] [-z only] [-s] [-u] [-p len] [-f frac] [-w window]   (--polyAlength --frac-f --windowAT)
     java -jar [-Xmx..] NanoporeBC_UMI_finder-2.1.jar assignumis --inFileNanopore <bam> -o <bam> [--annotationFile refFlat] [-v n] [-p] [-w] [-b ed] [-u ed] [-s]
+    java -jar [-Xmx..] NanoporeBC_UMI_finder-2.1.jar tagbamwithread --inFastq <fastq[.gz]> --inBam <bam> --outBam <bam> --readTag XX [--qvTag YY]
 
-become   python sicelore-2.1_amd scanfastq ... / assignumis ...   (the directory is runnable: __main__.py; a `java` wrapper that drops
+become   python sicelore-2.1_amd scanfastq ... / assignumis ... / tagbamwithread ...   (the directory is runnable: __main__.py; a `java` wrapper that drops
 `-jar`, `-Xmx..` and the jar's name makes /root/reference/quickrun-2.1.sh:35,42 run unchanged, tests/test_cli_gpu.py does exactly that).
 
 Reference units: option tables NanoporeReadScannerMain.cli_otions (NanoporeReadScannerMain.java:L336-469) and UmiFinderMain (L298-447);
 config discovery OneProgramMainBase.checkCfgFilePath (cwd, then the application's directory; -c names a file for assignumis);
-exit code 0, or 1 after a message (WorkerReadscanner.java:L376-378).
+exit code 0, or 1 after a message (WorkerReadscanner.java:L376-378).  tagbamwithread: TagWithReadSequenceMain.cli_otions (L138-166) and its messages (L42-61), single
+GPU (sicelore-nf/main.nf:116).  mergestats and parseillumina are refused by name.
 
 config.xml (round 6): the file's knobs are taken at RUN TIME -- thresholds, windows, adapter / complete TSO sequences and mismatch limits, the
 finalize folds, mergeBCsED, umi_length and the clustering distances go to the library as smi_run_knobs / call arguments (lib.KNOB_FIELDS,
@@ -444,6 +446,35 @@ def assignumis(argv):
     return 0
 
 
+# TagWithReadSequenceMain.cli_otions (L138-166): every option takes one argument; -b -f -o -r are required
+TAG_SPEC = {"inBam": ("b", "inBam", True), "inFastq": ("f", "inFastq", True), "outBam": ("o", "outBam", True), "readTag": ("r", "readTag", True),
+            "qvTag": ("q", "qvTag", True)}
+
+
+def tagbamwithread(argv):
+    try:
+        o = _parse(argv, TAG_SPEC, {})
+    except CliError as e:               # commons-cli: usage + "Command line parsing error: ..." and exit code 1 (L42-47)
+        raise CliError(f"sub-command tagbamwithread: Command line parsing error: {e}")
+    need = [TAG_SPEC[k][0] for k in ("inFastq", "outBam", "readTag", "inBam") if k not in o]
+    if need:
+        raise CliError(f"sub-command tagbamwithread: Missing required options: {', '.join(sorted(need, key='bfor'.index))}")
+    if "qvTag" in o and len(o["qvTag"]) != 2:
+        raise CliError("QV tag must be two characters")
+    if len(o["readTag"]) != 2:
+        raise CliError("read tag must be two characters")
+    for k in ("inFastq", "inBam"):
+        if not os.path.isfile(o[k]):
+            raise CliError(f"--{k} {o[k]}: no such file")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise CliError("tagbamwithread runs in one process on one GPU in this build: start it without torchrun")
+    from .tagbamwithread import tag_bam_with_reads
+    ctx = _context()
+    info = tag_bam_with_reads(ctx, o["inFastq"], o["inBam"], o["outBam"], o["readTag"], o.get("qvTag"), n_threads=_ncpu(o))
+    print(f"DONE -- {info['records']} records, {info['written']} written, {info['unmapped']} without a reference, {info['missing']} not in the FASTQ")
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
@@ -459,7 +490,9 @@ def main(argv=None):
                 if joined:
                     import torch.distributed as dist
                     dist.destroy_process_group()
-        raise CliError(f"sub-command {sub!r}: this build has scanfastq and assignumis (tagbamwithread, mergestats, illuminaparser: SURVEY 2, out of scope)")
+        if sub == "tagbamwithread":
+            return tagbamwithread(rest)
+        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis and tagbamwithread (mergestats, parseillumina: SURVEY 2, out of scope)")
     except CliError as e:
         print(f"ERROR: {e}", file=sys.stderr)
         return 1

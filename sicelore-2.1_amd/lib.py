@@ -65,6 +65,7 @@ EXPORTS = [
     "smi_gene_counts_tsv", "smi_umi_depths_tsv", "smi_gz_inflate_into", "smi_gene_counts_dump", "smi_gene_counts_load", "smi_gene_counts_merge_shard",
     "smi_set_stats", "smi_umi_padded_row", "smi_umi_padded_bytes", "smi_umi_dist_device_padded", "smi_ctx_set_random_barcodes", "smi_run_knobs_default", "smi_ctx_set_knobs", "smi_ctx_get_knobs", "smi_scan_config_from_knobs", "smi_chimera_config_from_knobs",
     "smi_bam_write_default_config", "smi_bam_write_batch", "smi_bam_chunk_inputs", "smi_bam_name_seen", "smi_name_set_create", "smi_name_set_free", "smi_name_set_seen",
+    "smi_tagbam_default_config", "smi_tagbam_create", "smi_tagbam_free", "smi_tagbam_records", "smi_tagbam_segment", "smi_tagbam_stage_ms",
 ]
 
 
@@ -229,6 +230,13 @@ def load_library():
     lib.smi_gene_counts_tsv.argtypes = [vp, ci, vp, sz, ctypes.POINTER(sz)]
     lib.smi_umi_depths_tsv.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
     lib.smi_finalize_used_list.argtypes = [vp, vp, sz, ctypes.c_uint32, ci, ci, ci, vp, vp, vp, ctypes.POINTER(sz)]
+    lib.smi_tagbam_default_config.argtypes = [vp]
+    lib.smi_tagbam_create.argtypes = [vp, vp, sz, vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_uint32)]
+    lib.smi_tagbam_free.argtypes = [vp]
+    lib.smi_tagbam_records.argtypes = [vp, ctypes.POINTER(sz)]
+    lib.smi_tagbam_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32, vp, sz, ctypes.POINTER(sz), vp, ctypes.POINTER(ctypes.c_int32),
+                                       ctypes.POINTER(ctypes.c_int32)]
+    lib.smi_tagbam_stage_ms.argtypes = [vp, vp]
     explicit = {"smi_last_error", "smi_version", "smi_read_planes_words", "smi_packed_planes_words", "smi_record_flags"}  # restype set above (char*, size_t)
     for name in EXPORTS:
         if name not in explicit:
@@ -489,6 +497,80 @@ class NameSet:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.smi_name_set_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class TagBamConfig(ctypes.Structure):
+    """smi_tagbam_config"""
+    _fields_ = [("read_tag", ctypes.c_char * 4), ("qv_tag", ctypes.c_char * 4), ("with_qv", ctypes.c_int32), ("hash_bits", ctypes.c_int32)]
+
+
+TAGBAM_STAGES = ("key", "build", "probe", "size", "assemble")
+
+
+class TagBam:
+    """K-TAG (smi_tagbam_*): the FASTQ text resident on the device as a table of read names, BAM segments tagged against it"""
+
+    def __init__(self, ctx, fastq_text, read_tag="US", qv_tag=None, hash_bits=0):
+        self._lib = load_library()
+        text = np.frombuffer(fastq_text, dtype=np.uint8) if not isinstance(fastq_text, np.ndarray) else fastq_text
+        if text.dtype != np.uint8 or text.ndim != 1 or not text.flags.c_contiguous:
+            raise ValueError("fastq_text: a contiguous 1-D uint8 array (or bytes)")
+        cfg = TagBamConfig()
+        self._lib.smi_tagbam_default_config(ctypes.byref(cfg))
+        cfg.read_tag = str(read_tag).encode()[:3]
+        cfg.with_qv = qv_tag is not None
+        if qv_tag is not None:
+            cfg.qv_tag = str(qv_tag).encode()[:3]
+        if len(str(read_tag).encode()) != 2:
+            raise SmiError("read tag must be two characters")
+        if qv_tag is not None and len(str(qv_tag).encode()) != 2:
+            raise SmiError("QV tag must be two characters")
+        cfg.hash_bits = int(hash_bits)
+        self._h, self.errors = ctypes.c_void_p(), ctypes.c_uint32(0)
+        if self._lib.smi_tagbam_create(ctx._h, text.ctypes.data if text.size else None, text.size, ctypes.byref(cfg), ctypes.byref(self._h),
+                                       ctypes.byref(self.errors)):
+            raise SmiError(self._lib.smi_last_error().decode())
+        self._ctx = ctx                       # (the handle runs on the context's stream: keep the context alive)
+        n = ctypes.c_size_t(0)
+        self._lib.smi_tagbam_records(self._h, ctypes.byref(n))
+        self.n_records = n.value
+
+    def segment(self, bam, recs, out=None):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it -> (output records as uint8 array, indices of
+        the records whose name is not in the FASTQ, number of unmapped records dropped).  out: a uint8 array to write into when it is large
+        enough (e.g. page-locked memory reused from call to call; a view of it is returned)"""
+        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
+            raise ValueError("bam: a contiguous 1-D uint8 array")
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != BAM_RECORD_DTYPE:
+            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
+        n = int(recs.size)
+        missing = np.zeros(max(n, 1), dtype=np.int32)
+        n_out, n_miss, n_unm = ctypes.c_size_t(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        if out is None:
+            out = np.empty(max(64, 2 * bam.size), dtype=np.uint8)
+        while True:
+            rc = self._lib.smi_tagbam_segment(self._h, bam.ctypes.data if bam.size else None, bam.size, recs.ctypes.data if n else None, n,
+                                              out.ctypes.data, out.size, ctypes.byref(n_out), missing.ctypes.data, ctypes.byref(n_miss),
+                                              ctypes.byref(n_unm))
+            if rc == 0:
+                return out[:n_out.value], missing[:n_miss.value], n_unm.value
+            if rc != 1:
+                raise SmiError(self._lib.smi_last_error().decode())
+            out = np.empty(n_out.value + (n_out.value >> 3), dtype=np.uint8)     # the sized segment stays on the device: written by the next call
+
+    def stage_ms(self):
+        """{stage: device ms} of the last create (key, build) and the last segment (probe, size, assemble)"""
+        ms = np.zeros(len(TAGBAM_STAGES), dtype=np.float32)
+        self._lib.smi_tagbam_stage_ms(self._h, ms.ctypes.data)
+        return dict(zip(TAGBAM_STAGES, (float(x) for x in ms)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.smi_tagbam_free(self._h)
             self._h = None
 
     __del__ = close

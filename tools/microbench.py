@@ -35,9 +35,9 @@ def main():
     wl = synth.make_whitelist(3_600_000, seed=1, device=dev)
     used = synth.pick_used(wl, 5000, seed=2)
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
-            "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate}
+            "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam}
     for name, fn in legs.items():
-        if only == name or (only is None and name != "bc2"):
+        if only == name or (only is None and name not in ("bc2", "tagbam")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -379,6 +379,108 @@ def leg_deflate(pkg, synth, ctx, dev, wl, used, res):
                           "sample_bytes": len(sample), "sample_member_bytes": len(zs), "sample_zlib6_bytes": z6, "sample_zlib1_bytes": z1,
                           "size_vs_zlib6": len(zs) / z6, "zlib6_MBps_one_thread": len(sample) / t6 / 1e6, "zlib1_MBps_one_thread": len(sample) / t1 / 1e6,
                           "note": "one call incl. the 16-byte read-back of size and flags; literals-only dynamic Huffman blocks of 64 KiB"}
+
+
+def _tagbam_files(d, n_reads, n_recs, read_len, seed=21):
+    """a FASTQ of n_reads reads (36-character UUID names with a ` runid=.. ch=..` comment, read_len bases) and a coordinate-sorted BAM of
+    n_recs alignments of read_len bases (names drawn from the FASTQ with repeats = secondary / supplementary records; 1 % of them absent from
+    the FASTQ, 0.5 % without a reference), both built with numpy; the BAM is written with the library's host BGZF writer"""
+    from sicelore_amd import lib
+
+    rng = np.random.default_rng(seed)
+    hexd = np.frombuffer(b"0123456789abcdef", dtype=np.uint8)
+    uuid = hexd[rng.integers(0, 16, (n_reads, 36))]
+    uuid[:, [8, 13, 18, 23]] = ord("-")
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    comment = np.frombuffer(b" runid=5f3c ch=101", dtype=np.uint8)
+    L = read_len
+    row = 1 + 36 + comment.size + 1 + L + 1 + 2 + L + 1
+    fq = np.empty((n_reads, row), dtype=np.uint8)
+    c = 0
+    for part, w in ((b"@", 1), (uuid, 36), (comment, comment.size), (b"\n", 1), (None, L), (b"\n+\n", 3), ("q", L), (b"\n", 1)):
+        if part is None:
+            fq[:, c:c + w] = acgt[rng.integers(0, 4, (n_reads, L), dtype=np.uint8)]
+        elif isinstance(part, str):
+            fq[:, c:c + w] = rng.integers(35, 75, (n_reads, L), dtype=np.uint8)
+        elif isinstance(part, bytes):
+            fq[:, c:c + w] = np.frombuffer(part, dtype=np.uint8)
+        else:
+            fq[:, c:c + w] = part
+        c += w
+    fq.reshape(-1).tofile(os.path.join(d, "reads.fastq"))
+    del fq
+    src = rng.integers(0, n_reads, n_recs)
+    absent = rng.random(n_recs) < 0.01
+    unmapped = rng.random(n_recs) < 0.005
+    names = uuid[src].copy()
+    names[absent, 0] = ord("z")                      # no FASTQ name starts with z
+    aux = np.frombuffer(b"NMc\x05tpAPs1i\x10\x00\x00\x00", dtype=np.uint8)
+    body = 32 + 37 + 4 + (L + 1) // 2 + L + aux.size
+    rec = np.zeros((n_recs, 4 + body), dtype=np.uint8)
+    hdr = np.zeros(n_recs, dtype=np.dtype([("bs", "<u4"), ("ref", "<i4"), ("pos", "<i4"), ("lrn", "u1"), ("mapq", "u1"), ("bin", "<u2"), ("ncig", "<u2"),
+                                          ("flag", "<u2"), ("lseq", "<i4"), ("nref", "<i4"), ("npos", "<i4"), ("tlen", "<i4")]))
+    hdr["bs"], hdr["ref"], hdr["pos"] = body, np.where(unmapped, -1, 0), np.where(unmapped, -1, np.arange(n_recs) * 40)
+    hdr["lrn"], hdr["mapq"], hdr["bin"], hdr["ncig"], hdr["lseq"], hdr["nref"], hdr["npos"] = 37, 60, 4680, 1, L, -1, -1
+    hdr["flag"] = np.where(unmapped, 4, rng.choice(np.array([0, 16, 256, 2048], dtype=np.uint16), n_recs, p=[0.45, 0.45, 0.05, 0.05]))
+    order = np.argsort(unmapped, kind="stable")         # the unplaced records last, as a coordinate sort leaves them
+    rec[:, :36] = hdr.view(np.uint8).reshape(n_recs, 36)
+    rec[:, 36:72] = names
+    c = 73
+    rec[:, c:c + 4] = np.frombuffer(np.array([(L << 4) | 0], dtype="<u4").tobytes(), dtype=np.uint8)
+    c += 4
+    rec[:, c:c + (L + 1) // 2] = rng.choice(np.array([0x12, 0x48, 0x84, 0x21, 0x44, 0x18], dtype=np.uint8), (n_recs, (L + 1) // 2))
+    c += (L + 1) // 2
+    rec[:, c:c + L] = 30
+    rec[:, c + L:] = aux
+    rec = rec[order]
+    head = b"BAM\1" + np.array([0], dtype="<u4").tobytes() + np.array([1], dtype="<u4").tobytes() + np.array([5], dtype="<u4").tobytes() \
+        + b"chr1\0" + np.array([2 ** 31 - 1], dtype="<u4").tobytes()
+    bam = np.concatenate([np.frombuffer(head, dtype=np.uint8), rec.reshape(-1)])
+    del rec
+    lib.bgzf_deflate(bam, level=1, n_threads=16).tofile(os.path.join(d, "in.bam"))
+    return int(bam.size)
+
+
+def leg_tagbam(pkg, synth, ctx, dev, wl, used, res):
+    """K-TAG (`tagbamwithread`) at the size of one run: SMI_MB_TAG_READS reads (2 M) of ~1 kb, 1.1 alignments per read.  File to file with the
+    device BGZF writer and with 16 host threads of zlib; device ms per stage from HIP events (the kernel times of a rocprofv3 run of this leg
+    are in profiles/tagbam/), each against its ceiling: build and probe as random gathers (43-48 G/s, BENCH_r06.json hbm_measured), assemble as
+    streamed bytes (8 TB/s)"""
+    import shutil
+    import tempfile
+
+    tb = importlib.import_module(graft.PKG_NAME + ".tagbamwithread")
+    n = int(os.environ.get("SMI_MB_TAG_READS", "2000000"))
+    m = int(n * 1.1)
+    d = tempfile.mkdtemp(prefix="tagbam_")
+    try:
+        t0 = time.perf_counter()
+        bam_bytes = _tagbam_files(d, n, m, 1000)
+        t_gen = time.perf_counter() - t0
+        fq_bytes = os.path.getsize(os.path.join(d, "reads.fastq"))
+        out = {"reads": n, "bam_records": m, "fastq_bytes": fq_bytes, "bam_inflated_bytes": bam_bytes, "bam_file_bytes": os.path.getsize(os.path.join(d, "in.bam")),
+               "fixture_s": t_gen}
+        for bgzf in ("device", "zlib"):
+            with open(os.devnull, "w") as err:
+                info = tb.tag_bam_with_reads(ctx, os.path.join(d, "reads.fastq"), os.path.join(d, "in.bam"), os.path.join(d, "out.bam"), "US", "QS",
+                                             n_threads=16, bgzf=bgzf, err=err)
+            out[bgzf] = {"wall_s": info["wall_s"], "records_per_s": info["records"] / info["wall_s"], "written": info["written"], "missing": info["missing"],
+                         "unmapped": info["unmapped"], "seconds": info["seconds"], "stage_ms": info["stage_ms"],
+                         "out_file_bytes": os.path.getsize(os.path.join(d, "out.bam"))}
+        ms = out["device"]["stage_ms"]
+        out_bytes = bam_bytes + 2 * 1000 * out["device"]["written"]         # (about: the records grow by their two Z strings)
+        out["ceilings"] = {
+            "key_GBps_text": fq_bytes / (ms["key"] * 1e6) if ms["key"] else None,
+            "build_Ggathers_per_s": 4 * n / (ms["build"] * 1e6) if ms["build"] else None,
+            "probe_Ggathers_per_s": 4 * m / (ms["probe"] * 1e6) if ms["probe"] else None,
+            "gather_ceiling_G_per_s": "43-48",
+            "assemble_TBps_streamed": (bam_bytes + out_bytes) / (ms["assemble"] * 1e9) if ms["assemble"] else None,
+            "stream_ceiling_TBps": 8.0,
+            "note": "4 dependent random reads per insert / probe (table word, key length, name start, name bytes); assemble streams the input records "
+                    "and the FASTQ payloads in and the output out"}
+        res["tagbam"] = out
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 def leg_inflate(pkg, synth, ctx, dev, wl, used, res):

@@ -1029,6 +1029,65 @@ int smi_tagbam_segment(smi_tagbam *h, const uint8_t *bam, size_t n_bam, const sm
 /* device time in ms of the stages of the last create / segment (HIP events on the context's stream) */
 int smi_tagbam_stage_ms(const smi_tagbam *h, float *ms);
 
+/* ---- ComputeConsensus (K-POA, smi_consensus.hip) ---------------------------------------------------------------------------------------
+ * Replaces ComputeConsensus.doWork (org/ipmc/sicelore/programs/ComputeConsensus.java:L67-107) with LongreadParser (LongreadParser.java:L42-115),
+ * LongreadRecord.fromSAMRecord (LongreadRecord.java:L71-195), Longread.getBestRecord (Longread.java:L56-60), MoleculeDataset(LongreadParser)
+ * and callConsensus (MoleculeDataset.java:L60-98, L659-719), Consensus.call (Consensus.java:L189-232) and ConsensusMsa.process
+ * (ConsensusMsa.java:L51-87); the external `spoa -r 2` of Consensus.call is this build's POA, not byte-identical to spoa.
+ * smi_consensus_add_segment: records of an inflated BAM segment (smi_bam_index_records) through the reference's filter; the kept ones are held
+ *   by the handle (the whole input's molecules stay in memory, as in the reference).  A value of another type than the reference casts to,
+ *   a mapped record without CIGAR or a kept record with neither cDNA tag fails the call with the read's name (the reference's parse loop
+ *   stops with a stack trace there).  cfg.n_threads host threads.
+ * smi_consensus_run: reads -> molecules -> read selection -> the 1- and 2-read rules on the host, K-POA for 3 or more reads; the FASTQ in
+ *   the order of each molecule's first kept record (the reference: hash order); kernel_ms (may be NULL): K-POA device time.  A molecule
+ *   K-POA cannot hold in cfg.scratch_bytes fails the call with its name (BC-UMI-n).
+ * smi_consensus_fastq: out == NULL -> size only; cap too small -> returns 1.  smi_consensus_counts: SMI_CONSENSUS_COUNTS entries, SMI_CC_*. */
+#define SMI_CONSENSUS_COUNTS 13
+#define SMI_CC_RECORDS 0        /* Total SAMrecords */
+#define SMI_CC_VALID 1          /* SAMrecords valid */
+#define SMI_CC_UNVALID 2        /* SAMrecords unvalid */
+#define SMI_CC_MAPQV0 3         /* SAMrecords mapqv=0 */
+#define SMI_CC_NO_GENE 4        /* SAMrecords no gene (always 0: the gene tag is not required, ComputeConsensus.java:L98) */
+#define SMI_CC_NO_UMI 5         /* SAMrecords no UMI */
+#define SMI_CC_CHIMERIA 6       /* SAMrecords chimeria */
+#define SMI_CC_NULL 7           /* no barcode or unmapped (part of unvalid) */
+#define SMI_CC_READS 8          /* Total reads */
+#define SMI_CC_READS_MULTI 9    /* Total reads multiSAM */
+#define SMI_CC_MOLECULES 10     /* Total molecules */
+#define SMI_CC_POA_MOLECULES 11 /* molecules of 3 or more selected reads (K-POA) */
+#define SMI_CC_POA_RERUN 12     /* of those, run again in a slot of their worst case (smi_poa_batch's *n_rerun) */
+typedef struct {
+    char cell_tag[4], umi_tag[4], gene_tag[4], tso_end_tag[4];  /* CELLTAG UMITAG GENETAG TSOENDTAG: two characters + NUL */
+    char polya_start_tag[4], cdna_tag[4], us_tag[4], rn_tag[4]; /* POLYASTARTTAG CDNATAG USTAG RNTAG */
+    int32_t max_clip;   /* MAXCLIP (150) */
+    int32_t mapqv0;     /* MAPQV0: keep mapq 0 secondary / supplementary records */
+    int32_t max_reads;  /* MAXREADS >= 1 */
+    int32_t min_ps;     /* MINPS: the QV of 1- and 2-read molecules */
+    int32_t max_ps;     /* MAXPS: the QV of a base all selected reads agree on */
+    int32_t n_threads;  /* -T */
+    int64_t scratch_bytes; /* K-POA's device scratch budget (smi_poa_batch); 0: half the free memory, at most 32 GiB */
+} smi_consensus_config;
+typedef struct smi_consensus smi_consensus;
+int smi_consensus_default_config(smi_consensus_config *cfg);
+int smi_consensus_create(smi_ctx *ctx, const smi_consensus_config *cfg, smi_consensus **out);
+int smi_consensus_add_segment(smi_consensus *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n);
+int smi_consensus_run(smi_consensus *h, float *kernel_ms);
+int smi_consensus_fastq(const smi_consensus *h, uint8_t *out, size_t cap, size_t *n_out);
+int smi_consensus_counts(const smi_consensus *h, int64_t *counts);
+int smi_consensus_free(smi_consensus *h);
+/* smi_poa_batch: K-POA alone (Consensus.call's `spoa -r 2` + ConsensusMsa.process for one batch of molecules).  Read r is
+ * seqs[read_off[r] .. read_off[r + 1]); molecule m has reads mol_off[m] .. mol_off[m + 1] in selection order (read_off[0] = mol_off[0] = 0).
+ * Out: molecule m's consensus at cons[read_off[mol_off[m]] ..] and its QVs at qv[read_off[mol_off[m]] ..], cons_len[m] bytes each (never
+ * more than the molecule's bases); the QV of a base is MAXPS when every read of the molecule passes its node, else
+ * 33 + floor(-10 log10(1 - same / reads) + 0.5).  scratch_bytes: the device scratch budget (0: half the free memory, at most 32 GiB).  Each
+ * molecule first runs in a slot of its estimate (a graph of 3 x its longest read, never above its worst case); one whose graph outgrows that
+ * slot, or whose estimate does not fit the budget, runs again in a slot of its worst case (the graph holds at most the bases of the reads
+ * before the one being aligned), and *n_rerun (may be NULL) counts those.  A molecule whose worst case does not fit the budget fails the call
+ * with its index.  DP rows are int16 for molecules whose reads have at most 6,000 bases, int32 above.  kernel_ms (may be NULL): device time.
+ * Host arrays; synchronous. */
+int smi_poa_batch(smi_ctx *ctx, const uint8_t *seqs, const uint64_t *read_off, const int32_t *mol_off, int32_t n_mol, int32_t max_ps,
+                  size_t scratch_bytes, uint8_t *cons, uint8_t *qv, int32_t *cons_len, float *kernel_ms, int32_t *n_rerun);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

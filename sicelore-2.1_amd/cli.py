@@ -5,7 +5,9 @@
     java -jar [-Xmx..] NanoporeBC_UMI_finder-2.1.jar assignumis --inFileNanopore <bam> -o <bam> [--annotationFile refFlat] [-v n] [-p] [-w] [-b ed] [-u ed] [-s]
     java -jar [-Xmx..] NanoporeBC_UMI_finder-2.1.jar tagbamwithread --inFastq <fastq[.gz]> --inBam <bam> --outBam <bam> --readTag XX [--qvTag YY]
 
-become   python sicelore-2.1_amd scanfastq ... / assignumis ... / tagbamwithread ...   (the directory is runnable: __main__.py; a `java` wrapper that drops
+    java -jar [-Xmx..] Sicelore-2.1.jar ComputeConsensus -I <bam> -O <fastq> [-T n] [-CELLTAG BC] ... [-MAXREADS 20] [-MINPS 3] [-MAXPS 20]   (or I=<bam> O=<fastq> ...)
+
+become   python sicelore-2.1_amd scanfastq ... / assignumis ... / tagbamwithread ... / ComputeConsensus ...   (the directory is runnable: __main__.py; a `java` wrapper that drops
 `-jar`, `-Xmx..` and the jar's name makes /root/reference/quickrun-2.1.sh:35,42 run unchanged, tests/test_cli_gpu.py does exactly that).
 
 Reference units: option tables NanoporeReadScannerMain.cli_otions (NanoporeReadScannerMain.java:L336-469) and UmiFinderMain (L298-447);
@@ -475,6 +477,80 @@ def tagbamwithread(argv):
     return 0
 
 
+# ComputeConsensus (ComputeConsensus.java:L23-60): Picard's option names -> (smi_consensus_config field or None, kind, default)
+CC_OPTIONS = {
+    "I": (None, "path", None), "O": (None, "path", None), "T": ("n_threads", "int", 20), "TMPDIR": (None, "str", "/export/data/scratch/sicelore/"),
+    "CELLTAG": ("cell_tag", "tag", "BC"), "UMITAG": ("umi_tag", "tag", "U8"), "GENETAG": ("gene_tag", "tag", "IG"),
+    "TSOENDTAG": ("tso_end_tag", "tag", "TE"), "POLYASTARTTAG": ("polya_start_tag", "tag", "PS"), "CDNATAG": ("cdna_tag", "tag", "CS"),
+    "USTAG": ("us_tag", "tag", "US"), "RNTAG": ("rn_tag", "tag", "RN"), "MAXCLIP": ("max_clip", "int", 150), "MAPQV0": ("mapqv0", "bool", False),
+    "MAXREADS": ("max_reads", "int", 20), "MINPS": ("min_ps", "int", 3), "MAXPS": ("max_ps", "int", 20), "DEBUG": (None, "bool", False),
+    "VALIDATION_STRINGENCY": (None, "stringency", "STRICT"),
+}
+CC_LONG = {"INPUT": "I", "OUTPUT": "O", "nThreads": "T"}
+
+
+def _cc_parse(argv):
+    """Picard's two syntaxes: `-NAME value` (or --NAME value, -NAME=value) and the legacy `NAME=value` -> {NAME: value}"""
+    o, i = {}, 0
+    while i < len(argv):
+        a = argv[i]
+        if a.startswith("-"):
+            name = a.lstrip("-")
+            if "=" in name:
+                name, v = name.split("=", 1)
+            else:
+                if i + 1 >= len(argv):
+                    raise CliError(f"sub-command ComputeConsensus: option {a} needs a value")
+                v = argv[i + 1]
+                i += 1
+        elif "=" in a:
+            name, v = a.split("=", 1)
+        else:
+            raise CliError(f"sub-command ComputeConsensus: unexpected argument {a!r}")
+        name = CC_LONG.get(name, name)
+        if name not in CC_OPTIONS:
+            raise CliError(f"sub-command ComputeConsensus: unknown option {name!r}")
+        field, kind, _default = CC_OPTIONS[name]
+        if kind == "int":
+            try:
+                v = int(v)
+            except ValueError:
+                raise CliError(f"sub-command ComputeConsensus: {name} {v!r} is not a number")
+        elif kind == "bool":
+            if v.lower() not in ("true", "false"):
+                raise CliError(f"sub-command ComputeConsensus: {name} takes true or false, not {v!r}")
+            v = v.lower() == "true"
+        elif kind == "tag" and len(v) != 2:
+            raise CliError(f"sub-command ComputeConsensus: {name} {v!r} is not a two-character tag")
+        elif kind == "stringency" and v not in ("STRICT", "LENIENT", "SILENT"):
+            raise CliError(f"sub-command ComputeConsensus: VALIDATION_STRINGENCY {v!r}: STRICT, LENIENT or SILENT")
+        o[name] = v
+        i += 1
+    return o
+
+
+def computeconsensus(argv):
+    """ComputeConsensus.doWork (L67-107).  TMPDIR and DEBUG are accepted and change nothing (no temporary files are made); so is
+    VALIDATION_STRINGENCY (the BAM reader checks what it decodes)."""
+    o = _cc_parse(argv)
+    need = [k for k in ("I", "O") if k not in o]
+    if need:
+        raise CliError(f"sub-command ComputeConsensus: missing required option(s) {', '.join(need)}")
+    if not os.path.isfile(o["I"]):
+        raise CliError(f"ComputeConsensus: I={o['I']}: no such file")       # IOUtil.assertFileIsReadable (L69)
+    cfg = {f: o.get(k, d) for k, (f, _kind, d) in CC_OPTIONS.items() if f is not None and f != "n_threads"}
+    if cfg["max_reads"] < 1:
+        raise CliError(f"ComputeConsensus: MAXREADS {cfg['max_reads']} must be at least 1")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise CliError("ComputeConsensus runs in one process on one GPU in this build: start it without torchrun")
+    from .computeconsensus import compute_consensus, parser_log
+    ctx = _context()
+    info = compute_consensus(ctx, o["I"], o["O"], n_threads=max(1, min(int(o.get("T", 20)), 256)), **cfg)
+    print(parser_log(info), file=sys.stderr)
+    print(f"DONE -- {info['molecules']} molecules written, {info['poa_molecules']} of them by K-POA", file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
@@ -492,7 +568,10 @@ def main(argv=None):
                     dist.destroy_process_group()
         if sub == "tagbamwithread":
             return tagbamwithread(rest)
-        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis and tagbamwithread (mergestats, parseillumina: SURVEY 2, out of scope)")
+        if sub == "ComputeConsensus":
+            return computeconsensus(rest)
+        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread and ComputeConsensus (mergestats, parseillumina: "
+                       "SURVEY 2, out of scope)")
     except CliError as e:
         print(f"ERROR: {e}", file=sys.stderr)
         return 1

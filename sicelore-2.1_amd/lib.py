@@ -66,6 +66,8 @@ EXPORTS = [
     "smi_set_stats", "smi_umi_padded_row", "smi_umi_padded_bytes", "smi_umi_dist_device_padded", "smi_ctx_set_random_barcodes", "smi_run_knobs_default", "smi_ctx_set_knobs", "smi_ctx_get_knobs", "smi_scan_config_from_knobs", "smi_chimera_config_from_knobs",
     "smi_bam_write_default_config", "smi_bam_write_batch", "smi_bam_chunk_inputs", "smi_bam_name_seen", "smi_name_set_create", "smi_name_set_free", "smi_name_set_seen",
     "smi_tagbam_default_config", "smi_tagbam_create", "smi_tagbam_free", "smi_tagbam_records", "smi_tagbam_segment", "smi_tagbam_stage_ms",
+    "smi_consensus_default_config", "smi_consensus_create", "smi_consensus_add_segment", "smi_consensus_run", "smi_consensus_fastq",
+    "smi_consensus_counts", "smi_consensus_free", "smi_poa_batch",
 ]
 
 
@@ -237,6 +239,15 @@ def load_library():
     lib.smi_tagbam_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32, vp, sz, ctypes.POINTER(sz), vp, ctypes.POINTER(ctypes.c_int32),
                                        ctypes.POINTER(ctypes.c_int32)]
     lib.smi_tagbam_stage_ms.argtypes = [vp, vp]
+    lib.smi_consensus_default_config.argtypes = [vp]
+    lib.smi_consensus_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
+    lib.smi_consensus_add_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32]
+    lib.smi_consensus_run.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    lib.smi_consensus_fastq.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_consensus_counts.argtypes = [vp, vp]
+    lib.smi_consensus_free.argtypes = [vp]
+    lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
+                                  ctypes.POINTER(ctypes.c_int32)]
     explicit = {"smi_last_error", "smi_version", "smi_read_planes_words", "smi_packed_planes_words", "smi_record_flags"}  # restype set above (char*, size_t)
     for name in EXPORTS:
         if name not in explicit:
@@ -574,6 +585,110 @@ class TagBam:
             self._h = None
 
     __del__ = close
+
+
+class ConsensusConfig(ctypes.Structure):
+    """smi_consensus_config"""
+    _fields_ = [("cell_tag", ctypes.c_char * 4), ("umi_tag", ctypes.c_char * 4), ("gene_tag", ctypes.c_char * 4), ("tso_end_tag", ctypes.c_char * 4),
+                ("polya_start_tag", ctypes.c_char * 4), ("cdna_tag", ctypes.c_char * 4), ("us_tag", ctypes.c_char * 4), ("rn_tag", ctypes.c_char * 4),
+                ("max_clip", ctypes.c_int32), ("mapqv0", ctypes.c_int32), ("max_reads", ctypes.c_int32), ("min_ps", ctypes.c_int32),
+                ("max_ps", ctypes.c_int32), ("n_threads", ctypes.c_int32), ("scratch_bytes", ctypes.c_int64)]
+
+
+# smi_consensus_counts, in SMI_CC_* order
+CONSENSUS_COUNTS = ("records", "valid", "unvalid", "mapqv0", "no_gene", "no_umi", "chimeria", "null", "reads", "reads_multi", "molecules",
+                    "poa_molecules", "poa_rerun")
+CONSENSUS_TAGS = ("cell_tag", "umi_tag", "gene_tag", "tso_end_tag", "polya_start_tag", "cdna_tag", "us_tag", "rn_tag")
+
+
+class Consensus:
+    """ComputeConsensus (smi_consensus_*): BAM segments in, the molecules' consensus FASTQ out.  Keywords: the fields of
+    smi_consensus_config (tags as two-character strings, mapqv0 as a bool)."""
+
+    def __init__(self, ctx, **kw):
+        self._lib = load_library()
+        cfg = ConsensusConfig()
+        self._lib.smi_consensus_default_config(ctypes.byref(cfg))
+        for k, v in kw.items():
+            if k in CONSENSUS_TAGS:
+                b = str(v).encode()
+                if len(b) != 2:
+                    raise SmiError(f"{k}: a tag is two characters")
+                setattr(cfg, k, b)
+            elif k in ("max_clip", "mapqv0", "max_reads", "min_ps", "max_ps", "n_threads", "scratch_bytes"):
+                setattr(cfg, k, int(v))
+            else:
+                raise ValueError(f"unknown smi_consensus_config field {k!r}")
+        self._h = ctypes.c_void_p()
+        if self._lib.smi_consensus_create(ctx._h, ctypes.byref(cfg), ctypes.byref(self._h)):
+            self._h = None
+            raise SmiError(self._lib.smi_last_error().decode())
+        self._ctx = ctx
+        self.kernel_ms = 0.0
+
+    def add_segment(self, bam, recs):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
+        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
+            raise ValueError("bam: a contiguous 1-D uint8 array")
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != BAM_RECORD_DTYPE:
+            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
+        if self._lib.smi_consensus_add_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)):
+            raise SmiError(self._lib.smi_last_error().decode())
+
+    def run(self):
+        """molecules, read selection, K-POA -> the FASTQ as bytes"""
+        ms = ctypes.c_float(0.0)
+        if self._lib.smi_consensus_run(self._h, ctypes.byref(ms)):
+            raise SmiError(self._lib.smi_last_error().decode())
+        self.kernel_ms = float(ms.value)
+        n = ctypes.c_size_t(0)
+        self._lib.smi_consensus_fastq(self._h, None, 0, ctypes.byref(n))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        if self._lib.smi_consensus_fastq(self._h, _ptr(out), out.size, ctypes.byref(n)):
+            raise SmiError(self._lib.smi_last_error().decode())
+        return out[:n.value].tobytes()
+
+    def counts(self):
+        c = np.zeros(len(CONSENSUS_COUNTS), dtype=np.int64)
+        self._lib.smi_consensus_counts(self._h, _ptr(c))
+        return dict(zip(CONSENSUS_COUNTS, (int(x) for x in c)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.smi_consensus_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def poa_batch(ctx, seqs, read_off, mol_off, max_ps=20, scratch_bytes=0):
+    """K-POA alone (smi_poa_batch).  seqs: uint8 bases of all reads back to back; read_off: uint64 [n_reads + 1]; mol_off: int32 [n_mol + 1],
+    both starting at 0 -> (list of consensus bytes, list of QV bytes, device ms, molecules run again in a slot of their worst case)"""
+    lib = load_library()
+    seqs = np.ascontiguousarray(seqs)
+    read_off = np.ascontiguousarray(read_off)
+    mol_off = np.ascontiguousarray(mol_off)
+    if seqs.dtype != np.uint8 or seqs.ndim != 1:
+        raise ValueError("seqs: a 1-D uint8 array")
+    if read_off.dtype != np.uint64 or read_off.ndim != 1 or mol_off.dtype != np.int32 or mol_off.ndim != 1 or mol_off.size < 1:
+        raise ValueError("read_off: 1-D uint64, mol_off: 1-D int32 with at least one entry")
+    n_mol = int(mol_off.size) - 1
+    if read_off.size != int(mol_off[-1]) + 1 or int(read_off[-1]) != seqs.size:
+        raise ValueError("read_off must have mol_off[-1] + 1 entries ending at seqs.size")
+    cons = np.zeros(max(seqs.size, 1), dtype=np.uint8)
+    qv = np.zeros_like(cons)
+    clen = np.zeros(max(n_mol, 1), dtype=np.int32)
+    ms, rerun = ctypes.c_float(0.0), ctypes.c_int32(0)
+    if lib.smi_poa_batch(ctx._h, _ptr(seqs) if seqs.size else None, _ptr(read_off), _ptr(mol_off), n_mol, int(max_ps), int(scratch_bytes),
+                         _ptr(cons), _ptr(qv), _ptr(clen), ctypes.byref(ms), ctypes.byref(rerun)):
+        raise SmiError(lib.smi_last_error().decode())
+    outs, qvs = [], []
+    for m in range(n_mol):
+        o, n = int(read_off[mol_off[m]]), int(clen[m])
+        outs.append(cons[o:o + n].tobytes())
+        qvs.append(qv[o:o + n].tobytes())
+    return outs, qvs, float(ms.value), int(rerun.value)
 
 
 def bam_chunk_inputs(bam, recs, idx):

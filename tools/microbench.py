@@ -35,9 +35,10 @@ def main():
     wl = synth.make_whitelist(3_600_000, seed=1, device=dev)
     used = synth.pick_used(wl, 5000, seed=2)
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
-            "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam}
+            "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
+            "consensus": leg_consensus}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -481,6 +482,103 @@ def leg_tagbam(pkg, synth, ctx, dev, wl, used, res):
         res["tagbam"] = out
     finally:
         shutil.rmtree(d, ignore_errors=True)
+
+
+def _noisy(rng, src, rate):
+    """ONT-like copy of src (uint8 bases): substitutions, insertions and deletions of rate / 3 each"""
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    x = rng.random(src.size)
+    out = src.copy()
+    sub = x < rate / 3
+    out[sub] = acgt[rng.integers(0, 4, int(sub.sum()))]
+    reps = np.ones(src.size, dtype=np.int64)
+    reps[(x >= rate / 3) & (x < 2 * rate / 3)] = 2        # the base and an inserted one
+    reps[(x >= 2 * rate / 3) & (x < rate)] = 0            # deleted
+    idx = np.repeat(np.arange(src.size), reps)
+    res = out[idx]
+    second = np.flatnonzero(idx[1:] == idx[:-1]) + 1
+    res[second] = acgt[rng.integers(0, 4, second.size)]
+    return res
+
+
+def _consensus_molecules(n_mol, seed=31, length=1000, rate=0.07):
+    """n_mol molecules of one ~1 kb cDNA each: half of them 1 or 2 reads, half 3 to 30 reads, every read a noisy copy"""
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    mols = []
+    for m in range(n_mol):
+        k = int(rng.integers(1, 3)) if m % 2 else int(rng.integers(3, 31))
+        src = acgt[rng.integers(0, 4, length)]
+        mols.append([_noisy(rng, src, rate).tobytes() for _ in range(k)])
+    return mols
+
+
+def _consensus_bam(mols, seed=32):
+    """one BAM record per read: BC / U8, US = 20 bases of TSO side + cDNA + 30 of polyA side, TE / PS, de; no SEQ (ComputeConsensus reads US)"""
+    import struct
+
+    from sicelore_amd import lib
+
+    rng = np.random.default_rng(seed)
+    recs = []
+    k = 0
+    for m, reads in enumerate(mols):
+        for r in reads:
+            us = b"T" * 20 + r + b"A" * 30
+            aux = (b"BCZ" + b"CELL%05d-1" % (m % 3000) + b"\0" + b"U8Z" + b"UMI%07d" % m + b"\0" + b"USZ" + us + b"\0"
+                   + b"TEs" + struct.pack("<h", 20) + b"PSS" + struct.pack("<H", 20 + len(r)) + b"def" + struct.pack("<f", float(rng.integers(0, 50)) / 500))
+            name = b"read%08d\0" % k
+            body = struct.pack("<iiBBHHHiiii", 0, 100 + k, len(name), 60, 4680, 1, 0, 0, -1, -1, 0) + name + struct.pack("<I", (len(r) << 4) | 0) + aux
+            recs.append(struct.pack("<I", len(body)) + body)
+            k += 1
+    head = b"BAM\1" + struct.pack("<I", 0) + struct.pack("<I", 1) + struct.pack("<I", 5) + b"chr1\0" + struct.pack("<I", 2 ** 31 - 1)
+    bam = np.frombuffer(head + b"".join(recs), dtype=np.uint8)
+    return lib.bgzf_deflate(bam, level=1, n_threads=16), k
+
+
+def leg_consensus(pkg, synth, ctx, dev, wl, used, res):
+    """K-POA (`ComputeConsensus`): SMI_MB_CC_MOLS molecules (4000) of a 1 kb cDNA with ~7 % ONT-like errors, 1 to 30 reads, about half with
+    3 or more.  Device: smi_poa_batch over the multi-read molecules with their first 20 reads (MAXREADS), molecules/s and DP cells/s (cells
+    counted against the consensus length: a lower bound, the graph has more nodes than its consensus).  File to file: compute_consensus
+    on a BAM of one record per read."""
+    import shutil
+    import tempfile
+
+    from sicelore_amd import lib
+
+    cc = importlib.import_module(graft.PKG_NAME + ".computeconsensus")
+    n = int(os.environ.get("SMI_MB_CC_MOLS", "4000"))
+    t0 = time.perf_counter()
+    mols = _consensus_molecules(n)
+    out = {"molecules": n, "reads": sum(len(m) for m in mols), "fixture_s": time.perf_counter() - t0}
+    multi = [m[:20] for m in mols if len(m) >= 3]
+    seqs = np.frombuffer(b"".join(r for m in multi for r in m), dtype=np.uint8).copy()
+    read_off = np.zeros(sum(len(m) for m in multi) + 1, dtype=np.uint64)
+    read_off[1:] = np.cumsum([len(r) for m in multi for r in m])
+    mol_off = np.zeros(len(multi) + 1, dtype=np.int32)
+    mol_off[1:] = np.cumsum([len(m) for m in multi])
+    lib.poa_batch(ctx, seqs[:int(read_off[mol_off[min(50, len(multi))]])].copy(), read_off[:mol_off[min(50, len(multi))] + 1].copy(),
+                  mol_off[:min(50, len(multi)) + 1].copy())                                   # warm-up
+    t0 = time.perf_counter()
+    cons, _qv, ms, rerun = lib.poa_batch(ctx, seqs, read_off, mol_off)
+    wall = time.perf_counter() - t0
+    cells = sum(len(r) * len(c) for m, c in zip(multi, cons) for r in m[1:])
+    out["device"] = {"poa_molecules": len(multi), "reads": int(mol_off[-1]), "kernel_ms": ms, "call_s": wall, "rerun": rerun,
+                     "molecules_per_s": len(multi) / (ms / 1e3), "cells_lower_bound": cells, "cells_per_s": cells / (ms / 1e3),
+                     "mean_consensus_len": float(np.mean([len(c) for c in cons]))}
+    d = tempfile.mkdtemp(prefix="consensus_")
+    try:
+        t0 = time.perf_counter()
+        z, n_rec = _consensus_bam(mols)
+        z.tofile(os.path.join(d, "in.bam"))
+        out["bam_fixture_s"] = time.perf_counter() - t0
+        info = cc.compute_consensus(ctx, os.path.join(d, "in.bam"), os.path.join(d, "out.fq"), n_threads=16)
+        out["file_to_file"] = {"records": info["records"], "molecules": info["molecules"], "poa_molecules": info["poa_molecules"], "wall_s": info["wall_s"],
+                               "records_per_s": info["records"] / info["wall_s"], "molecules_per_s": info["molecules"] / info["wall_s"],
+                               "seconds": info["seconds"], "poa_kernel_ms": info["poa_kernel_ms"]}
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    res["consensus"] = out
 
 
 def leg_inflate(pkg, synth, ctx, dev, wl, used, res):

@@ -1088,6 +1088,82 @@ int smi_consensus_free(smi_consensus *h);
 int smi_poa_batch(smi_ctx *ctx, const uint8_t *seqs, const uint64_t *read_off, const int32_t *mol_off, int32_t n_mol, int32_t max_ps,
                   size_t scratch_bytes, uint8_t *cons, uint8_t *qv, int32_t *cons_len, float *kernel_ms, int32_t *n_rerun);
 
+/* ---- IsoformMatrix (K-ISO + K-MTX, smi_isoform.hip) -----------------------------------------------------------------------------------
+ * IsoformMatrix.process (IsoformMatrix.java:L93-160), METHOD=STRICT, DESIGN.md section 8d.
+ * smi_isoform_create: the refFlat text (a line of fewer than 11 fields or with a bad integer fails the call naming the line) and the -CSV
+ * cell list (one barcode per line, "-1" removed).  smi_isoform_add_segment: records of an inflated BAM segment (smi_bam_index_records)
+ * through LongreadParser's filter with the gene mandatory; kept records are held.  smi_isoform_run: reads -> molecules -> K-ISO (STRICT
+ * assignment, junction sets) -> K-MTX (counts, dense rows in blocks of at most budget_bytes of device memory) -> every output text.
+ * stage_ms (may be NULL): SMI_ISOFORM_STAGES device times: K-ISO, sort + run-length encoding, render.  smi_isoform_output: text of
+ * SMI_ISO_OUT_*; out == NULL -> size only; cap too small -> returns 1.  smi_isoform_counts: SMI_ISOFORM_COUNTS entries, SMI_ISO_*. */
+#define SMI_ISO_RECORDS 0          /* Total SAMrecords */
+#define SMI_ISO_VALID 1            /* SAMrecords valid */
+#define SMI_ISO_UNVALID 2          /* SAMrecords unvalid */
+#define SMI_ISO_MAPQV0 3           /* SAMrecords mapqv=0 */
+#define SMI_ISO_NO_GENE 4          /* SAMrecords no gene */
+#define SMI_ISO_NO_UMI 5           /* SAMrecords no UMI */
+#define SMI_ISO_CHIMERIA 6         /* SAMrecords chimeria */
+#define SMI_ISO_NULL 7             /* no barcode or unmapped (part of unvalid) */
+#define SMI_ISO_READS 8            /* Total reads */
+#define SMI_ISO_READS_MULTI 9      /* Total reads multiSAM */
+#define SMI_ISO_MOLECULES 10       /* Total molecules */
+#define SMI_ISO_MOLECULE_READS 11  /* Total molecule reads */
+#define SMI_ISO_MULTI_IG 12        /* Total molecule multiIG */
+#define SMI_ISO_GENES 13           /* UCSCRefFlatParser genes */
+#define SMI_ISO_TRANSCRIPTS 14     /* UCSCRefFlatParser transcripts */
+#define SMI_ISO_MONOEXON 15        /* SetIsoforms monoexon */
+#define SMI_ISO_NOMATCH 16         /* SetIsoforms no match */
+#define SMI_ISO_ONEMATCH 17        /* SetIsoforms one match */
+#define SMI_ISO_AMBIGUOUS 18       /* SetIsoforms ambiguous */
+#define SMI_ISO_CELLS 19           /* Matrix cells size */
+#define SMI_ISO_MATRIX_GENES 20    /* Matrix genes size */
+#define SMI_ISO_MATRIX_JUNCTIONS 21 /* Matrix junctions size */
+#define SMI_ISO_MATRIX_ISOFORMS 22 /* Matrix isoforms size */
+#define SMI_ISO_TOTAL_COUNT 23     /* Matrix isoforms counts */
+#define SMI_ISO_DEF 24             /* Matrix isoforms define */
+#define SMI_ISO_UNDEF 25           /* Matrix isoforms undefined */
+#define SMI_ISO_SPILL 26           /* molecules whose candidate counts lived in HBM (more transcripts than lds_tx) */
+#define SMI_ISO_RENDER_BLOCKS 27   /* row blocks rendered, the three matrices together */
+#define SMI_ISOFORM_COUNTS 28
+#define SMI_ISO_OUT_ISOMATRIX 0
+#define SMI_ISO_OUT_ISOMETRICS 1
+#define SMI_ISO_OUT_MOLINFOS 2
+#define SMI_ISO_OUT_GENEMATRIX 3
+#define SMI_ISO_OUT_GENEMETRICS 4
+#define SMI_ISO_OUT_CELLMETRICS 5
+#define SMI_ISO_OUT_JUNCMATRIX 6
+#define SMI_ISO_OUT_JUNCMETRICS 7
+#define SMI_ISO_OUT_BULKGENE 8     /* TOBULK only */
+#define SMI_ISO_OUT_BULKISO 9      /* TOBULK only */
+#define SMI_ISOFORM_OUTPUTS 10
+#define SMI_ISOFORM_STAGES 3
+typedef struct {
+    char cell_tag[4], umi_tag[4], gene_tag[4], rn_tag[4];  /* CELLTAG UMITAG GENETAG RNTAG: two characters + NUL */
+    int32_t max_clip;      /* MAXCLIP (150) */
+    int32_t mapqv0;        /* MAPQV0: keep mapq 0 secondary / supplementary records */
+    int32_t delta;         /* DELTA (2) */
+    int32_t to_bulk;       /* TOBULK: also the bulkgene / bulkiso texts */
+    int32_t n_threads;     /* host parser threads */
+    int32_t lds_tx;        /* candidate transcripts per molecule counted in LDS, 1 .. 2048 (default); more spill to HBM */
+    int64_t budget_bytes;  /* K-MTX device memory per row block (0: 1 GiB) */
+} smi_isoform_config;
+typedef struct smi_isoform smi_isoform;
+int smi_isoform_default_config(smi_isoform_config *cfg);
+int smi_isoform_create(smi_ctx *ctx, const smi_isoform_config *cfg, const char *refflat, size_t n_refflat, const char *csv, size_t n_csv,
+                       smi_isoform **out);
+int smi_isoform_add_segment(smi_isoform *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n);
+int smi_isoform_run(smi_isoform *h, float *stage_ms);
+int smi_isoform_output(const smi_isoform *h, int32_t which, uint8_t *out, size_t cap, size_t *n_out);
+int smi_isoform_counts(const smi_isoform *h, int64_t *counts);
+int smi_isoform_free(smi_isoform *h);
+/* ISOBAM (IsoformMatrix.java:L135-159), after smi_isoform_run: every record of an inflated BAM segment (unmapped and filtered ones too) with
+ * IG / IT = the gene / transcript of the molecule keyed by the RAW CELLTAG value ":" the UMITAG value ("null" for a missing tag), "undef" when
+ * there is none; the attributes re-encoded by K-TAG's rules (sorted by binary tag, the last duplicate wins, integers narrowed, H as B:c).
+ * out: the records back to back in input order; out == NULL -> makes them and returns their size; cap too small -> returns 1.  A call
+ * with out != NULL and the same bam, recs and n as the call before copies the records that call made. */
+int smi_isoform_isobam(smi_isoform *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n, uint8_t *out, size_t cap,
+                       size_t *n_out);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

@@ -489,7 +489,7 @@ CC_OPTIONS = {
 CC_LONG = {"INPUT": "I", "OUTPUT": "O", "nThreads": "T"}
 
 
-def _cc_parse(argv):
+def _picard_parse(argv, prog, options, long_names):
     """Picard's two syntaxes: `-NAME value` (or --NAME value, -NAME=value) and the legacy `NAME=value` -> {NAME: value}"""
     o, i = {}, 0
     while i < len(argv):
@@ -500,33 +500,37 @@ def _cc_parse(argv):
                 name, v = name.split("=", 1)
             else:
                 if i + 1 >= len(argv):
-                    raise CliError(f"sub-command ComputeConsensus: option {a} needs a value")
+                    raise CliError(f"sub-command {prog}: option {a} needs a value")
                 v = argv[i + 1]
                 i += 1
         elif "=" in a:
             name, v = a.split("=", 1)
         else:
-            raise CliError(f"sub-command ComputeConsensus: unexpected argument {a!r}")
-        name = CC_LONG.get(name, name)
-        if name not in CC_OPTIONS:
-            raise CliError(f"sub-command ComputeConsensus: unknown option {name!r}")
-        field, kind, _default = CC_OPTIONS[name]
+            raise CliError(f"sub-command {prog}: unexpected argument {a!r}")
+        name = long_names.get(name, name)
+        if name not in options:
+            raise CliError(f"sub-command {prog}: unknown option {name!r}")
+        field, kind, _default = options[name]
         if kind == "int":
             try:
                 v = int(v)
             except ValueError:
-                raise CliError(f"sub-command ComputeConsensus: {name} {v!r} is not a number")
+                raise CliError(f"sub-command {prog}: {name} {v!r} is not a number")
         elif kind == "bool":
             if v.lower() not in ("true", "false"):
-                raise CliError(f"sub-command ComputeConsensus: {name} takes true or false, not {v!r}")
+                raise CliError(f"sub-command {prog}: {name} takes true or false, not {v!r}")
             v = v.lower() == "true"
         elif kind == "tag" and len(v) != 2:
-            raise CliError(f"sub-command ComputeConsensus: {name} {v!r} is not a two-character tag")
+            raise CliError(f"sub-command {prog}: {name} {v!r} is not a two-character tag")
         elif kind == "stringency" and v not in ("STRICT", "LENIENT", "SILENT"):
-            raise CliError(f"sub-command ComputeConsensus: VALIDATION_STRINGENCY {v!r}: STRICT, LENIENT or SILENT")
+            raise CliError(f"sub-command {prog}: VALIDATION_STRINGENCY {v!r}: STRICT, LENIENT or SILENT")
         o[name] = v
         i += 1
     return o
+
+
+def _cc_parse(argv):
+    return _picard_parse(argv, "ComputeConsensus", CC_OPTIONS, CC_LONG)
 
 
 def computeconsensus(argv):
@@ -551,6 +555,51 @@ def computeconsensus(argv):
     return 0
 
 
+# IsoformMatrix (IsoformMatrix.java:L33-72): Picard's option names -> (smi_isoform_config field or None, kind, default).  TSOENDTAG,
+# POLYASTARTTAG, CDNATAG and USTAG name tags the reference does not read without sequences; AMBIGUOUS_ASSIGN changes nothing under STRICT.
+IM_OPTIONS = {
+    "I": (None, "path", None), "REFFLAT": (None, "path", None), "CSV": (None, "path", None), "DELTA": ("delta", "int", 2),
+    "OUTDIR": (None, "path", None), "PREFIX": (None, "str", "sicelore"), "ISOBAM": (None, "bool", False), "METHOD": (None, "str", "STRICT"),
+    "CELLTAG": ("cell_tag", "tag", "BC"), "UMITAG": ("umi_tag", "tag", "U8"), "GENETAG": ("gene_tag", "tag", "GE"),
+    "TSOENDTAG": (None, "tag", "TE"), "POLYASTARTTAG": (None, "tag", "PS"), "CDNATAG": (None, "tag", "CS"), "USTAG": (None, "tag", "US"),
+    "RNTAG": ("rn_tag", "tag", "RN"), "MAXCLIP": ("max_clip", "int", 150), "AMBIGUOUS_ASSIGN": (None, "bool", False),
+    "MAPQV0": ("mapqv0", "bool", False), "TOBULK": ("to_bulk", "bool", False), "VALIDATION_STRINGENCY": (None, "stringency", "STRICT"),
+}
+IM_LONG = {"INPUT": "I"}
+
+
+def isoformmatrix(argv):
+    """IsoformMatrix.doWork (L74-91) and process (L93-160).  VALIDATION_STRINGENCY is accepted and changes nothing."""
+    o = _picard_parse(argv, "IsoformMatrix", IM_OPTIONS, IM_LONG)
+    need = [k for k in ("I", "REFFLAT", "CSV", "OUTDIR") if k not in o]
+    if need:
+        raise CliError(f"sub-command IsoformMatrix: missing required option(s) {', '.join(need)}")
+    for k in ("REFFLAT", "I", "CSV"):                                       # IOUtil.assertFileIsReadable (L75-77)
+        if not os.path.isfile(o[k]):
+            raise CliError(f"IsoformMatrix: {k}={o[k]}: no such file")
+    opt = {k: o.get(k, d) for k, (_f, _kind, d) in IM_OPTIONS.items()}
+    if opt["METHOD"] != "STRICT":                                          # L84-87: logged, exit 0, nothing written
+        print(f"\tIsoform method: [{opt['METHOD']}] not allowed, only STRICT method allowed (SCORE disabled)", file=sys.stderr)
+        return 0
+    if not os.path.isdir(opt["OUTDIR"]):
+        raise CliError(f"IsoformMatrix: OUTDIR={opt['OUTDIR']}: no such directory")
+    if opt["DELTA"] < 0:
+        raise CliError(f"IsoformMatrix: DELTA {opt['DELTA']} must be 0 or more")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise CliError("IsoformMatrix runs in one process on one GPU in this build: start it without torchrun")
+    cfg = {f: opt[k] for k, (f, _kind, _d) in IM_OPTIONS.items() if f is not None}
+    jb = lambda b: "true" if b else "false"  # noqa: E731 -- Java's boolean text
+    params = [("INPUT", o["I"]), ("REFFLAT", o["REFFLAT"]), ("CSV", o["CSV"]), ("DELTA", opt["DELTA"]), ("METHOD", opt["METHOD"]),
+              ("CELLTAG", opt["CELLTAG"]), ("UMITAG", opt["UMITAG"]), ("GENETAG", opt["GENETAG"]), ("MAXCLIP", opt["MAXCLIP"]),
+              ("AMBIGUOUS_ASSIGN", jb(opt["AMBIGUOUS_ASSIGN"])), ("MAPQV0", jb(opt["MAPQV0"]))]
+    from .isoformmatrix import isoform_matrix
+    ctx = _context()
+    info = isoform_matrix(ctx, o["I"], o["REFFLAT"], o["CSV"], opt["OUTDIR"], prefix=opt["PREFIX"], n_threads=_ncpu({}), log_params=params,
+                          isobam=opt["ISOBAM"], **cfg)
+    print(f"DONE -- {info['molecules']} molecules, {info['matrix_isoforms']} isoform rows, {info['cells']} cells", file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
@@ -570,7 +619,9 @@ def main(argv=None):
             return tagbamwithread(rest)
         if sub == "ComputeConsensus":
             return computeconsensus(rest)
-        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread and ComputeConsensus (mergestats, parseillumina: "
+        if sub == "IsoformMatrix":
+            return isoformmatrix(rest)
+        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus and IsoformMatrix (mergestats, parseillumina: "
                        "SURVEY 2, out of scope)")
     except CliError as e:
         print(f"ERROR: {e}", file=sys.stderr)

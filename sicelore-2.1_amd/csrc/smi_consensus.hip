@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "smi_internal.h"
+#include "smi_longread.h"
 
 namespace smi {
 namespace {
@@ -714,59 +715,15 @@ struct Parsed {
     std::string err;
 };
 
-struct Aux {
-    const uint8_t *p = nullptr;  // the field (tag, type, value)
-    size_t n = 0;
-};
-
-int aux_size(const uint8_t *p, const uint8_t *end, size_t *n) {
-    if (end - p < 3) return -1;
-    const uint8_t t = p[2];
-    switch (t) {
-        case 'A': case 'c': case 'C': *n = 4; break;
-        case 's': case 'S': *n = 5; break;
-        case 'i': case 'I': case 'f': *n = 7; break;
-        case 'Z': case 'H': {
-            const uint8_t *z = (const uint8_t *)std::memchr(p + 3, 0, end - p - 3);
-            if (!z) return -1;
-            *n = (size_t)(z - p) + 1;
-            break;
-        }
-        case 'B': {
-            if (end - p < 8) return -1;
-            size_t w;
-            switch (p[3]) {
-                case 'c': case 'C': w = 1; break;
-                case 's': case 'S': w = 2; break;
-                case 'i': case 'I': case 'f': w = 4; break;
-                default: return -1;
-            }
-            uint32_t cnt;
-            std::memcpy(&cnt, p + 4, 4);
-            *n = 8 + w * cnt;
-            break;
-        }
-        default: return -1;
-    }
-    return p + *n <= end ? 0 : -1;
-}
-
-bool float_less(float a, float b) {  // Float.compare(a, b) < 0
-    if (a < b) return true;
-    if (a > b) return false;
-    auto bits = [](float x) {
-        int32_t i;
-        if (x != x) return (int32_t)0x7fc00000;
-        std::memcpy(&i, &x, 4);
-        return i;
-    };
-    return bits(a) < bits(b);
-}
+using lr::Aux;
+using lr::aux_size;
+using lr::float_less;
+using lr::tag16;
+using lr::valid_tag;
 
 struct TagSet {
     uint16_t cell, umi, gene, te, ps, cs, us, rn, de, df;
 };
-uint16_t tag16(const char *t) { return (uint16_t)((uint8_t)t[0] | (uint8_t)t[1] << 8); }
 
 void parse_record(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg, const smi_consensus_config &cfg, Parsed &out) {
     out.name = std::string_view((const char *)bam + r.name_off, r.l_read_name ? r.l_read_name - 1 : 0);
@@ -807,16 +764,7 @@ void parse_record(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg,
         return true;
     };
     auto integer = [&](const Aux &a, int64_t &v) {  // (Integer) getAttribute: htsjdk boxes c C s S i, and I up to 2^31 - 1, as Integer
-        if (!a.p) return true;
-        const uint8_t *q = a.p + 3;
-        switch (a.p[2]) {
-            case 'c': v = (int8_t)q[0]; return true;
-            case 'C': v = q[0]; return true;
-            case 's': { int16_t x; std::memcpy(&x, q, 2); v = x; return true; }
-            case 'S': { uint16_t x; std::memcpy(&x, q, 2); v = x; return true; }
-            case 'i': { int32_t x; std::memcpy(&x, q, 4); v = x; return true; }
-            case 'I': { uint32_t x; std::memcpy(&x, q, 4); v = x; if (x <= 0x7fffffffu) return true; break; }
-        }
+        if (!a.p || lr::aux_integer(a, v)) return true;
         bad(a);
         return false;
     };
@@ -857,8 +805,7 @@ void parse_record(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg,
     uint32_t c0, c1;
     std::memcpy(&c0, bam + r.cigar_off, 4);
     std::memcpy(&c1, bam + r.cigar_off + 4 * ((size_t)r.n_cigar - 1), 4);
-    auto clip = [&](uint32_t c) { return ((c & 15) == 4 || (c & 15) == 5) && (int64_t)(c >> 4) > (int64_t)cfg.max_clip; };
-    if (clip(c0) || clip(c1)) {  // L108-112
+    if (lr::chimeric(c0, c1, cfg.max_clip)) {  // L108-112
         out.what = kChimeric;
         return;
     }
@@ -897,8 +844,6 @@ void parse_record(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg,
     }
     out.what = kKept;
 }
-
-int valid_tag(const char *t) { return t[0] > ' ' && t[0] <= '~' && t[1] > ' ' && t[1] <= '~' && t[2] == 0; }
 
 }  // namespace
 }  // namespace smi

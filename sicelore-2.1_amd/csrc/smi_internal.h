@@ -13,6 +13,13 @@ namespace smi {
 void set_error(const std::string &msg);
 int hip_fail(hipError_t e, const char *what);
 
+// smi_tagbam.hip: K-TAG-ASM over n records already on the device, each record i rewritten with two Z attributes tag_a / tag_b whose payloads
+// are d_text[d_a_start[k] ..+ d_a_len[k]) and d_text[d_b_start[k] ..+ d_b_len[k]) for k = d_entry[i] (k < 0: the record is dropped), under
+// htsjdk's attribute rules -> the records back to back in out (host).  ms (may be NULL): device time added.  Synchronous on s.
+int tag_assemble_z2(hipStream_t s, const uint8_t *d_bam, const smi_bam_record *d_recs, size_t n, const int32_t *d_entry, const uint8_t *d_text,
+                    const uint64_t *d_a_start, const uint32_t *d_a_len, const uint64_t *d_b_start, const uint32_t *d_b_len, const char *tag_a,
+                    const char *tag_b, std::vector<uint8_t> &out, float *ms);
+
 // smi_inflate_host.hip: the host's DEFLATE decoder and CRC-32
 uint32_t host_crc32(uint32_t crc, const uint8_t *p, size_t n);                                   // zlib's crc32()
 int host_inflate_exact(const uint8_t *in, size_t n_in, uint8_t *out, size_t n_out);               // 0 = the stream filled out[0 .. n_out)

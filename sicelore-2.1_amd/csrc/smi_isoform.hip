@@ -1,0 +1,1473 @@
+// smi_isoform.hip -- `IsoformMatrix` (org/ipmc/sicelore/programs/IsoformMatrix.java:L93-160), STRICT method: K-ISO assigns every
+// molecule its transcript on the device, K-MTX counts and renders the three dense matrices; the refFlat model, the cell list, the record
+// parser, the read and molecule grouping and the metrics files are host work.  The rules are DESIGN.md section 8d's; tests/isoformmodel.py
+// implements the same ones.
+//
+// Host, in the reference's order:
+//   model     UCSCRefFlatParser(File) L44-77 over TranscriptRecord.fromRefFlat: exons (start + 1, end), junctions (exon[i-1].end,
+//             exon[i].start); a line whose exon bases sum to 0 is dropped; transcripts grouped by gene (column 0) in file order.  A line of
+//             fewer than 11 fields or with a bad integer ends the reference's parse silently: here it fails the call naming the line.
+//             Keys `txId|geneId` are interned (ids in byte order of the key), so that duplicate lines of one transcript count as one
+//             candidate; select(gene, tx) (L114-125) = the last line of the key.
+//   cells     CellList: one barcode per line, every "-1" removed, duplicates collapse; columns in byte order.
+//   records   LongreadParser.parseSAMRecord over LongreadRecord.fromSAMRecord(r, load_sequence = false) with gene and UMI mandatory:
+//             null / unmapped -> chimeric -> no gene (null, "" or "undef") -> no UMI -> mapq 0 and secondary / supplementary unless
+//             MAPQV0.  The junction list is the literal walk of L120-150 (see walk_junctions).  A cast the reference would fail, a mapped
+//             record without CIGAR or alignment block, or a walk past the last block fails the call with the read's name.
+//   reads     by name in order of the first kept record; barcode, UMI and rn of the last record; genes = union of GENETAG split on ','.
+//   molecules `barcode:umi` in order of their first read; rn of the first read; pctId = 1f - de of the first record of the last read.
+// K-ISO: one wavefront per molecule (setIsoformStrictNew, MoleculeDataset.java L161-236): lanes over (record, transcript) pairs, the
+//   match test of map() per pair, candidate counts per candidate transcript in LDS (in an HBM slice when the molecule has more than
+//   lds_tx transcripts), counts summed per key; best / tie (smallest key) / monoexon / nomatch (most lines, then first gene); then the
+//   molecule's junction set as ids of the table of unique model junctions (a second launch writes them at the scanned offsets).
+// K-MTX: 64-bit (row << 32 | cell) codes per counted molecule; hipcub radix sort + run-length encoding give the UMI counts (a molecule is
+//   one UMI of its cell); the dense rows are rendered in row blocks under a device-memory budget, one wavefront per row: a length pass, a
+//   scan, the write.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <charconv>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <string_view>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+#include "smi_internal.h"
+#include "smi_longread.h"
+
+namespace smi {
+namespace {
+
+constexpr int kIsoWaves = 4;     // waves per block of K-ISO
+constexpr int kLdsTx = 2048;     // candidate counts of one wave held in LDS
+constexpr int kRenderWaves = 4;  // waves per block of the renderer
+
+enum IsoStatus : int32_t { kNone = 0, kMono = 1, kOne = 2, kAmbiguous = 3, kNomatch = 4 };
+
+struct IsoArgs {
+    const int32_t *mol_rec_off;   // n_mol + 1: records of molecule m (reads in order, records in order)
+    const int32_t *rec_j_off;     // n_rec + 1: junctions of record r in rj
+    const int2 *rj;
+    const int32_t *mol_gene_off;  // n_mol + 1: the molecule's model genes, ascending
+    const int32_t *mol_gene;
+    const int32_t *gene_tx_off;   // n_gene + 1: transcripts (refFlat lines) of gene g in file order
+    const int32_t *gene_tx;
+    const int32_t *tx_j_off;      // n_tx + 1: junctions of line t in tj
+    const int2 *tj;
+    const int32_t *tx_key;        // key id of line t (`txId|geneId` in byte order)
+    const int32_t *tx_rep;        // position in its gene's list of the first line of line t's key (duplicate lines count there)
+    const int32_t *gene_u_off;    // n_gene + 1: unique junction ids of gene g, ascending
+    const int32_t *gene_u;
+    const int2 *ujunc;            // the unique model junctions
+    int32_t n_mol, delta, lds_tx;
+    const int64_t *spill_off;     // per molecule: offset of its counts in spill, or -1 (they fit in LDS)
+    int32_t *spill;
+    int32_t *out_key, *out_gene, *out_status, *out_support, *out_njunc;
+    const int64_t *junc_off;      // WRITE: molecule m's junction ids go to junc_out[junc_off[m] ..)
+    int32_t *junc_out;
+};
+
+__device__ __forceinline__ bool near(int2 a, int2 b, int d) { return abs(a.x - b.x) <= d && abs(a.y - b.y) <= d; }
+
+// isIn(j, lst, DELTA) (L309-318)
+__device__ __forceinline__ bool is_in(int2 j, const int2 *__restrict__ lst, int n, int d) {
+    for (int i = 0; i < n; i++)
+        if (near(lst[i], j, d)) return true;
+    return false;
+}
+
+// the j-th candidate transcript of a molecule (genes in order, their lines in file order); *base: the index of its gene's first line
+__device__ __forceinline__ int tx_of(const IsoArgs &a, int g0, int g1, int j, int *base = nullptr) {
+    int b = 0;
+    for (int g = g0; g < g1; g++) {
+        const int gene = a.mol_gene[g];
+        const int n = a.gene_tx_off[gene + 1] - a.gene_tx_off[gene];
+        if (j < n) {
+            if (base) *base = b;
+            return a.gene_tx[a.gene_tx_off[gene] + j];
+        }
+        j -= n;
+        b += n;
+    }
+    return -1;
+}
+
+__device__ __forceinline__ long long wave_max64(long long v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (long long)__shfl_xor(v, o));
+    return v;
+}
+
+// COUNT: the assignment and the size of the junction set; WRITE: the junction set at junc_off
+template <bool WRITE>
+__global__ __launch_bounds__(64 * kIsoWaves) void k_iso(IsoArgs a) {
+    __shared__ int32_t lds_cnt[kIsoWaves][kLdsTx];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int m = blockIdx.x * kIsoWaves + wv;
+    if (m >= a.n_mol) return;
+    const int g0 = a.mol_gene_off[m], g1 = a.mol_gene_off[m + 1];
+    const int r0 = a.mol_rec_off[m], r1 = a.mol_rec_off[m + 1];
+    const int j0 = a.rec_j_off[r0], j1 = a.rec_j_off[r1];  // every junction of every record of the molecule
+    int nT = 0;
+    for (int g = g0; g < g1; g++) nT += a.gene_tx_off[a.mol_gene[g] + 1] - a.gene_tx_off[a.mol_gene[g]];
+    const int d = a.delta;
+    const bool mono = nT == 1 && a.tx_j_off[tx_of(a, g0, g1, 0) + 1] == a.tx_j_off[tx_of(a, g0, g1, 0)];
+    if (!WRITE) {
+        int32_t key = -1, gene = -1, status = kNone, support = 0;
+        if (mono) {
+            const int t = tx_of(a, g0, g1, 0);
+            key = a.tx_key[t];
+            status = kMono;
+            support = 1;
+        } else if (nT > 0) {
+            int32_t *cnt = a.spill_off[m] >= 0 ? a.spill + a.spill_off[m] : lds_cnt[wv];
+            for (int j = lane; j < nT; j += 64) cnt[j] = 0;
+            __threadfence_block();
+            wave_sync();
+            const int nR = r1 - r0;
+            for (long long p = lane; p < (long long)nR * nT; p += 64) {  // map(readJ, refJ, DELTA) per (record, transcript)
+                const int r = r0 + (int)(p / nT), j = (int)(p % nT);
+                int base = 0;
+                const int t = tx_of(a, g0, g1, j, &base);
+                const int nr = a.rec_j_off[r + 1] - a.rec_j_off[r];
+                const int nt = a.tx_j_off[t + 1] - a.tx_j_off[t];
+                if (nt == 0 || nt != nr) continue;
+                const int2 *rl = a.rj + a.rec_j_off[r];
+                const int2 *tl = a.tj + a.tx_j_off[t];
+                bool ok = true;
+                for (int k = 0; k < nt && ok; k++) ok = is_in(tl[k], rl, nr, d);
+                if (ok) atomicAdd(&cnt[base + a.tx_rep[t]], 1);  // counted per key: at the key's first line
+            }
+            __threadfence_block();
+            wave_sync();
+            // one entry per key (at its first line); best = the highest count, then the smallest key
+            long long best = -1;
+            for (int j = lane; j < nT; j += 64)
+                if (cnt[j] > 0) best = max(best, (long long)cnt[j] << 32 | (long long)(0x7fffffff - a.tx_key[tx_of(a, g0, g1, j)]));
+            best = wave_max64(best);
+            if (best > 0) {
+                const int bk = 0x7fffffff - (int)(best & 0xffffffff), btot = (int)(best >> 32);
+                int tied = 0;
+                for (int j = lane; j < nT; j += 64) tied += cnt[j] == btot;
+                for (int o = 32; o > 0; o >>= 1) tied += __shfl_xor(tied, o);
+                key = bk;
+                support = btot;
+                status = tied > 1 ? kAmbiguous : kOne;
+            } else {  // getGeneIdForMostComplexTranscript: the gene of the most lines, the first gene on a tie
+                status = kNomatch;
+                int bn = -1;
+                for (int g = g0; g < g1; g++) {
+                    const int n = a.gene_tx_off[a.mol_gene[g] + 1] - a.gene_tx_off[a.mol_gene[g]];
+                    if (n > bn) {
+                        bn = n;
+                        gene = a.mol_gene[g];
+                    }
+                }
+            }
+        }
+        if (lane == 0) {
+            a.out_key[m] = key;
+            a.out_gene[m] = gene;
+            a.out_status[m] = status;
+            a.out_support[m] = support;
+        }
+    }
+    // the junction set (map() L291-296 for every (record, transcript) pair): every unique junction of the candidate genes that is isIn
+    // some junction of some record; none for a monoexon molecule (the match loop does not run)
+    int n_out = 0;
+    if (!mono) {
+        for (int g = g0; g < g1; g++) {
+            const int gene = a.mol_gene[g];
+            const int u0 = a.gene_u_off[gene], u1 = a.gene_u_off[gene + 1];
+            for (int base = u0; base < u1; base += 64) {
+                const int ui = base + lane;
+                bool keep = false;
+                int u = -1;
+                if (ui < u1) {
+                    u = a.gene_u[ui];
+                    keep = is_in(a.ujunc[u], a.rj + j0, j1 - j0, d);
+                    for (int h = g0; h < g && keep; h++) {  // already taken from an earlier gene of the molecule
+                        const int og = a.mol_gene[h];
+                        int lo = a.gene_u_off[og], hi = a.gene_u_off[og + 1];
+                        while (lo < hi) {
+                            const int mid = (lo + hi) >> 1;
+                            if (a.gene_u[mid] < u) lo = mid + 1;
+                            else hi = mid;
+                        }
+                        if (lo < a.gene_u_off[og + 1] && a.gene_u[lo] == u) keep = false;
+                    }
+                }
+                const unsigned long long bal = __ballot(keep);
+                if (WRITE && keep) {
+                    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+                    a.junc_out[a.junc_off[m] + n_out + before] = u;
+                }
+                n_out += __popcll(bal);
+            }
+        }
+    }
+    if (!WRITE && lane == 0) a.out_njunc[m] = n_out;
+}
+
+// ---- K-MTX renderer ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int digits(uint32_t v) {
+    int n = 1;
+    while (v >= 10) {
+        v /= 10;
+        n++;
+    }
+    return n;
+}
+
+// dense[(row - r0) * nc + cell] = count, for the runs of rows r0 ..
+__global__ void k_mtx_scatter(const uint64_t *__restrict__ code, const uint32_t *__restrict__ cnt, int64_t k0, int64_t k1, int32_t r0, int32_t nc,
+                              uint32_t *__restrict__ dense) {
+    const int64_t k = k0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (k >= k1) return;
+    const uint64_t c = code[k];
+    dense[(int64_t)((int32_t)(c >> 32) - r0) * nc + (uint32_t)c] = cnt[k];
+}
+
+// LEN: bytes of row r0 + i (label, "\t" + count per cell, "\n") into len[i]; WRITE: the row at off[i]
+template <bool WRITE>
+__global__ __launch_bounds__(64 * kRenderWaves) void k_mtx_render(const uint32_t *__restrict__ dense, int32_t n_rows, int32_t nc, int32_t r0,
+                                                                   const uint8_t *__restrict__ labels, const uint64_t *__restrict__ lab_off,
+                                                                   uint64_t *__restrict__ len, uint8_t *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
+    if (i >= n_rows) return;
+    const uint32_t *row = dense + (int64_t)i * nc;
+    const uint64_t l0 = lab_off[r0 + i], ln = lab_off[r0 + i + 1] - l0;
+    if (!WRITE) {
+        uint64_t n = 0;
+        for (int c = lane; c < nc; c += 64) n += 1 + digits(row[c]);
+        for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+        if (lane == 0) len[i] = n + ln + 1;
+        return;
+    }
+    uint8_t *dst = out + len[i];  // (the exclusive scan of the lengths)
+    for (uint64_t k = lane; k < ln; k += 64) dst[k] = labels[l0 + k];
+    uint64_t pos = ln;
+    for (int c0 = 0; c0 < nc; c0 += 64) {
+        const int c = c0 + lane;
+        const uint32_t v = c < nc ? row[c] : 0;
+        const int w = c < nc ? 1 + digits(v) : 0;
+        int incl = w;  // inclusive prefix sum across the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(incl, o);
+            if (lane >= o) incl += y;
+        }
+        if (c < nc) {
+            uint8_t *p = dst + pos + (incl - w);
+            p[0] = '\t';
+            uint32_t x = v;
+            for (int k = w - 1; k >= 1; k--) {
+                p[k] = (uint8_t)('0' + x % 10);
+                x /= 10;
+            }
+        }
+        pos += __shfl(incl, 63);
+    }
+    if (lane == 0) dst[pos] = '\n';
+}
+
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t n) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        if (hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
+            set_error("IsoformMatrix: device allocation of " + std::to_string(n * sizeof(T)) + " bytes failed");
+            return SMI_ERR_HIP;
+        }
+        return SMI_OK;
+    }
+    int put(const std::vector<T> &v, hipStream_t s) {
+        if (int rc = alloc(v.size())) return rc;
+        if (!v.empty()) SMI_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
+        return SMI_OK;
+    }
+};
+
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    int begin(hipStream_t s) {
+        if (!a) SMI_HIP(hipEventCreate(&a));
+        if (!b) SMI_HIP(hipEventCreate(&b));
+        SMI_HIP(hipEventRecord(a, s));
+        return SMI_OK;
+    }
+    int end(hipStream_t s, float *acc) {
+        SMI_HIP(hipEventRecord(b, s));
+        SMI_HIP(hipEventSynchronize(b));
+        float ms = 0.f;
+        SMI_HIP(hipEventElapsedTime(&ms, a, b));
+        *acc += ms;
+        return SMI_OK;
+    }
+};
+
+// ---- host parsing -----------------------------------------------------------------------------------------------------------------------
+using lr::Aux;
+
+std::string drop_minus1(std::string_view v) {  // String.replace("-1", ""): every occurrence, left to right
+    std::string s(v);
+    for (size_t k = s.find("-1"); k != std::string::npos; k = s.find("-1", k)) s.erase(k, 2);
+    return s;
+}
+
+// Java's String.split(regex) for a one-character separator: trailing empty strings removed
+std::vector<std::string_view> jsplit(std::string_view s, char sep) {
+    std::vector<std::string_view> out;
+    size_t b = 0;
+    for (size_t i = 0; i <= s.size(); i++)
+        if (i == s.size() || s[i] == sep) {
+            out.push_back(s.substr(b, i - b));
+            b = i + 1;
+        }
+    while (!out.empty() && out.back().empty()) out.pop_back();
+    if (s.empty()) out.assign(1, std::string_view());  // "".split(x) = [""]
+    return out;
+}
+
+// Integer.valueOf
+bool jint(std::string_view s, int32_t &v) {
+    if (s.empty()) return false;
+    size_t i = 0;
+    bool neg = false;
+    if (s[0] == '-' || s[0] == '+') {
+        neg = s[0] == '-';
+        i = 1;
+        if (s.size() == 1) return false;
+    }
+    int64_t x = 0;
+    for (; i < s.size(); i++) {
+        if (s[i] < '0' || s[i] > '9') return false;
+        x = x * 10 + (s[i] - '0');
+        if (x > 2147483648ll) return false;
+    }
+    if (neg) x = -x;
+    if (x > 2147483647ll || x < -2147483648ll) return false;
+    v = (int32_t)x;
+    return true;
+}
+
+// LongreadRecord.fromSAMRecord L120-150, literally: the walk over cigar.replaceAll("[0-9]+[IS]", "") split into cigartype ("[0-9]+") and
+// cigarsize ("[A-Z]"); cigartype[i] is the operation BEFORE cigarsize[i], so the last operation is never looked at.  false: the reference
+// throws (no block, a block index past the end, a size that is no integer)
+bool walk_junctions(const uint8_t *bam, const smi_bam_record &r, std::vector<int2> &out) {
+    static const char ops[] = "MIDNSHP=XBBBBBBB";
+    std::string cig;
+    struct Block {
+        int64_t start, len;
+    };
+    std::vector<Block> blocks;  // AlignmentBlocks: M = X
+    int64_t ref = (int64_t)r.pos + 1;
+    for (int k = 0; k < r.n_cigar; k++) {
+        uint32_t c;
+        std::memcpy(&c, bam + r.cigar_off + 4ull * k, 4);
+        const uint32_t op = c & 15, n = c >> 4;
+        if (op == 0 || op == 7 || op == 8) {
+            blocks.push_back({ref, n});
+            ref += n;
+        } else if (op == 2 || op == 3) {
+            ref += n;
+        }
+        if (op == 1 || op == 4) continue;  // replaceAll("[0-9]+[IS]", "")
+        cig += std::to_string(n);
+        cig += ops[op];
+    }
+    if (blocks.empty()) return false;
+    std::vector<std::string_view> type, size;  // cigar.split("[0-9]+"), cigar.split("[A-Z]")
+    {
+        std::string_view s(cig);
+        size_t i = 0;
+        type.push_back(std::string_view());  // the digits at position 0 give a leading ""
+        while (i < s.size()) {
+            while (i < s.size() && s[i] >= '0' && s[i] <= '9') i++;
+            const size_t b = i;
+            while (i < s.size() && !(s[i] >= '0' && s[i] <= '9')) i++;
+            if (i > b) type.push_back(s.substr(b, i - b));
+        }
+        if (s.empty()) type.assign(1, std::string_view());
+        size_t b = 0;
+        for (size_t k = 0; k <= s.size(); k++)
+            if (k == s.size() || (s[k] >= 'A' && s[k] <= 'Z')) {
+                size.push_back(s.substr(b, k - b));
+                b = k + 1;
+            }
+        while (!size.empty() && size.back().empty()) size.pop_back();
+        if (s.empty()) size.assign(1, std::string_view());
+    }
+    int64_t s = blocks[0].start, e = blocks[0].start;
+    std::vector<int64_t> xs, xe;
+    size_t bi = 0;
+    for (size_t i = 0; i < size.size(); i++) {
+        if (bi >= blocks.size() || i >= type.size()) return false;
+        const Block cur = blocks[bi];
+        const std::string_view t = type[i];
+        if (t == "M") bi++;
+        if (t == "N") {
+            xs.push_back(s);
+            xe.push_back(e);
+            s = cur.start;
+        } else if (t == "D") {
+            int32_t len;
+            if (i == 0 || !jint(size[i - 1], len)) return false;
+            if (len > 20) {  // a short intron minimap2 calls a deletion
+                xs.push_back(s);
+                xe.push_back(e);
+                s = cur.start;
+            }
+        }
+        if (t != "D") e = cur.start + cur.len - 1;
+    }
+    xs.push_back(s);
+    xe.push_back(e);
+    out.clear();
+    for (size_t i = 1; i < xs.size(); i++) out.push_back(make_int2((int)xe[i - 1], (int)xs[i]));
+    return true;
+}
+
+enum Outcome : uint8_t { kKept, kNull, kChimeric, kNoGene, kNoUmi, kMapq0, kError };
+
+struct Parsed {
+    Outcome what = kError;
+    float de = 1.0f;
+    int32_t rn = 1;
+    std::string_view name, bc, umi, gene;
+    std::vector<int2> junc;
+    std::string err;
+};
+
+struct TagSet {
+    uint16_t cell, umi, gene, rn, de, df;
+};
+
+void parse_record(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg, const smi_isoform_config &cfg, Parsed &out) {
+    out.name = std::string_view((const char *)bam + r.name_off, r.l_read_name ? r.l_read_name - 1 : 0);
+    const uint8_t *p = bam + r.aux_off, *end = p + r.aux_len;
+    Aux cell, umi, gene, rn, de, df;
+    while (p < end) {
+        size_t n;
+        if (lr::aux_size(p, end, &n)) {
+            out.what = kError;
+            out.err = "malformed attributes";
+            return;
+        }
+        const uint16_t t = (uint16_t)(p[0] | p[1] << 8);
+        const Aux a{p, n};
+        if (t == tg.cell) cell = a;  // (a repeated tag keeps its last value, as htsjdk reads it)
+        if (t == tg.umi) umi = a;
+        if (t == tg.gene) gene = a;
+        if (t == tg.rn) rn = a;
+        if (t == tg.de) de = a;
+        if (t == tg.df) df = a;
+        p += n;
+    }
+    auto bad = [&](const Aux &a) {
+        out.what = kError;
+        out.err = std::string("attribute ") + (char)a.p[0] + (char)a.p[1] + " of type " + (char)a.p[2] + " is not the type IsoformMatrix reads";
+    };
+    auto zstr = [&](const Aux &a, std::string_view &v) {
+        if (!a.p) return true;
+        if (a.p[2] != 'Z') {
+            bad(a);
+            return false;
+        }
+        v = std::string_view((const char *)a.p + 3, a.n - 4);
+        return true;
+    };
+    if (!zstr(gene, out.gene) || !zstr(cell, out.bc) || !zstr(umi, out.umi)) return;  // L75-77
+    if (!cell.p || (r.flag & 4)) {
+        out.what = kNull;
+        return;
+    }
+    for (const Aux *a : {&de, &df}) {  // L92-94: de, else df, else 1
+        if (!a->p) continue;
+        if (a->p[2] != 'f') {
+            bad(*a);
+            return;
+        }
+        std::memcpy(&out.de, a->p + 3, 4);
+        break;
+    }
+    int64_t iv = 1;
+    if (rn.p && !lr::aux_integer(rn, iv)) {  // L95
+        bad(rn);
+        return;
+    }
+    out.rn = (int32_t)iv;
+    if (r.n_cigar == 0) {
+        out.what = kError;
+        out.err = "no CIGAR";
+        return;
+    }
+    uint32_t c0, c1;
+    std::memcpy(&c0, bam + r.cigar_off, 4);
+    std::memcpy(&c1, bam + r.cigar_off + 4 * ((size_t)r.n_cigar - 1), 4);
+    const bool chim = lr::chimeric(c0, c1, cfg.max_clip);  // L108-112
+    if (!walk_junctions(bam, r, out.junc)) {                // (the walk runs for chimeric records too)
+        out.what = kError;
+        out.err = "the CIGAR walk runs past the alignment blocks";
+        return;
+    }
+    if (chim) {
+        out.what = kChimeric;
+        return;
+    }
+    if (!gene.p || out.gene.empty() || out.gene == "undef") {  // LongreadParser L101
+        out.what = kNoGene;
+        return;
+    }
+    if (!umi.p) {
+        out.what = kNoUmi;
+        return;
+    }
+    if (!cfg.mapqv0 && r.mapq == 0 && (r.flag & 0x900)) {
+        out.what = kMapq0;
+        return;
+    }
+    out.what = kKept;
+}
+
+// Float.toString: the shortest decimal that reads back as the float; d.ddd in [1e-3, 1e7), else d.dddE<exp>
+std::string java_float(float x) {
+    if (std::isnan(x)) return "NaN";
+    if (std::isinf(x)) return x > 0 ? "Infinity" : "-Infinity";
+    if (x == 0) return std::signbit(x) ? "-0.0" : "0.0";
+    char buf[64];
+    auto r = std::to_chars(buf, buf + sizeof(buf), x, std::chars_format::scientific);
+    std::string sci(buf, r.ptr);
+    std::string sign;
+    if (sci[0] == '-') {
+        sign = "-";
+        sci.erase(0, 1);
+    }
+    const size_t ep = sci.find('e');
+    const int exp = std::stoi(sci.substr(ep + 1));
+    std::string dig;
+    for (size_t i = 0; i < ep; i++)
+        if (sci[i] != '.') dig += sci[i];
+    const float ax = std::fabs(x);
+    std::string out;
+    if (ax >= 1e-3f && ax < 1e7f) {
+        if (exp >= 0) {
+            std::string ip = dig.substr(0, std::min<size_t>(dig.size(), exp + 1));
+            while ((int)ip.size() < exp + 1) ip += '0';
+            std::string fp = (int)dig.size() > exp + 1 ? dig.substr(exp + 1) : "0";
+            out = ip + "." + fp;
+        } else {
+            out = "0." + std::string(-exp - 1, '0') + dig;
+        }
+    } else {
+        out = dig.substr(0, 1) + "." + (dig.size() > 1 ? dig.substr(1) : "0") + "E" + std::to_string(exp);
+    }
+    return sign + out;
+}
+
+struct Model {
+    std::vector<std::string> genes;             // model genes in order of their first line
+    std::unordered_map<std::string, int32_t> gene_id;
+    std::vector<int32_t> tx_gene, tx_key, tx_rep, tx_nexon, tx_j_off{0};
+    std::vector<int2> tj;
+    std::vector<int32_t> gene_tx_off, gene_tx;  // CSR
+    std::vector<std::string> key_tx, key_gene;  // per key id (byte order of txId|geneId)
+    std::vector<int32_t> key_nexon;             // select(gene, tx): the last line of the key
+    std::vector<int2> ujunc;                    // unique (start, end), ascending
+    std::vector<int32_t> gene_u_off, gene_u;
+    int64_t n_lines = 0;
+};
+
+int parse_model(const char *text, size_t n, Model &M) {
+    std::vector<std::string> line_tx;
+    std::unordered_map<std::string, int32_t> key_of;
+    std::vector<std::string> key_str;
+    std::vector<int32_t> line_key;
+    std::vector<int32_t> line_gene;
+    size_t b = 0;
+    int64_t lineno = 0;
+    std::vector<std::vector<int32_t>> by_gene;
+    while (b < n) {
+        size_t e = b;
+        while (e < n && text[e] != '\n') e++;
+        std::string_view line(text + b, e - b);
+        if (!line.empty() && line.back() == '\r') line.remove_suffix(1);  // BufferedReader.readLine
+        b = e + 1;
+        lineno++;
+        auto f = jsplit(line, '\t');
+        auto fail = [&](const std::string &why) {
+            set_error("IsoformMatrix: REFFLAT line " + std::to_string(lineno) + ": " + why);
+            return SMI_ERR_INVALID;
+        };
+        if (f.size() < 11) return fail("has " + std::to_string(f.size()) + " fields, at least 11 are needed");
+        int32_t v;
+        for (int k = 4; k <= 8; k++)
+            if (!jint(f[k], v)) return fail("field " + std::to_string(k + 1) + " is not an integer");
+        std::vector<int32_t> xs, xe;
+        for (int k = 9; k <= 10; k++) {
+            std::string_view s = f[k];
+            while (!s.empty() && s.back() == ',') s.remove_suffix(1);  // StringUtils.stripEnd(str, ",")
+            for (auto t : jsplit(s, ',')) {
+                if (!jint(t, v)) return fail("field " + std::to_string(k + 1) + " is not a list of integers");
+                (k == 9 ? xs : xe).push_back(v);
+            }
+        }
+        if (xe.size() < xs.size()) return fail("fewer exon ends than exon starts");
+        int64_t bases = 0;
+        for (size_t i = 0; i < xs.size(); i++) bases += (int64_t)xe[i] - xs[i];
+        if ((int32_t)bases == 0) continue;  // parseLine: getExonBases() == 0 -> dropped (int arithmetic)
+        M.n_lines++;
+        const std::string gname(f[0]);
+        auto git = M.gene_id.emplace(gname, (int32_t)M.genes.size());
+        if (git.second) {
+            M.genes.push_back(gname);
+            by_gene.emplace_back();
+        }
+        const int32_t t = (int32_t)M.tx_gene.size();
+        M.tx_gene.push_back(git.first->second);
+        by_gene[git.first->second].push_back(t);
+        M.tx_nexon.push_back((int32_t)xs.size());
+        for (size_t i = 1; i < xs.size(); i++) M.tj.push_back(make_int2(xe[i - 1], xs[i] + 1));
+        M.tx_j_off.push_back((int32_t)M.tj.size());
+        std::string key = std::string(f[1]) + "|" + gname;
+        auto kit = key_of.emplace(key, (int32_t)key_str.size());
+        if (kit.second) {
+            key_str.push_back(key);
+            line_tx.push_back(std::string(f[1]));
+            line_gene.push_back(git.first->second);
+        }
+        line_key.push_back(kit.first->second);
+    }
+    // key ids in byte order of the key
+    std::vector<int32_t> ord(key_str.size()), rank(key_str.size());
+    for (size_t i = 0; i < ord.size(); i++) ord[i] = (int32_t)i;
+    std::sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return key_str[x] < key_str[y]; });
+    M.key_tx.resize(ord.size());
+    M.key_gene.resize(ord.size());
+    M.key_nexon.assign(ord.size(), 0);
+    for (size_t i = 0; i < ord.size(); i++) {
+        rank[ord[i]] = (int32_t)i;
+        M.key_tx[i] = line_tx[ord[i]];
+        M.key_gene[i] = M.genes[line_gene[ord[i]]];
+    }
+    M.tx_key.resize(line_key.size());
+    for (size_t t = 0; t < line_key.size(); t++) {
+        M.tx_key[t] = rank[line_key[t]];
+        M.key_nexon[M.tx_key[t]] = M.tx_nexon[t];  // the last line wins
+    }
+    M.gene_tx_off.assign(1, 0);
+    M.tx_rep.assign(M.tx_key.size(), 0);
+    for (auto &l : by_gene) {
+        M.gene_tx.insert(M.gene_tx.end(), l.begin(), l.end());
+        M.gene_tx_off.push_back((int32_t)M.gene_tx.size());
+        for (size_t i = 0; i < l.size(); i++) {  // a key's lines are all in one gene (the key holds the gene)
+            size_t f = 0;
+            while (M.tx_key[l[f]] != M.tx_key[l[i]]) f++;
+            M.tx_rep[l[i]] = (int32_t)f;
+        }
+    }
+    // unique junctions and per gene the ascending ids of its junctions
+    M.ujunc = M.tj;
+    auto lt = [](int2 x, int2 y) { return x.x != y.x ? x.x < y.x : x.y < y.y; };
+    std::sort(M.ujunc.begin(), M.ujunc.end(), lt);
+    M.ujunc.erase(std::unique(M.ujunc.begin(), M.ujunc.end(), [](int2 x, int2 y) { return x.x == y.x && x.y == y.y; }), M.ujunc.end());
+    M.gene_u_off.assign(1, 0);
+    for (auto &l : by_gene) {
+        std::vector<int32_t> u;
+        for (int32_t t : l)
+            for (int32_t k = M.tx_j_off[t]; k < M.tx_j_off[t + 1]; k++)
+                u.push_back((int32_t)(std::lower_bound(M.ujunc.begin(), M.ujunc.end(), M.tj[k], lt) - M.ujunc.begin()));
+        std::sort(u.begin(), u.end());
+        u.erase(std::unique(u.begin(), u.end()), u.end());
+        M.gene_u.insert(M.gene_u.end(), u.begin(), u.end());
+        M.gene_u_off.push_back((int32_t)M.gene_u.size());
+    }
+    return SMI_OK;
+}
+
+}  // namespace
+}  // namespace smi
+
+using namespace smi;
+
+struct smi_isoform {
+    smi_ctx *ctx = nullptr;
+    smi_isoform_config cfg = {};
+    TagSet tags = {};
+    Model M;
+    std::vector<std::string> cells;  // byte order
+    std::unordered_map<std::string, int32_t> cell_id;
+    // kept records in file order
+    std::string text;
+    std::vector<uint64_t> name_off, bc_off, umi_off, gene_off;
+    std::vector<uint32_t> name_len, bc_len, umi_len, gene_len;
+    std::vector<float> de;
+    std::vector<int32_t> rn, rj_off{0};
+    std::vector<int2> rj;
+    int64_t counts[SMI_ISOFORM_COUNTS] = {};
+    std::string out[SMI_ISOFORM_OUTPUTS];
+    bool ran = false;
+    // ISOBAM: molecules by `barcode:umi`, entry 0 = undef / undef, entry m + 1 = molecule m's IG / IT in iso_text
+    std::unordered_map<std::string, int32_t> mol_by_key;
+    std::vector<uint8_t> iso_text;
+    std::vector<uint64_t> ig_start, it_start;
+    std::vector<uint32_t> ig_len, it_len;
+    uint8_t *d_iso_text = nullptr;
+    uint64_t *d_ig_start = nullptr, *d_it_start = nullptr;
+    uint32_t *d_ig_len = nullptr, *d_it_len = nullptr;
+    std::vector<uint8_t> isobam;  // the last segment's records
+    const uint8_t *last_bam = nullptr;
+    const smi_bam_record *last_recs = nullptr;
+    int32_t last_n = -1;
+    float isobam_ms = 0.f;
+    ~smi_isoform() {
+        for (void *p : {(void *)d_iso_text, (void *)d_ig_start, (void *)d_it_start, (void *)d_ig_len, (void *)d_it_len})
+            if (p) (void)hipFree(p);
+    }
+};
+
+extern "C" int smi_isoform_default_config(smi_isoform_config *cfg) {
+    if (!cfg) {
+        set_error("smi_isoform_default_config: null argument");
+        return SMI_ERR_INVALID;
+    }
+    *cfg = {};
+    std::memcpy(cfg->cell_tag, "BC", 3);
+    std::memcpy(cfg->umi_tag, "U8", 3);
+    std::memcpy(cfg->gene_tag, "GE", 3);
+    std::memcpy(cfg->rn_tag, "RN", 3);
+    cfg->max_clip = 150;
+    cfg->mapqv0 = 0;
+    cfg->delta = 2;
+    cfg->to_bulk = 0;
+    cfg->n_threads = 20;
+    cfg->lds_tx = kLdsTx;
+    cfg->budget_bytes = 0;
+    return SMI_OK;
+}
+
+extern "C" int smi_isoform_create(smi_ctx *ctx, const smi_isoform_config *cfg, const char *refflat, size_t n_refflat, const char *csv, size_t n_csv,
+                                  smi_isoform **out) {
+    if (!ctx || !cfg || !out || (n_refflat && !refflat) || (n_csv && !csv)) {
+        set_error("smi_isoform_create: null argument");
+        return SMI_ERR_INVALID;
+    }
+    *out = nullptr;
+    const char *tags[] = {cfg->cell_tag, cfg->umi_tag, cfg->gene_tag, cfg->rn_tag};
+    const char *what[] = {"CELLTAG", "UMITAG", "GENETAG", "RNTAG"};
+    for (int i = 0; i < 4; i++)
+        if (!lr::valid_tag(tags[i])) {
+            set_error(std::string(what[i]) + " must be two characters");
+            return SMI_ERR_INVALID;
+        }
+    if (cfg->delta < 0) {
+        set_error("DELTA must be 0 or more");
+        return SMI_ERR_INVALID;
+    }
+    if (cfg->lds_tx < 1 || cfg->lds_tx > kLdsTx) {
+        set_error("smi_isoform_config.lds_tx must be 1 .. " + std::to_string(kLdsTx));
+        return SMI_ERR_INVALID;
+    }
+    smi_isoform *h = new smi_isoform();
+    h->ctx = ctx;
+    h->cfg = *cfg;
+    h->cfg.n_threads = std::max(1, std::min(cfg->n_threads, 256));
+    h->tags = TagSet{lr::tag16(cfg->cell_tag), lr::tag16(cfg->umi_tag), lr::tag16(cfg->gene_tag), lr::tag16(cfg->rn_tag), lr::tag16("de"),
+                     lr::tag16("df")};
+    if (int rc = parse_model(refflat, n_refflat, h->M)) {
+        delete h;
+        return rc;
+    }
+    // CellList: every line (readLine: \n, \r\n or \r) with "-1" removed
+    std::vector<std::string> cells;
+    size_t b = 0;
+    while (b < n_csv) {
+        size_t e = b;
+        while (e < n_csv && csv[e] != '\n' && csv[e] != '\r') e++;
+        cells.push_back(drop_minus1(std::string_view(csv + b, e - b)));
+        if (e < n_csv && csv[e] == '\r' && e + 1 < n_csv && csv[e + 1] == '\n') e++;
+        b = e + 1;
+    }
+    std::sort(cells.begin(), cells.end());
+    cells.erase(std::unique(cells.begin(), cells.end()), cells.end());
+    h->cells = std::move(cells);
+    for (size_t i = 0; i < h->cells.size(); i++) h->cell_id.emplace(h->cells[i], (int32_t)i);
+    h->counts[SMI_ISO_GENES] = (int64_t)h->M.genes.size();
+    h->counts[SMI_ISO_TRANSCRIPTS] = h->M.n_lines;
+    h->counts[SMI_ISO_CELLS] = (int64_t)h->cells.size();
+    *out = h;
+    return SMI_OK;
+}
+
+extern "C" int smi_isoform_free(smi_isoform *h) {
+    delete h;
+    return SMI_OK;
+}
+
+extern "C" int smi_isoform_add_segment(smi_isoform *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n) {
+    if (!h || n < 0 || (n && (!bam || !recs))) {
+        set_error("smi_isoform_add_segment: null argument");
+        return SMI_ERR_INVALID;
+    }
+    if (h->ran) {
+        set_error("smi_isoform_add_segment: the matrices were already built (smi_isoform_run)");
+        return SMI_ERR_STATE;
+    }
+    for (int32_t i = 0; i < n; i++) {
+        const smi_bam_record &r = recs[i];
+        if (r.name_off + r.l_read_name > n_bam || r.cigar_off + 4ull * r.n_cigar > n_bam || r.aux_off + r.aux_len > n_bam) {
+            set_error("smi_isoform_add_segment: record " + std::to_string(i) + " lies outside the segment");
+            return SMI_ERR_INVALID;
+        }
+    }
+    std::vector<Parsed> parsed(n);
+    const int nt = std::max(1, std::min<int>(h->cfg.n_threads, (n + 4095) / 4096));
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; t++)
+        th.emplace_back([&, t] {
+            for (int32_t i = (int32_t)((int64_t)n * t / nt); i < (int32_t)((int64_t)n * (t + 1) / nt); i++)
+                parse_record(bam, recs[i], h->tags, h->cfg, parsed[i]);
+        });
+    for (auto &x : th) x.join();
+    for (int32_t i = 0; i < n; i++)
+        if (parsed[i].what == kError) {
+            set_error("IsoformMatrix: read " + std::string(parsed[i].name) + ": " + parsed[i].err);
+            return SMI_ERR_INVALID;
+        }
+    int64_t *c = h->counts;
+    auto put = [&](std::string_view s, std::vector<uint64_t> &off, std::vector<uint32_t> &len) {
+        off.push_back(h->text.size());
+        len.push_back((uint32_t)s.size());
+        h->text.append(s);
+    };
+    for (int32_t i = 0; i < n; i++) {
+        const Parsed &p = parsed[i];
+        c[SMI_ISO_RECORDS]++;
+        if (p.what != kKept) {
+            c[SMI_ISO_UNVALID]++;
+            c[p.what == kNull ? SMI_ISO_NULL : p.what == kChimeric ? SMI_ISO_CHIMERIA : p.what == kNoGene ? SMI_ISO_NO_GENE
+                                                                     : p.what == kNoUmi ? SMI_ISO_NO_UMI : SMI_ISO_MAPQV0]++;
+            continue;
+        }
+        c[SMI_ISO_VALID]++;
+        put(p.name, h->name_off, h->name_len);
+        put(drop_minus1(p.bc), h->bc_off, h->bc_len);
+        put(p.umi, h->umi_off, h->umi_len);
+        put(p.gene, h->gene_off, h->gene_len);
+        h->de.push_back(p.de);
+        h->rn.push_back(p.rn);
+        h->rj.insert(h->rj.end(), p.junc.begin(), p.junc.end());
+        h->rj_off.push_back((int32_t)h->rj.size());
+    }
+    return SMI_OK;
+}
+
+namespace {
+
+// K-MTX for one matrix: codes (row << 32 | cell) -> counts per (row, cell) (sorted codes, device) and the dense rows rendered in blocks
+int matrix(smi_isoform *h, std::vector<uint64_t> &codes, const std::vector<std::string> &labels, std::string &dst, std::vector<int64_t> &row_total,
+           float *ms_sort, float *ms_render) {
+    hipStream_t s = h->ctx->stream;
+    const int64_t nrows = (int64_t)labels.size();
+    const int32_t nc = (int32_t)h->cells.size();
+    row_total.assign(nrows, 0);
+    const size_t n = codes.size();
+    std::vector<uint64_t> ucode;
+    std::vector<uint32_t> ucnt;
+    Events ev;
+    if (n > (size_t)INT32_MAX) {
+        set_error("IsoformMatrix: " + std::to_string(n) + " matrix entries in one matrix; at most 2^31 - 1 are counted in one sort");
+        return SMI_ERR_INVALID;
+    }
+    int end_bit = 32;  // cells < 2^31 in the low word; the row in as many bits above as the rows need
+    while (end_bit < 64 && ((uint64_t)1 << (end_bit - 32)) < (uint64_t)nrows) end_bit++;
+    if (n) {
+        DevBuf<uint64_t> d_in, d_sorted, d_unique;
+        DevBuf<uint32_t> d_cnt;
+        DevBuf<int64_t> d_nrun;
+        DevBuf<uint8_t> d_tmp;
+        if (int rc = d_in.put(codes, s)) return rc;
+        if (int rc = d_sorted.alloc(n)) return rc;
+        if (int rc = d_unique.alloc(n)) return rc;
+        if (int rc = d_cnt.alloc(n)) return rc;
+        if (int rc = d_nrun.alloc(1)) return rc;
+        size_t t1 = 0, t2 = 0;
+        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, d_in.p, d_sorted.p, (int)n, 0, end_bit, s));
+        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, d_sorted.p, d_unique.p, d_cnt.p, d_nrun.p, (int)n, s));
+        if (int rc = d_tmp.alloc(std::max(t1, t2))) return rc;
+        size_t tmp = std::max(t1, t2);
+        if (int rc = ev.begin(s)) return rc;
+        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(d_tmp.p, tmp, d_in.p, d_sorted.p, (int)n, 0, end_bit, s));
+        tmp = std::max(t1, t2);
+        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(d_tmp.p, tmp, d_sorted.p, d_unique.p, d_cnt.p, d_nrun.p, (int)n, s));
+        if (int rc = ev.end(s, ms_sort)) return rc;
+        int64_t nrun = 0;
+        SMI_HIP(hipMemcpy(&nrun, d_nrun.p, sizeof(nrun), hipMemcpyDeviceToHost));
+        ucode.resize(nrun);
+        ucnt.resize(nrun);
+        SMI_HIP(hipMemcpy(ucode.data(), d_unique.p, nrun * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(ucnt.data(), d_cnt.p, nrun * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    for (size_t k = 0; k < ucode.size(); k++) row_total[ucode[k] >> 32] += ucnt[k];
+    if (nrows == 0) return SMI_OK;
+    // labels back to back; the largest count gives the widest field
+    std::vector<uint8_t> lab;
+    std::vector<uint64_t> lab_off{0};
+    for (auto &l : labels) {
+        lab.insert(lab.end(), l.begin(), l.end());
+        lab_off.push_back(lab.size());
+    }
+    uint32_t maxc = 0;
+    for (uint32_t x : ucnt) maxc = std::max(maxc, x);
+    const int wd = 1 + (int)std::to_string(maxc).size();
+    const int64_t budget = h->cfg.budget_bytes > 0 ? h->cfg.budget_bytes : (int64_t)1 << 30;
+    DevBuf<uint8_t> d_lab;
+    DevBuf<uint64_t> d_lab_off, d_ucode;
+    DevBuf<uint32_t> d_ucnt;
+    if (int rc = d_lab.put(lab, s)) return rc;
+    if (int rc = d_lab_off.put(lab_off, s)) return rc;
+    if (int rc = d_ucode.put(ucode, s)) return rc;
+    if (int rc = d_ucnt.put(ucnt, s)) return rc;
+    std::vector<uint8_t> host;
+    int64_t r0 = 0;
+    size_t k0 = 0;
+    while (r0 < nrows) {
+        // rows of this block: dense counts + the widest rendering of each row within the budget (at least one row)
+        int64_t r1 = r0, bytes = 0;
+        while (r1 < nrows) {
+            const int64_t rb = (int64_t)nc * 4 + (int64_t)(lab_off[r1 + 1] - lab_off[r1]) + (int64_t)nc * wd + 1 + 8;
+            if (r1 > r0 && bytes + rb > budget) break;
+            bytes += rb;
+            r1++;
+        }
+        const int32_t nb = (int32_t)(r1 - r0);
+        size_t k1 = k0;
+        while (k1 < ucode.size() && (int64_t)(ucode[k1] >> 32) < r1) k1++;
+        DevBuf<uint32_t> d_dense;
+        DevBuf<uint64_t> d_len, d_off;
+        DevBuf<uint8_t> d_out, d_tmp;
+        if (int rc = d_dense.alloc((size_t)nb * std::max(nc, 1))) return rc;
+        if (int rc = d_len.alloc(nb + 1)) return rc;
+        if (int rc = d_off.alloc(nb + 1)) return rc;
+        if (int rc = ev.begin(s)) return rc;
+        SMI_HIP(hipMemsetAsync(d_dense.p, 0, (size_t)nb * std::max(nc, 1) * 4, s));
+        SMI_HIP(hipMemsetAsync(d_len.p, 0, (nb + 1) * sizeof(uint64_t), s));
+        if (k1 > k0)
+            hipLaunchKernelGGL(k_mtx_scatter, dim3((unsigned)((k1 - k0 + 255) / 256)), dim3(256), 0, s, d_ucode.p, d_ucnt.p, (int64_t)k0, (int64_t)k1,
+                               (int32_t)r0, nc, d_dense.p);
+        const unsigned gb = (unsigned)((nb + kRenderWaves - 1) / kRenderWaves);
+        hipLaunchKernelGGL(k_mtx_render<false>, dim3(gb), dim3(64 * kRenderWaves), 0, s, d_dense.p, nb, nc, (int32_t)r0, d_lab.p, d_lab_off.p,
+                           d_len.p, (uint8_t *)nullptr);
+        SMI_HIP(hipGetLastError());
+        size_t tmp = 0;
+        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_len.p, d_off.p, nb + 1, s));
+        if (int rc = d_tmp.alloc(tmp)) return rc;
+        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp, d_len.p, d_off.p, nb + 1, s));
+        uint64_t total = 0;
+        SMI_HIP(hipMemcpyAsync(&total, d_off.p + nb, sizeof(total), hipMemcpyDeviceToHost, s));
+        SMI_HIP(hipStreamSynchronize(s));
+        if (int rc = d_out.alloc(total)) return rc;
+        hipLaunchKernelGGL(k_mtx_render<true>, dim3(gb), dim3(64 * kRenderWaves), 0, s, d_dense.p, nb, nc, (int32_t)r0, d_lab.p, d_lab_off.p,
+                           d_off.p, d_out.p);
+        SMI_HIP(hipGetLastError());
+        const size_t at = dst.size();
+        dst.resize(at + total);
+        SMI_HIP(hipMemcpyAsync(&dst[at], d_out.p, total, hipMemcpyDeviceToHost, s));
+        if (int rc = ev.end(s, ms_render)) return rc;
+        h->counts[SMI_ISO_RENDER_BLOCKS]++;
+        r0 = r1;
+        k0 = k1;
+    }
+    return SMI_OK;
+}
+
+}  // namespace
+
+extern "C" int smi_isoform_run(smi_isoform *h, float *stage_ms) {
+    if (!h) {
+        set_error("smi_isoform_run: null argument");
+        return SMI_ERR_INVALID;
+    }
+    float ms[SMI_ISOFORM_STAGES] = {};
+    if (stage_ms) std::memset(stage_ms, 0, sizeof(ms));
+    if (h->ran) {
+        set_error("smi_isoform_run: already run");
+        return SMI_ERR_STATE;
+    }
+    h->ran = true;
+    SMI_HIP(hipSetDevice(h->ctx->device));
+    hipStream_t s = h->ctx->stream;
+    const Model &M = h->M;
+    const char *T = h->text.data();
+    auto sv = [&](const std::vector<uint64_t> &off, const std::vector<uint32_t> &len, size_t i) { return std::string_view(T + off[i], len[i]); };
+    const size_t nk = h->de.size();
+    int64_t *c = h->counts;
+    // reads by name in order of their first kept record
+    std::unordered_map<std::string_view, int32_t> by_name;
+    by_name.reserve(nk * 2 + 1);
+    std::vector<int32_t> read_first, read_last, rec_read(nk);
+    std::vector<int32_t> read_n;
+    for (size_t i = 0; i < nk; i++) {
+        auto it = by_name.emplace(sv(h->name_off, h->name_len, i), (int32_t)read_first.size());
+        if (it.second) {
+            read_first.push_back((int32_t)i);
+            read_last.push_back((int32_t)i);
+            read_n.push_back(1);
+        } else {
+            read_last[it.first->second] = (int32_t)i;
+            read_n[it.first->second]++;
+        }
+        rec_read[i] = it.first->second;
+    }
+    const size_t n_reads = read_first.size();
+    c[SMI_ISO_READS] = (int64_t)n_reads;
+    for (int32_t x : read_n) c[SMI_ISO_READS_MULTI] += x > 1;
+    std::vector<int64_t> rstart(n_reads + 1, 0);
+    for (size_t r = 0; r < n_reads; r++) rstart[r + 1] = rstart[r] + read_n[r];
+    std::vector<int32_t> rrecs(nk), rfill(n_reads, 0);
+    for (size_t i = 0; i < nk; i++) rrecs[rstart[rec_read[i]] + rfill[rec_read[i]]++] = (int32_t)i;
+    // molecules keyed barcode:umi of the read's last record, in order of their first read
+    std::unordered_map<std::string, int32_t> by_key;
+    by_key.reserve(n_reads + 1);
+    std::vector<int32_t> mol_of(n_reads), mol_n, mol_first_read, mol_last_read;
+    for (size_t r = 0; r < n_reads; r++) {
+        std::string key(sv(h->bc_off, h->bc_len, read_last[r]));
+        key += ':';
+        key.append(sv(h->umi_off, h->umi_len, read_last[r]));
+        auto it = by_key.emplace(std::move(key), (int32_t)mol_n.size());
+        if (it.second) {
+            mol_n.push_back(0);
+            mol_first_read.push_back((int32_t)r);
+            mol_last_read.push_back((int32_t)r);
+        }
+        mol_of[r] = it.first->second;
+        mol_n[it.first->second]++;
+        mol_last_read[it.first->second] = (int32_t)r;
+    }
+    const size_t n_mol = mol_n.size();
+    c[SMI_ISO_MOLECULES] = (int64_t)n_mol;
+    std::vector<int64_t> mstart(n_mol + 1, 0);
+    for (size_t m = 0; m < n_mol; m++) mstart[m + 1] = mstart[m] + mol_n[m];
+    std::vector<int32_t> mreads(n_reads), mfill(n_mol, 0);
+    for (size_t r = 0; r < n_reads; r++) mreads[mstart[mol_of[r]] + mfill[mol_of[r]]++] = (int32_t)r;
+    c[SMI_ISO_MOLECULE_READS] = (int64_t)n_reads;
+    // per molecule: records (CSR), its distinct genes (multiIG), its model genes (ascending)
+    std::vector<int32_t> mol_rec_off{0}, mrec_j_off{0};
+    std::vector<int2> mrj;
+    std::vector<int32_t> mol_gene_off{0}, mol_gene;
+    std::vector<std::string_view> gl;
+    for (size_t m = 0; m < n_mol; m++) {
+        gl.clear();
+        for (int64_t k = mstart[m]; k < mstart[m + 1]; k++) {
+            const int32_t r = mreads[k];
+            for (int64_t q = rstart[r]; q < rstart[r + 1]; q++) {
+                const int32_t i = rrecs[q];
+                for (auto g : jsplit(sv(h->gene_off, h->gene_len, i), ',')) gl.push_back(g);
+                mrj.insert(mrj.end(), h->rj.begin() + h->rj_off[i], h->rj.begin() + h->rj_off[i + 1]);
+                mrec_j_off.push_back((int32_t)mrj.size());
+            }
+        }
+        mol_rec_off.push_back((int32_t)mrec_j_off.size() - 1);
+        std::sort(gl.begin(), gl.end());
+        gl.erase(std::unique(gl.begin(), gl.end()), gl.end());
+        c[SMI_ISO_MULTI_IG] += gl.size() > 1;
+        const size_t before = mol_gene.size();
+        for (auto g : gl) {
+            auto it = M.gene_id.find(std::string(g));
+            if (it != M.gene_id.end()) mol_gene.push_back(it->second);
+        }
+        std::sort(mol_gene.begin() + before, mol_gene.end());
+        mol_gene_off.push_back((int32_t)mol_gene.size());
+    }
+    // spill slices for molecules of more candidate transcripts than the LDS holds
+    std::vector<int64_t> spill_off(n_mol, -1);
+    int64_t spill_n = 0;
+    for (size_t m = 0; m < n_mol; m++) {
+        int64_t nT = 0;
+        for (int32_t g = mol_gene_off[m]; g < mol_gene_off[m + 1]; g++) nT += M.gene_tx_off[mol_gene[g] + 1] - M.gene_tx_off[mol_gene[g]];
+        if (nT > h->cfg.lds_tx) {
+            spill_off[m] = spill_n;
+            spill_n += nT;
+            c[SMI_ISO_SPILL]++;
+        }
+    }
+    // K-ISO
+    std::vector<int32_t> m_key(n_mol), m_gene(n_mol), m_status(n_mol), m_support(n_mol), m_nj(n_mol);
+    std::vector<int32_t> jset;
+    std::vector<int64_t> joff(n_mol + 1, 0);
+    if (n_mol) {
+        DevBuf<int32_t> d_mro, d_rjo, d_mgo, d_mg, d_gto, d_gt, d_tjo, d_tk, d_tr, d_guo, d_gu, d_spill, d_key, d_gene, d_st, d_sup, d_nj, d_jout;
+        DevBuf<int2> d_rj, d_tj, d_uj;
+        DevBuf<int64_t> d_so, d_jo;
+        int rc = 0;
+        if ((rc = d_mro.put(mol_rec_off, s)) || (rc = d_rjo.put(mrec_j_off, s)) || (rc = d_rj.put(mrj, s)) || (rc = d_mgo.put(mol_gene_off, s)) ||
+            (rc = d_mg.put(mol_gene, s)) || (rc = d_gto.put(M.gene_tx_off, s)) || (rc = d_gt.put(M.gene_tx, s)) || (rc = d_tjo.put(M.tx_j_off, s)) ||
+            (rc = d_tj.put(M.tj, s)) || (rc = d_tk.put(M.tx_key, s)) || (rc = d_tr.put(M.tx_rep, s)) || (rc = d_guo.put(M.gene_u_off, s)) || (rc = d_gu.put(M.gene_u, s)) ||
+            (rc = d_uj.put(M.ujunc, s)) || (rc = d_so.put(spill_off, s)) || (rc = d_spill.alloc(spill_n)) || (rc = d_key.alloc(n_mol)) ||
+            (rc = d_gene.alloc(n_mol)) || (rc = d_st.alloc(n_mol)) || (rc = d_sup.alloc(n_mol)) || (rc = d_nj.alloc(n_mol)))
+            return rc;
+        IsoArgs a = {d_mro.p, d_rjo.p, d_rj.p, d_mgo.p, d_mg.p, d_gto.p, d_gt.p, d_tjo.p, d_tj.p, d_tk.p, d_tr.p, d_guo.p, d_gu.p, d_uj.p,
+                     (int32_t)n_mol, h->cfg.delta, h->cfg.lds_tx, d_so.p, d_spill.p, d_key.p, d_gene.p, d_st.p, d_sup.p, d_nj.p, nullptr, nullptr};
+        const unsigned grid = (unsigned)((n_mol + kIsoWaves - 1) / kIsoWaves);
+        Events ev;
+        if ((rc = ev.begin(s))) return rc;
+        hipLaunchKernelGGL(k_iso<false>, dim3(grid), dim3(64 * kIsoWaves), 0, s, a);
+        SMI_HIP(hipGetLastError());
+        if ((rc = ev.end(s, &ms[0]))) return rc;
+        SMI_HIP(hipMemcpy(m_key.data(), d_key.p, n_mol * 4, hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(m_gene.data(), d_gene.p, n_mol * 4, hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(m_status.data(), d_st.p, n_mol * 4, hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(m_support.data(), d_sup.p, n_mol * 4, hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(m_nj.data(), d_nj.p, n_mol * 4, hipMemcpyDeviceToHost));
+        for (size_t m = 0; m < n_mol; m++) joff[m + 1] = joff[m] + m_nj[m];
+        if (joff[n_mol]) {
+            if ((rc = d_jo.put(joff, s)) || (rc = d_jout.alloc(joff[n_mol]))) return rc;
+            a.junc_off = d_jo.p;
+            a.junc_out = d_jout.p;
+            if ((rc = ev.begin(s))) return rc;
+            hipLaunchKernelGGL(k_iso<true>, dim3(grid), dim3(64 * kIsoWaves), 0, s, a);
+            SMI_HIP(hipGetLastError());
+            if ((rc = ev.end(s, &ms[0]))) return rc;
+            jset.resize(joff[n_mol]);
+            SMI_HIP(hipMemcpy(jset.data(), d_jout.p, jset.size() * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    // molecule gene / transcript ids: a model gene index (or -1 = "undef"), a key id (or -1)
+    const auto undef_gene = M.gene_id.find("undef");
+    std::vector<int32_t> gid(n_mol);
+    for (size_t m = 0; m < n_mol; m++) {
+        switch (m_status[m]) {
+            case kMono: c[SMI_ISO_MONOEXON]++; break;
+            case kOne: c[SMI_ISO_ONEMATCH]++; break;
+            case kAmbiguous: c[SMI_ISO_AMBIGUOUS]++; break;
+            case kNomatch: c[SMI_ISO_NOMATCH]++; break;
+        }
+        if (m_key[m] >= 0) {
+            auto it = M.gene_id.find(M.key_gene[m_key[m]]);
+            gid[m] = it == M.gene_id.end() ? -1 : it->second;
+        } else if (m_status[m] == kNomatch) {
+            gid[m] = m_gene[m];
+        } else {
+            gid[m] = undef_gene == M.gene_id.end() ? -2 : undef_gene->second;  // "undef" counts only if it is a model gene
+        }
+    }
+    // counted molecules (produceMatrix / addMolecule): barcode in the cell list, gene in the model
+    std::vector<int32_t> cnt_mol, mol_cell(n_mol, -1);
+    for (size_t m = 0; m < n_mol; m++) {
+        auto it = h->cell_id.find(std::string(sv(h->bc_off, h->bc_len, read_last[mol_first_read[m]])));
+        if (it == h->cell_id.end() || gid[m] < 0) continue;
+        mol_cell[m] = it->second;
+        cnt_mol.push_back((int32_t)m);
+    }
+    auto bc_of = [&](int32_t m) { return sv(h->bc_off, h->bc_len, read_last[mol_first_read[m]]); };
+    auto umi_of = [&](int32_t m) { return sv(h->umi_off, h->umi_len, read_last[mol_first_read[m]]); };
+    auto gene_name = [&](int32_t m) { return M.genes[gid[m]]; };
+    auto tx_name = [&](int32_t m) { return m_key[m] >= 0 ? M.key_tx[m_key[m]] : std::string("undef"); };
+    // rows in byte order of their text: the distinct (gene, key / junction) integer pairs are found first, only their labels are sorted
+    auto rows_of = [&](const std::vector<uint64_t> &item, auto label_of, std::vector<std::string> &labels, std::vector<int32_t> &row_of_item) {
+        std::vector<uint64_t> u(item);
+        std::sort(u.begin(), u.end());
+        u.erase(std::unique(u.begin(), u.end()), u.end());
+        std::vector<std::string> lab(u.size());
+        for (size_t k = 0; k < u.size(); k++) lab[k] = label_of(u[k]);
+        std::vector<int32_t> ord(u.size()), rank(u.size());
+        for (size_t k = 0; k < u.size(); k++) ord[k] = (int32_t)k;
+        std::sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return lab[x] < lab[y]; });
+        labels.resize(u.size());
+        for (size_t k = 0; k < u.size(); k++) {
+            rank[ord[k]] = (int32_t)k;
+            labels[k] = std::move(lab[ord[k]]);
+        }
+        row_of_item.resize(item.size());
+        for (size_t i = 0; i < item.size(); i++) row_of_item[i] = rank[std::lower_bound(u.begin(), u.end(), item[i]) - u.begin()];
+    };
+    auto pair = [](int32_t hi, int32_t lo) { return (uint64_t)(uint32_t)hi << 32 | (uint32_t)(lo + 1); };  // lo -1 (undef) sorts first
+    const size_t nc = cnt_mol.size();
+    std::vector<std::string> iso_rows, gene_rows, junc_rows;
+    std::vector<int32_t> iso_row, gene_row, junc_row;
+    std::vector<uint64_t> items(nc);
+    for (size_t i = 0; i < nc; i++) items[i] = pair(gid[cnt_mol[i]], m_key[cnt_mol[i]]);
+    rows_of(items, [&](uint64_t x) { const int32_t k = (int32_t)(uint32_t)x - 1;
+                                     return M.genes[x >> 32] + "\t" + (k >= 0 ? M.key_tx[k] : std::string("undef")); }, iso_rows, iso_row);
+    for (size_t i = 0; i < nc; i++) items[i] = pair(gid[cnt_mol[i]], 0);
+    rows_of(items, [&](uint64_t x) { return M.genes[x >> 32]; }, gene_rows, gene_row);
+    std::vector<int64_t> jitem_mol;
+    items.clear();
+    for (size_t i = 0; i < nc; i++)
+        for (int64_t k = joff[cnt_mol[i]]; k < joff[cnt_mol[i] + 1]; k++) {
+            jitem_mol.push_back(cnt_mol[i]);
+            items.push_back(pair(gid[cnt_mol[i]], jset[k]));
+        }
+    rows_of(items, [&](uint64_t x) { const int2 j = M.ujunc[(int32_t)(uint32_t)x - 1];
+                                     return M.genes[x >> 32] + ":" + std::to_string(j.x) + "-" + std::to_string(j.y); }, junc_rows, junc_row);
+    std::string head;
+    for (auto &cell : h->cells) head += "\t" + cell;
+    head += "\n";
+    std::vector<int64_t> iso_tot, gene_tot, junc_tot;
+    std::vector<uint64_t> codes;
+    int rc;
+    // isoforms
+    std::vector<std::string> iso_lab(iso_rows.size());
+    std::vector<int32_t> iso_nex(iso_rows.size());
+    for (size_t r = 0; r < iso_rows.size(); r++) {
+        const size_t tab = iso_rows[r].find('\t');
+        const std::string g = iso_rows[r].substr(0, tab), t = iso_rows[r].substr(tab + 1);
+        int32_t nex = 0;  // select(gene, tx): the last line of gene g with that transcript
+        auto git = M.gene_id.find(g);
+        if (git != M.gene_id.end())
+            for (int32_t k = M.gene_tx_off[git->second]; k < M.gene_tx_off[git->second + 1]; k++)
+                if (M.key_tx[M.tx_key[M.gene_tx[k]]] == t) nex = M.tx_nexon[M.gene_tx[k]];
+        iso_nex[r] = nex;
+        iso_lab[r] = iso_rows[r] + "\t" + std::to_string(nex);
+    }
+    codes.resize(nc);
+    for (size_t i = 0; i < nc; i++) codes[i] = (uint64_t)iso_row[i] << 32 | (uint32_t)mol_cell[cnt_mol[i]];
+    std::string &isom = h->out[SMI_ISO_OUT_ISOMATRIX];
+    isom = "geneId\ttranscriptId\tnbExons" + head;
+    if ((rc = matrix(h, codes, iso_lab, isom, iso_tot, &ms[1], &ms[2]))) return rc;
+    std::string &isomet = h->out[SMI_ISO_OUT_ISOMETRICS];
+    isomet = "geneId\ttranscriptId\tnbExons\tnbUmis\n";
+    for (size_t r = 0; r < iso_rows.size(); r++) {
+        isomet += iso_lab[r] + "\t" + std::to_string(iso_tot[r]) + "\n";
+        c[SMI_ISO_TOTAL_COUNT] += iso_tot[r];
+    }
+    // genes
+    for (size_t i = 0; i < nc; i++) codes[i] = (uint64_t)gene_row[i] << 32 | (uint32_t)mol_cell[cnt_mol[i]];
+    codes.resize(nc);
+    std::string &genm = h->out[SMI_ISO_OUT_GENEMATRIX];
+    genm = "geneId" + head;
+    if ((rc = matrix(h, codes, gene_rows, genm, gene_tot, &ms[1], &ms[2]))) return rc;
+    // junctions
+    codes.resize(jitem_mol.size());
+    for (size_t i = 0; i < jitem_mol.size(); i++) codes[i] = (uint64_t)junc_row[i] << 32 | (uint32_t)mol_cell[jitem_mol[i]];
+    std::string &junm = h->out[SMI_ISO_OUT_JUNCMATRIX];
+    junm = "junctionId" + head;
+    if ((rc = matrix(h, codes, junc_rows, junm, junc_tot, &ms[1], &ms[2]))) return rc;
+    std::string &junmet = h->out[SMI_ISO_OUT_JUNCMETRICS];
+    junmet = "junctionId\tnbUmis\n";
+    for (size_t r = 0; r < junc_rows.size(); r++) junmet += junc_rows[r] + "\t" + std::to_string(junc_tot[r]) + "\n";
+    // gene metrics, cell metrics, molecule infos
+    std::vector<int64_t> g_known(gene_rows.size(), 0), g_undef(gene_rows.size(), 0);
+    std::vector<int64_t> c_reads(h->cells.size(), 0), c_umis(h->cells.size(), 0), c_known(h->cells.size(), 0), c_undef(h->cells.size(), 0);
+    std::vector<std::vector<int32_t>> c_genes(h->cells.size());
+    for (size_t i = 0; i < nc; i++) {
+        const int32_t m = cnt_mol[i], cell = mol_cell[m];
+        const bool undef = m_key[m] < 0;
+        (undef ? g_undef : g_known)[gene_row[i]]++;
+        (undef ? c_undef : c_known)[cell]++;
+        c_umis[cell]++;
+        c_reads[cell] += mol_n[m];
+        c_genes[cell].push_back(gene_row[i]);
+        (undef ? c[SMI_ISO_UNDEF] : c[SMI_ISO_DEF])++;
+    }
+    std::string &genmet = h->out[SMI_ISO_OUT_GENEMETRICS];
+    genmet = "geneId\tnbUmis\tnbIsoformSet\tnbIsoformNotSet\n";
+    for (size_t r = 0; r < gene_rows.size(); r++)
+        genmet += gene_rows[r] + "\t" + std::to_string(g_known[r] + g_undef[r]) + "\t" + std::to_string(g_known[r]) + "\t" + std::to_string(g_undef[r]) + "\n";
+    std::string &cellmet = h->out[SMI_ISO_OUT_CELLMETRICS];
+    cellmet = "cellBC\tnbReads\tnbGenes\tnbUmis\tnbIsoformSet\tnbIsoformNotSet\n";
+    for (size_t k = 0; k < h->cells.size(); k++) {
+        auto &gs = c_genes[k];
+        std::sort(gs.begin(), gs.end());
+        const size_t ng = std::unique(gs.begin(), gs.end()) - gs.begin();
+        cellmet += h->cells[k] + "\t" + std::to_string(c_reads[k]) + "\t" + std::to_string(ng) + "\t" + std::to_string(c_umis[k]) + "\t" +
+                   std::to_string(c_known[k]) + "\t" + std::to_string(c_undef[k]) + "\n";
+    }
+    std::vector<int32_t> mo(cnt_mol);
+    std::sort(mo.begin(), mo.end(), [&](int32_t x, int32_t y) {
+        const auto bx = bc_of(x), by = bc_of(y);
+        return bx != by ? bx < by : umi_of(x) < umi_of(y);
+    });
+    std::string &mol = h->out[SMI_ISO_OUT_MOLINFOS];
+    mol = "cellBC\tUMI\tnbReads\tnbSupportingReads\tmappingPctId\tsnpPhredScore\tgeneId\ttranscriptId\n";
+    for (int32_t m : mo) {
+        const int32_t rn = h->rn[read_last[mol_first_read[m]]];  // Molecule.rn: the first read's rn (of its last record)
+        const int32_t nreads = rn > 1 ? rn : mol_n[m];
+        const float pct = 1.0f - h->de[read_first[mol_last_read[m]]];
+        mol.append(bc_of(m));
+        mol += '\t';
+        mol.append(umi_of(m));
+        mol += "\t" + std::to_string(nreads) + "\t" + std::to_string(m_support[m]) + "\t" + java_float(pct) + "\t\t" + gene_name(m) + "\t" +
+               tx_name(m) + "\n";
+    }
+    if (h->cfg.to_bulk) {  // writeBulk, with its second loop writing into the bulkgene stream as well
+        std::string &bg = h->out[SMI_ISO_OUT_BULKGENE], &bi = h->out[SMI_ISO_OUT_BULKISO];
+        bg = "geneId\tcount\n";
+        bi = "transcriptId\texons\tcount\n";
+        for (size_t r = 0; r < gene_rows.size(); r++) bg += gene_rows[r] + "\t" + std::to_string(gene_tot[r]) + "\n";
+        for (size_t r = 0; r < iso_rows.size(); r++) {
+            bg += iso_lab[r];
+            bi += iso_lab[r] + "\t" + std::to_string(iso_tot[r]) + "\n";
+        }
+    }
+    // ISOBAM's table: "undef" first, then every model gene and every key's transcript
+    {
+        std::vector<uint64_t> gs(M.genes.size()), ks(M.key_tx.size());
+        auto add = [&](const std::string &x) {
+            const uint64_t o = h->iso_text.size();
+            h->iso_text.insert(h->iso_text.end(), x.begin(), x.end());
+            return o;
+        };
+        add("undef");
+        for (size_t g = 0; g < gs.size(); g++) gs[g] = add(M.genes[g]);
+        for (size_t k = 0; k < ks.size(); k++) ks[k] = add(M.key_tx[k]);
+        h->ig_start.assign(n_mol + 1, 0);
+        h->it_start.assign(n_mol + 1, 0);
+        h->ig_len.assign(n_mol + 1, 5);
+        h->it_len.assign(n_mol + 1, 5);
+        for (size_t m = 0; m < n_mol; m++) {
+            if (gid[m] >= 0) {
+                h->ig_start[m + 1] = gs[gid[m]];
+                h->ig_len[m + 1] = (uint32_t)M.genes[gid[m]].size();
+            }
+            if (m_key[m] >= 0) {
+                h->it_start[m + 1] = ks[m_key[m]];
+                h->it_len[m + 1] = (uint32_t)M.key_tx[m_key[m]].size();
+            }
+        }
+        h->mol_by_key = std::move(by_key);
+    }
+    c[SMI_ISO_MATRIX_GENES] = (int64_t)gene_rows.size();
+    c[SMI_ISO_MATRIX_JUNCTIONS] = (int64_t)junc_rows.size();
+    c[SMI_ISO_MATRIX_ISOFORMS] = (int64_t)iso_rows.size();
+    if (stage_ms) std::memcpy(stage_ms, ms, sizeof(ms));
+    return SMI_OK;
+}
+
+extern "C" int smi_isoform_output(const smi_isoform *h, int32_t which, uint8_t *out, size_t cap, size_t *n_out) {
+    if (!h || !n_out || which < 0 || which >= SMI_ISOFORM_OUTPUTS) {
+        set_error("smi_isoform_output: bad argument");
+        return SMI_ERR_INVALID;
+    }
+    const std::string &s = h->out[which];
+    *n_out = s.size();
+    if (!out) return SMI_OK;
+    if (cap < s.size()) return 1;
+    std::memcpy(out, s.data(), s.size());
+    return SMI_OK;
+}
+
+extern "C" int smi_isoform_counts(const smi_isoform *h, int64_t *counts) {
+    if (!h || !counts) {
+        set_error("smi_isoform_counts: null argument");
+        return SMI_ERR_INVALID;
+    }
+    std::memcpy(counts, h->counts, sizeof(h->counts));
+    return SMI_OK;
+}
+
+extern "C" int smi_isoform_isobam(smi_isoform *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n, uint8_t *out, size_t cap,
+                                  size_t *n_out) {
+    if (!h || !n_out || n < 0 || (n && (!bam || !recs))) {
+        set_error("smi_isoform_isobam: bad argument");
+        return SMI_ERR_INVALID;
+    }
+    if (!h->ran) {
+        set_error("smi_isoform_isobam: the molecules are not assigned yet (smi_isoform_run)");
+        return SMI_ERR_STATE;
+    }
+    *n_out = 0;
+    if (!out || !(h->last_n == n && h->last_bam == bam && h->last_recs == recs)) {  // a size query always makes the records
+        h->last_n = -1;
+        for (int32_t i = 0; i < n; i++) {  // every record inside the buffer, its attributes at its end (K-TAG-ASM reads nothing else)
+            const smi_bam_record &r = recs[i];
+            if (r.rec_len < 36 || r.rec_off + r.rec_len > n_bam || r.name_off + r.l_read_name > n_bam || r.aux_off < r.rec_off + 36 ||
+                r.aux_off + r.aux_len != r.rec_off + r.rec_len) {
+                set_error("smi_isoform_isobam: record " + std::to_string(i) + " lies outside the segment");
+                return SMI_ERR_INVALID;
+            }
+        }
+        // the lookup key: the raw CELLTAG and UMITAG strings ("null" when absent), as (String) r.getAttribute casts them
+        std::vector<int32_t> entry(n > 0 ? n : 1, 0);
+        std::vector<int32_t> bad(n > 0 ? n : 1, 0);
+        const int nt = std::max(1, std::min<int>(h->cfg.n_threads, (n + 4095) / 4096));
+        std::vector<std::thread> th;
+        for (int t = 0; t < nt; t++)
+            th.emplace_back([&, t] {
+                std::string key;
+                for (int32_t i = (int32_t)((int64_t)n * t / nt); i < (int32_t)((int64_t)n * (t + 1) / nt); i++) {
+                    const uint8_t *p = bam + recs[i].aux_off, *end = p + recs[i].aux_len;
+                    lr::Aux cell, umi;
+                    while (p < end) {
+                        size_t k;
+                        if (lr::aux_size(p, end, &k)) {
+                            bad[i] = 1;
+                            break;
+                        }
+                        const uint16_t tg = (uint16_t)(p[0] | p[1] << 8);
+                        if (tg == h->tags.cell) cell = lr::Aux{p, k};
+                        if (tg == h->tags.umi) umi = lr::Aux{p, k};
+                        p += k;
+                    }
+                    if (bad[i]) continue;
+                    if ((cell.p && cell.p[2] != 'Z') || (umi.p && umi.p[2] != 'Z')) {
+                        bad[i] = 2;
+                        continue;
+                    }
+                    key.assign(cell.p ? std::string_view((const char *)cell.p + 3, cell.n - 4) : std::string_view("null"));
+                    key += ':';
+                    key.append(umi.p ? std::string_view((const char *)umi.p + 3, umi.n - 4) : std::string_view("null"));
+                    auto it = h->mol_by_key.find(key);
+                    entry[i] = it == h->mol_by_key.end() ? 0 : it->second + 1;
+                }
+            });
+        for (auto &x : th) x.join();
+        for (int32_t i = 0; i < n; i++)
+            if (bad[i]) {
+                const smi_bam_record &r = recs[i];
+                set_error("IsoformMatrix: ISOBAM: read " + std::string((const char *)bam + r.name_off, r.l_read_name ? r.l_read_name - 1 : 0) +
+                          (bad[i] == 1 ? ": malformed attributes" : ": CELLTAG or UMITAG is not a string"));
+                return SMI_ERR_INVALID;
+            }
+        SMI_HIP(hipSetDevice(h->ctx->device));
+        hipStream_t s = h->ctx->stream;
+        if (!h->d_iso_text) {
+            DevBuf<uint8_t> a;
+            DevBuf<uint64_t> b, c2;
+            DevBuf<uint32_t> d, e;
+            int rc;
+            if ((rc = a.put(h->iso_text, s)) || (rc = b.put(h->ig_start, s)) || (rc = c2.put(h->it_start, s)) || (rc = d.put(h->ig_len, s)) ||
+                (rc = e.put(h->it_len, s)))
+                return rc;
+            SMI_HIP(hipStreamSynchronize(s));
+            h->d_iso_text = a.p, a.p = nullptr;
+            h->d_ig_start = b.p, b.p = nullptr;
+            h->d_it_start = c2.p, c2.p = nullptr;
+            h->d_ig_len = d.p, d.p = nullptr;
+            h->d_it_len = e.p, e.p = nullptr;
+        }
+        DevBuf<uint8_t> d_bam;
+        DevBuf<smi_bam_record> d_recs;
+        DevBuf<int32_t> d_entry;
+        int rc;
+        if ((rc = d_bam.alloc(n_bam + 1)) || (rc = d_recs.alloc(n)) || (rc = d_entry.put(entry, s))) return rc;
+        if (n_bam) SMI_HIP(hipMemcpyAsync(d_bam.p, bam, n_bam, hipMemcpyHostToDevice, s));
+        if (n) SMI_HIP(hipMemcpyAsync(d_recs.p, recs, (size_t)n * sizeof(smi_bam_record), hipMemcpyHostToDevice, s));
+        if ((rc = tag_assemble_z2(s, d_bam.p, d_recs.p, (size_t)n, d_entry.p, h->d_iso_text, h->d_ig_start, h->d_ig_len, h->d_it_start,
+                                  h->d_it_len, "IG", "IT", h->isobam, &h->isobam_ms))) {
+            set_error(std::string("IsoformMatrix: ISOBAM: ") + smi_last_error());
+            return rc;
+        }
+        h->last_bam = bam;
+        h->last_recs = recs;
+        h->last_n = n;
+    }
+    *n_out = h->isobam.size();
+    if (!out) return SMI_OK;
+    if (cap < h->isobam.size()) return 1;
+    std::memcpy(out, h->isobam.data(), h->isobam.size());
+    return SMI_OK;
+}

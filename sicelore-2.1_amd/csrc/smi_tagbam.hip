@@ -165,7 +165,8 @@ __device__ bool put_field(Field *f, int &n, const Field &x) {
 
 // lane 0: the attribute list of record rec as written, in f[0 .. n), sorted by binary tag; returns SMI_TAG_* error bits (0 = fine)
 __device__ uint32_t parse_fields(const uint8_t *__restrict__ bam, const smi_bam_record &rec, const uint8_t *__restrict__ text, uint64_t seq_start,
-                                 uint64_t qual_start, uint32_t seq_len, uint32_t read_key, uint32_t qv_key, bool with_qv, Field *f, int &n) {
+                                 uint64_t qual_start, uint32_t seq_len, uint32_t qual_len, uint32_t read_key, uint32_t qv_key, bool with_qv, Field *f,
+                                 int &n) {
     n = 0;
     const uint64_t end = rec.aux_off + rec.aux_len;
     uint64_t p = rec.aux_off;
@@ -232,6 +233,7 @@ __device__ uint32_t parse_fields(const uint8_t *__restrict__ bam, const smi_bam_
     if (with_qv) {
         s.key = (uint16_t)qv_key;
         s.src = qual_start;
+        s.len = qual_len;
         if (!put_field(f, n, s)) return SMI_TAG_TOO_MANY_ATTRS;
     }
     for (int i = 1; i < n; i++) {  // insertion sort by binary tag (keys are distinct)
@@ -250,7 +252,8 @@ template <bool WRITE>
 __global__ __launch_bounds__(64 * kAsmWaves) void k_tag_asm(const uint8_t *__restrict__ bam, const smi_bam_record *__restrict__ recs, size_t n,
                                                              const int32_t *__restrict__ res, const uint8_t *__restrict__ text,
                                                              const uint64_t *__restrict__ seq_start, const uint32_t *__restrict__ seq_len,
-                                                             const uint64_t *__restrict__ qual_start, uint32_t read_key, uint32_t qv_key, int with_qv,
+                                                             const uint64_t *__restrict__ qual_start, const uint32_t *__restrict__ qual_len,
+                                                             uint32_t read_key, uint32_t qv_key, int with_qv,
                                                              uint64_t *__restrict__ size, const uint64_t *__restrict__ off, uint8_t *__restrict__ out,
                                                              uint64_t out_cap, uint32_t *__restrict__ err) {
     __shared__ Field fields[kAsmWaves][kMaxFields];
@@ -268,7 +271,7 @@ __global__ __launch_bounds__(64 * kAsmWaves) void k_tag_asm(const uint8_t *__res
     Field *f = fields[wv];
     if (lane == 0) {
         int nf = 0;
-        uint32_t b = parse_fields(bam, rec, text, seq_start[fq], qual_start[fq], seq_len[fq], read_key, qv_key, with_qv != 0, f, nf);
+        uint32_t b = parse_fields(bam, rec, text, seq_start[fq], qual_start[fq], seq_len[fq], qual_len[fq], read_key, qv_key, with_qv != 0, f, nf);
         uint64_t o = rec.aux_off - rec.rec_off;  // block_size word + fixed part + name + CIGAR + sequence + qualities
         for (int j = 0; j < nf; j++) {
             f[j].out = o;
@@ -346,6 +349,79 @@ __global__ __launch_bounds__(64 * kAsmWaves) void k_tag_asm(const uint8_t *__res
 unsigned blocks_for(size_t n, unsigned per) { return (unsigned)std::max<size_t>(1, (n + per - 1) / per); }
 
 }  // namespace
+
+// K-TAG-ASM for records already on the device (smi_internal.h)
+int tag_assemble_z2(hipStream_t s, const uint8_t *d_bam, const smi_bam_record *d_recs, size_t n, const int32_t *d_entry, const uint8_t *d_text,
+                    const uint64_t *d_a_start, const uint32_t *d_a_len, const uint64_t *d_b_start, const uint32_t *d_b_len, const char *tag_a,
+                    const char *tag_b, std::vector<uint8_t> &out, float *ms) {
+    out.clear();
+    if (!n) return SMI_OK;
+    const uint32_t ka = (uint32_t)(uint8_t)tag_a[1] << 8 | (uint8_t)tag_a[0], kb = (uint32_t)(uint8_t)tag_b[1] << 8 | (uint8_t)tag_b[0];
+    uint64_t *d_size = nullptr, *d_off = nullptr;
+    uint32_t *d_err = nullptr;
+    void *d_cub = nullptr;
+    uint8_t *d_out = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = SMI_OK;
+    auto fin = [&](int r) {
+        for (void *p : {(void *)d_size, (void *)d_off, (void *)d_err, d_cub, (void *)d_out})
+            if (p) (void)hipFree(p);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        return r;
+    };
+#define SMI_Z2(call)                                          \
+    do {                                                      \
+        hipError_t e__ = (call);                              \
+        if (e__ != hipSuccess) return fin(hip_fail(e__, #call)); \
+    } while (0)
+    size_t cub = 0;
+    SMI_Z2(hipcub::DeviceScan::ExclusiveSum(nullptr, cub, (uint64_t *)nullptr, (uint64_t *)nullptr, n + 1, s));
+    SMI_Z2(hipMalloc((void **)&d_size, (n + 1) * 8));
+    SMI_Z2(hipMalloc((void **)&d_off, (n + 1) * 8));
+    SMI_Z2(hipMalloc((void **)&d_err, 4));
+    SMI_Z2(hipMalloc(&d_cub, std::max<size_t>(cub, 1)));
+    SMI_Z2(hipEventCreate(&e0));
+    SMI_Z2(hipEventCreate(&e1));
+    SMI_Z2(hipMemsetAsync(d_err, 0, 4, s));
+    SMI_Z2(hipMemsetAsync(d_size + n, 0, 8, s));
+    SMI_Z2(hipEventRecord(e0, s));
+    hipLaunchKernelGGL(k_tag_asm<false>, dim3(blocks_for(n, kAsmWaves)), dim3(64 * kAsmWaves), 0, s, d_bam, d_recs, n, d_entry, d_text, d_a_start,
+                       d_a_len, d_b_start, d_b_len, ka, kb, 1, d_size, (const uint64_t *)nullptr, (uint8_t *)nullptr, (uint64_t)0, d_err);
+    SMI_Z2(hipGetLastError());
+    SMI_Z2(hipcub::DeviceScan::ExclusiveSum(d_cub, cub, d_size, d_off, n + 1, s));
+    uint64_t total = 0;
+    uint32_t err = 0;
+    SMI_Z2(hipMemcpyAsync(&total, d_off + n, 8, hipMemcpyDeviceToHost, s));
+    SMI_Z2(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s));
+    SMI_Z2(hipStreamSynchronize(s));
+    if (err) {
+        set_error(std::string("a record's attributes cannot be rewritten:") + (err & SMI_TAG_BAD_AUX ? " malformed or unknown attribute type;" : "") +
+                  (err & SMI_TAG_BAD_HEX ? " H attribute that is not hex;" : "") +
+                  (err & SMI_TAG_TOO_MANY_ATTRS ? " more than " + std::to_string(kMaxFields) + " attributes;" : std::string()));
+        return fin(SMI_ERR_INVALID);
+    }
+    SMI_Z2(hipMalloc((void **)&d_out, std::max<uint64_t>(total, 1)));
+    hipLaunchKernelGGL(k_tag_asm<true>, dim3(blocks_for(n, kAsmWaves)), dim3(64 * kAsmWaves), 0, s, d_bam, d_recs, n, d_entry, d_text, d_a_start,
+                       d_a_len, d_b_start, d_b_len, ka, kb, 1, (uint64_t *)nullptr, (const uint64_t *)d_off, d_out, (uint64_t)total, d_err);
+    SMI_Z2(hipGetLastError());
+    SMI_Z2(hipEventRecord(e1, s));
+    out.resize(total);
+    SMI_Z2(hipMemcpyAsync(out.data(), d_out, total, hipMemcpyDeviceToHost, s));
+    SMI_Z2(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s));
+    SMI_Z2(hipStreamSynchronize(s));
+#undef SMI_Z2
+    if (ms) {
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) *ms += t;
+    }
+    if (err) {
+        set_error("the output buffer of the device was too small for a record (internal error)");
+        rc = SMI_ERR_INVALID;
+    }
+    return fin(rc);
+}
+
 }  // namespace smi
 
 using namespace smi;
@@ -627,7 +703,8 @@ extern "C" int smi_tagbam_segment(smi_tagbam *h, const uint8_t *bam, size_t n_ba
         if (n)
             hipLaunchKernelGGL(k_tag_asm<false>, dim3(blocks_for(n, kAsmWaves)), dim3(64 * kAsmWaves), 0, s, (const uint8_t *)h->d_bam,
                                (const smi_bam_record *)h->d_recs, (size_t)n, (const int32_t *)h->d_res, (const uint8_t *)h->d_text,
-                               (const uint64_t *)h->d_seq_start, (const uint32_t *)h->d_seq_len, (const uint64_t *)h->d_qual_start, rk, qk,
+                               (const uint64_t *)h->d_seq_start, (const uint32_t *)h->d_seq_len, (const uint64_t *)h->d_qual_start,
+                               (const uint32_t *)h->d_seq_len, rk, qk,
                                h->cfg.with_qv, h->d_size, (const uint64_t *)nullptr, (uint8_t *)nullptr, (uint64_t)0, h->d_err);
         SMI_HIP(hipGetLastError());
         SMI_HIP(hipcub::DeviceScan::ExclusiveSum(h->d_cub, cub, h->d_size, h->d_off, n + 1, s));
@@ -670,7 +747,8 @@ extern "C" int smi_tagbam_segment(smi_tagbam *h, const uint8_t *bam, size_t n_ba
     SMI_HIP(hipEventRecord(h->ev[4], s));
     hipLaunchKernelGGL(k_tag_asm<true>, dim3(blocks_for(n, kAsmWaves)), dim3(64 * kAsmWaves), 0, s, (const uint8_t *)h->d_bam,
                        (const smi_bam_record *)h->d_recs, (size_t)n, (const int32_t *)h->d_res, (const uint8_t *)h->d_text,
-                       (const uint64_t *)h->d_seq_start, (const uint32_t *)h->d_seq_len, (const uint64_t *)h->d_qual_start, tag_key(h->cfg.read_tag),
+                       (const uint64_t *)h->d_seq_start, (const uint32_t *)h->d_seq_len, (const uint64_t *)h->d_qual_start, (const uint32_t *)h->d_seq_len,
+                       tag_key(h->cfg.read_tag),
                        tag_key(h->cfg.qv_tag), h->cfg.with_qv, (uint64_t *)nullptr, (const uint64_t *)h->d_off, h->d_out, (uint64_t)h->out_cap, h->d_err);
     SMI_HIP(hipGetLastError());
     SMI_HIP(hipEventRecord(h->ev[5], s));

@@ -68,6 +68,8 @@ EXPORTS = [
     "smi_tagbam_default_config", "smi_tagbam_create", "smi_tagbam_free", "smi_tagbam_records", "smi_tagbam_segment", "smi_tagbam_stage_ms",
     "smi_consensus_default_config", "smi_consensus_create", "smi_consensus_add_segment", "smi_consensus_run", "smi_consensus_fastq",
     "smi_consensus_counts", "smi_consensus_free", "smi_poa_batch",
+    "smi_isoform_default_config", "smi_isoform_create", "smi_isoform_add_segment", "smi_isoform_run", "smi_isoform_output",
+    "smi_isoform_counts", "smi_isoform_free", "smi_isoform_isobam",
 ]
 
 
@@ -246,6 +248,14 @@ def load_library():
     lib.smi_consensus_fastq.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
     lib.smi_consensus_counts.argtypes = [vp, vp]
     lib.smi_consensus_free.argtypes = [vp]
+    lib.smi_isoform_default_config.argtypes = [vp]
+    lib.smi_isoform_create.argtypes = [vp, vp, vp, sz, vp, sz, ctypes.POINTER(vp)]
+    lib.smi_isoform_add_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32]
+    lib.smi_isoform_run.argtypes = [vp, vp]
+    lib.smi_isoform_output.argtypes = [vp, ctypes.c_int32, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_isoform_counts.argtypes = [vp, vp]
+    lib.smi_isoform_free.argtypes = [vp]
+    lib.smi_isoform_isobam.argtypes = [vp, vp, sz, vp, ctypes.c_int32, vp, sz, ctypes.POINTER(sz)]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     explicit = {"smi_last_error", "smi_version", "smi_read_planes_words", "smi_packed_planes_words", "smi_record_flags"}  # restype set above (char*, size_t)
@@ -657,6 +667,104 @@ class Consensus:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.smi_consensus_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class IsoformConfig(ctypes.Structure):
+    """smi_isoform_config"""
+    _fields_ = [("cell_tag", ctypes.c_char * 4), ("umi_tag", ctypes.c_char * 4), ("gene_tag", ctypes.c_char * 4), ("rn_tag", ctypes.c_char * 4),
+                ("max_clip", ctypes.c_int32), ("mapqv0", ctypes.c_int32), ("delta", ctypes.c_int32), ("to_bulk", ctypes.c_int32),
+                ("n_threads", ctypes.c_int32), ("lds_tx", ctypes.c_int32), ("budget_bytes", ctypes.c_int64)]
+
+
+# smi_isoform_counts, in SMI_ISO_* order
+ISOFORM_COUNTS = ("records", "valid", "unvalid", "mapqv0", "no_gene", "no_umi", "chimeria", "null", "reads", "reads_multi", "molecules",
+                  "molecule_reads", "multi_ig", "genes", "transcripts", "monoexon", "nomatch", "onematch", "ambiguous", "cells", "matrix_genes",
+                  "matrix_junctions", "matrix_isoforms", "total_count", "isoforms_def", "isoforms_undef", "spill", "render_blocks")
+# smi_isoform_output, in SMI_ISO_OUT_* order: the file name suffixes (PREFIX_<name>)
+ISOFORM_OUTPUTS = ("isomatrix.txt", "isometrics.txt", "molinfos.txt", "genematrix.txt", "genemetrics.txt", "cellmetrics.txt", "juncmatrix.txt",
+                   "juncmetrics.txt", "bulkgene.txt", "bulkiso.txt")
+ISOFORM_TAGS = ("cell_tag", "umi_tag", "gene_tag", "rn_tag")
+
+
+class Isoform:
+    """IsoformMatrix (smi_isoform_*): the refFlat and cell-list texts, then BAM segments in; the output texts out.  Keywords: the fields
+    of smi_isoform_config (tags as two-character strings, mapqv0 / to_bulk as bools)."""
+
+    def __init__(self, ctx, refflat, csv, **kw):
+        self._lib = load_library()
+        cfg = IsoformConfig()
+        self._lib.smi_isoform_default_config(ctypes.byref(cfg))
+        for k, v in kw.items():
+            if k in ISOFORM_TAGS:
+                b = str(v).encode()
+                if len(b) != 2:
+                    raise SmiError(f"{k}: a tag is two characters")
+                setattr(cfg, k, b)
+            elif k in ("max_clip", "mapqv0", "delta", "to_bulk", "n_threads", "lds_tx", "budget_bytes"):
+                setattr(cfg, k, int(v))
+            else:
+                raise ValueError(f"unknown smi_isoform_config field {k!r}")
+        rf = np.frombuffer(bytes(refflat), dtype=np.uint8)
+        cs = np.frombuffer(bytes(csv), dtype=np.uint8)
+        self._h = ctypes.c_void_p()
+        if self._lib.smi_isoform_create(ctx._h, ctypes.byref(cfg), _ptr(rf) if rf.size else None, rf.size, _ptr(cs) if cs.size else None, cs.size,
+                                        ctypes.byref(self._h)):
+            self._h = None
+            raise SmiError(self._lib.smi_last_error().decode())
+        self._ctx = ctx
+        self.stage_ms = dict(iso=0.0, sort=0.0, render=0.0)
+
+    def add_segment(self, bam, recs):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
+        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
+            raise ValueError("bam: a contiguous 1-D uint8 array")
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != BAM_RECORD_DTYPE:
+            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
+        if self._lib.smi_isoform_add_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)):
+            raise SmiError(self._lib.smi_last_error().decode())
+
+    def run(self):
+        """reads, molecules, K-ISO, K-MTX -> {file name suffix: bytes} (the bulk files only with to_bulk)"""
+        ms = np.zeros(3, dtype=np.float32)
+        if self._lib.smi_isoform_run(self._h, _ptr(ms)):
+            raise SmiError(self._lib.smi_last_error().decode())
+        self.stage_ms = dict(iso=float(ms[0]), sort=float(ms[1]), render=float(ms[2]))
+        outs = {}
+        for i, name in enumerate(ISOFORM_OUTPUTS):
+            n = ctypes.c_size_t(0)
+            self._lib.smi_isoform_output(self._h, i, None, 0, ctypes.byref(n))
+            out = np.zeros(max(n.value, 1), dtype=np.uint8)
+            if self._lib.smi_isoform_output(self._h, i, _ptr(out), out.size, ctypes.byref(n)):
+                raise SmiError(self._lib.smi_last_error().decode())
+            outs[name] = out[:n.value].tobytes()
+        return outs
+
+    def isobam(self, bam, recs):
+        """ISOBAM after run(): the segment's records with IG / IT (inflated BAM record bytes, input order)"""
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != BAM_RECORD_DTYPE:
+            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
+        n = ctypes.c_size_t(0)
+        args = (self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size))
+        if self._lib.smi_isoform_isobam(*args, None, 0, ctypes.byref(n)):
+            raise SmiError(self._lib.smi_last_error().decode())
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        if self._lib.smi_isoform_isobam(*args, _ptr(out), out.size, ctypes.byref(n)):
+            raise SmiError(self._lib.smi_last_error().decode())
+        return out[:n.value]
+
+    def counts(self):
+        c = np.zeros(len(ISOFORM_COUNTS), dtype=np.int64)
+        self._lib.smi_isoform_counts(self._h, _ptr(c))
+        return dict(zip(ISOFORM_COUNTS, (int(x) for x in c)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.smi_isoform_free(self._h)
             self._h = None
 
     __del__ = close

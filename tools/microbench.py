@@ -36,9 +36,9 @@ def main():
     used = synth.pick_used(wl, 5000, seed=2)
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
-            "consensus": leg_consensus}
+            "consensus": leg_consensus, "isoform": leg_isoform}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -579,6 +579,94 @@ def leg_consensus(pkg, synth, ctx, dev, wl, used, res):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     res["consensus"] = out
+
+
+def _isoform_fixture(n_genes, n_recs, n_cells, seed=41):
+    """a seeded refFlat (n_genes genes of 1..19 transcripts, 1..40 exons each) and a BAM of n_recs records: molecules of 1..3 reads, each
+    read spliced along one transcript with junction ends moved by up to 3 bases"""
+    import struct
+
+    from sicelore_amd import lib
+
+    rng = np.random.default_rng(seed)
+    lines, genes = [], []
+    pos = 10_000
+    for g in range(n_genes):
+        n_ex = int(rng.integers(1, 41))
+        span = []
+        p = pos
+        for _e in range(n_ex):
+            ln = int(rng.integers(60, 400))
+            span.append((p, p + ln))
+            p += ln + int(rng.integers(200, 3000))
+        txs = []
+        for t in range(int(rng.integers(1, 20))):
+            keep = [e for e in span if rng.random() < 0.8] or span[:1]
+            txs.append(keep)
+            lines.append(f"GENE{g}\tTX{g}.{t}\tchr1\t+\t{keep[0][0]}\t{keep[-1][1]}\t{keep[0][0]}\t{keep[-1][1]}\t{len(keep)}\t"
+                         + "".join(f"{a}," for a, _b in keep) + "\t" + "".join(f"{b}," for _a, b in keep) + "\n")
+        genes.append(txs)
+        pos = p + 5000
+    recs, k, m = [], 0, 0
+    while k < n_recs:
+        g = int(rng.integers(n_genes))
+        ex = genes[g][int(rng.integers(len(genes[g])))]
+        cell, umi = b"CELL%05d-1" % int(rng.integers(n_cells)), b"U%09d" % m
+        aux_m = b"BCZ" + cell + b"\0" + b"U8Z" + umi + b"\0" + b"GEZ" + b"GENE%d" % g + b"\0"
+        for _r in range(int(rng.integers(1, 4))):
+            cig, cur, p1 = [], None, ex[0][0] + 1
+            for i, (a, b) in enumerate(ex):
+                s0, e0 = a + 1, b
+                if i:
+                    s0 += int(rng.integers(-3, 4))
+                if i < len(ex) - 1:
+                    e0 += int(rng.integers(-3, 4))
+                if cur is not None:
+                    cig.append((s0 - cur - 1) << 4 | 3)
+                cig.append(max(1, e0 - s0 + 1) << 4 | 0)
+                cur = s0 + max(1, e0 - s0 + 1) - 1
+            name = b"r%09d\0" % k
+            aux = aux_m + b"def" + struct.pack("<f", float(rng.integers(0, 50)) / 500)
+            body = struct.pack("<iiBBHHHiiii", 0, p1 - 1, len(name), 60, 4680, len(cig), 0, 0, -1, -1, 0) + name + struct.pack(f"<{len(cig)}I", *cig) + aux
+            recs.append(struct.pack("<I", len(body)) + body)
+            k += 1
+        m += 1
+    head = b"BAM\1" + struct.pack("<I", 0) + struct.pack("<I", 1) + struct.pack("<I", 5) + b"chr1\0" + struct.pack("<I", 2 ** 31 - 1)
+    bam = np.frombuffer(head + b"".join(recs), dtype=np.uint8)
+    csv = "".join(f"CELL{c:05d}-1\n" for c in range(n_cells))
+    return "".join(lines), csv, lib.bgzf_deflate(bam, level=1, n_threads=16), k, m
+
+
+def leg_isoform(pkg, synth, ctx, dev, wl, used, res):
+    """K-ISO + K-MTX (`IsoformMatrix`): a seeded refFlat of SMI_MB_ISO_GENES genes (20,000; about 10 transcripts each, up to 40 exons), 5,000
+    cells, SMI_MB_ISO_RECS records (2,000,000).  File to file with ISOBAM: device ms of K-ISO, sort + RLE and render (HIP events), wall
+    seconds per phase, bytes written per second."""
+    import shutil
+    import tempfile
+
+    iso = importlib.import_module(graft.PKG_NAME + ".isoformmatrix")
+    n_genes = int(os.environ.get("SMI_MB_ISO_GENES", "20000"))
+    n_recs = int(os.environ.get("SMI_MB_ISO_RECS", "2000000"))
+    t0 = time.perf_counter()
+    ref, csv, z, n_rec, n_mol = _isoform_fixture(n_genes, n_recs, 5000)
+    out = {"genes": n_genes, "records": n_rec, "molecules_generated": n_mol, "cells": 5000, "fixture_s": time.perf_counter() - t0}
+    d = tempfile.mkdtemp(prefix="isoform_")
+    try:
+        z.tofile(os.path.join(d, "in.bam"))
+        with open(os.path.join(d, "r.refFlat"), "w") as f:
+            f.write(ref)
+        with open(os.path.join(d, "c.csv"), "w") as f:
+            f.write(csv)
+        info = iso.isoform_matrix(ctx, os.path.join(d, "in.bam"), os.path.join(d, "r.refFlat"), os.path.join(d, "c.csv"), d, n_threads=16,
+                                  isobam=True)
+        keys = ("records", "molecules", "onematch", "ambiguous", "nomatch", "monoexon", "matrix_isoforms", "matrix_genes", "matrix_junctions",
+                "spill", "render_blocks")
+        out["file_to_file"] = dict({k: info[k] for k in keys}, stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"],
+                                   bytes_written=info["bytes_written"], bytes_per_s=info["bytes_written"] / info["wall_s"],
+                                   records_per_s=info["records"] / info["wall_s"])
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    res["isoform"] = out
 
 
 def leg_inflate(pkg, synth, ctx, dev, wl, used, res):

@@ -8,14 +8,17 @@ one MI355X per rank.  A step = one pass of the hot path over the rank's batch, i
 N > 1 without WORLD_SIZE in the environment: this process starts the N ranks itself (`python -m torch.distributed.run
 --nproc-per-node N bench.py ...` as a child, before anything here touches the GPU) and exits with the child's code; under
 torch.distributed.run it is one of the ranks (one per GPU, RCCL).  Prints ONE JSON line on rank 0 (contract in the task
-statement) with `roofline` and `cpu_baseline` objects, `two_pass` (pass 1 -> RCCL all-reduce of the used-barcode histogram ->
-finalize -> pass 2 -> all-reduce of the BarcodesAssigned counters: the one exchange of the path) and
-`value_full_pass2` (the whole of pass 2 from FASTQ text in HBM, beside `value`, never part of it).
+statement) with `config` and `roofline` (from the timed steps' own kernel times).  A plain run does only that: set-up, warm-up,
+the timed steps, --dump-outputs, the line.
 
-`umi_stage` (the second half of BASELINE's metric: assignumis' UMI stage on the device, fed with names from a real pass 2 of the same
-generator behind synthetic alignments), `value_bc_umi` (both stages in sequence), `host_to_host` (pass 2 through the packed boundary:
-host FASTQ text in, `passed` / `failed` text out, PCIe and host threads included) and `file_to_file` (a directory of *.fastq.gz through both
-passes to *_passed.fastq.gz / *_failed.fastq.gz + the two TSVs) ride along, bounded so that the default run stays within minutes.
+--full adds what is measured beside the step, never part of `value`: `cpu_baseline`, the one-time set build (`set_build_ms`,
+`value_one_shot`), `hbm_measured`, `two_pass` (pass 1 -> RCCL all-reduce of the used-barcode histogram -> finalize -> pass 2 ->
+all-reduce of the BarcodesAssigned counters: the one exchange of the path), `value_full_pass2` (the whole of pass 2 from
+FASTQ text in HBM), `umi_stage` (the second half of BASELINE's metric: assignumis' UMI stage on the device, fed with names from a real
+pass 2 of the same generator behind synthetic alignments), `value_bc_umi` (both stages in sequence), `host_to_host` (pass 2 through
+the packed boundary: host FASTQ text in, `passed` / `failed` text out, PCIe and host threads included) and `file_to_file` (a directory
+of *.fastq.gz through both passes to *_passed.fastq.gz / *_failed.fastq.gz + the two TSVs), bounded so that such a run stays within
+minutes.
 
   --total-reads N: strong scaling (BASELINE configs[3]): N reads in all, sharded over the ranks in 1 M-read chunks with global seeds, so
                    every world size processes the same reads; `scaling` is then "strong".
@@ -104,6 +107,9 @@ def parse_args():
     ap.add_argument("--pack-kernel", action="store_true",
                     help="build the step's packed read ends with K-PACK (smi_pack_ends_device) from ASCII reads materialised on the device, instead of "
                          "the generator's own torch packer (same ends; outside the timed region either way)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured beside the timed step: CPU baseline, set build, HBM probe and the two-pass, end-to-end, UMI, "
+                         "host-to-host and file-to-file legs (without it: set-up, warm-up, the timed steps, --dump-outputs, the line)")
     ap.add_argument("--exchange-only", action="store_true")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default: nccl with GPUs, gloo without)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -1063,8 +1069,9 @@ def main():
     used = synth.pick_used(wl, args.cells, seed=2)
     ctx.set_barcode_set_device(wl.to(torch.int32), mode=1)                   # -g semantics: search set = whole list
     set_cold = ctx.set_stats()                                                # the first build of the process: with the allocation of its 18.5 GB
-    ctx.set_barcode_set_device(wl.to(torch.int32), mode=1)                   # ... and once more into the structures that now exist
-    set_warm = ctx.set_stats()
+    if args.full:
+        ctx.set_barcode_set_device(wl.to(torch.int32), mode=1)               # ... and once more into the structures that now exist
+        set_warm = ctx.set_stats()
     ends = torch.empty((28, 2 * max(n, 1)), dtype=torch.int32, device=dev)   # packed read ends (bit-planes)
     lens = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     truth = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
@@ -1085,7 +1092,7 @@ def main():
             ends[:, 2 * c0:2 * (c0 + m)] = synth.pack_ends(rd["head"], rd["tail"])
             lens[c0:c0 + m] = (2 * synth.END_BASES + rd["mid_len"]).to(torch.int32)
         truth[c0:c0 + m] = rd["truth"]
-        if c0 == 0 and rank == 0:
+        if c0 == 0 and rank == 0 and args.full and not args.no_cpu_baseline:
             k = min(args.cpu_sample, m)
             cpu_reads = {key: (v[:k].cpu() if torch.is_tensor(v) else v) for key, v in rd.items()}
         del rd
@@ -1180,7 +1187,7 @@ def main():
         n_all = n
 
     two_pass = None
-    if args.two_pass_reads > 0:
+    if args.full and args.two_pass_reads > 0:
         two_pass = two_pass_leg(pkg, synth, dev, dist, rank, world, wl, used, args.two_pass_reads)   # collective: every rank takes part
 
     if rank != 0:
@@ -1207,7 +1214,7 @@ def main():
                      "the matching mutation steps off one bucket of a table of that neighbourhood (P.nt, three slots per entry: a second bucket "
                      "is rare) instead of making the 124 probes: the algorithmic figure counts probes answered, not bytes moved, so `frac` is "
                      "the counter traffic over the HBM peak")
-    probe = hbm_probe(dev) if world == 1 else None
+    probe = hbm_probe(dev) if args.full and world == 1 else None
     if probe and "gather_512MiB_G_per_s" in probe and tj and "k_bc_match_ed1" in tj and tj["k_bc_match_ed1"].get("l2_misses_per_launch"):
         # K-BC1 against what random sector reads can reach on this GPU: its L2 misses per second beside the measured gather rates
         miss_rate = tj["k_bc_match_ed1"]["l2_misses_per_launch"] * (n / tj["k_bc_match_ed1"]["reads_per_launch"]) / (k_match * 1e-3) / 1e9
@@ -1261,22 +1268,23 @@ def main():
     # The one-time cost behind K-BC1: the pyramid, the offset filter nb / nb5 and the neighbourhood table nt of the WHOLE list are built
     # once per job (-g semantics; the default two-pass flow loads the list as membership only, ~10 ms, and builds these for the used list, a few ms).
     # `value` repeats the step on resident structures; `value_one_shot` is the same batch as a job of its own: build (with its allocations) + one step.
-    res["set_build_ms"] = set_warm["build_ms"]
-    res["set_build_cold_ms"] = set_cold["build_ms"]
-    res["set_hbm_bytes"] = set_warm["hbm_bytes"]
-    res["value_one_shot"] = n * world / (set_cold["build_ms"] * 1e-3 + ms_per_step * 1e-3)
-    res["value_one_shot_warm_allocator"] = n * world / (set_warm["build_ms"] * 1e-3 + ms_per_step * 1e-3)   # (a second job of the same process: no hipMalloc)
-    res["set_build_note"] = ("smi_set_barcode_set_device of the 3.6 M list: membership pyramid + nb (512 MiB, atomics) + nb5 (2.5 GiB, transposed from nb) on a side "
-                             "stream beside nt (3 slots per neighbour + bucket counters); profiles/r06/set_build_kernel_stats.csv has the kernels; "
-                             "set_build_cold_ms includes hipMalloc of set_hbm_bytes")
+    if args.full:
+        res["set_build_ms"] = set_warm["build_ms"]
+        res["set_build_cold_ms"] = set_cold["build_ms"]
+        res["set_hbm_bytes"] = set_warm["hbm_bytes"]
+        res["value_one_shot"] = n * world / (set_cold["build_ms"] * 1e-3 + ms_per_step * 1e-3)
+        res["value_one_shot_warm_allocator"] = n * world / (set_warm["build_ms"] * 1e-3 + ms_per_step * 1e-3)   # (a second job of the same process: no hipMalloc)
+        res["set_build_note"] = ("smi_set_barcode_set_device of the 3.6 M list: membership pyramid + nb (512 MiB, atomics) + nb5 (2.5 GiB, transposed from nb) on a "
+                                 "side stream beside nt (3 slots per neighbour + bucket counters); profiles/r06/set_build_kernel_stats.csv has the kernels; "
+                                 "set_build_cold_ms includes hipMalloc of set_hbm_bytes")
     if probe:
         res["hbm_measured"] = probe
     if two_pass is not None:
         res["two_pass"] = two_pass
-    if world == 1 and args.single_process_gpus > 0:
+    if args.full and world == 1 and args.single_process_gpus > 0:
         res["two_pass_single_process"] = two_pass_single_process(pkg, synth, wl, used, max(args.two_pass_reads, 50_000),
                                                                  min(args.single_process_gpus, torch.cuda.device_count()))
-    if world == 1 and args.e2e_reads > 0:
+    if args.full and world == 1 and args.e2e_reads > 0:
         res["end_to_end"] = end_to_end_leg(ctx, synth, dev, used, args.e2e_reads, lane_counts=tuple(int(x) for x in args.e2e_lanes.split(",")))
         # the number that corresponds to "pass 2" as the reference runs it: FASTQ text in HBM -> passed / failed text in HBM,
         # chimera splitter, K-PACK and the writer included (beside `value`, never part of it)
@@ -1284,19 +1292,19 @@ def main():
         # lanes is `reads_per_s_best_lanes` / `value_full_pass2_lanes`, with `lanes_at_best`)
         res["value_full_pass2"] = res["end_to_end"]["reads_per_s"]
         res["value_full_pass2_lanes"] = res["end_to_end"]["reads_per_s_best_lanes"]
-    if world == 1 and args.umi_molecules > 0:
+    if args.full and world == 1 and args.umi_molecules > 0:
         res["umi_stage"] = umi_stage_leg(pkg, synth, ctx, used, args.umi_molecules)
         r_umi = res["umi_stage"]["records_per_s"]
         res["value_bc_umi"] = n / (ms_per_step * 1e-3 + n_found / r_umi)
         if args.assignumis_file_records > 0:
             rows = umi_stage_leg.rows[:args.assignumis_file_records]
             res["assignumis_file_to_file"] = assignumis_file_leg(pkg, synth, ctx, rows, n_threads=16)
-    if world == 1 and args.h2h_reads > 0:
+    if args.full and world == 1 and args.h2h_reads > 0:
         res["host_to_host"] = host_to_host_leg(pkg, synth, ctx, dev, used, args.h2h_reads)
         res["value_host_to_host"] = res["host_to_host"]["reads_per_s"]
-    if world == 1 and args.f2f_reads > 0:
+    if args.full and world == 1 and args.f2f_reads > 0:
         res["file_to_file"] = file_to_file_leg(pkg, synth, ctx, dev, wl, used, args.f2f_reads, scratch=args.f2f_dir)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         sor = graft.load_oracle()
         sor.build()
         cores = host_cpu_quota()     # OpenMP threads = the CPUs the cgroup grants (the box shows 256, the pool grants 16)

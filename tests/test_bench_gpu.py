@@ -31,7 +31,7 @@ def _common(d, steps):
 
 def test_bench_config1_small():
     d = _run("--reads", "300000", "--whitelist", "400000", "--steps", "2", "--warmup", "1", "--cpu-sample", "20000", "--e2e-reads", "30000",
-             "--two-pass-reads", "20000")
+             "--two-pass-reads", "20000", "--full")
     _common(d, 2)
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["matches_gpu"] is True
     assert d["end_to_end"]["reads_per_s"] > 0 and d["value_full_pass2"] == d["end_to_end"]["reads_per_s"] == d["end_to_end"]["reads_per_s_one_lane"]
@@ -42,6 +42,16 @@ def test_bench_config1_small():
     assert d["two_pass"]["collective"]["ranks_counted"] == 1
     assert d["two_pass"]["same_used_list_on_all_ranks"] is True and d["two_pass"]["pass2_assigned"] > 0
     assert set(d["roofline"]["kernels_ms"]) == {"k_scan<10>", "k_bc_match_ed1<1>"}
+
+
+def test_bench_plain_run_is_the_step_alone():
+    """without --full the line holds the timed step, its config and roofline, and none of what is measured beside it"""
+    d = _run("--reads", "200000", "--whitelist", "400000", "--steps", "2", "--warmup", "1")
+    _common(d, 2)
+    assert set(d["roofline"]["kernels_ms"]) == {"k_scan<10>", "k_bc_match_ed1<1>"} and d["config"]["bc_assigned_total"] > 0
+    for key in ("cpu_baseline", "set_build_ms", "value_one_shot", "hbm_measured", "two_pass", "end_to_end", "value_full_pass2", "umi_stage",
+                "value_bc_umi", "assignumis_file_to_file", "host_to_host", "file_to_file"):
+        assert key not in d, key
 
 
 def test_bench_pack_kernel_gives_the_same_step():
@@ -121,7 +131,7 @@ def test_bench_two_ranks_on_one_gpu_weak_and_strong():
     on the GPU with two ranks that share the box's one device (SMI_BENCH_SHARE_GPU, gloo: RCCL refuses two ranks on one device) --
     a rehearsal of the driver's multi-GPU run, not a measurement"""
     small = ["--whitelist", "400000", "--steps", "2", "--warmup", "1", "--e2e-reads", "0", "--umi-molecules", "0", "--h2h-reads", "0",
-             "--f2f-reads", "0", "--two-pass-reads", "20000"]
+             "--f2f-reads", "0", "--two-pass-reads", "20000", "--full"]
     two = ["--gpus", "2", "--backend", "gloo"]
     env = {"SMI_BENCH_SHARE_GPU": "1"}
     w = _run("--reads", "200000", *small, *two, env=env)

@@ -15,7 +15,7 @@ ulimit -c 0
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 ROOT=$(pwd)
-OFF="--two-pass-reads 0 --umi-molecules 0 --h2h-reads 0 --f2f-reads 0 --assignumis-file-records 0"
+OFF="--full --two-pass-reads 0 --umi-molecules 0 --h2h-reads 0 --f2f-reads 0 --assignumis-file-records 0"   # --full, but only the end-to-end leg and the CPU baseline
 while [ $# -gt 0 ]; do
   part=$1; shift
   case $part in

@@ -1164,6 +1164,56 @@ int smi_isoform_free(smi_isoform *h);
 int smi_isoform_isobam(smi_isoform *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n, uint8_t *out, size_t cap,
                        size_t *n_out);
 
+/* ---- SNPMatrix (K-SNP + K-MTX, smi_snp.hip) ---------------------------------------------------------------------------------------------
+ * SNPMatrix.doWork (SNPMatrix.java:L72-216), DESIGN.md section 8e.
+ * smi_snp_create: the SNP text (L100-120: `chromosome,position[|position...],strand,name` per line up to the first empty line; a line whose
+ * chromosome is not among ref_names -- the BAM's @SQ names in dictionary order, smi_bam_header -- is skipped; fewer than 4 fields or a
+ * position that is no integer fails the call naming the line) and the CSV cell list (CellList: one barcode per line, "-1" removed).
+ * smi_snp_add_segment: records of an inflated BAM segment (smi_bam_index_records) in any order; K-SNP evaluates every line against every
+ * record (samReader.query L121, the strand test L126, LongreadRecord.fromSAMRecord L128, getReadPositionAtReferencePosition L140, the
+ * MINRN / MINQV filters L165-180) and the hits of listed cells are held.  A record the reference would fail on in mid-run (attributes of
+ * another type than it casts, a CIGAR fromSAMRecord cannot walk, no qualities, a kept hit without UMI) fails the call naming the read.
+ * smi_snp_run: rows, distinct UMIs per (row, cell), the dense matrix (Matrix.addMolecule L62-105, writeIsoformMatrix L158-223 with a null
+ * model); with no row every output stays empty (L209-210).  stage_ms (may be NULL): SMI_SNP_STAGES device times: K-SNP (all segments),
+ * sorts + de-duplication + run-length encoding, render.  smi_snp_output: text of SMI_SNP_OUT_*; out == NULL -> size only; cap too small
+ * -> returns 1.  smi_snp_counts: SMI_SNP_COUNTS entries.  smi_snp_line_counts: per line read from the SNP text, in file order, hits,
+ * lowRN, lowQV (the "processing..." line L193), -1 -1 -1 for a skipped line; counts == NULL -> *n_lines only; cap_lines too small -> 1. */
+#define SMI_SNP_RECORDS 0        /* records seen */
+#define SMI_SNP_LINES 1          /* SNP lines on a chromosome of the BAM */
+#define SMI_SNP_CELLS 2          /* cells of the list */
+#define SMI_SNP_HITS 3           /* STATISTICS hits (cells outside the list included) */
+#define SMI_SNP_LOWRN 4          /* STATISTICS lowRN */
+#define SMI_SNP_LOWQV 5          /* STATISTICS lowQV */
+#define SMI_SNP_PAIRS 6          /* (record, line) pairs with every position on the read: hits + lowRN + lowQV */
+#define SMI_SNP_KEPT 7           /* hits of listed cells: the molinfos lines */
+#define SMI_SNP_ROWS 8           /* matrix rows */
+#define SMI_SNP_TOTAL_COUNT 9    /* sum of the matrix */
+#define SMI_SNP_RENDER_BLOCKS 10 /* row blocks rendered */
+#define SMI_SNP_COUNTS 11
+#define SMI_SNP_OUT_MATRIX 0
+#define SMI_SNP_OUT_METRICS 1
+#define SMI_SNP_OUT_MOLINFOS 2
+#define SMI_SNP_OUTPUTS 3
+#define SMI_SNP_STAGES 3
+typedef struct {
+    char cell_tag[4], umi_tag[4], gene_tag[4], rn_tag[4];  /* CELLTAG UMITAG GENETAG RNTAG: two characters + NUL */
+    int32_t max_clip;      /* MAXCLIP (150): accepted, chimeric records are not dropped on this path */
+    int32_t min_rn;        /* MINRN (0) */
+    int32_t min_qv;        /* MINQV (0) */
+    int32_t n_threads;     /* host threads of the record checks */
+    int64_t budget_bytes;  /* K-MTX device memory per row block (0: 1 GiB) */
+} smi_snp_config;
+typedef struct smi_snp smi_snp;
+int smi_snp_default_config(smi_snp_config *cfg);
+int smi_snp_create(smi_ctx *ctx, const smi_snp_config *cfg, const char *snp, size_t n_snp, const char *csv, size_t n_csv,
+                   const char *const *ref_names, int32_t n_refs, smi_snp **out);
+int smi_snp_add_segment(smi_snp *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n);
+int smi_snp_run(smi_snp *h, float *stage_ms);
+int smi_snp_output(const smi_snp *h, int32_t which, uint8_t *out, size_t cap, size_t *n_out);
+int smi_snp_counts(const smi_snp *h, int64_t *counts);
+int smi_snp_line_counts(const smi_snp *h, int64_t *counts, size_t cap_lines, size_t *n_lines);
+int smi_snp_free(smi_snp *h);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

@@ -6,6 +6,7 @@
     java -jar [-Xmx..] NanoporeBC_UMI_finder-2.1.jar tagbamwithread --inFastq <fastq[.gz]> --inBam <bam> --outBam <bam> --readTag XX [--qvTag YY]
 
     java -jar [-Xmx..] Sicelore-2.1.jar ComputeConsensus -I <bam> -O <fastq> [-T n] [-CELLTAG BC] ... [-MAXREADS 20] [-MINPS 3] [-MAXPS 20]   (or I=<bam> O=<fastq> ...)
+    java -jar [-Xmx..] Sicelore-2.1.jar SNPMatrix I=<bam> CSV=<barcodes> SNP=<sites.csv> O=<dir> [PREFIX=snp] [MINRN=0] [MINQV=0] [CELLTAG=BC] [UMITAG=U8] [RNTAG=RN] ...
 
 become   python sicelore-2.1_amd scanfastq ... / assignumis ... / tagbamwithread ... / ComputeConsensus ...   (the directory is runnable: __main__.py; a `java` wrapper that drops
 `-jar`, `-Xmx..` and the jar's name makes /root/reference/quickrun-2.1.sh:35,42 run unchanged, tests/test_cli_gpu.py does exactly that).
@@ -600,6 +601,41 @@ def isoformmatrix(argv):
     return 0
 
 
+# SNPMatrix (SNPMatrix.java:L28-61): Picard's option names -> (smi_snp_config field or None, kind, default).  GENETAG names a tag whose
+# type the parser checks; TSOENDTAG, POLYASTARTTAG, CDNATAG, USTAG and MAXCLIP change nothing on this path (no sequences are loaded and
+# chimeric records are not dropped).
+SNP_OPTIONS = {
+    "I": (None, "path", None), "CSV": (None, "path", None), "SNP": (None, "path", None), "O": (None, "path", None),
+    "PREFIX": (None, "str", "snp"), "CELLTAG": ("cell_tag", "tag", "BC"), "UMITAG": ("umi_tag", "tag", "U8"),
+    "GENETAG": ("gene_tag", "tag", "GE"), "TSOENDTAG": (None, "tag", "TE"), "POLYASTARTTAG": (None, "tag", "PS"), "CDNATAG": (None, "tag", "CS"),
+    "USTAG": (None, "tag", "US"), "RNTAG": ("rn_tag", "tag", "RN"), "MAXCLIP": ("max_clip", "int", 150), "MINRN": ("min_rn", "int", 0),
+    "MINQV": ("min_qv", "int", 0), "VALIDATION_STRINGENCY": (None, "stringency", "STRICT"),
+}
+SNP_LONG = {"INPUT": "I", "OUTPUT": "O"}
+
+
+def snpmatrix(argv):
+    """SNPMatrix.doWork (L72-216).  VALIDATION_STRINGENCY is accepted and changes nothing."""
+    o = _picard_parse(argv, "SNPMatrix", SNP_OPTIONS, SNP_LONG)
+    need = [k for k in ("I", "CSV", "SNP", "O") if k not in o]
+    if need:
+        raise CliError(f"sub-command SNPMatrix: missing required option(s) {', '.join(need)}")
+    for k in ("I", "CSV", "SNP"):                                           # IOUtil.assertFileIsReadable (L74-76)
+        if not os.path.isfile(o[k]):
+            raise CliError(f"SNPMatrix: {k}={o[k]}: no such file")
+    opt = {k: o.get(k, d) for k, (_f, _kind, d) in SNP_OPTIONS.items()}
+    if not os.path.isdir(opt["O"]):
+        raise CliError(f"SNPMatrix: O={opt['O']}: no such directory")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise CliError("SNPMatrix runs in one process on one GPU in this build: start it without torchrun")
+    cfg = {f: opt[k] for k, (f, _kind, _d) in SNP_OPTIONS.items() if f is not None}
+    from .snpmatrix import snp_matrix
+    ctx = _context()
+    info = snp_matrix(ctx, o["I"], o["CSV"], o["SNP"], opt["O"], prefix=opt["PREFIX"], n_threads=_ncpu({}), log=sys.stderr, **cfg)
+    print(f"DONE -- {info['records']} records, {info['lines']} SNP lines, {info['rows']} rows, {info['cells']} cells", file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
@@ -621,7 +657,9 @@ def main(argv=None):
             return computeconsensus(rest)
         if sub == "IsoformMatrix":
             return isoformmatrix(rest)
-        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus and IsoformMatrix (mergestats, parseillumina: "
+        if sub == "SNPMatrix":
+            return snpmatrix(rest)
+        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus, IsoformMatrix and SNPMatrix (mergestats, parseillumina: "
                        "SURVEY 2, out of scope)")
     except CliError as e:
         print(f"ERROR: {e}", file=sys.stderr)

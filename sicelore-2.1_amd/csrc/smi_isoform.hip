@@ -22,7 +22,7 @@
 //   molecule's junction set as ids of the table of unique model junctions (a second launch writes them at the scanned offsets).
 // K-MTX: 64-bit (row << 32 | cell) codes per counted molecule; hipcub radix sort + run-length encoding give the UMI counts (a molecule is
 //   one UMI of its cell); the dense rows are rendered in row blocks under a device-memory budget, one wavefront per row: a length pass, a
-//   scan, the write.
+//   scan, the write (smi_mtx.h, shared with SNPMatrix).
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -37,13 +37,16 @@
 
 #include "smi_internal.h"
 #include "smi_longread.h"
+#include "smi_mtx.h"
 
 namespace smi {
 namespace {
 
+using mtx::DevBuf;
+using mtx::Events;
+
 constexpr int kIsoWaves = 4;     // waves per block of K-ISO
 constexpr int kLdsTx = 2048;     // candidate counts of one wave held in LDS
-constexpr int kRenderWaves = 4;  // waves per block of the renderer
 
 enum IsoStatus : int32_t { kNone = 0, kMono = 1, kOne = 2, kAmbiguous = 3, kNomatch = 4 };
 
@@ -211,235 +214,14 @@ __global__ __launch_bounds__(64 * kIsoWaves) void k_iso(IsoArgs a) {
     if (!WRITE && lane == 0) a.out_njunc[m] = n_out;
 }
 
-// ---- K-MTX renderer ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int digits(uint32_t v) {
-    int n = 1;
-    while (v >= 10) {
-        v /= 10;
-        n++;
-    }
-    return n;
-}
-
-// dense[(row - r0) * nc + cell] = count, for the runs of rows r0 ..
-__global__ void k_mtx_scatter(const uint64_t *__restrict__ code, const uint32_t *__restrict__ cnt, int64_t k0, int64_t k1, int32_t r0, int32_t nc,
-                              uint32_t *__restrict__ dense) {
-    const int64_t k = k0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (k >= k1) return;
-    const uint64_t c = code[k];
-    dense[(int64_t)((int32_t)(c >> 32) - r0) * nc + (uint32_t)c] = cnt[k];
-}
-
-// LEN: bytes of row r0 + i (label, "\t" + count per cell, "\n") into len[i]; WRITE: the row at off[i]
-template <bool WRITE>
-__global__ __launch_bounds__(64 * kRenderWaves) void k_mtx_render(const uint32_t *__restrict__ dense, int32_t n_rows, int32_t nc, int32_t r0,
-                                                                   const uint8_t *__restrict__ labels, const uint64_t *__restrict__ lab_off,
-                                                                   uint64_t *__restrict__ len, uint8_t *__restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
-    if (i >= n_rows) return;
-    const uint32_t *row = dense + (int64_t)i * nc;
-    const uint64_t l0 = lab_off[r0 + i], ln = lab_off[r0 + i + 1] - l0;
-    if (!WRITE) {
-        uint64_t n = 0;
-        for (int c = lane; c < nc; c += 64) n += 1 + digits(row[c]);
-        for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-        if (lane == 0) len[i] = n + ln + 1;
-        return;
-    }
-    uint8_t *dst = out + len[i];  // (the exclusive scan of the lengths)
-    for (uint64_t k = lane; k < ln; k += 64) dst[k] = labels[l0 + k];
-    uint64_t pos = ln;
-    for (int c0 = 0; c0 < nc; c0 += 64) {
-        const int c = c0 + lane;
-        const uint32_t v = c < nc ? row[c] : 0;
-        const int w = c < nc ? 1 + digits(v) : 0;
-        int incl = w;  // inclusive prefix sum across the wave
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(incl, o);
-            if (lane >= o) incl += y;
-        }
-        if (c < nc) {
-            uint8_t *p = dst + pos + (incl - w);
-            p[0] = '\t';
-            uint32_t x = v;
-            for (int k = w - 1; k >= 1; k--) {
-                p[k] = (uint8_t)('0' + x % 10);
-                x /= 10;
-            }
-        }
-        pos += __shfl(incl, 63);
-    }
-    if (lane == 0) dst[pos] = '\n';
-}
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        if (hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
-            set_error("IsoformMatrix: device allocation of " + std::to_string(n * sizeof(T)) + " bytes failed");
-            return SMI_ERR_HIP;
-        }
-        return SMI_OK;
-    }
-    int put(const std::vector<T> &v, hipStream_t s) {
-        if (int rc = alloc(v.size())) return rc;
-        if (!v.empty()) SMI_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-        return SMI_OK;
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-    int begin(hipStream_t s) {
-        if (!a) SMI_HIP(hipEventCreate(&a));
-        if (!b) SMI_HIP(hipEventCreate(&b));
-        SMI_HIP(hipEventRecord(a, s));
-        return SMI_OK;
-    }
-    int end(hipStream_t s, float *acc) {
-        SMI_HIP(hipEventRecord(b, s));
-        SMI_HIP(hipEventSynchronize(b));
-        float ms = 0.f;
-        SMI_HIP(hipEventElapsedTime(&ms, a, b));
-        *acc += ms;
-        return SMI_OK;
-    }
-};
 
 // ---- host parsing -----------------------------------------------------------------------------------------------------------------------
 using lr::Aux;
+using lr::drop_minus1;
+using lr::jint;
+using lr::jsplit;
+using lr::walk_junctions;
 
-std::string drop_minus1(std::string_view v) {  // String.replace("-1", ""): every occurrence, left to right
-    std::string s(v);
-    for (size_t k = s.find("-1"); k != std::string::npos; k = s.find("-1", k)) s.erase(k, 2);
-    return s;
-}
-
-// Java's String.split(regex) for a one-character separator: trailing empty strings removed
-std::vector<std::string_view> jsplit(std::string_view s, char sep) {
-    std::vector<std::string_view> out;
-    size_t b = 0;
-    for (size_t i = 0; i <= s.size(); i++)
-        if (i == s.size() || s[i] == sep) {
-            out.push_back(s.substr(b, i - b));
-            b = i + 1;
-        }
-    while (!out.empty() && out.back().empty()) out.pop_back();
-    if (s.empty()) out.assign(1, std::string_view());  // "".split(x) = [""]
-    return out;
-}
-
-// Integer.valueOf
-bool jint(std::string_view s, int32_t &v) {
-    if (s.empty()) return false;
-    size_t i = 0;
-    bool neg = false;
-    if (s[0] == '-' || s[0] == '+') {
-        neg = s[0] == '-';
-        i = 1;
-        if (s.size() == 1) return false;
-    }
-    int64_t x = 0;
-    for (; i < s.size(); i++) {
-        if (s[i] < '0' || s[i] > '9') return false;
-        x = x * 10 + (s[i] - '0');
-        if (x > 2147483648ll) return false;
-    }
-    if (neg) x = -x;
-    if (x > 2147483647ll || x < -2147483648ll) return false;
-    v = (int32_t)x;
-    return true;
-}
-
-// LongreadRecord.fromSAMRecord L120-150, literally: the walk over cigar.replaceAll("[0-9]+[IS]", "") split into cigartype ("[0-9]+") and
-// cigarsize ("[A-Z]"); cigartype[i] is the operation BEFORE cigarsize[i], so the last operation is never looked at.  false: the reference
-// throws (no block, a block index past the end, a size that is no integer)
-bool walk_junctions(const uint8_t *bam, const smi_bam_record &r, std::vector<int2> &out) {
-    static const char ops[] = "MIDNSHP=XBBBBBBB";
-    std::string cig;
-    struct Block {
-        int64_t start, len;
-    };
-    std::vector<Block> blocks;  // AlignmentBlocks: M = X
-    int64_t ref = (int64_t)r.pos + 1;
-    for (int k = 0; k < r.n_cigar; k++) {
-        uint32_t c;
-        std::memcpy(&c, bam + r.cigar_off + 4ull * k, 4);
-        const uint32_t op = c & 15, n = c >> 4;
-        if (op == 0 || op == 7 || op == 8) {
-            blocks.push_back({ref, n});
-            ref += n;
-        } else if (op == 2 || op == 3) {
-            ref += n;
-        }
-        if (op == 1 || op == 4) continue;  // replaceAll("[0-9]+[IS]", "")
-        cig += std::to_string(n);
-        cig += ops[op];
-    }
-    if (blocks.empty()) return false;
-    std::vector<std::string_view> type, size;  // cigar.split("[0-9]+"), cigar.split("[A-Z]")
-    {
-        std::string_view s(cig);
-        size_t i = 0;
-        type.push_back(std::string_view());  // the digits at position 0 give a leading ""
-        while (i < s.size()) {
-            while (i < s.size() && s[i] >= '0' && s[i] <= '9') i++;
-            const size_t b = i;
-            while (i < s.size() && !(s[i] >= '0' && s[i] <= '9')) i++;
-            if (i > b) type.push_back(s.substr(b, i - b));
-        }
-        if (s.empty()) type.assign(1, std::string_view());
-        size_t b = 0;
-        for (size_t k = 0; k <= s.size(); k++)
-            if (k == s.size() || (s[k] >= 'A' && s[k] <= 'Z')) {
-                size.push_back(s.substr(b, k - b));
-                b = k + 1;
-            }
-        while (!size.empty() && size.back().empty()) size.pop_back();
-        if (s.empty()) size.assign(1, std::string_view());
-    }
-    int64_t s = blocks[0].start, e = blocks[0].start;
-    std::vector<int64_t> xs, xe;
-    size_t bi = 0;
-    for (size_t i = 0; i < size.size(); i++) {
-        if (bi >= blocks.size() || i >= type.size()) return false;
-        const Block cur = blocks[bi];
-        const std::string_view t = type[i];
-        if (t == "M") bi++;
-        if (t == "N") {
-            xs.push_back(s);
-            xe.push_back(e);
-            s = cur.start;
-        } else if (t == "D") {
-            int32_t len;
-            if (i == 0 || !jint(size[i - 1], len)) return false;
-            if (len > 20) {  // a short intron minimap2 calls a deletion
-                xs.push_back(s);
-                xe.push_back(e);
-                s = cur.start;
-            }
-        }
-        if (t != "D") e = cur.start + cur.len - 1;
-    }
-    xs.push_back(s);
-    xe.push_back(e);
-    out.clear();
-    for (size_t i = 1; i < xs.size(); i++) out.push_back(make_int2((int)xe[i - 1], (int)xs[i]));
-    return true;
-}
 
 enum Outcome : uint8_t { kKept, kNull, kChimeric, kNoGene, kNoUmi, kMapq0, kError };
 
@@ -875,126 +657,6 @@ extern "C" int smi_isoform_add_segment(smi_isoform *h, const uint8_t *bam, size_
     return SMI_OK;
 }
 
-namespace {
-
-// K-MTX for one matrix: codes (row << 32 | cell) -> counts per (row, cell) (sorted codes, device) and the dense rows rendered in blocks
-int matrix(smi_isoform *h, std::vector<uint64_t> &codes, const std::vector<std::string> &labels, std::string &dst, std::vector<int64_t> &row_total,
-           float *ms_sort, float *ms_render) {
-    hipStream_t s = h->ctx->stream;
-    const int64_t nrows = (int64_t)labels.size();
-    const int32_t nc = (int32_t)h->cells.size();
-    row_total.assign(nrows, 0);
-    const size_t n = codes.size();
-    std::vector<uint64_t> ucode;
-    std::vector<uint32_t> ucnt;
-    Events ev;
-    if (n > (size_t)INT32_MAX) {
-        set_error("IsoformMatrix: " + std::to_string(n) + " matrix entries in one matrix; at most 2^31 - 1 are counted in one sort");
-        return SMI_ERR_INVALID;
-    }
-    int end_bit = 32;  // cells < 2^31 in the low word; the row in as many bits above as the rows need
-    while (end_bit < 64 && ((uint64_t)1 << (end_bit - 32)) < (uint64_t)nrows) end_bit++;
-    if (n) {
-        DevBuf<uint64_t> d_in, d_sorted, d_unique;
-        DevBuf<uint32_t> d_cnt;
-        DevBuf<int64_t> d_nrun;
-        DevBuf<uint8_t> d_tmp;
-        if (int rc = d_in.put(codes, s)) return rc;
-        if (int rc = d_sorted.alloc(n)) return rc;
-        if (int rc = d_unique.alloc(n)) return rc;
-        if (int rc = d_cnt.alloc(n)) return rc;
-        if (int rc = d_nrun.alloc(1)) return rc;
-        size_t t1 = 0, t2 = 0;
-        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, d_in.p, d_sorted.p, (int)n, 0, end_bit, s));
-        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, d_sorted.p, d_unique.p, d_cnt.p, d_nrun.p, (int)n, s));
-        if (int rc = d_tmp.alloc(std::max(t1, t2))) return rc;
-        size_t tmp = std::max(t1, t2);
-        if (int rc = ev.begin(s)) return rc;
-        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(d_tmp.p, tmp, d_in.p, d_sorted.p, (int)n, 0, end_bit, s));
-        tmp = std::max(t1, t2);
-        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(d_tmp.p, tmp, d_sorted.p, d_unique.p, d_cnt.p, d_nrun.p, (int)n, s));
-        if (int rc = ev.end(s, ms_sort)) return rc;
-        int64_t nrun = 0;
-        SMI_HIP(hipMemcpy(&nrun, d_nrun.p, sizeof(nrun), hipMemcpyDeviceToHost));
-        ucode.resize(nrun);
-        ucnt.resize(nrun);
-        SMI_HIP(hipMemcpy(ucode.data(), d_unique.p, nrun * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        SMI_HIP(hipMemcpy(ucnt.data(), d_cnt.p, nrun * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    for (size_t k = 0; k < ucode.size(); k++) row_total[ucode[k] >> 32] += ucnt[k];
-    if (nrows == 0) return SMI_OK;
-    // labels back to back; the largest count gives the widest field
-    std::vector<uint8_t> lab;
-    std::vector<uint64_t> lab_off{0};
-    for (auto &l : labels) {
-        lab.insert(lab.end(), l.begin(), l.end());
-        lab_off.push_back(lab.size());
-    }
-    uint32_t maxc = 0;
-    for (uint32_t x : ucnt) maxc = std::max(maxc, x);
-    const int wd = 1 + (int)std::to_string(maxc).size();
-    const int64_t budget = h->cfg.budget_bytes > 0 ? h->cfg.budget_bytes : (int64_t)1 << 30;
-    DevBuf<uint8_t> d_lab;
-    DevBuf<uint64_t> d_lab_off, d_ucode;
-    DevBuf<uint32_t> d_ucnt;
-    if (int rc = d_lab.put(lab, s)) return rc;
-    if (int rc = d_lab_off.put(lab_off, s)) return rc;
-    if (int rc = d_ucode.put(ucode, s)) return rc;
-    if (int rc = d_ucnt.put(ucnt, s)) return rc;
-    std::vector<uint8_t> host;
-    int64_t r0 = 0;
-    size_t k0 = 0;
-    while (r0 < nrows) {
-        // rows of this block: dense counts + the widest rendering of each row within the budget (at least one row)
-        int64_t r1 = r0, bytes = 0;
-        while (r1 < nrows) {
-            const int64_t rb = (int64_t)nc * 4 + (int64_t)(lab_off[r1 + 1] - lab_off[r1]) + (int64_t)nc * wd + 1 + 8;
-            if (r1 > r0 && bytes + rb > budget) break;
-            bytes += rb;
-            r1++;
-        }
-        const int32_t nb = (int32_t)(r1 - r0);
-        size_t k1 = k0;
-        while (k1 < ucode.size() && (int64_t)(ucode[k1] >> 32) < r1) k1++;
-        DevBuf<uint32_t> d_dense;
-        DevBuf<uint64_t> d_len, d_off;
-        DevBuf<uint8_t> d_out, d_tmp;
-        if (int rc = d_dense.alloc((size_t)nb * std::max(nc, 1))) return rc;
-        if (int rc = d_len.alloc(nb + 1)) return rc;
-        if (int rc = d_off.alloc(nb + 1)) return rc;
-        if (int rc = ev.begin(s)) return rc;
-        SMI_HIP(hipMemsetAsync(d_dense.p, 0, (size_t)nb * std::max(nc, 1) * 4, s));
-        SMI_HIP(hipMemsetAsync(d_len.p, 0, (nb + 1) * sizeof(uint64_t), s));
-        if (k1 > k0)
-            hipLaunchKernelGGL(k_mtx_scatter, dim3((unsigned)((k1 - k0 + 255) / 256)), dim3(256), 0, s, d_ucode.p, d_ucnt.p, (int64_t)k0, (int64_t)k1,
-                               (int32_t)r0, nc, d_dense.p);
-        const unsigned gb = (unsigned)((nb + kRenderWaves - 1) / kRenderWaves);
-        hipLaunchKernelGGL(k_mtx_render<false>, dim3(gb), dim3(64 * kRenderWaves), 0, s, d_dense.p, nb, nc, (int32_t)r0, d_lab.p, d_lab_off.p,
-                           d_len.p, (uint8_t *)nullptr);
-        SMI_HIP(hipGetLastError());
-        size_t tmp = 0;
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_len.p, d_off.p, nb + 1, s));
-        if (int rc = d_tmp.alloc(tmp)) return rc;
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp, d_len.p, d_off.p, nb + 1, s));
-        uint64_t total = 0;
-        SMI_HIP(hipMemcpyAsync(&total, d_off.p + nb, sizeof(total), hipMemcpyDeviceToHost, s));
-        SMI_HIP(hipStreamSynchronize(s));
-        if (int rc = d_out.alloc(total)) return rc;
-        hipLaunchKernelGGL(k_mtx_render<true>, dim3(gb), dim3(64 * kRenderWaves), 0, s, d_dense.p, nb, nc, (int32_t)r0, d_lab.p, d_lab_off.p,
-                           d_off.p, d_out.p);
-        SMI_HIP(hipGetLastError());
-        const size_t at = dst.size();
-        dst.resize(at + total);
-        SMI_HIP(hipMemcpyAsync(&dst[at], d_out.p, total, hipMemcpyDeviceToHost, s));
-        if (int rc = ev.end(s, ms_render)) return rc;
-        h->counts[SMI_ISO_RENDER_BLOCKS]++;
-        r0 = r1;
-        k0 = k1;
-    }
-    return SMI_OK;
-}
-
-}  // namespace
 
 extern "C" int smi_isoform_run(smi_isoform *h, float *stage_ms) {
     if (!h) {
@@ -1237,7 +899,8 @@ extern "C" int smi_isoform_run(smi_isoform *h, float *stage_ms) {
     for (size_t i = 0; i < nc; i++) codes[i] = (uint64_t)iso_row[i] << 32 | (uint32_t)mol_cell[cnt_mol[i]];
     std::string &isom = h->out[SMI_ISO_OUT_ISOMATRIX];
     isom = "geneId\ttranscriptId\tnbExons" + head;
-    if ((rc = matrix(h, codes, iso_lab, isom, iso_tot, &ms[1], &ms[2]))) return rc;
+    if ((rc = mtx::matrix(s, "IsoformMatrix", (int32_t)h->cells.size(), h->cfg.budget_bytes, codes, iso_lab, isom, iso_tot, &ms[1], &ms[2],
+                          &c[SMI_ISO_RENDER_BLOCKS]))) return rc;
     std::string &isomet = h->out[SMI_ISO_OUT_ISOMETRICS];
     isomet = "geneId\ttranscriptId\tnbExons\tnbUmis\n";
     for (size_t r = 0; r < iso_rows.size(); r++) {
@@ -1249,13 +912,15 @@ extern "C" int smi_isoform_run(smi_isoform *h, float *stage_ms) {
     codes.resize(nc);
     std::string &genm = h->out[SMI_ISO_OUT_GENEMATRIX];
     genm = "geneId" + head;
-    if ((rc = matrix(h, codes, gene_rows, genm, gene_tot, &ms[1], &ms[2]))) return rc;
+    if ((rc = mtx::matrix(s, "IsoformMatrix", (int32_t)h->cells.size(), h->cfg.budget_bytes, codes, gene_rows, genm, gene_tot, &ms[1], &ms[2],
+                          &c[SMI_ISO_RENDER_BLOCKS]))) return rc;
     // junctions
     codes.resize(jitem_mol.size());
     for (size_t i = 0; i < jitem_mol.size(); i++) codes[i] = (uint64_t)junc_row[i] << 32 | (uint32_t)mol_cell[jitem_mol[i]];
     std::string &junm = h->out[SMI_ISO_OUT_JUNCMATRIX];
     junm = "junctionId" + head;
-    if ((rc = matrix(h, codes, junc_rows, junm, junc_tot, &ms[1], &ms[2]))) return rc;
+    if ((rc = mtx::matrix(s, "IsoformMatrix", (int32_t)h->cells.size(), h->cfg.budget_bytes, codes, junc_rows, junm, junc_tot, &ms[1], &ms[2],
+                          &c[SMI_ISO_RENDER_BLOCKS]))) return rc;
     std::string &junmet = h->out[SMI_ISO_OUT_JUNCMETRICS];
     junmet = "junctionId\tnbUmis\n";
     for (size_t r = 0; r < junc_rows.size(); r++) junmet += junc_rows[r] + "\t" + std::to_string(junc_tot[r]) + "\n";

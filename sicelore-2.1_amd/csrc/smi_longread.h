@@ -1,8 +1,15 @@
 // smi_longread.h -- the attribute helpers of the LongreadRecord.fromSAMRecord parsers (ComputeConsensus in smi_consensus.hip,
-// IsoformMatrix in smi_isoform.hip): host only.
+// IsoformMatrix in smi_isoform.hip, SNPMatrix in smi_snp.hip), its CIGAR walk and the Java text rules they share: host only.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cstdint>
 #include <cstring>
+#include <string>
+#include <string_view>
+#include <vector>
+
+#include "sicelore_mi.h"
 
 namespace smi {
 namespace lr {
@@ -78,6 +85,125 @@ inline int valid_tag(const char *t) { return t[0] > ' ' && t[0] <= '~' && t[1] >
 inline bool chimeric(uint32_t first, uint32_t last, int32_t max_clip) {
     auto clip = [&](uint32_t c) { return ((c & 15) == 4 || (c & 15) == 5) && (int64_t)(c >> 4) > (int64_t)max_clip; };
     return clip(first) || clip(last);
+}
+
+inline std::string drop_minus1(std::string_view v) {  // String.replace("-1", ""): every occurrence, left to right
+    std::string s(v);
+    for (size_t k = s.find("-1"); k != std::string::npos; k = s.find("-1", k)) s.erase(k, 2);
+    return s;
+}
+
+// Java's String.split(regex) for a one-character separator: trailing empty strings removed
+inline std::vector<std::string_view> jsplit(std::string_view s, char sep) {
+    std::vector<std::string_view> out;
+    size_t b = 0;
+    for (size_t i = 0; i <= s.size(); i++)
+        if (i == s.size() || s[i] == sep) {
+            out.push_back(s.substr(b, i - b));
+            b = i + 1;
+        }
+    while (!out.empty() && out.back().empty()) out.pop_back();
+    if (s.empty()) out.assign(1, std::string_view());  // "".split(x) = [""]
+    return out;
+}
+
+// Integer.valueOf
+inline bool jint(std::string_view s, int32_t &v) {
+    if (s.empty()) return false;
+    size_t i = 0;
+    bool neg = false;
+    if (s[0] == '-' || s[0] == '+') {
+        neg = s[0] == '-';
+        i = 1;
+        if (s.size() == 1) return false;
+    }
+    int64_t x = 0;
+    for (; i < s.size(); i++) {
+        if (s[i] < '0' || s[i] > '9') return false;
+        x = x * 10 + (s[i] - '0');
+        if (x > 2147483648ll) return false;
+    }
+    if (neg) x = -x;
+    if (x > 2147483647ll || x < -2147483648ll) return false;
+    v = (int32_t)x;
+    return true;
+}
+
+// LongreadRecord.fromSAMRecord L120-150, literally: the walk over cigar.replaceAll("[0-9]+[IS]", "") split into cigartype ("[0-9]+") and
+// cigarsize ("[A-Z]"); cigartype[i] is the operation BEFORE cigarsize[i], so the last operation is never looked at.  false: the reference
+// throws (no block, a block index past the end, a size that is no integer)
+inline bool walk_junctions(const uint8_t *bam, const smi_bam_record &r, std::vector<int2> &out) {
+    static const char ops[] = "MIDNSHP=XBBBBBBB";
+    std::string cig;
+    struct Block {
+        int64_t start, len;
+    };
+    std::vector<Block> blocks;  // AlignmentBlocks: M = X
+    int64_t ref = (int64_t)r.pos + 1;
+    for (int k = 0; k < r.n_cigar; k++) {
+        uint32_t c;
+        std::memcpy(&c, bam + r.cigar_off + 4ull * k, 4);
+        const uint32_t op = c & 15, n = c >> 4;
+        if (op == 0 || op == 7 || op == 8) {
+            blocks.push_back({ref, n});
+            ref += n;
+        } else if (op == 2 || op == 3) {
+            ref += n;
+        }
+        if (op == 1 || op == 4) continue;  // replaceAll("[0-9]+[IS]", "")
+        cig += std::to_string(n);
+        cig += ops[op];
+    }
+    if (blocks.empty()) return false;
+    std::vector<std::string_view> type, size;  // cigar.split("[0-9]+"), cigar.split("[A-Z]")
+    {
+        std::string_view s(cig);
+        size_t i = 0;
+        type.push_back(std::string_view());  // the digits at position 0 give a leading ""
+        while (i < s.size()) {
+            while (i < s.size() && s[i] >= '0' && s[i] <= '9') i++;
+            const size_t b = i;
+            while (i < s.size() && !(s[i] >= '0' && s[i] <= '9')) i++;
+            if (i > b) type.push_back(s.substr(b, i - b));
+        }
+        if (s.empty()) type.assign(1, std::string_view());
+        size_t b = 0;
+        for (size_t k = 0; k <= s.size(); k++)
+            if (k == s.size() || (s[k] >= 'A' && s[k] <= 'Z')) {
+                size.push_back(s.substr(b, k - b));
+                b = k + 1;
+            }
+        while (!size.empty() && size.back().empty()) size.pop_back();
+        if (s.empty()) size.assign(1, std::string_view());
+    }
+    int64_t s = blocks[0].start, e = blocks[0].start;
+    std::vector<int64_t> xs, xe;
+    size_t bi = 0;
+    for (size_t i = 0; i < size.size(); i++) {
+        if (bi >= blocks.size() || i >= type.size()) return false;
+        const Block cur = blocks[bi];
+        const std::string_view t = type[i];
+        if (t == "M") bi++;
+        if (t == "N") {
+            xs.push_back(s);
+            xe.push_back(e);
+            s = cur.start;
+        } else if (t == "D") {
+            int32_t len;
+            if (i == 0 || !jint(size[i - 1], len)) return false;
+            if (len > 20) {  // a short intron minimap2 calls a deletion
+                xs.push_back(s);
+                xe.push_back(e);
+                s = cur.start;
+            }
+        }
+        if (t != "D") e = cur.start + cur.len - 1;
+    }
+    xs.push_back(s);
+    xe.push_back(e);
+    out.clear();
+    for (size_t i = 1; i < xs.size(); i++) out.push_back(make_int2((int)xe[i - 1], (int)xs[i]));
+    return true;
 }
 
 }  // namespace lr

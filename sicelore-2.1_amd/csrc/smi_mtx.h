@@ -1,0 +1,247 @@
+// smi_mtx.h -- K-MTX, the dense count matrices of Matrix.writeIsoformMatrix / writeGeneMatrix / writeJunctionMatrix (Matrix.java L158-290),
+// shared by IsoformMatrix (smi_isoform.hip) and SNPMatrix (smi_snp.hip): 64-bit (row << 32 | cell) codes, one per counted UMI; hipcub radix
+// sort + run-length encoding give the counts per (row, cell); the dense rows are rendered in row blocks under a device-memory budget, one
+// wavefront per row: a length pass, a scan, the write.  Also the device buffer and the event pair both programs hold their launches with.
+#pragma once
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "smi_internal.h"
+
+namespace smi {
+namespace mtx {
+
+constexpr int kRenderWaves = 4;  // waves per block of the renderer
+
+__device__ __forceinline__ int digits(uint32_t v) {
+    int n = 1;
+    while (v >= 10) {
+        v /= 10;
+        n++;
+    }
+    return n;
+}
+
+// dense[(row - r0) * nc + cell] = count, for the runs of rows r0 ..
+static __global__ void k_mtx_scatter(const uint64_t *__restrict__ code, const uint32_t *__restrict__ cnt, int64_t k0, int64_t k1, int32_t r0, int32_t nc,
+                              uint32_t *__restrict__ dense) {
+    const int64_t k = k0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (k >= k1) return;
+    const uint64_t c = code[k];
+    dense[(int64_t)((int32_t)(c >> 32) - r0) * nc + (uint32_t)c] = cnt[k];
+}
+
+// LEN: bytes of row r0 + i (label, "\t" + count per cell, "\n") into len[i]; WRITE: the row at off[i]
+template <bool WRITE>
+__global__ __launch_bounds__(64 * kRenderWaves) void k_mtx_render(const uint32_t *__restrict__ dense, int32_t n_rows, int32_t nc, int32_t r0,
+                                                                   const uint8_t *__restrict__ labels, const uint64_t *__restrict__ lab_off,
+                                                                   uint64_t *__restrict__ len, uint8_t *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kRenderWaves + (threadIdx.x >> 6);
+    if (i >= n_rows) return;
+    const uint32_t *row = dense + (int64_t)i * nc;
+    const uint64_t l0 = lab_off[r0 + i], ln = lab_off[r0 + i + 1] - l0;
+    if (!WRITE) {
+        uint64_t n = 0;
+        for (int c = lane; c < nc; c += 64) n += 1 + digits(row[c]);
+        for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+        if (lane == 0) len[i] = n + ln + 1;
+        return;
+    }
+    uint8_t *dst = out + len[i];  // (the exclusive scan of the lengths)
+    for (uint64_t k = lane; k < ln; k += 64) dst[k] = labels[l0 + k];
+    uint64_t pos = ln;
+    for (int c0 = 0; c0 < nc; c0 += 64) {
+        const int c = c0 + lane;
+        const uint32_t v = c < nc ? row[c] : 0;
+        const int w = c < nc ? 1 + digits(v) : 0;
+        int incl = w;  // inclusive prefix sum across the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(incl, o);
+            if (lane >= o) incl += y;
+        }
+        if (c < nc) {
+            uint8_t *p = dst + pos + (incl - w);
+            p[0] = '\t';
+            uint32_t x = v;
+            for (int k = w - 1; k >= 1; k--) {
+                p[k] = (uint8_t)('0' + x % 10);
+                x /= 10;
+            }
+        }
+        pos += __shfl(incl, 63);
+    }
+    if (lane == 0) dst[pos] = '\n';
+}
+
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    const char *who = "IsoformMatrix";  // the program named when an allocation fails
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t n) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        if (hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
+            set_error(std::string(who) + ": device allocation of " + std::to_string(n * sizeof(T)) + " bytes failed");
+            return SMI_ERR_HIP;
+        }
+        return SMI_OK;
+    }
+    int put(const std::vector<T> &v, hipStream_t s) {
+        if (int rc = alloc(v.size())) return rc;
+        if (!v.empty()) SMI_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
+        return SMI_OK;
+    }
+};
+
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    int begin(hipStream_t s) {
+        if (!a) SMI_HIP(hipEventCreate(&a));
+        if (!b) SMI_HIP(hipEventCreate(&b));
+        SMI_HIP(hipEventRecord(a, s));
+        return SMI_OK;
+    }
+    int end(hipStream_t s, float *acc) {
+        SMI_HIP(hipEventRecord(b, s));
+        SMI_HIP(hipEventSynchronize(b));
+        float ms = 0.f;
+        SMI_HIP(hipEventElapsedTime(&ms, a, b));
+        *acc += ms;
+        return SMI_OK;
+    }
+};
+
+// K-MTX for one matrix: codes (row << 32 | cell), one per counted UMI -> counts per (row, cell) (sorted codes, device) and the dense rows
+// of `labels` x nc cells appended to dst, rendered in blocks of at most budget_bytes (0: 1 GiB) of device memory; row_total: the sum of
+// each row; *blocks is raised by the row blocks rendered.  who: the program named in an error.
+inline int matrix(hipStream_t s, const char *who, int32_t nc, int64_t budget_bytes, std::vector<uint64_t> &codes, const std::vector<std::string> &labels,
+                  std::string &dst, std::vector<int64_t> &row_total, float *ms_sort, float *ms_render, int64_t *blocks) {
+    const int64_t nrows = (int64_t)labels.size();
+    row_total.assign(nrows, 0);
+    const size_t n = codes.size();
+    std::vector<uint64_t> ucode;
+    std::vector<uint32_t> ucnt;
+    Events ev;
+    if (n > (size_t)INT32_MAX) {
+        set_error(std::string(who) + ": " + std::to_string(n) + " matrix entries in one matrix; at most 2^31 - 1 are counted in one sort");
+        return SMI_ERR_INVALID;
+    }
+    int end_bit = 32;  // cells < 2^31 in the low word; the row in as many bits above as the rows need
+    while (end_bit < 64 && ((uint64_t)1 << (end_bit - 32)) < (uint64_t)nrows) end_bit++;
+    if (n) {
+        DevBuf<uint64_t> d_in, d_sorted, d_unique;
+        DevBuf<uint32_t> d_cnt;
+        DevBuf<int64_t> d_nrun;
+        DevBuf<uint8_t> d_tmp;
+        d_in.who = d_sorted.who = d_unique.who = d_cnt.who = d_nrun.who = d_tmp.who = who;
+        if (int rc = d_in.put(codes, s)) return rc;
+        if (int rc = d_sorted.alloc(n)) return rc;
+        if (int rc = d_unique.alloc(n)) return rc;
+        if (int rc = d_cnt.alloc(n)) return rc;
+        if (int rc = d_nrun.alloc(1)) return rc;
+        size_t t1 = 0, t2 = 0;
+        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, d_in.p, d_sorted.p, (int)n, 0, end_bit, s));
+        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, d_sorted.p, d_unique.p, d_cnt.p, d_nrun.p, (int)n, s));
+        if (int rc = d_tmp.alloc(std::max(t1, t2))) return rc;
+        size_t tmp = std::max(t1, t2);
+        if (int rc = ev.begin(s)) return rc;
+        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(d_tmp.p, tmp, d_in.p, d_sorted.p, (int)n, 0, end_bit, s));
+        tmp = std::max(t1, t2);
+        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(d_tmp.p, tmp, d_sorted.p, d_unique.p, d_cnt.p, d_nrun.p, (int)n, s));
+        if (int rc = ev.end(s, ms_sort)) return rc;
+        int64_t nrun = 0;
+        SMI_HIP(hipMemcpy(&nrun, d_nrun.p, sizeof(nrun), hipMemcpyDeviceToHost));
+        ucode.resize(nrun);
+        ucnt.resize(nrun);
+        SMI_HIP(hipMemcpy(ucode.data(), d_unique.p, nrun * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(ucnt.data(), d_cnt.p, nrun * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    for (size_t k = 0; k < ucode.size(); k++) row_total[ucode[k] >> 32] += ucnt[k];
+    if (nrows == 0) return SMI_OK;
+    // labels back to back; the largest count gives the widest field
+    std::vector<uint8_t> lab;
+    std::vector<uint64_t> lab_off{0};
+    for (auto &l : labels) {
+        lab.insert(lab.end(), l.begin(), l.end());
+        lab_off.push_back(lab.size());
+    }
+    uint32_t maxc = 0;
+    for (uint32_t x : ucnt) maxc = std::max(maxc, x);
+    const int wd = 1 + (int)std::to_string(maxc).size();
+    const int64_t budget = budget_bytes > 0 ? budget_bytes : (int64_t)1 << 30;
+    DevBuf<uint8_t> d_lab;
+    DevBuf<uint64_t> d_lab_off, d_ucode;
+    DevBuf<uint32_t> d_ucnt;
+    d_lab.who = d_lab_off.who = d_ucode.who = d_ucnt.who = who;
+    if (int rc = d_lab.put(lab, s)) return rc;
+    if (int rc = d_lab_off.put(lab_off, s)) return rc;
+    if (int rc = d_ucode.put(ucode, s)) return rc;
+    if (int rc = d_ucnt.put(ucnt, s)) return rc;
+    int64_t r0 = 0;
+    size_t k0 = 0;
+    while (r0 < nrows) {
+        // rows of this block: dense counts + the widest rendering of each row within the budget (at least one row)
+        int64_t r1 = r0, bytes = 0;
+        while (r1 < nrows) {
+            const int64_t rb = (int64_t)nc * 4 + (int64_t)(lab_off[r1 + 1] - lab_off[r1]) + (int64_t)nc * wd + 1 + 8;
+            if (r1 > r0 && bytes + rb > budget) break;
+            bytes += rb;
+            r1++;
+        }
+        const int32_t nb = (int32_t)(r1 - r0);
+        size_t k1 = k0;
+        while (k1 < ucode.size() && (int64_t)(ucode[k1] >> 32) < r1) k1++;
+        DevBuf<uint32_t> d_dense;
+        DevBuf<uint64_t> d_len, d_off;
+        DevBuf<uint8_t> d_out, d_tmp;
+        d_dense.who = d_len.who = d_off.who = d_out.who = d_tmp.who = who;
+        if (int rc = d_dense.alloc((size_t)nb * std::max(nc, 1))) return rc;
+        if (int rc = d_len.alloc(nb + 1)) return rc;
+        if (int rc = d_off.alloc(nb + 1)) return rc;
+        if (int rc = ev.begin(s)) return rc;
+        SMI_HIP(hipMemsetAsync(d_dense.p, 0, (size_t)nb * std::max(nc, 1) * 4, s));
+        SMI_HIP(hipMemsetAsync(d_len.p, 0, (nb + 1) * sizeof(uint64_t), s));
+        if (k1 > k0)
+            hipLaunchKernelGGL(k_mtx_scatter, dim3((unsigned)((k1 - k0 + 255) / 256)), dim3(256), 0, s, d_ucode.p, d_ucnt.p, (int64_t)k0, (int64_t)k1,
+                               (int32_t)r0, nc, d_dense.p);
+        const unsigned gb = (unsigned)((nb + kRenderWaves - 1) / kRenderWaves);
+        hipLaunchKernelGGL(k_mtx_render<false>, dim3(gb), dim3(64 * kRenderWaves), 0, s, d_dense.p, nb, nc, (int32_t)r0, d_lab.p, d_lab_off.p,
+                           d_len.p, (uint8_t *)nullptr);
+        SMI_HIP(hipGetLastError());
+        size_t tmp = 0;
+        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_len.p, d_off.p, nb + 1, s));
+        if (int rc = d_tmp.alloc(tmp)) return rc;
+        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp, d_len.p, d_off.p, nb + 1, s));
+        uint64_t total = 0;
+        SMI_HIP(hipMemcpyAsync(&total, d_off.p + nb, sizeof(total), hipMemcpyDeviceToHost, s));
+        SMI_HIP(hipStreamSynchronize(s));
+        if (int rc = d_out.alloc(total)) return rc;
+        hipLaunchKernelGGL(k_mtx_render<true>, dim3(gb), dim3(64 * kRenderWaves), 0, s, d_dense.p, nb, nc, (int32_t)r0, d_lab.p, d_lab_off.p,
+                           d_off.p, d_out.p);
+        SMI_HIP(hipGetLastError());
+        const size_t at = dst.size();
+        dst.resize(at + total);
+        SMI_HIP(hipMemcpyAsync(&dst[at], d_out.p, total, hipMemcpyDeviceToHost, s));
+        if (int rc = ev.end(s, ms_render)) return rc;
+        if (blocks) (*blocks)++;
+        r0 = r1;
+        k0 = k1;
+    }
+    return SMI_OK;
+}
+
+}  // namespace mtx
+}  // namespace smi

@@ -70,6 +70,8 @@ EXPORTS = [
     "smi_consensus_counts", "smi_consensus_free", "smi_poa_batch",
     "smi_isoform_default_config", "smi_isoform_create", "smi_isoform_add_segment", "smi_isoform_run", "smi_isoform_output",
     "smi_isoform_counts", "smi_isoform_free", "smi_isoform_isobam",
+    "smi_snp_default_config", "smi_snp_create", "smi_snp_add_segment", "smi_snp_run", "smi_snp_output", "smi_snp_counts",
+    "smi_snp_line_counts", "smi_snp_free",
 ]
 
 
@@ -256,6 +258,14 @@ def load_library():
     lib.smi_isoform_counts.argtypes = [vp, vp]
     lib.smi_isoform_free.argtypes = [vp]
     lib.smi_isoform_isobam.argtypes = [vp, vp, sz, vp, ctypes.c_int32, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_snp_default_config.argtypes = [vp]
+    lib.smi_snp_create.argtypes = [vp, vp, vp, sz, vp, sz, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.POINTER(vp)]
+    lib.smi_snp_add_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32]
+    lib.smi_snp_run.argtypes = [vp, vp]
+    lib.smi_snp_output.argtypes = [vp, ctypes.c_int32, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_snp_counts.argtypes = [vp, vp]
+    lib.smi_snp_line_counts.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_snp_free.argtypes = [vp]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     explicit = {"smi_last_error", "smi_version", "smi_read_planes_words", "smi_packed_planes_words", "smi_record_flags"}  # restype set above (char*, size_t)
@@ -765,6 +775,97 @@ class Isoform:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.smi_isoform_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class SnpConfig(ctypes.Structure):
+    """smi_snp_config"""
+    _fields_ = [("cell_tag", ctypes.c_char * 4), ("umi_tag", ctypes.c_char * 4), ("gene_tag", ctypes.c_char * 4), ("rn_tag", ctypes.c_char * 4),
+                ("max_clip", ctypes.c_int32), ("min_rn", ctypes.c_int32), ("min_qv", ctypes.c_int32), ("n_threads", ctypes.c_int32),
+                ("budget_bytes", ctypes.c_int64)]
+
+
+# smi_snp_counts, in SMI_SNP_* order
+SNP_COUNTS = ("records", "lines", "cells", "hits", "lowRN", "lowQV", "pairs", "kept", "rows", "total_count", "render_blocks")
+# smi_snp_output, in SMI_SNP_OUT_* order: the file name suffixes (PREFIX_<name>)
+SNP_OUTPUTS = ("snpmatrix.txt", "snpmetrics.txt", "snpmolinfos.txt")
+
+
+class Snp:
+    """SNPMatrix (smi_snp_*): the SNP and cell-list texts and the BAM's reference names, then BAM segments in; the output texts out.
+    Keywords: the fields of smi_snp_config (tags as two-character strings)."""
+
+    def __init__(self, ctx, snp, csv, ref_names, **kw):
+        self._lib = load_library()
+        cfg = SnpConfig()
+        self._lib.smi_snp_default_config(ctypes.byref(cfg))
+        for k, v in kw.items():
+            if k in ISOFORM_TAGS:
+                b = str(v).encode()
+                if len(b) != 2:
+                    raise SmiError(f"{k}: a tag is two characters")
+                setattr(cfg, k, b)
+            elif k in ("max_clip", "min_rn", "min_qv", "n_threads", "budget_bytes"):
+                setattr(cfg, k, int(v))
+            else:
+                raise ValueError(f"unknown smi_snp_config field {k!r}")
+        sn = np.frombuffer(bytes(snp), dtype=np.uint8)
+        cs = np.frombuffer(bytes(csv), dtype=np.uint8)
+        names = [str(r).rstrip("\0").encode("latin-1") for r in ref_names]
+        arr = (ctypes.c_char_p * max(len(names), 1))(*names)
+        self._h = ctypes.c_void_p()
+        if self._lib.smi_snp_create(ctx._h, ctypes.byref(cfg), _ptr(sn) if sn.size else None, sn.size, _ptr(cs) if cs.size else None, cs.size,
+                                    arr, len(names), ctypes.byref(self._h)):
+            self._h = None
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._ctx = ctx
+        self.stage_ms = dict(snp=0.0, sort=0.0, render=0.0)
+
+    def add_segment(self, bam, recs):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
+        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
+            raise ValueError("bam: a contiguous 1-D uint8 array")
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != BAM_RECORD_DTYPE:
+            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
+        if self._lib.smi_snp_add_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+
+    def run(self):
+        """rows, distinct UMIs, K-MTX -> {file name suffix: bytes}, all empty when there is no row"""
+        ms = np.zeros(3, dtype=np.float32)
+        if self._lib.smi_snp_run(self._h, _ptr(ms)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self.stage_ms = dict(snp=float(ms[0]), sort=float(ms[1]), render=float(ms[2]))
+        outs = {}
+        for i, name in enumerate(SNP_OUTPUTS):
+            n = ctypes.c_size_t(0)
+            self._lib.smi_snp_output(self._h, i, None, 0, ctypes.byref(n))
+            out = np.zeros(max(n.value, 1), dtype=np.uint8)
+            if self._lib.smi_snp_output(self._h, i, _ptr(out), out.size, ctypes.byref(n)):
+                raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+            outs[name] = out[:n.value].tobytes()
+        return outs
+
+    def counts(self):
+        c = np.zeros(len(SNP_COUNTS), dtype=np.int64)
+        self._lib.smi_snp_counts(self._h, _ptr(c))
+        return dict(zip(SNP_COUNTS, (int(x) for x in c)))
+
+    def line_counts(self):
+        """per line read from the SNP text: (hits, lowRN, lowQV), or (-1, -1, -1) for a line on a chromosome outside the BAM"""
+        n = ctypes.c_size_t(0)
+        self._lib.smi_snp_line_counts(self._h, None, 0, ctypes.byref(n))
+        c = np.zeros((max(n.value, 1), 3), dtype=np.int64)
+        if self._lib.smi_snp_line_counts(self._h, _ptr(c), n.value, ctypes.byref(n)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        return c[:n.value]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.smi_snp_free(self._h)
             self._h = None
 
     __del__ = close

@@ -1,0 +1,179 @@
+"""SNPMatrix on the GPU against tests/snpmodel.py, every output file byte for byte and every counter: the hand-built BAM through the
+library (several segments) and through `bin/java`, MINRN / MINQV, a 40-position line on a CIGAR of more than 5,000 operations, a seeded
+unsorted run of about 50,000 records on two chromosomes, a many-block render, and the errors of DESIGN.md section 8e's deviation list."""
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import bammodel
+import snpmodel as sm
+import tagbammodel as tm
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FILES = ("snpmatrix.txt", "snpmetrics.txt", "snpmolinfos.txt")
+
+
+@pytest.fixture(scope="module")
+def snp(pkg):
+    return importlib.import_module("sicelore_amd.snpmatrix")
+
+
+def _run(snp, ctx, tmp_path, bam, snp_text, csv, block=400, segment_bytes=250, model=None, **kw):
+    (tmp_path / "in.bam").write_bytes(bammodel.bgzf_compress(bam, block=block))
+    (tmp_path / "s.csv").write_text(snp_text)
+    (tmp_path / "c.csv").write_text(csv)
+    out = tmp_path / "out"
+    out.mkdir(exist_ok=True)
+    info = snp.snp_matrix(ctx, str(tmp_path / "in.bam"), str(tmp_path / "c.csv"), str(tmp_path / "s.csv"), str(out), prefix="t",
+                          segment_bytes=segment_bytes, n_threads=3, **kw)
+    want, cnt, per_line = model or sm.snp_matrix(bam, snp_text, csv, **{k: v for k, v in kw.items() if k in ("min_rn", "min_qv")})
+    assert sorted(os.listdir(out)) == sorted(f"t_{n}" for n in want)
+    for name, data in want.items():
+        assert (out / f"t_{name}").read_bytes() == data, name
+    assert {k: info[k] for k in cnt} == cnt
+    assert info["line_counts"] == per_line
+    return info, cnt
+
+
+def test_hand_built_case_in_several_segments(snp, gpu_ctx, tmp_path):
+    bam = sm.hand_bam()
+    assert len(bammodel.bgzf_compress(bam, block=400)) > 4 * 250          # several segments, records split across them
+    info, cnt = _run(snp, gpu_ctx, tmp_path, bam, sm.SNP, sm.CSV)
+    assert cnt["hits"] == 12 and cnt["kept"] == 11 and cnt["rows"] == 10
+    mi = (tmp_path / "out" / "t_snpmolinfos.txt").read_bytes()
+    assert b"CELL3\tUMI5\t1\t0\tnull\t12,13\trevN\tchr1:6010|6011..A\n" in mi and mi.count(b"swapped\tchr1:7302|7101..CG\n") == 2
+
+
+@pytest.mark.parametrize("kw,low", [(dict(min_rn=2), "lowRN"), (dict(min_qv=13), "lowQV"), (dict(min_qv=101), "lowQV")])
+def test_minrn_minqv(snp, gpu_ctx, tmp_path, kw, low):
+    _info, cnt = _run(snp, gpu_ctx, tmp_path, sm.hand_bam(), sm.SNP, sm.CSV, **kw)
+    assert cnt[low] > 0
+
+
+def test_empty_result_writes_nothing(snp, gpu_ctx, tmp_path):
+    info, _cnt = _run(snp, gpu_ctx, tmp_path, sm.hand_bam(), "chr1,2000,+,clipS\n", "CELL9\n")
+    assert info["hits"] == 2 and info["rows"] == 0 and info["bytes_written"] == 0
+
+
+def test_bin_java_child_process(pkg, gpu_ctx, tmp_path):
+    bam = sm.hand_bam()
+    (tmp_path / "in.bam").write_bytes(bammodel.bgzf_compress(bam))
+    (tmp_path / "s.csv").write_text(sm.SNP)
+    (tmp_path / "c.csv").write_text(sm.CSV)
+    java = os.path.join(ROOT, "sicelore-2.1_amd", "bin", "java")
+    r = subprocess.run(["bash", java, "-jar", "Jar/Sicelore-2.1.jar", "SNPMatrix", f"I={tmp_path / 'in.bam'}", "MINRN=0", "MINQV=0", f"CSV={tmp_path / 'c.csv'}",
+                        f"SNP={tmp_path / 's.csv'}", f"O={tmp_path}", "PREFIX=snp"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    want, _cnt, _pl = sm.snp_matrix(bam, sm.SNP, sm.CSV)
+    for name in FILES:
+        assert (tmp_path / f"snp_{name}").read_bytes() == want[name], name
+    assert "processing...\t\tchr1,2000,+,clipS\t2 hits, 0 lowRN, 0 lowQV" in r.stderr
+    assert "STATISTICS...\t\thits=12, lowRN=0, lowQV= 0" in r.stderr and "nochrom" not in r.stderr
+
+
+def test_forty_positions_on_a_cigar_of_5000_operations(snp, gpu_ctx, tmp_path):
+    """2M 1D repeated 2,600 times (5,200 operations, 82 rounds of 64): the 40 positions are spread over the whole alignment; a second
+    line asks for one deleted base among them and must give nothing"""
+    n_rep = 2600
+    cig = [("M", 2), ("D", 1)] * n_rep
+    cig[-1] = ("M", 1)                                     # ends on a match
+    n_read = 2 * n_rep + 1
+    rng = np.random.default_rng(5)
+    seq = "".join("ACGTN"[int(x)] for x in rng.integers(0, 5, n_read))
+    qual = bytes(int(x) for x in rng.integers(1, 60, n_read))
+    recs = [sm.rec("long_f", cig, 1000, "CELL1", "U1", seq=seq, qual=qual), sm.rec("long_r", cig, 1000, "CELL2", "U2", seq=seq, qual=qual, flag=16),
+            sm.rec("short", [("M", 50)], 1000, "CELL1", "U3")]
+    pos = [1000 + 3 * int(k) + int(o) for k, o in zip(rng.choice(n_rep - 1, 40, replace=False), rng.integers(0, 2, 40))]
+    text = (f"chr1,{'|'.join(map(str, pos))},+,forty\n" f"chr1,{'|'.join(map(str, pos))},-,fortyrev\n"
+            f"chr1,{'|'.join(map(str, pos[:20] + [1002 + 3 * 700] + pos[20:]))},+,deleted\n" "chr1,1001|1004,+,both\n")
+    bam = bammodel.bam_bytes(sm.HEAD, sm.REFS, recs)
+    info, cnt = _run(snp, gpu_ctx, tmp_path, bam, text, sm.CSV, block=0xFF00, segment_bytes=1 << 20)
+    assert [c["hits"] for c in info["line_counts"]] == [1, 1, 0, 2] and cnt["rows"] == 4
+
+
+def _seeded(n_rec, n_lines, seed=7):
+    rng = np.random.default_rng(seed)
+    sites = [(int(rng.integers(0, 2)), int(rng.integers(2000, 200000))) for _ in range(n_lines)]
+    lines = []
+    for i, (ref, p) in enumerate(sites):
+        k = int(rng.integers(1, 5))
+        pos = [p + int(x) for x in rng.choice(120, k, replace=False)]
+        lines.append(f"chr{ref + 1},{'|'.join(map(str, pos))},{'-' if rng.random() < 0.4 else '+'},site{i}")
+    recs = []
+    for i in range(n_rec):
+        ref, p = sites[int(rng.integers(n_lines))]
+        start = p - int(rng.integers(0, 300))
+        cig = [("S", int(rng.integers(1, 30)))] if rng.random() < 0.3 else []
+        for _b in range(int(rng.integers(1, 6))):
+            cig.append(("M", int(rng.integers(20, 200))))
+            x = rng.random()
+            cig.append(("I", int(rng.integers(1, 4))) if x < 0.25 else ("D", int(rng.integers(1, 30))) if x < 0.6 else ("N", int(rng.integers(30, 200))) if x < 0.8
+                       else ("X", int(rng.integers(1, 3))))
+        cig.append(("M", int(rng.integers(20, 100))))
+        n = sum(ln for op, ln in cig if op in "MIS=X")
+        seq = "".join("ACGTN"[int(x)] for x in rng.choice(5, n, p=[0.24, 0.24, 0.24, 0.24, 0.04]))
+        qual = bytes(int(x) for x in rng.integers(2, 41, n))
+        flag = (16 if rng.random() < 0.4 else 0) | (256 if rng.random() < 0.1 else 0)
+        bc, umi = f"CELL{int(rng.integers(60)):03d}", f"U{int(rng.integers(4000)):05d}"
+        r = sm.rec(f"r{i}", cig, start, bc + ("-1" if rng.random() < 0.5 else ""), umi,
+                   rn=None if rng.random() < 0.3 else int(rng.integers(1, 9)), flag=flag, ref=ref, seq=seq, qual=qual)
+        recs.append(r)
+        if rng.random() < 0.05:
+            recs.append(sm.rec(f"r{i}", cig, start, bc, umi, flag=flag | 256,       # a secondary duplicate: the same (cell, UMI) on the same rows
+                               ref=ref, seq=seq, qual=qual))
+    return bammodel.bam_bytes(sm.HEAD, sm.REFS, recs), "".join(x + "\n" for x in lines), "".join(f"CELL{c:03d}\n" for c in range(50)), recs
+
+
+def test_seeded_unsorted_run_and_many_render_blocks(snp, gpu_ctx, tmp_path):
+    bam, text, csv, _recs = _seeded(50000, 500)
+    model = sm.snp_matrix(bam, text, csv, min_rn=2, min_qv=4)
+    cnt = model[1]
+    assert cnt["rows"] >= 1000 and cnt["lowRN"] > 0 and cnt["lowQV"] > 0 and cnt["kept"] < cnt["hits"]
+    _t, _r, recs = bammodel.parse_bam(bam)
+    in_del = 0                                                # a requested position inside a deletion of an overlapping record
+    for L in sm.parse_snp(text, ["chr1", "chr2"])[:50]:
+        for r in recs:
+            if r["ref_id"] == L["ref"] and r["pos0"] < L["arr"][0] < r["pos0"] + sm.reference_length(r["cigar"]):
+                ref = r["pos0"] + 1
+                for op, n in r["cigar"]:
+                    if op == "D" and any(ref <= p < ref + n for p in L["arr"]):
+                        in_del += 1
+                    if op in "M=XDN":
+                        ref += n
+    assert in_del > 0
+    info, _cnt = _run(snp, gpu_ctx, tmp_path, bam, text, csv, block=0xFF00, segment_bytes=300000, min_rn=2, min_qv=4, budget_bytes=40000, model=model)
+    assert info["render_blocks"] > 10
+
+
+@pytest.mark.parametrize("what,msg", [
+    ("noqual", "read bad: no base qualities"), ("noumi", "read bad: a hit of cell CELL1 without the UMI"), ("badrn", "read bad: an attribute"),
+    ("walk", "read bad: the CIGAR walk"), ("nocigar", "read bad: no CIGAR"), ("position", "SNP line 2 (chr1,12x,+,g): position '12x' is not an integer"),
+    ("fields", "SNP line 1 (chr1,1010,+): has 3 fields")])
+def test_errors_name_the_line_or_the_read(pkg, snp, gpu_ctx, tmp_path, what, msg):
+    text = "chr1,1010,+,s\n"
+    r = dict(noqual=lambda: sm.rec("bad", [("M", 100)], 1000, "CELL1", "U", qual=b"\xff" * 100),
+             noumi=lambda: sm.rec("bad", [("M", 100)], 1000, "CELL1", None),
+             badrn=lambda: sm.rec("bad", [("M", 100)], 1000, "CELL1", "U", extra=tm.aux_z("RN", "5")),
+             walk=lambda: sm.rec("bad", [("M", 100), ("D", 10), ("H", 5)], 1000, "CELL1", "U"),
+             nocigar=lambda: sm.rec("bad", [], 1010, "CELL1", "U", seq="ACGT"))
+    recs = [sm.rec("good", [("M", 100)], 1000, "CELL1", "U0")] + ([r[what]()] if what in r else [])
+    if what == "position":
+        text += "chr1,12x,+,g\n"
+    if what == "fields":
+        text = "chr1,1010,+\n"
+    if what == "nocigar":                                    # without a CIGAR the alignment ends in front of its start: two positions around it
+        text = "chr1,1000|1020,+,s\n"
+    (tmp_path / "in.bam").write_bytes(bammodel.bgzf_compress(bammodel.bam_bytes(sm.HEAD, sm.REFS, recs)))
+    (tmp_path / "s.csv").write_text(text)
+    (tmp_path / "c.csv").write_text(sm.CSV)
+    args = (str(tmp_path / "in.bam"), str(tmp_path / "c.csv"), str(tmp_path / "s.csv"), str(tmp_path))
+    with pytest.raises(pkg.SmiError) as e:
+        snp.snp_matrix(gpu_ctx, *args)
+    assert msg in str(e.value)
+    cli = importlib.import_module("sicelore_amd.cli")
+    assert cli.main(["SNPMatrix", f"I={args[0]}", f"CSV={args[1]}", f"SNP={args[2]}", f"O={args[3]}"]) == 1
+    assert not [f for f in os.listdir(tmp_path) if f.startswith("snp_")]

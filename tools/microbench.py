@@ -36,9 +36,9 @@ def main():
     used = synth.pick_used(wl, 5000, seed=2)
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
-            "consensus": leg_consensus, "isoform": leg_isoform}
+            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -667,6 +667,97 @@ def leg_isoform(pkg, synth, ctx, dev, wl, used, res):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     res["isoform"] = out
+
+
+def _snp_fixture(n_recs, n_lines, n_cells, seed=51):
+    """a seeded molecule BAM of n_recs fixed-size records (aM bD cM over 200 bases, BC / U8 / RN, both strands, two chromosomes, unsorted)
+    around n_lines sites of 1..4 positions each -> (SNP text, cell list, BGZF bytes, inflated bytes)"""
+    import struct
+
+    from sicelore_amd import lib
+
+    rng = np.random.default_rng(seed)
+    site_ref = rng.integers(0, 2, n_lines)
+    site_pos = rng.integers(10_000, 50_000_000, n_lines)
+    lines = []
+    for i in range(n_lines):
+        pos = site_pos[i] + rng.choice(150, int(rng.integers(1, 5)), replace=False)
+        lines.append(f"chr{site_ref[i] + 1},{'|'.join(map(str, pos))},{'-' if rng.random() < 0.5 else '+'},site{i}\n")
+    L = 200
+    rec = np.zeros((n_recs, 392), dtype=np.uint8)     # 4 + 32 fixed, name 11, CIGAR 12, bases 100, qualities 200, attributes 33
+    s = rng.integers(0, n_lines, n_recs)
+
+    def put(col, values, dtype):
+        rec[:, col:col + np.dtype(dtype).itemsize] = np.ascontiguousarray(np.asarray(values).astype(dtype)).view(np.uint8).reshape(n_recs, -1)
+
+    def digits(col, values, width):
+        for k in range(width):
+            rec[:, col + width - 1 - k] = 48 + (values // 10 ** k) % 10
+    put(0, np.full(n_recs, 388), "<u4")
+    put(4, site_ref[s], "<i4")
+    put(8, site_pos[s] - rng.integers(0, 150, n_recs) - 1, "<i4")
+    rec[:, 12], rec[:, 13] = 11, 60
+    put(14, np.full(n_recs, 4680), "<u2")
+    put(16, np.full(n_recs, 3), "<u2")
+    put(18, np.where(rng.random(n_recs) < 0.5, 16, 0), "<u2")
+    put(20, np.full(n_recs, L), "<i4")
+    put(24, np.full(n_recs, -1), "<i4")
+    put(28, np.full(n_recs, -1), "<i4")
+    rec[:, 36] = ord("r")
+    digits(37, np.arange(n_recs), 9)
+    a = rng.integers(20, 180, n_recs)
+    put(47, a << 4, "<u4")
+    put(51, rng.integers(1, 20, n_recs) << 4 | 2, "<u4")
+    put(55, (L - a) << 4, "<u4")
+    code = np.array([1, 2, 4, 8], dtype=np.uint8)
+    rec[:, 59:159] = code[rng.integers(0, 4, (n_recs, 100))] << 4 | code[rng.integers(0, 4, (n_recs, 100))]
+    rec[:, 159:359] = rng.integers(2, 41, (n_recs, L), dtype=np.uint8)
+    rec[:, 359:366] = np.frombuffer(b"BCZCELL", dtype=np.uint8)
+    digits(366, rng.integers(0, n_cells, n_recs), 5)
+    rec[:, 371:373] = np.frombuffer(b"-1", dtype=np.uint8)
+    rec[:, 374:378] = np.frombuffer(b"U8ZU", dtype=np.uint8)
+    digits(378, rng.integers(0, 10 ** 9, n_recs), 9)
+    rec[:, 388:391] = np.frombuffer(b"RNC", dtype=np.uint8)
+    rec[:, 391] = rng.integers(1, 9, n_recs)
+    head = b"BAM\1" + struct.pack("<I", 0) + struct.pack("<I", 2) + b"".join(struct.pack("<I", 5) + nm + struct.pack("<I", 2 ** 31 - 1)
+                                                                              for nm in (b"chr1\0", b"chr2\0"))
+    bam = np.concatenate([np.frombuffer(head, dtype=np.uint8), rec.reshape(-1)])
+    csv = "".join(f"CELL{c:05d}-1\n" for c in range(n_cells))
+    return "".join(lines), csv, lib.bgzf_deflate(bam, level=1, n_threads=16), int(bam.size)
+
+
+def leg_snp(pkg, synth, ctx, dev, wl, used, res):
+    """K-SNP + K-MTX (`SNPMatrix`): a seeded molecule BAM of SMI_MB_SNP_RECS records (2,000,000) against SMI_MB_SNP_LINES site lines (4,000) of
+    1..4 positions, 5,000 cells, file to file: device ms of K-SNP (both launches and the scans, all segments), sorts + de-duplication + RLE and
+    render (HIP events), wall seconds per phase.  snp_gbytes_per_s: the inflated BAM bytes, once per launch, over K-SNP's device time -- the
+    bytes the kernel is handed, an upper bound of what it reads (it skips the bases and qualities it is not asked for)."""
+    import shutil
+    import tempfile
+
+    snp = importlib.import_module(graft.PKG_NAME + ".snpmatrix")
+    n_recs = int(os.environ.get("SMI_MB_SNP_RECS", "2000000"))
+    n_lines = int(os.environ.get("SMI_MB_SNP_LINES", "4000"))
+    t0 = time.perf_counter()
+    text, csv, z, inflated = _snp_fixture(n_recs, n_lines, 5000)
+    out = {"records": n_recs, "lines": n_lines, "cells": 5000, "inflated_bytes": inflated, "fixture_s": time.perf_counter() - t0}
+    d = tempfile.mkdtemp(prefix="snp_")
+    try:
+        z.tofile(os.path.join(d, "in.bam"))
+        with open(os.path.join(d, "s.csv"), "w") as f:
+            f.write(text)
+        with open(os.path.join(d, "c.csv"), "w") as f:
+            f.write(csv)
+        runs = []
+        for _rep in range(2):          # the first run loads the code objects
+            info = snp.snp_matrix(ctx, os.path.join(d, "in.bam"), os.path.join(d, "c.csv"), os.path.join(d, "s.csv"), d, n_threads=16)
+            keys = ("records", "lines", "pairs", "hits", "lowRN", "lowQV", "kept", "rows", "total_count", "render_blocks")
+            runs.append(dict({k: info[k] for k in keys}, stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"],
+                             bytes_written=info["bytes_written"], records_per_s=info["records"] / info["wall_s"],
+                             snp_gbytes_per_s=2 * inflated / (info["stage_ms"]["snp"] * 1e-3) / 1e9))
+        out["first_run"], out["file_to_file"] = runs
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    res["snp"] = out
 
 
 def leg_inflate(pkg, synth, ctx, dev, wl, used, res):

@@ -265,3 +265,40 @@ def test_other_polya_window_through_the_chunk_workers(pkg, synth, sor, gpu_ctx, 
     again, _f, _ = gpu_ctx.scanfastq_pass2_chunk(text, split_chimeras=False)
     assert bytes(again) == base_p
 
+
+def test_files_the_device_hands_back_go_through_the_host(pkg, synth, gpu_ctx, tmp_path):
+    """inflate="device": a file K-INFLATE reports with a status (run_files.py: device_part) is inflated by the host decoder and the run writes
+    what it writes when all six files inflate on the device -- the same texts in three other wrappings: two concatenated members (the ISIZE
+    at the end of the file, the capacity, is the second member's alone), BGZF of more than 256 members, 512 zero bytes behind the member"""
+    import zlib
+
+    from sicelore_amd import lib as libmod
+
+    run_files = importlib.import_module("sicelore_amd.run_files")
+    dev = torch.device("cuda", gpu_ctx.device)
+    wl = synth.make_whitelist(60_000, seed=871, device=dev)
+    used = synth.pick_used(wl, 60, seed=872)
+    keys = np.sort(wl.cpu().numpy().astype(np.uint64))
+    in_dir, one, two = str(tmp_path / "in"), str(tmp_path / "one"), str(tmp_path / "two")
+    n = run_files.write_synthetic_dir(synth, in_dir, 6, 1000, used, dev, seed=880, chimera_frac=0.08)
+    kw = dict(max_ed=1, n_workers=3, reads_per_chunk=400, whitelist_keys=keys, gz="device", inflate="device")
+    a = run_files.run(gpu_ctx, in_dir, one, **kw)
+    assert a["files_inflated_on_device"] == 6 and a["reads"] == n
+    path = lambda k: os.path.join(in_dir, f"synth_{k:04d}.fastq.gz")  # noqa: E731
+    text = gzip.open(path(1)).read()
+    cut = text.index(b"\n@", len(text) // 3) + 1
+    open(path(1), "wb").write(gzip.compress(text[:cut], 6) + gzip.compress(text[cut:], 1))
+    text = gzip.open(path(3)).read()
+    z = libmod.bgzf_deflate(text, level=6, block_bytes=max(512, len(text) // 300), n_threads=4).tobytes()
+    assert z.count(b"\x1f\x8b\x08\x04") > 257 and zlib.decompress(z[:z.index(b"\x1f\x8b\x08\x04", 18)], 31) == text[:max(512, len(text) // 300)]
+    open(path(3), "wb").write(z)
+    open(path(4), "ab").write(bytes(512))
+    b = run_files.run(gpu_ctx, in_dir, two, **kw)
+    assert b["files_inflated_on_device"] == 3 and b["reads"] == n and b["assigned"] == a["assigned"]
+    for sub in ("passed", "failed"):
+        names = sorted(os.listdir(os.path.join(one, sub)))
+        assert names == sorted(os.listdir(os.path.join(two, sub))) and len(names) == 6
+        for f in names:
+            assert open(os.path.join(one, sub, f), "rb").read() == open(os.path.join(two, sub, f), "rb").read(), f
+    for f in ("BarcodeList.tsv", "BarcodesAssigned.tsv", "ReadScanner.tsv", "stats.tsv"):
+        assert open(os.path.join(one, f)).read() == open(os.path.join(two, f)).read(), f

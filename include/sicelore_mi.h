@@ -1214,6 +1214,55 @@ int smi_snp_counts(const smi_snp *h, int64_t *counts);
 int smi_snp_line_counts(const smi_snp *h, int64_t *counts, size_t cap_lines, size_t *n_lines);
 int smi_snp_free(smi_snp *h);
 
+/* ---- DeduplicateMolecule (K-DD-*, smi_dedup.hip) ------------------------------------------------------------------------------------------
+ * DeduplicateMolecule.doWork (DeduplicateMolecule.java:L41-302, Molecule.java:L40-60), DESIGN.md section 8f: one record per molecule
+ * (ids[0] + ids[1] of the name `ids0-ids1-rn`) of a FASTQ or single-line FASTA text of any size, in two passes over its segments.
+ * smi_dedup_add_segment (pass 1): the next bytes of the input; a segment starts outside a record.  *consumed = the offset of the first
+ * record start whose lines are not all inside the segment, else one past the last LF (is_last: n_bytes); the caller passes the bytes
+ * from there on again in front of the next segment.  *consumed == 0 without is_last: nothing was taken (no whole line, or one record
+ * longer than the segment) and the caller comes again with more bytes.  A name with fewer than three fields or a third field that is no
+ * Java int, a record cut short by the end of the input and a line of 2^32 bytes or more fail the call (SMI_ERR_INVALID);
+ * smi_dedup_error_line then gives the smallest such line, 1-based over the whole input (0: none), and the handle takes no more input.
+ * smi_dedup_select: after the last segment; builds the molecule table and picks each molecule's record.  stage_ms (may be NULL):
+ * SMI_DEDUP_STAGES device times so far.  smi_dedup_emit_segment (pass 2): `segment` counts the calls of pass 1 that took bytes, `text`
+ * the same bytes again (at least the consumed ones); out: the segment's winners as the reference writes them (L241-245, L162-164,
+ * L287), in input order.  out == NULL -> *n_out only; cap too small -> returns 1.  smi_dedup_counts: SMI_DEDUP_COUNTS entries.
+ * smi_dedup_stage_ms: the device times, the writer's included. */
+#define SMI_DEDUP_LINES 0        /* lines of the input */
+#define SMI_DEDUP_RECORDS 1      /* records folded: the reference's `count` */
+#define SMI_DEDUP_NULL 2         /* records whose sequence line is `null`: dropped, not counted */
+#define SMI_DEDUP_SKIPPED 3      /* lines outside a record that start none */
+#define SMI_DEDUP_MOLECULES 4    /* the reference's map.size(): records written */
+#define SMI_DEDUP_BYTES 5        /* bytes of the whole output */
+#define SMI_DEDUP_SEGMENTS 6     /* segments taken */
+#define SMI_DEDUP_TABLE_SLOTS 7  /* slots of the molecule table */
+#define SMI_DEDUP_PROBE_STEPS 8  /* slots passed over by K-DD-INSERT, all records together */
+#define SMI_DEDUP_WRAPS 9        /* of those, steps from the last slot to the first */
+#define SMI_DEDUP_COUNTS 10
+#define SMI_DEDUP_MS_INDEX 0     /* line table, K-DD-STATE, record starts */
+#define SMI_DEDUP_MS_PARSE 1     /* K-DD-PARSE */
+#define SMI_DEDUP_MS_INSERT 2    /* K-DD-INSERT */
+#define SMI_DEDUP_MS_PICK 3      /* K-DD-PICK and the output layout */
+#define SMI_DEDUP_MS_WRITE 4     /* K-DD-WRITE */
+#define SMI_DEDUP_STAGES 5
+typedef struct {
+    int32_t fasta;            /* 0: FASTQ ('@', four lines); 1: single-line FASTA ('>', two lines) */
+    int32_t select;           /* SELECT (1): FASTQ only; 0 keeps the first record of every molecule */
+    int32_t hash_bits;        /* (64) the key's hash is masked to this many bits before its slot is chosen; 0: one probe chain */
+    int32_t reserved;
+    int64_t min_table_slots;  /* (0) floor of the slot count, which is a power of two of at least two slots per record */
+} smi_dedup_config;
+typedef struct smi_dedup smi_dedup;
+int smi_dedup_default_config(smi_dedup_config *cfg);
+int smi_dedup_create(smi_ctx *ctx, const smi_dedup_config *cfg, smi_dedup **out);
+int smi_dedup_add_segment(smi_dedup *h, const uint8_t *text, size_t n_bytes, int32_t is_last, size_t *consumed);
+int smi_dedup_select(smi_dedup *h, float *stage_ms);
+int smi_dedup_emit_segment(smi_dedup *h, int32_t segment, const uint8_t *text, size_t n_bytes, uint8_t *out, size_t cap, size_t *n_out);
+int smi_dedup_counts(const smi_dedup *h, int64_t *counts);
+int smi_dedup_stage_ms(const smi_dedup *h, float *stage_ms);
+int smi_dedup_error_line(const smi_dedup *h, int64_t *line);
+int smi_dedup_free(smi_dedup *h);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

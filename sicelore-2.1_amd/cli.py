@@ -7,6 +7,7 @@
 
     java -jar [-Xmx..] Sicelore-2.1.jar ComputeConsensus -I <bam> -O <fastq> [-T n] [-CELLTAG BC] ... [-MAXREADS 20] [-MINPS 3] [-MAXPS 20]   (or I=<bam> O=<fastq> ...)
     java -jar [-Xmx..] Sicelore-2.1.jar SNPMatrix I=<bam> CSV=<barcodes> SNP=<sites.csv> O=<dir> [PREFIX=snp] [MINRN=0] [MINQV=0] [CELLTAG=BC] [UMITAG=U8] [RNTAG=RN] ...
+    java -jar [-Xmx..] Sicelore-2.1.jar DeduplicateMolecule -I <fastq|fasta> -O <fastq|fasta> [-SELECT true] [-TSO seq] [-MAXPOS 100]                  (or I=<..> O=<..> ...)
 
 become   python sicelore-2.1_amd scanfastq ... / assignumis ... / tagbamwithread ... / ComputeConsensus ...   (the directory is runnable: __main__.py; a `java` wrapper that drops
 `-jar`, `-Xmx..` and the jar's name makes /root/reference/quickrun-2.1.sh:35,42 run unchanged, tests/test_cli_gpu.py does exactly that).
@@ -636,6 +637,35 @@ def snpmatrix(argv):
     return 0
 
 
+# DeduplicateMolecule (DeduplicateMolecule.java:L24-33).  TSO and MAXPOS are accepted and change nothing: every cleanTso call of the
+# reference is commented out (L120, L200, L277).
+DD_OPTIONS = {
+    "I": (None, "path", None), "O": (None, "path", None), "TSO": (None, "str", "AACGCAGAGTACATGG"), "MAXPOS": (None, "int", 100),
+    "SELECT": (None, "bool", True), "VALIDATION_STRINGENCY": (None, "stringency", "STRICT"),
+}
+DD_LONG = {"INPUT": "I", "OUTPUT": "O"}
+
+
+def deduplicatemolecule(argv):
+    """DeduplicateMolecule.doWork (L41-56).  VALIDATION_STRINGENCY is accepted and changes nothing."""
+    o = _picard_parse(argv, "DeduplicateMolecule", DD_OPTIONS, DD_LONG)
+    need = [k for k in ("I", "O") if k not in o]
+    if need:
+        raise CliError(f"sub-command DeduplicateMolecule: missing required option(s) {', '.join(need)}")
+    if not os.path.isfile(o["I"]):
+        raise CliError(f"DeduplicateMolecule: I={o['I']}: no such file")     # IOUtil.assertFileIsReadable (L43)
+    if o["I"].lower().endswith(".gz"):
+        raise CliError(f"DeduplicateMolecule: I={o['I']}: a .gz input is not read (the reference would take its compressed bytes for FASTA): "
+                       "decompress it first")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise CliError("DeduplicateMolecule runs in one process on one GPU in this build: start it without torchrun")
+    from .dedupmolecule import deduplicate_molecule
+    ctx = _context()
+    info = deduplicate_molecule(ctx, o["I"], o["O"], select=o.get("SELECT", True), log=sys.stderr)
+    print(f"DONE -- {info['records']} records, {info['molecules']} molecules, {info['bytes_written']} bytes written", file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
@@ -659,7 +689,9 @@ def main(argv=None):
             return isoformmatrix(rest)
         if sub == "SNPMatrix":
             return snpmatrix(rest)
-        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus, IsoformMatrix and SNPMatrix (mergestats, parseillumina: "
+        if sub == "DeduplicateMolecule":
+            return deduplicatemolecule(rest)
+        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus, DeduplicateMolecule, IsoformMatrix and SNPMatrix (mergestats, parseillumina: "
                        "SURVEY 2, out of scope)")
     except CliError as e:
         print(f"ERROR: {e}", file=sys.stderr)

@@ -286,6 +286,30 @@ int launch_fastq_sweep(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, size
     return SMI_OK;
 }
 
+// The line starts alone, for a caller with record rules of its own (smi_dedup.hip): line_start[L] for every line L < cap_lines, entry
+// [number of newlines] = one past the last newline included.  Right behind launch_fastq_sweep on the same text it continues from that
+// sweep's flags; otherwise it makes them.  Nothing waits for the host.
+int launch_fastq_line_starts(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, uint64_t *d_line_start, size_t cap_lines, hipStream_t s) {
+    if (!n_bytes) return SMI_OK;
+    size_t cub_a = 0;
+    SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_a, (uint32_t *)nullptr, (uint64_t *)nullptr, (int)((n_bytes + kFqTile - 1) / kFqTile), s));
+    const FqScratch L = fq_scratch(n_bytes, false, cub_a);
+    const bool swept = ctx->fq_swept_text == d_text && ctx->fq_swept_bytes == n_bytes && L.total <= ctx->scan_tmp_bytes;
+    ctx->fq_swept_text = nullptr;
+    if (int rc = ensure_scan_tmp(ctx, L.total)) return rc;
+    uint8_t *tmp = (uint8_t *)ctx->scan_tmp;
+    uint32_t *counts = (uint32_t *)tmp;
+    uint64_t *bases = (uint64_t *)(tmp + L.off_base);
+    uint64_t *masks = (uint64_t *)(tmp + L.off_masks);
+    if (!swept) {
+        hipLaunchKernelGGL(k_fq_count_masks, dim3((unsigned)L.n_blocks), dim3(kFqBlock), 0, s, d_text, n_bytes, counts, masks);
+        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(tmp + L.off_cub, cub_a, counts, bases, (int)L.n_blocks, s));
+    }
+    hipLaunchKernelGGL(k_fq_lines_masks, dim3((unsigned)L.n_blocks), dim3(kFqBlock), 0, s, masks, bases, d_line_start, cap_lines);
+    SMI_HIP(hipGetLastError());
+    return SMI_OK;
+}
+
 int launch_fastq_index(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, uint64_t *d_line_start, size_t cap_lines,
                        uint64_t *d_name_start, uint32_t *d_name_len, uint64_t *d_seq_start, uint32_t *d_seq_len,
                        uint64_t *d_qual_start, uint64_t *d_offsets, size_t cap_records, size_t *n_records, uint32_t *errors,

@@ -255,6 +255,8 @@ int launch_split_offsets(smi_ctx *ctx, const smi_chimera_result *d_chim, const u
                          uint32_t *d_scratch, uint64_t *d_total, uint64_t *d_frag_offsets, uint32_t *d_frag_src,
                          hipStream_t s);
 int launch_fastq_sweep(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, size_t *n_lines, hipStream_t s);  // first half of the index + line count
+int launch_fastq_line_starts(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, uint64_t *d_line_start, size_t cap_lines,
+                             hipStream_t s);  // second half alone: the line starts, for record rules other than K-FQ's (smi_dedup.hip)
 int launch_fastq_index(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, uint64_t *d_line_start, size_t cap_lines,
                        uint64_t *d_name_start, uint32_t *d_name_len, uint64_t *d_seq_start, uint32_t *d_seq_len,
                        uint64_t *d_qual_start, uint64_t *d_offsets, size_t cap_records, size_t *n_records, uint32_t *errors,

@@ -72,6 +72,8 @@ EXPORTS = [
     "smi_isoform_counts", "smi_isoform_free", "smi_isoform_isobam",
     "smi_snp_default_config", "smi_snp_create", "smi_snp_add_segment", "smi_snp_run", "smi_snp_output", "smi_snp_counts",
     "smi_snp_line_counts", "smi_snp_free",
+    "smi_dedup_default_config", "smi_dedup_create", "smi_dedup_add_segment", "smi_dedup_select", "smi_dedup_emit_segment",
+    "smi_dedup_counts", "smi_dedup_stage_ms", "smi_dedup_error_line", "smi_dedup_free",
 ]
 
 
@@ -266,6 +268,15 @@ def load_library():
     lib.smi_snp_counts.argtypes = [vp, vp]
     lib.smi_snp_line_counts.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
     lib.smi_snp_free.argtypes = [vp]
+    lib.smi_dedup_default_config.argtypes = [vp]
+    lib.smi_dedup_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
+    lib.smi_dedup_add_segment.argtypes = [vp, vp, sz, ctypes.c_int32, ctypes.POINTER(sz)]
+    lib.smi_dedup_select.argtypes = [vp, vp]
+    lib.smi_dedup_emit_segment.argtypes = [vp, ctypes.c_int32, vp, sz, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_dedup_counts.argtypes = [vp, vp]
+    lib.smi_dedup_stage_ms.argtypes = [vp, vp]
+    lib.smi_dedup_error_line.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_dedup_free.argtypes = [vp]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     explicit = {"smi_last_error", "smi_version", "smi_read_planes_words", "smi_packed_planes_words", "smi_record_flags"}  # restype set above (char*, size_t)
@@ -866,6 +877,96 @@ class Snp:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.smi_snp_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class DedupConfig(ctypes.Structure):
+    """smi_dedup_config"""
+    _fields_ = [("fasta", ctypes.c_int32), ("select", ctypes.c_int32), ("hash_bits", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("min_table_slots", ctypes.c_int64)]
+
+
+# smi_dedup_counts, in SMI_DEDUP_* order
+DEDUP_COUNTS = ("lines", "records", "null_records", "skipped_lines", "molecules", "bytes_out", "segments", "table_slots", "probe_steps", "wraps")
+# smi_dedup_stage_ms, in SMI_DEDUP_MS_* order
+DEDUP_STAGES = ("index", "parse", "insert", "pick", "write")
+
+
+class DedupError(SmiError):
+    """an input DeduplicateMolecule stops on; .line: the smallest offending line, 1-based"""
+
+    def __init__(self, msg, line):
+        super().__init__(msg)
+        self.line = line
+
+
+class Dedup:
+    """DeduplicateMolecule (smi_dedup_*): the text in segments (pass 1), select, the same segments again (pass 2).
+    Keywords: the fields of smi_dedup_config."""
+
+    def __init__(self, ctx, **kw):
+        self._lib = load_library()
+        cfg = DedupConfig()
+        self._lib.smi_dedup_default_config(ctypes.byref(cfg))
+        for k, v in kw.items():
+            if k not in ("fasta", "select", "hash_bits", "min_table_slots"):
+                raise ValueError(f"unknown smi_dedup_config field {k!r}")
+            setattr(cfg, k, int(v))
+        self._h = ctypes.c_void_p()
+        if self._lib.smi_dedup_create(ctx._h, ctypes.byref(cfg), ctypes.byref(self._h)):
+            self._h = None
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._ctx = ctx
+
+    @staticmethod
+    def _bytes(text):
+        if not isinstance(text, np.ndarray) or text.dtype != np.uint8 or text.ndim != 1 or not text.flags.c_contiguous:
+            raise ValueError("text: a contiguous 1-D uint8 array")
+        return text
+
+    def add_segment(self, text, is_last):
+        """-> bytes consumed; 0 without is_last: nothing was taken, come again with more bytes"""
+        text = self._bytes(text)
+        used = ctypes.c_size_t(0)
+        if self._lib.smi_dedup_add_segment(self._h, _ptr(text) if text.size else None, text.size, int(bool(is_last)), ctypes.byref(used)):
+            msg = self._lib.smi_last_error().decode(errors="replace")
+            line = ctypes.c_int64(0)
+            self._lib.smi_dedup_error_line(self._h, ctypes.byref(line))
+            raise DedupError(msg, line.value) if line.value else SmiError(msg)
+        return used.value
+
+    def select(self):
+        if self._lib.smi_dedup_select(self._h, None):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+
+    def emit_segment(self, segment, text):
+        """-> the segment's part of the output (bytes)"""
+        text = self._bytes(text)
+        n = ctypes.c_size_t(0)
+        if self._lib.smi_dedup_emit_segment(self._h, segment, None, 0, None, 0, ctypes.byref(n)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        if n.value == 0:
+            return b""
+        out = np.empty(n.value, dtype=np.uint8)
+        if self._lib.smi_dedup_emit_segment(self._h, segment, _ptr(text) if text.size else None, text.size, _ptr(out), out.size, ctypes.byref(n)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        return out[:n.value].tobytes()
+
+    def counts(self):
+        c = np.zeros(len(DEDUP_COUNTS), dtype=np.int64)
+        self._lib.smi_dedup_counts(self._h, _ptr(c))
+        return dict(zip(DEDUP_COUNTS, (int(x) for x in c)))
+
+    def stage_ms(self):
+        ms = np.zeros(len(DEDUP_STAGES), dtype=np.float32)
+        self._lib.smi_dedup_stage_ms(self._h, _ptr(ms))
+        return dict(zip(DEDUP_STAGES, (float(x) for x in ms)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.smi_dedup_free(self._h)
             self._h = None
 
     __del__ = close

@@ -36,9 +36,9 @@ def main():
     used = synth.pick_used(wl, 5000, seed=2)
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
-            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp}
+            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -758,6 +758,62 @@ def leg_snp(pkg, synth, ctx, dev, wl, used, res):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     res["snp"] = out
+
+
+def _dedup_fixture(n_recs, seq_len, seed=61):
+    """a consensus FASTQ as ComputeConsensus writes it (`@BC16-UMI12-rn`), records of one width so that numpy can lay it out: about 10 % of the
+    records repeat the key of another, rn 10 .. 99, in shuffled order -> uint8 array"""
+    rng = np.random.default_rng(seed)
+    n_keys = n_recs - n_recs // 10
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    keys = acgt[rng.integers(0, 4, size=(n_keys, 28), dtype=np.uint8)]
+    which = np.concatenate([np.arange(n_keys), rng.integers(0, n_keys, size=n_recs - n_keys)])
+    rng.shuffle(which)
+    width = 1 + 16 + 1 + 12 + 1 + 2 + 1 + seq_len + 3 + seq_len + 1
+    text = np.empty((n_recs, width), dtype=np.uint8)
+    text[:, 0] = ord("@")
+    text[:, 1:17] = keys[which, :16]
+    text[:, 17] = ord("-")
+    text[:, 18:30] = keys[which, 16:]
+    text[:, 30] = ord("-")
+    rn = rng.integers(10, 100, size=n_recs)
+    text[:, 31] = ord("0") + rn // 10
+    text[:, 32] = ord("0") + rn % 10
+    text[:, 33] = ord("\n")
+    text[:, 34:34 + seq_len] = acgt[rng.integers(0, 4, size=(n_recs, seq_len), dtype=np.uint8)]
+    text[:, 34 + seq_len:37 + seq_len] = np.frombuffer(b"\n+\n", dtype=np.uint8)
+    text[:, 37 + seq_len:37 + 2 * seq_len] = rng.integers(33, 74, size=(n_recs, seq_len), dtype=np.uint8)
+    text[:, -1] = ord("\n")
+    return text.reshape(-1), n_keys
+
+
+def leg_dedup(pkg, synth, ctx, dev, wl, used, res):
+    """K-DD-* (`DeduplicateMolecule`): a seeded FASTQ of SMI_MB_DEDUP_RECS records (2,000,000) of SMI_MB_DEDUP_LEN bases (300), about 10 % of them
+    with the key of another record, file to file in segments of 256 MiB: device ms per stage (HIP events, all segments together) and wall
+    seconds per pass.  The text goes to the device twice, once per pass; text_gbytes_per_s is the file size over the wall time."""
+    import shutil
+    import tempfile
+
+    dd = importlib.import_module(graft.PKG_NAME + ".dedupmolecule")
+    n_recs = int(os.environ.get("SMI_MB_DEDUP_RECS", "2000000"))
+    seq_len = int(os.environ.get("SMI_MB_DEDUP_LEN", "300"))
+    t0 = time.perf_counter()
+    text, n_keys = _dedup_fixture(n_recs, seq_len)
+    out = {"records": n_recs, "keys": n_keys, "seq_len": seq_len, "text_bytes": int(text.size), "fixture_s": time.perf_counter() - t0}
+    d = tempfile.mkdtemp(prefix="dedup_")
+    try:
+        text.tofile(os.path.join(d, "in.fq"))
+        del text
+        runs = []
+        for _rep in range(2):          # the first run loads the code objects
+            info = dd.deduplicate_molecule(ctx, os.path.join(d, "in.fq"), os.path.join(d, "out.fq"))
+            keys = ("lines", "records", "molecules", "segments", "table_slots", "probe_steps", "wraps", "bytes_written")
+            runs.append(dict({k: info[k] for k in keys}, stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"],
+                             records_per_s=info["records"] / info["wall_s"], text_gbytes_per_s=out["text_bytes"] / info["wall_s"] / 1e9))
+        out["first_run"], out["file_to_file"] = runs
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    res["dedup"] = out
 
 
 def leg_inflate(pkg, synth, ctx, dev, wl, used, res):

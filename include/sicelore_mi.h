@@ -1029,6 +1029,62 @@ int smi_tagbam_segment(smi_tagbam *h, const uint8_t *bam, size_t n_bam, const sm
 /* device time in ms of the stages of the last create / segment (HIP events on the context's stream) */
 int smi_tagbam_stage_ms(const smi_tagbam *h, float *ms);
 
+/* ---- AddBamMoleculeTags / AddGeneNameTag (K-NAME, K-GENE, K-EDIT; smi_moltag.hip) --------------------------------------------------------
+ * Replaces AddBamMoleculeTags.doWork (org/ipmc/sicelore/programs/AddBamMoleculeTags.java:L38-67) and AddGeneNameTag.process / setGeneExons and
+ * helpers (AddGeneNameTag.java:L76-395) over picard's Gene / RefFlatReader and htsjdk's OverlapDetector (the model of smi_genes_load_refflat).
+ * Every record of a segment is written back in input order with up to three attributes set, replaced or removed; the attribute list is the one
+ * htsjdk writes (smi_tagbam_* above: ordered by binary tag, a repeated tag keeping its last value, integers in the smallest type, H as B:c;
+ * SMI_TAG_* errors fail the call).
+ * SMI_MOLTAG_MOLECULE (L48-57): the read name split at '-' (String.split: trailing empty pieces dropped, leading and inner ones kept), split
+ *   at '|' instead when that gave exactly one piece; exactly three pieces -> cell_tag = piece 0 (Z), umi_tag = piece 1 (Z), rn_tag =
+ *   Integer(piece 2) in that order (a later one wins when tags coincide); any other count leaves the record as it is.  Unmapped records
+ *   are tagged like the others.
+ * SMI_MOLTAG_GENE (L116-160): per mapped record (neither FLAG 4 nor reference -1; the others get no edit) function_tag = the top locus
+ *   function over the genes whose interval overlaps [alignment start, alignment end] (INTERGENIC without one), gene_tag / strand_tag = the
+ *   comma-joined names and signs of the genes with an exon under an alignment block and a CODING or UTR function, on the read's strand
+ *   with use_strand_info -- both REMOVED when no gene is kept.  allow_multi_gene_reads = 0 keeps no gene at all, as the reference's
+ *   retainAll on an empty set does (L208).  A value of two or more genes lists them in the reference's HashSet order: those records are
+ *   counted (SMI_MOLTAG_MULTI_GENE) and ordered by the host code behind smi_gene_tag_chunk.
+ * DEVIATION: where the reference's loop dies in an exception its catch swallows (L62-64 / L111), leaving a cut-off file -- a third name piece
+ *   that is no int (L56); a mapped record without an M / = / X operation whose interval [start, start + reference length - 1] overlaps a gene
+ *   (L362) -- smi_moltag_segment returns 2, smi_last_error and smi_moltag_error_read name the first such read in input order, and the
+ *   caller writes no file.
+ * smi_moltag_segment: bam / recs / out / cap / *n_out and the two-call protocol are those of smi_tagbam_segment.  smi_moltag_counts:
+ * SMI_MOLTAG_COUNTS entries summed over the segments (the five ReadTaggingMetric counters L399-403 wrap like Java ints and stay 0 without
+ * use_strand_info).  smi_moltag_stage_ms: device ms of K-NAME, K-GENE, K-EDIT SIZE + scan, K-EDIT WRITE of the last segment. */
+#define SMI_MOLTAG_MOLECULE 0
+#define SMI_MOLTAG_GENE 1
+#define SMI_MOLTAG_RECORDS 0            /* records seen */
+#define SMI_MOLTAG_TAGGED 1             /* MOLECULE: records with three name pieces; GENE: mapped records */
+#define SMI_MOLTAG_TOTAL_READS 2        /* TOTAL_READS */
+#define SMI_MOLTAG_WRONG_STRAND 3       /* READS_WRONG_STRAND */
+#define SMI_MOLTAG_RIGHT_STRAND 4       /* READS_RIGHT_STRAND */
+#define SMI_MOLTAG_AMBIGUOUS_FIXED 5    /* READ_AMBIGUOUS_GENE_FIXED */
+#define SMI_MOLTAG_AMBIGUOUS_REJECTED 6 /* AMBIGUOUS_READS_REJECTED: always 0 (L183-187) */
+#define SMI_MOLTAG_MULTI_GENE 7         /* records that keep two or more genes (ordered on the host) */
+#define SMI_MOLTAG_WITH_GENE 8          /* records that keep at least one gene */
+#define SMI_MOLTAG_N_GENES 9            /* genes of the model: OverlapDetector.getAll().size() (L84) */
+#define SMI_MOLTAG_COUNTS 10
+#define SMI_MOLTAG_STAGES 4
+typedef struct {
+    int32_t program;                                  /* SMI_MOLTAG_MOLECULE / SMI_MOLTAG_GENE */
+    char cell_tag[4], umi_tag[4], rn_tag[4];          /* CELLTAG, UMITAG, RNTAG (AddBamMoleculeTags.java:L26-31): two characters + NUL */
+    char gene_tag[4], strand_tag[4], function_tag[4]; /* GENETAG, STRANDTAG, FUNCTIONTAG (AddGeneNameTag.java:L38-43) */
+    int32_t use_strand_info;                          /* USE_STRAND_INFO (L44-45) */
+    int32_t allow_multi_gene_reads;                   /* ALLOW_MULTI_GENE_READS (L46-47) */
+} smi_moltag_config;
+typedef struct smi_moltag smi_moltag;
+int smi_moltag_default_config(int32_t program, smi_moltag_config *cfg);
+/* genes: the model for SMI_MOLTAG_GENE (it must outlive the handle), NULL otherwise */
+int smi_moltag_create(smi_ctx *ctx, const smi_moltag_config *cfg, const smi_genes *genes, smi_moltag **out);
+int smi_moltag_segment(smi_moltag *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n, uint8_t *out, size_t cap,
+                       size_t *n_out);
+int smi_moltag_counts(const smi_moltag *h, int64_t *counts);
+/* the read that ended the run (smi_moltag_segment returned 2): its name (cut to cap - 1 bytes) and its index over all segments; -1 = none */
+int smi_moltag_error_read(const smi_moltag *h, char *name, size_t cap, int64_t *record);
+int smi_moltag_stage_ms(const smi_moltag *h, float *ms);
+int smi_moltag_free(smi_moltag *h);
+
 /* ---- ComputeConsensus (K-POA, smi_consensus.hip) ---------------------------------------------------------------------------------------
  * Replaces ComputeConsensus.doWork (org/ipmc/sicelore/programs/ComputeConsensus.java:L67-107) with LongreadParser (LongreadParser.java:L42-115),
  * LongreadRecord.fromSAMRecord (LongreadRecord.java:L71-195), Longread.getBestRecord (Longread.java:L56-60), MoleculeDataset(LongreadParser)

@@ -666,6 +666,57 @@ def deduplicatemolecule(argv):
     return 0
 
 
+# AddBamMoleculeTags (AddBamMoleculeTags.java:L22-31) and AddGeneNameTag (AddGeneNameTag.java:L32-49): Picard's option names -> (keyword of
+# moltags.add_bam_molecule_tags / add_gene_name_tag or None, kind, default)
+MT_OPTIONS = {
+    "I": (None, "path", None), "O": (None, "path", None), "CELLTAG": ("cell_tag", "tag", "BC"), "UMITAG": ("umi_tag", "tag", "U8"),
+    "RNTAG": ("rn_tag", "tag", "RN"), "VALIDATION_STRINGENCY": (None, "stringency", "STRICT"),
+}
+GN_OPTIONS = {
+    "I": (None, "path", None), "O": (None, "path", None), "REFFLAT": (None, "path", None), "GENETAG": ("gene_tag", "tag", "GE"),
+    "STRANDTAG": ("strand_tag", "tag", "GS"), "FUNCTIONTAG": ("function_tag", "tag", "XF"), "USE_STRAND_INFO": ("use_strand_info", "bool", True),
+    "ALLOW_MULTI_GENE_READS": ("allow_multi_gene_reads", "bool", True), "DEBUG": (None, "bool", False),
+    "VALIDATION_STRINGENCY": (None, "stringency", "STRICT"),
+}
+MT_LONG = {"INPUT": "I", "OUTPUT": "O"}
+
+
+def _moltag_options(argv, prog, options, files):
+    o = _picard_parse(argv, prog, options, MT_LONG)
+    need = [k for k in files + ("O",) if k not in o]
+    if need:
+        raise CliError(f"sub-command {prog}: missing required option(s) {', '.join(need)}")
+    for k in files:                                                         # IOUtil.assertFileIsReadable
+        if not os.path.isfile(o[k]):
+            raise CliError(f"{prog}: {k}={o[k]}: no such file")
+    if not o["O"].endswith(".bam"):                                         # makeSAMOrBAMWriter picks the format by the name: only BAM is written
+        raise CliError(f"{prog}: O={o['O']}: this build writes BAM only, the output name must end in .bam")
+    if not os.path.isdir(os.path.dirname(os.path.abspath(o["O"]))):         # IOUtil.assertFileIsWritable
+        raise CliError(f"{prog}: O={o['O']}: no such directory")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise CliError(f"{prog} runs in one process on one GPU in this build: start it without torchrun")
+    return o, {f: o.get(k, d) for k, (f, _kind, d) in options.items() if f is not None}
+
+
+def addbammoleculetags(argv):
+    """AddBamMoleculeTags.doWork (L38-67).  VALIDATION_STRINGENCY is accepted and changes nothing."""
+    o, cfg = _moltag_options(argv, "AddBamMoleculeTags", MT_OPTIONS, ("I",))
+    from .moltags import add_bam_molecule_tags
+    info = add_bam_molecule_tags(_context(), o["I"], o["O"], n_threads=_ncpu({}), **cfg)
+    print(f"DONE -- {info['records']} records, {info['tagged']} of them tagged", file=sys.stderr)
+    return 0
+
+
+def addgenenametag(argv):
+    """AddGeneNameTag.doWork (L61-74) and process (L76-114).  DEBUG and VALIDATION_STRINGENCY are accepted and change nothing; the
+    Defaults.allDefaults() dump (L69) is not written."""
+    o, cfg = _moltag_options(argv, "AddGeneNameTag", GN_OPTIONS, ("REFFLAT", "I"))
+    from .moltags import add_gene_name_tag
+    info = add_gene_name_tag(_context(), o["I"], o["O"], o["REFFLAT"], n_threads=_ncpu({}), log=sys.stderr, **cfg)
+    print(f"DONE -- {info['records']} records, {info['with_gene']} of them with a gene", file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
@@ -691,7 +742,11 @@ def main(argv=None):
             return snpmatrix(rest)
         if sub == "DeduplicateMolecule":
             return deduplicatemolecule(rest)
-        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus, DeduplicateMolecule, IsoformMatrix and SNPMatrix (mergestats, parseillumina: "
+        if sub == "AddBamMoleculeTags":
+            return addbammoleculetags(rest)
+        if sub == "AddGeneNameTag":
+            return addgenenametag(rest)
+        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus, DeduplicateMolecule, AddBamMoleculeTags, AddGeneNameTag, IsoformMatrix and SNPMatrix (mergestats, parseillumina: "
                        "SURVEY 2, out of scope)")
     except CliError as e:
         print(f"ERROR: {e}", file=sys.stderr)

@@ -638,6 +638,12 @@ int top_scoring(const std::vector<int> &fs) {  // getTopScoringLocusFunction L34
 
 extern "C" int smi_gene_tag_chunk(const smi_genes *G, const int32_t *ref_id, const uint16_t *flags, const int32_t *pos0, const uint32_t *cigars,
                                   const uint32_t *cigar_off, int32_t n, char *out, size_t cap, uint32_t *out_off, size_t *n_out) {
+    return gene_tag_chunk_opt(G, ref_id, flags, pos0, cigars, cigar_off, n, true, out, cap, out_off, n_out);
+}
+
+// smi_gene_tag_chunk with the strand filter as an option (smi_internal.h): use_strand false lists every kept gene, in the same iteration order
+int smi::gene_tag_chunk_opt(const smi_genes *G, const int32_t *ref_id, const uint16_t *flags, const int32_t *pos0, const uint32_t *cigars,
+                            const uint32_t *cigar_off, int32_t n, bool use_strand, char *out, size_t cap, uint32_t *out_off, size_t *n_out) {
     if (!G || !n_out || n < 0 || (n && (!ref_id || !flags || !pos0 || !cigar_off || !out_off))) {
         set_error("smi_gene_tag_chunk: null argument");
         return SMI_ERR_INVALID;
@@ -743,7 +749,7 @@ extern "C" int smi_gene_tag_chunk(const smi_genes *G, const int32_t *ref_id, con
         // getGenesConsistentWithReadStrand L125-154
         const bool neg_read = (flags[i] & 16) != 0;
         std::vector<int> same, opposite;
-        for (int gi : genes) (G->genes[(size_t)gi].negative == neg_read ? same : opposite).push_back(gi);
+        for (int gi : genes) (!use_strand || G->genes[(size_t)gi].negative == neg_read ? same : opposite).push_back(gi);
         (void)opposite;  // only counted in the reference's metrics; a read with opposite-strand genes only gets no GE
         std::string ge, gs;
         for (size_t k = 0; k < same.size(); k++) {
@@ -804,4 +810,33 @@ extern "C" int smi_gene_tag_bam(const smi_genes *G, const uint8_t *bam, size_t n
     }
     if (cg.empty()) cg.push_back(0);
     return smi_gene_tag_chunk(G, rid.data(), fl.data(), p0.data(), cg.data(), off.data(), n, out, cap, out_off, n_out);
+}
+
+// the loaded model flattened for the device (smi_internal.h): nothing is decided here that the loaders have not decided
+void smi::genes_flatten(const smi_genes *G, FlatGenes &f) {
+    f = FlatGenes();
+    f.n_loaded = G->genes.size();
+    f.contig_off.push_back(0);
+    for (const std::vector<int> &v : G->by_contig) {
+        int32_t run = -2147483647 - 1;
+        for (int gi : v) {
+            const Gene &g = G->genes[(size_t)gi];
+            run = std::max(run, (int32_t)g.end);
+            f.g_start.push_back(g.start);
+            f.g_end.push_back(g.end);
+            f.g_runmax.push_back(run);
+            f.g_neg.push_back(g.negative ? 1 : 0);
+            f.g_hash.push_back(g.hash);
+            f.g_name.push_back(g.name);
+            f.g_tx_off.push_back((int32_t)f.tx.size() / 4);
+            for (const Transcript &t : g.tx) {
+                f.tx.insert(f.tx.end(), {t.tx_start, t.tx_end, t.cds_start, t.cds_end});
+                f.t_ex_off.push_back((int32_t)f.exons.size() / 2);
+                for (const auto &e : t.exons) f.exons.insert(f.exons.end(), {e.first, e.second});
+            }
+        }
+        f.contig_off.push_back((int32_t)f.g_start.size());
+    }
+    f.g_tx_off.push_back((int32_t)f.tx.size() / 4);
+    f.t_ex_off.push_back((int32_t)f.exons.size() / 2);
 }

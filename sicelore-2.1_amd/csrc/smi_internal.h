@@ -20,6 +20,23 @@ int tag_assemble_z2(hipStream_t s, const uint8_t *d_bam, const smi_bam_record *d
                     const uint64_t *d_a_start, const uint32_t *d_a_len, const uint64_t *d_b_start, const uint32_t *d_b_len, const char *tag_a,
                     const char *tag_b, std::vector<uint8_t> &out, float *ms);
 
+// smi_gene.hip: the loaded gene model flattened for K-GENE (smi_moltag.hip).  Genes per contig in by_contig order ((start, end) ascending) with the
+// running maximum of `end`, K-SNP's layout for its lines; transcripts in Gene.iterator() order; exons as the loader keeps them (ascending, disjoint).
+struct FlatGenes {
+    size_t n_loaded = 0;                  // OverlapDetector.getAll().size()
+    std::vector<int32_t> contig_off;      // [n_refs + 1] into the gene arrays
+    std::vector<int32_t> g_start, g_end, g_runmax, g_hash, g_tx_off;  // g_tx_off: [genes + 1] into tx / 4
+    std::vector<uint8_t> g_neg;
+    std::vector<std::string> g_name;
+    std::vector<int32_t> tx;              // tx_start, tx_end, cds_start, cds_end per transcript (1-based, inclusive)
+    std::vector<int32_t> t_ex_off;        // [transcripts + 1] into exons / 2
+    std::vector<int32_t> exons;           // start, end
+};
+void genes_flatten(const smi_genes *g, FlatGenes &out);
+// smi_gene_tag_chunk with getGenesConsistentWithReadStrand as an option (AddGeneNameTag's USE_STRAND_INFO)
+int gene_tag_chunk_opt(const smi_genes *g, const int32_t *ref_id, const uint16_t *flags, const int32_t *pos0, const uint32_t *cigars,
+                       const uint32_t *cigar_off, int32_t n, bool use_strand, char *out, size_t cap, uint32_t *out_off, size_t *n_out);
+
 // smi_inflate_host.hip: the host's DEFLATE decoder and CRC-32
 uint32_t host_crc32(uint32_t crc, const uint8_t *p, size_t n);                                   // zlib's crc32()
 int host_inflate_exact(const uint8_t *in, size_t n_in, uint8_t *out, size_t n_out);               // 0 = the stream filled out[0 .. n_out)

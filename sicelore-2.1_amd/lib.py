@@ -74,6 +74,8 @@ EXPORTS = [
     "smi_snp_line_counts", "smi_snp_free",
     "smi_dedup_default_config", "smi_dedup_create", "smi_dedup_add_segment", "smi_dedup_select", "smi_dedup_emit_segment",
     "smi_dedup_counts", "smi_dedup_stage_ms", "smi_dedup_error_line", "smi_dedup_free",
+    "smi_moltag_default_config", "smi_moltag_create", "smi_moltag_segment", "smi_moltag_counts", "smi_moltag_error_read", "smi_moltag_stage_ms",
+    "smi_moltag_free",
 ]
 
 
@@ -277,6 +279,13 @@ def load_library():
     lib.smi_dedup_stage_ms.argtypes = [vp, vp]
     lib.smi_dedup_error_line.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]
     lib.smi_dedup_free.argtypes = [vp]
+    lib.smi_moltag_default_config.argtypes = [ctypes.c_int32, vp]
+    lib.smi_moltag_create.argtypes = [vp, vp, vp, ctypes.POINTER(vp)]
+    lib.smi_moltag_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_moltag_counts.argtypes = [vp, vp]
+    lib.smi_moltag_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_moltag_stage_ms.argtypes = [vp, vp]
+    lib.smi_moltag_free.argtypes = [vp]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     explicit = {"smi_last_error", "smi_version", "smi_read_planes_words", "smi_packed_planes_words", "smi_record_flags"}  # restype set above (char*, size_t)
@@ -967,6 +976,96 @@ class Dedup:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.smi_dedup_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class MolTagConfig(ctypes.Structure):
+    """smi_moltag_config"""
+    _fields_ = [("program", ctypes.c_int32), ("cell_tag", ctypes.c_char * 4), ("umi_tag", ctypes.c_char * 4), ("rn_tag", ctypes.c_char * 4),
+                ("gene_tag", ctypes.c_char * 4), ("strand_tag", ctypes.c_char * 4), ("function_tag", ctypes.c_char * 4),
+                ("use_strand_info", ctypes.c_int32), ("allow_multi_gene_reads", ctypes.c_int32)]
+
+
+MOLTAG_MOLECULE, MOLTAG_GENE = 0, 1
+# smi_moltag_counts, in SMI_MOLTAG_* order
+MOLTAG_COUNTS = ("records", "tagged", "total_reads", "wrong_strand", "right_strand", "ambiguous_fixed", "ambiguous_rejected", "multi_gene_records",
+                 "with_gene", "genes")
+MOLTAG_STAGES = ("name", "gene", "size", "write")
+
+
+class MolTagError(SmiError):
+    """a record on which the reference's loop dies (smi_moltag_segment returned 2); .read: its name, .record: its index in the input"""
+
+    def __init__(self, msg, read, record):
+        super().__init__(msg)
+        self.read, self.record = read, record
+
+
+class MolTag:
+    """AddBamMoleculeTags / AddGeneNameTag (smi_moltag_*): BAM segments rewritten with their attributes edited.  program: MOLTAG_MOLECULE or
+    MOLTAG_GENE (then genes: a GeneTagger, kept alive by this object).  Keywords: the other fields of smi_moltag_config."""
+
+    def __init__(self, ctx, program, genes=None, **kw):
+        self._lib = load_library()
+        cfg = MolTagConfig()
+        if self._lib.smi_moltag_default_config(int(program), ctypes.byref(cfg)):
+            raise SmiError(self._lib.smi_last_error().decode())
+        for k, v in kw.items():
+            if k in ("use_strand_info", "allow_multi_gene_reads"):
+                setattr(cfg, k, int(bool(v)))
+            elif k in ("cell_tag", "umi_tag", "rn_tag", "gene_tag", "strand_tag", "function_tag"):
+                b = str(v).encode("latin-1")
+                if len(b) != 2:
+                    raise SmiError(f"{k} {v!r} is not a two-character tag")
+                setattr(cfg, k, b)
+            else:
+                raise ValueError(f"unknown smi_moltag_config field {k!r}")
+        self._h = ctypes.c_void_p()
+        self._genes, self._ctx = genes, ctx       # (the handle reads the model and runs on the context's stream: keep both alive)
+        if self._lib.smi_moltag_create(ctx._h, ctypes.byref(cfg), genes._h if genes is not None else None, ctypes.byref(self._h)):
+            self._h = None
+            raise SmiError(self._lib.smi_last_error().decode())
+
+    def segment(self, bam, recs, out=None):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it -> every record as written (uint8 array)"""
+        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
+            raise ValueError("bam: a contiguous 1-D uint8 array")
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != BAM_RECORD_DTYPE:
+            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
+        n = int(recs.size)
+        n_out = ctypes.c_size_t(0)
+        if out is None:
+            out = np.empty(max(64, bam.size + 64 * n), dtype=np.uint8)
+        while True:
+            rc = self._lib.smi_moltag_segment(self._h, bam.ctypes.data if bam.size else None, bam.size, recs.ctypes.data if n else None, n,
+                                              out.ctypes.data, out.size, ctypes.byref(n_out))
+            if rc == 0:
+                return out[:n_out.value]
+            msg = self._lib.smi_last_error().decode(errors="replace")
+            if rc == 2:
+                name, rec = ctypes.create_string_buffer(256), ctypes.c_int64(-1)
+                self._lib.smi_moltag_error_read(self._h, name, 256, ctypes.byref(rec))
+                raise MolTagError(msg, name.value.decode("latin-1"), rec.value)
+            if rc != 1:
+                raise SmiError(msg)
+            out = np.empty(n_out.value + (n_out.value >> 3), dtype=np.uint8)     # the sized segment stays on the device: written by the next call
+
+    def counts(self):
+        c = np.zeros(len(MOLTAG_COUNTS), dtype=np.int64)
+        self._lib.smi_moltag_counts(self._h, _ptr(c))
+        return dict(zip(MOLTAG_COUNTS, (int(x) for x in c)))
+
+    def stage_ms(self):
+        ms = np.zeros(len(MOLTAG_STAGES), dtype=np.float32)
+        self._lib.smi_moltag_stage_ms(self._h, _ptr(ms))
+        return dict(zip(MOLTAG_STAGES, (float(x) for x in ms)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.smi_moltag_free(self._h)
             self._h = None
 
     __del__ = close

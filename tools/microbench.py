@@ -36,9 +36,9 @@ def main():
     used = synth.pick_used(wl, 5000, seed=2)
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
-            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup}
+            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -581,7 +581,7 @@ def leg_consensus(pkg, synth, ctx, dev, wl, used, res):
     res["consensus"] = out
 
 
-def _isoform_fixture(n_genes, n_recs, n_cells, seed=41):
+def _isoform_fixture(n_genes, n_recs, n_cells, seed=41, molecule_names=False):
     """a seeded refFlat (n_genes genes of 1..19 transcripts, 1..40 exons each) and a BAM of n_recs records: molecules of 1..3 reads, each
     read spliced along one transcript with junction ends moved by up to 3 bases"""
     import struct
@@ -626,6 +626,8 @@ def _isoform_fixture(n_genes, n_recs, n_cells, seed=41):
                 cig.append(max(1, e0 - s0 + 1) << 4 | 0)
                 cur = s0 + max(1, e0 - s0 + 1) - 1
             name = b"r%09d\0" % k
+            if molecule_names:                       # what DeduplicateMolecule leaves: BC-U8-rn
+                name = cell[:-2] + b"-" + umi + b"-%d\0" % int(rng.integers(1, 60))
             aux = aux_m + b"def" + struct.pack("<f", float(rng.integers(0, 50)) / 500)
             body = struct.pack("<iiBBHHHiiii", 0, p1 - 1, len(name), 60, 4680, len(cig), 0, 0, -1, -1, 0) + name + struct.pack(f"<{len(cig)}I", *cig) + aux
             recs.append(struct.pack("<I", len(body)) + body)
@@ -667,6 +669,48 @@ def leg_isoform(pkg, synth, ctx, dev, wl, used, res):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     res["isoform"] = out
+
+
+def leg_moltag(pkg, synth, ctx, dev, wl, used, res):
+    """K-NAME / K-GENE / K-EDIT (`AddBamMoleculeTags`, then `AddGeneNameTag` on its output): the isoform leg's seeded refFlat and spliced
+    records (SMI_MB_MOLTAG_GENES genes, SMI_MB_MOLTAG_RECS records, 2,000,000) under names BC-U8-rn.  File to file: device ms per stage
+    (HIP events, summed over the segments), seconds in the device calls (copies included), in deflate and in file writes, wall seconds;
+    beside K-GENE the wall time of smi_gene_tag_bam, the host code it restates, on the same records."""
+    import shutil
+    import tempfile
+
+    mt = importlib.import_module(graft.PKG_NAME + ".moltags")
+    lib = importlib.import_module(graft.PKG_NAME + ".lib")
+    n_genes = int(os.environ.get("SMI_MB_MOLTAG_GENES", "20000"))
+    n_recs = int(os.environ.get("SMI_MB_MOLTAG_RECS", "2000000"))
+    t0 = time.perf_counter()
+    ref, _csv, z, n_rec, n_mol = _isoform_fixture(n_genes, n_recs, 5000, molecule_names=True)
+    out = {"genes": n_genes, "records": n_rec, "molecules_generated": n_mol, "fixture_s": time.perf_counter() - t0}
+    d = tempfile.mkdtemp(prefix="moltag_")
+    try:
+        z.tofile(os.path.join(d, "in.bam"))
+        with open(os.path.join(d, "r.refFlat"), "w") as f:
+            f.write(ref)
+        for name, run in (("AddBamMoleculeTags", lambda: mt.add_bam_molecule_tags(ctx, os.path.join(d, "in.bam"), os.path.join(d, "tags.bam"), n_threads=16)),
+                          ("AddGeneNameTag", lambda: mt.add_gene_name_tag(ctx, os.path.join(d, "tags.bam"), os.path.join(d, "ge.bam"),
+                                                                          os.path.join(d, "r.refFlat"), n_threads=16))):
+            info = run()
+            kernel_s = sum(info["stage_ms"].values()) / 1e3
+            out[name] = dict({k: info[k] for k in lib.MOLTAG_COUNTS}, stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"],
+                             bytes_written=info["bytes_written"], records_per_s=info["records"] / info["wall_s"],
+                             copy_share_of_wall=max(0.0, info["seconds"]["device"] - kernel_s) / info["wall_s"])
+        bam, _used = lib.bgzf_inflate(np.fromfile(os.path.join(d, "tags.bam"), dtype=np.uint8), n_threads=16)
+        _text, refs, start = lib.bam_header(bam)
+        recs, _end = lib.bam_index_records(bam, start, cap=n_rec + 1)
+        tagger = lib.GeneTagger(ref, [r[0] for r in refs])
+        t0 = time.perf_counter()
+        tagger.tag_bam_raw(bam, recs)
+        out["smi_gene_tag_bam_wall_s"] = time.perf_counter() - t0
+        out["k_gene_device_s"] = out["AddGeneNameTag"]["stage_ms"]["gene"] / 1e3
+        tagger.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    res["moltag"] = out
 
 
 def _snp_fixture(n_recs, n_lines, n_cells, seed=51):

@@ -1319,6 +1319,88 @@ int smi_dedup_stage_ms(const smi_dedup *h, float *stage_ms);
 int smi_dedup_error_line(const smi_dedup *h, int64_t *line);
 int smi_dedup_free(smi_dedup *h);
 
+/* ---- CollapseModel (K-COLLAPSE, K-COLSTAT, K-FILTER / K-CLASS, smi_collapse.hip) --------------------------------------------------------
+ * CollapseModel.process (CollapseModel.java:L151-193) without the validator, DESIGN.md section 8h: novel isoforms from the IT = undef records
+ * of an ISOBAM.
+ * smi_collapse_default_config: the defaults of CollapseModel.java:L28-57 (MINEVIDENCE 2, GENETAG IG).
+ * smi_collapse_create: the refFlat text (UCSCRefFlatParser(File) L48-80 over TranscriptRecord.fromRefFlat L92-164; a line of fewer than 11
+ * fields, with a bad integer or strand fails the call naming the line) and the CSV cell list (CellList.java:L15-27, "-1" removed).
+ * smi_collapse_set_references: the BAM's @SQ names in dictionary order (smi_bam_header), before smi_collapse_run: the chromosome printed is
+ * that of a transcript's last evidence record (TranscriptRecord.initialize L365-368).
+ * smi_collapse_add_segment: records of an inflated BAM segment (smi_bam_index_records) through the filter of UCSCRefFlatParser.loader
+ * L138-208 over LongreadRecord.fromSAMRecord L71-184; kept records are held as evidence of (GENETAG, ISOFORMTAG).  A record the reference
+ * throws on inside the loader (an attribute of another type than it casts, a CIGAR the walk runs off, a kept record whose ISOFORMTAG is
+ * neither "undef" nor a transcript of that gene in the refFlat) fails the call; smi_last_error and smi_collapse_error_read name the first
+ * such read in file order (record: its index over all segments), and the handle takes no more input.
+ * smi_collapse_run: K-COLLAPSE (collapse L639-671, isExactSameStructure L673-692) per gene with undef records; K-COLSTAT
+ * (TranscriptRecord.initialize L357-399, the Novel.<n> numbers of L661); the stable sort of compareTo L85-90; K-FILTER / K-CLASS (filter
+ * L243-263, isPartOfLonger L429-460, isIn L368-377, isAllInclude L694-703, noveltyDetector L379-427, junctionsFromExons L705-715); the texts
+ * of exportFiles L595-637 (printLegendTxt, printTxt, printRefflat, printGff, getColor: TranscriptRecord.java L248-338).  Genes are in byte
+ * order of their name.  stage_ms (may be NULL): SMI_COLLAPSE_STAGES device times: K-COLLAPSE, K-COLSTAT (scan, statistics, sort, run-length
+ * encoding), K-FILTER / K-CLASS.  smi_collapse_output: text of SMI_COL_OUT_*; out == NULL -> size only; cap too small -> returns 1.
+ * smi_collapse_counts: SMI_COLLAPSE_COUNTS entries, SMI_COL_*, those from SMI_COL_ISOFORMS on being statistics() L535-592. */
+#define SMI_COL_RECORDS 0            /* records seen */
+#define SMI_COL_KEPT 1               /* evidence records */
+#define SMI_COL_NULL 2               /* no CELLTAG, unmapped, or on no reference sequence */
+#define SMI_COL_MAPQ0 3              /* of the rest: mapq 0 */
+#define SMI_COL_CHIMERIC 4           /* of the rest: clipped by more than MAXCLIP */
+#define SMI_COL_LOW_RN 5             /* of the rest: RN < RNMIN */
+#define SMI_COL_NOT_LISTED 6         /* of the rest: the raw CELLTAG value is not in the cell list */
+#define SMI_COL_NO_GENE 7            /* of the rest: GENETAG missing, "" or "undef" */
+#define SMI_COL_CELLS 8              /* Cells detected */
+#define SMI_COL_MODEL_GENES 9        /* genes of the refFlat */
+#define SMI_COL_MODEL_TRANSCRIPTS 10 /* lines of the refFlat kept */
+#define SMI_COL_GENES 11             /* total_genes */
+#define SMI_COL_UNDEF_RECORDS 12     /* evidence records with ISOFORMTAG undef */
+#define SMI_COL_MONOEXON 13          /* of those: without a junction (they found and join nothing) */
+#define SMI_COL_FOUNDERS 14          /* founders created: the highest Novel.<n> */
+#define SMI_COL_NOVEL_EVIDENCED 15   /* founders of at least MINEVIDENCE records */
+#define SMI_COL_NOVEL_FILTERED 16    /* of those: dropped by filter() */
+#define SMI_COL_ISOFORMS 17          /* total_isoforms */
+#define SMI_COL_EVIDENCES 18         /* total_isoforms (UMI) */
+#define SMI_COL_GENCODE 19           /* gencode, then its UMIs; the valid set equals these two */
+#define SMI_COL_GENCODE_EV 20
+#define SMI_COL_CKJ 21               /* combination_of_known_junctions, then its UMIs */
+#define SMI_COL_CKJ_EV 22
+#define SMI_COL_CKS 23               /* combination_of_known_splicesites */
+#define SMI_COL_CKS_EV 24
+#define SMI_COL_NSS 25               /* at_least_one_novel_splicesite */
+#define SMI_COL_NSS_EV 26
+#define SMI_COL_LONG_LISTS 27        /* undef records whose junction list is longer than lds_junc */
+#define SMI_COL_MAX_UNDEF 28         /* the longest undef list of a gene */
+#define SMI_COL_MAX_FOUNDERS 29      /* the most founders of a gene */
+#define SMI_COLLAPSE_COUNTS 30
+#define SMI_COL_OUT_TXT 0
+#define SMI_COL_OUT_REFFLAT 1
+#define SMI_COL_OUT_FINAL_REFFLAT 2
+#define SMI_COL_OUT_GFF 3
+#define SMI_COL_OUT_FINAL_GFF 4
+#define SMI_COLLAPSE_OUTPUTS 5
+#define SMI_COLLAPSE_STAGES 3
+typedef struct {
+    char cell_tag[4], umi_tag[4], gene_tag[4], iso_tag[4], rn_tag[4];  /* CELLTAG UMITAG GENETAG ISOFORMTAG RNTAG: two characters + NUL */
+    int32_t max_clip;      /* MAXCLIP (150) */
+    int32_t delta;         /* DELTA (2) */
+    int32_t min_evidence;  /* MINEVIDENCE (2) */
+    int32_t rn_min;        /* RNMIN (1) */
+    int32_t n_threads;     /* host loader threads */
+    int32_t lds_junc;      /* junctions of a founder K-COLLAPSE stages in LDS, 1 .. 1024 (default); a longer list is read from global memory */
+} smi_collapse_config;
+typedef struct smi_collapse smi_collapse;
+int smi_collapse_default_config(smi_collapse_config *cfg);
+int smi_collapse_create(smi_ctx *ctx, const smi_collapse_config *cfg, const char *refflat, size_t n_refflat, const char *csv, size_t n_csv,
+                        smi_collapse **out);
+int smi_collapse_set_references(smi_collapse *h, const char *const *ref_names, int32_t n_refs);
+int smi_collapse_add_segment(smi_collapse *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n);
+int smi_collapse_run(smi_collapse *h, float *stage_ms);
+int smi_collapse_output(const smi_collapse *h, int32_t which, uint8_t *out, size_t cap, size_t *n_out);
+int smi_collapse_counts(const smi_collapse *h, int64_t *counts);
+int smi_collapse_error_read(const smi_collapse *h, char *name, size_t cap, int64_t *record);
+int smi_collapse_free(smi_collapse *h);
+/* after smi_collapse_run: collapse() L639-671 as the reference runs it, one host thread over the arrays K-COLLAPSE was given: its wall time
+ * (the baseline tools/microbench.py reports beside K-COLLAPSE) and the number of undef records whose founder differs from the device's (0) */
+int smi_collapse_host_loop(const smi_collapse *h, double *seconds, int64_t *mismatches);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

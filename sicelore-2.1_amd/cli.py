@@ -7,6 +7,7 @@
 
     java -jar [-Xmx..] Sicelore-2.1.jar ComputeConsensus -I <bam> -O <fastq> [-T n] [-CELLTAG BC] ... [-MAXREADS 20] [-MINPS 3] [-MAXPS 20]   (or I=<bam> O=<fastq> ...)
     java -jar [-Xmx..] Sicelore-2.1.jar SNPMatrix I=<bam> CSV=<barcodes> SNP=<sites.csv> O=<dir> [PREFIX=snp] [MINRN=0] [MINQV=0] [CELLTAG=BC] [UMITAG=U8] [RNTAG=RN] ...
+    java -jar [-Xmx..] Sicelore-2.1.jar CollapseModel I=<isobam> CSV=<barcodes> REFFLAT=<refFlat> OUTDIR=<dir> [PREFIX=CollapseModel] [DELTA=2] [MINEVIDENCE=2] [RNMIN=1] ...   (or -I <isobam> ...)
     java -jar [-Xmx..] Sicelore-2.1.jar DeduplicateMolecule -I <fastq|fasta> -O <fastq|fasta> [-SELECT true] [-TSO seq] [-MAXPOS 100]                  (or I=<..> O=<..> ...)
 
 become   python sicelore-2.1_amd scanfastq ... / assignumis ... / tagbamwithread ... / ComputeConsensus ...   (the directory is runnable: __main__.py; a `java` wrapper that drops
@@ -717,6 +718,49 @@ def addgenenametag(argv):
     return 0
 
 
+# CollapseModel (CollapseModel.java:L22-87): Picard's option names -> (smi_collapse_config field or None, kind, default).  The options of
+# the consensus caller (CONSENSUS is the constant false, L96) and the validator's cut-offs are accepted and change nothing.
+CM_OPTIONS = {
+    "I": (None, "path", None), "REFFLAT": (None, "path", None), "CSV": (None, "path", None), "OUTDIR": (None, "path", None),
+    "DELTA": ("delta", "int", 2), "MINEVIDENCE": ("min_evidence", "int", 2), "RNMIN": ("rn_min", "int", 1),
+    "PREFIX": (None, "str", "CollapseModel"), "CELLTAG": ("cell_tag", "tag", "BC"), "UMITAG": ("umi_tag", "tag", "U8"),
+    "GENETAG": ("gene_tag", "tag", "IG"), "ISOFORMTAG": ("iso_tag", "tag", "IT"), "RNTAG": ("rn_tag", "tag", "RN"),
+    "MAXCLIP": ("max_clip", "int", 150), "TSOENDTAG": (None, "tag", "TE"), "POLYASTARTTAG": (None, "tag", "PS"), "CDNATAG": (None, "tag", "CS"),
+    "USTAG": (None, "tag", "US"), "TMPDIR": (None, "str", None), "T": (None, "int", 20), "MAXUMIS": (None, "int", 20), "MINPS": (None, "int", 3),
+    "MAXPS": (None, "int", 20), "DEBUG": (None, "bool", False), "SHORT": (None, "path", None), "CAGE": (None, "path", None),
+    "POLYA": (None, "path", None), "cageCo": (None, "int", 50), "polyaCo": (None, "int", 50), "juncCo": (None, "int", 1),
+    "VALIDATION_STRINGENCY": (None, "stringency", "STRICT"),
+}
+CM_LONG = {"INPUT": "I", "nThreads": "T"}
+
+
+def collapsemodel(argv):
+    """CollapseModel.doWork (L107-138) and process (L151-193) without the validator: with CAGE, POLYA and SHORT all naming existing files the
+    reference validates (L166-171), and this build refuses the run; with any of them missing it does not, and neither does this build."""
+    o = _picard_parse(argv, "CollapseModel", CM_OPTIONS, CM_LONG)
+    need = [k for k in ("I", "REFFLAT", "CSV", "OUTDIR") if k not in o]
+    if need:
+        raise CliError(f"sub-command CollapseModel: missing required option(s) {', '.join(need)}")
+    for k in ("REFFLAT", "I", "CSV"):                                       # IOUtil.assertFileIsReadable (L109-111)
+        if not os.path.isfile(o[k]):
+            raise CliError(f"CollapseModel: {k}={o[k]}: no such file")
+    opt = {k: o.get(k, d) for k, (_f, _kind, d) in CM_OPTIONS.items()}
+    if not os.path.isdir(opt["OUTDIR"]):
+        raise CliError(f"CollapseModel: OUTDIR={opt['OUTDIR']}: no such directory")
+    if all(opt[k] is not None and os.path.exists(opt[k]) for k in ("CAGE", "POLYA", "SHORT")):
+        raise CliError("CollapseModel: CAGE, POLYA and SHORT all exist, which asks for the validation of the novel isoforms "
+                       "(UCSCRefFlatParser.validator): the validator is not part of this build; leave one of them out to run without it")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise CliError("CollapseModel runs in one process on one GPU in this build: start it without torchrun")
+    cfg = {f: opt[k] for k, (f, _kind, _d) in CM_OPTIONS.items() if f is not None}
+    from .collapsemodel import collapse_model
+    ctx = _context()
+    info = collapse_model(ctx, o["I"], o["REFFLAT"], o["CSV"], opt["OUTDIR"], prefix=opt["PREFIX"], n_threads=_ncpu({}), log=sys.stderr, **cfg)
+    print(f"DONE -- {info['kept']} of {info['records']} records, {info['genes']} genes, {info['isoforms']} isoforms, "
+          f"{info['isoforms'] - info['gencode']} of them novel", file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
@@ -746,7 +790,9 @@ def main(argv=None):
             return addbammoleculetags(rest)
         if sub == "AddGeneNameTag":
             return addgenenametag(rest)
-        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus, DeduplicateMolecule, AddBamMoleculeTags, AddGeneNameTag, IsoformMatrix and SNPMatrix (mergestats, parseillumina: "
+        if sub == "CollapseModel":
+            return collapsemodel(rest)
+        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus, DeduplicateMolecule, AddBamMoleculeTags, AddGeneNameTag, IsoformMatrix, SNPMatrix and CollapseModel (mergestats, parseillumina: "
                        "SURVEY 2, out of scope)")
     except CliError as e:
         print(f"ERROR: {e}", file=sys.stderr)

@@ -1,0 +1,1044 @@
+// smi_collapse.hip -- `CollapseModel` (org/ipmc/sicelore/programs/CollapseModel.java:L151-193, the reference README's step 7, "Novel isoform
+// discovery"): the unassigned (IT = undef) molecules of an ISOBAM are collapsed into novel isoforms per gene on the device, counted,
+// filtered against the longer isoforms and the model, and classified; the refFlat model, the cell list, the record loader and the five
+// output texts are host work.  The rules are DESIGN.md section 8h's; tests/collapsemodel.py implements the same ones.
+//
+// Host, in the reference's order:
+//   model     UCSCRefFlatParser(File) L48-80 over TranscriptRecord.fromRefFlat L92-164: exons (start + 1, end), junctions (exon[i-1].end,
+//             exon[i].start); a line whose exon bases sum to 0 is dropped; lines grouped by gene (column 0), in file order.  A line of fewer
+//             than 11 fields, with a bad integer or a strand Strand.toStrand refuses ends the reference's parse silently: here it fails the
+//             call naming the line.  select(gene, tx) (L120-131) = the last line of that gene with that transcript id.
+//   cells     CellList.java L15-27: one barcode per line, every "-1" removed.
+//   loader    UCSCRefFlatParser.loader L138-208 over LongreadRecord.fromSAMRecord(r, false) L71-184: a record is evidence of (IG, IT) when
+//             it has a CELLTAG, is mapped, has mapq > 0, is not chimeric, RN >= RNMIN, its RAW CELLTAG value is in the cell list and its
+//             GENETAG value is not null, "" or "undef".  The junction list is the literal walk of L138-171 (walk_junctions).  The evidence
+//             order of a gene is reference-dictionary order (the loader queries sequence by sequence), then file order.
+// K-COLLAPSE: one block per gene with an undef list (collapse L639-671 with isExactSameStructure L673-692), by rounds.
+// K-COLSTAT: TranscriptRecord.initialize L357-399 per transcript, known and founder alike: evidence count, min txStart, max txEnd, the
+//   last evidence record; distinct cells from (transcript << 32 | cell) codes, hipcub radix sort + run-length encoding; an exclusive scan
+//   of the founder counts gives the Novel.<n> numbers (NOVELINDEX, L661).
+// K-FILTER / K-CLASS: one wavefront per gene: filter L243-263 with isPartOfLonger L429-460 over the list the host sorted (Collections.sort
+//   by TranscriptRecord.compareTo L85-90, stable), and noveltyDetector L379-427 for every novel it keeps.
+// Host again: statistics L535-592 as counters, exportFiles L595-637 over printLegendTxt / printTxt / printRefflat / printGff
+//   (TranscriptRecord.java L248-327).
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <chrono>
+#include <climits>
+#include <cstring>
+#include <string>
+#include <string_view>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+#include "smi_internal.h"
+#include "smi_longread.h"
+#include "smi_mtx.h"
+
+namespace smi {
+namespace {
+
+using mtx::Events;
+
+template <class T>
+struct DevBuf : mtx::DevBuf<T> {
+    DevBuf() { this->who = "CollapseModel"; }
+};
+
+constexpr int kColThreads = 256;  // threads of one K-COLLAPSE block: 4 waves
+constexpr int kColWaves = kColThreads / 64;
+constexpr int kLdsJunc = 1024;    // junctions of a founder staged in LDS (8 KiB); a longer list is read from global memory
+constexpr int kFcWaves = 4;       // waves per block of K-FILTER / K-CLASS
+
+__device__ __forceinline__ bool near(int2 a, int2 b, int d) { return abs(a.x - b.x) <= d && abs(a.y - b.y) <= d; }
+
+// isIn(j, lst, DELTA) (UCSCRefFlatParser L368-377)
+__device__ __forceinline__ bool is_in(int2 j, const int2 *lst, int n, int d) {
+    for (int i = 0; i < n; i++)
+        if (near(lst[i], j, d)) return true;
+    return false;
+}
+
+// isAllInclude(j1, j2) (L694-703): every junction of j1 isIn j2
+__device__ __forceinline__ bool all_include(const int2 *__restrict__ j1, int n1, const int2 *__restrict__ j2, int n2, int d) {
+    for (int i = 0; i < n1; i++)
+        if (!is_in(j1[i], j2, n2, d)) return false;
+    return true;
+}
+
+// K-COLLAPSE.  The reference's loop takes the undef records of a gene in order: record i joins the FIRST founder created before it for
+// which isExactSameStructure holds, else it founds a transcript if it has a junction.  By rounds this is the same: round k takes the
+// smallest record that is neither assigned nor mono-exonic -- every record in front of it has joined a founder of an earlier round or
+// can never found, so it is exactly the reference's k-th founder, and founders arise in increasing record order -- and every unassigned
+// record BEHIND it tests it.  A record still unassigned in round k matched none of the founders 0 .. k-1, so the founder it joins is
+// the first that matches among those created before it; a founder behind the record is never tested against it (the reference has not
+// created it yet when the record is looked at), and a mono-exonic record matches nothing (equal, non-zero junction counts).
+// isExactSameStructure is one-sided, as in the reference: every FOUNDER junction isIn the record's junctions.
+struct ColArgs {
+    const int32_t *cg_off;   // n_cg + 1: undef records of collapse gene c, in evidence order
+    const int32_t *u_j_off;  // n_u + 1: junctions of undef record u in uj
+    const int2 *uj;
+    int32_t delta, lds_junc;
+    int32_t *u_founder;      // per undef record: ordinal of its founder within the gene, -1 none
+    int32_t *cg_nf;          // per collapse gene: founders created
+};
+
+__global__ __launch_bounds__(kColThreads) void k_collapse(ColArgs a) {
+    __shared__ int2 s_j[kLdsJunc];
+    __shared__ int s_min[2][kColWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int u0 = a.cg_off[blockIdx.x], n = a.cg_off[blockIdx.x + 1] - u0;
+    const int32_t *joff = a.u_j_off + u0;
+    int32_t *founder = a.u_founder + u0;
+    for (int i = tid; i < n; i += kColThreads) founder[i] = -1;
+    __syncthreads();
+    int nf = 0, cursor = 0, par = 0;
+    while (cursor < n) {
+        // the smallest unassigned multi-exon record from cursor on: a block reduction per chunk of kColThreads records
+        int first = INT_MAX;
+        for (int base = cursor; base < n && first == INT_MAX; base += kColThreads) {
+            const int i = base + tid;
+            const bool cand = i < n && founder[i] < 0 && joff[i + 1] > joff[i];
+            const unsigned long long bal = __ballot(cand);
+            if (lane == 0) s_min[par][wv] = bal ? base + wv * 64 + __ffsll((long long)bal) - 1 : INT_MAX;
+            __syncthreads();
+            for (int w = 0; w < kColWaves; w++) first = min(first, s_min[par][w]);
+            par ^= 1;  // the next chunk writes the other half: no second barrier per chunk
+        }
+        if (first == INT_MAX) break;
+        const int nj = joff[first + 1] - joff[first];
+        const int2 *fj = a.uj + joff[first];
+        const bool in_lds = nj <= a.lds_junc;
+        if (in_lds)
+            for (int k = tid; k < nj; k += kColThreads) s_j[k] = fj[k];
+        if (tid == 0) founder[first] = nf;
+        __syncthreads();
+        const int2 *fl = in_lds ? s_j : fj;
+        for (int r = first + 1 + tid; r < n; r += kColThreads) {
+            if (founder[r] >= 0 || joff[r + 1] - joff[r] != nj) continue;
+            const int2 *rl = a.uj + joff[r];
+            bool ok = true;
+            for (int k = 0; k < nj && ok; k++) ok = is_in(fl[k], rl, nj, a.delta);
+            if (ok) founder[r] = nf;  // only this thread writes record r
+        }
+        nf++;
+        cursor = first + 1;
+        __syncthreads();
+    }
+    if (tid == 0) a.cg_nf[blockIdx.x] = nf;
+}
+
+// K-COLSTAT: per evidence record its transcript (a known slot, or n_slots + the founder's global number), the per-transcript statistics
+// and the (transcript, cell) code
+struct StatArgs {
+    const int32_t *rec_slot;  // n_rec: known slot, or -1 = an undef record
+    const int32_t *rec_u;     // n_rec: its index among the undef records
+    const int32_t *u_cg;      // n_u: its collapse gene
+    const int32_t *u_founder;
+    const int32_t *cg_base;   // exclusive scan of cg_nf: Novel.<cg_base + ordinal + 1>
+    const int32_t *tx_start, *tx_end, *cell;
+    int32_t n_rec, n_slots;
+    int32_t *t_count, *t_min, *t_max, *t_last;
+    uint64_t *code;
+};
+
+__global__ void k_colstat(StatArgs a) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.n_rec) return;
+    int t = a.rec_slot[r];
+    if (t < 0) {
+        const int u = a.rec_u[r], f = a.u_founder[u];
+        t = f < 0 ? -1 : a.n_slots + a.cg_base[a.u_cg[u]] + f;
+    }
+    if (t < 0) {  // a mono-exonic undef record: evidence of nothing
+        a.code[r] = ~0ull;
+        return;
+    }
+    atomicAdd(&a.t_count[t], 1);
+    atomicMin(&a.t_min[t], a.tx_start[r]);
+    atomicMax(&a.t_max[t], a.tx_end[r]);
+    atomicMax(&a.t_last[t], r);  // records are numbered in evidence order
+    a.code[r] = (uint64_t)(uint32_t)t << 32 | (uint32_t)a.cell[r];
+}
+
+__global__ void k_colstat_init(int32_t *t_count, int32_t *t_min, int32_t *t_max, int32_t *t_last, int32_t *t_cells, int32_t n) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    t_count[t] = 0;
+    t_min[t] = INT_MAX;
+    t_max[t] = INT_MIN;
+    t_last[t] = -1;
+    t_cells[t] = 0;
+}
+
+// one distinct (transcript, cell) code = one cell of that transcript
+__global__ void k_colstat_cells(const uint64_t *__restrict__ ucode, const int64_t *__restrict__ n_run, int32_t *t_cells) {
+    const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (k >= *n_run || ucode[k] == ~0ull) return;
+    atomicAdd(&t_cells[ucode[k] >> 32], 1);
+}
+
+// K-FILTER / K-CLASS
+struct FcArgs {
+    const int32_t *e_off;    // n_gene + 1: the gene's transcripts, sorted by exon count (descending, stable)
+    const int32_t *e_j_off;  // per entry: its junctions in pool
+    const int32_t *e_nj;
+    const uint8_t *e_known;
+    const int32_t *e_k_off;  // per entry: its junction kinds in kind (novels only)
+    const int32_t *g_line0, *g_line1;  // per gene: its model lines [line0, line1), gene-major
+    const int32_t *l_j_off;  // n_line + 1: junctions of model line l in pool (the model's junctions come first, gene-major)
+    const int2 *pool;
+    int32_t n_gene, delta;
+    int32_t *keep;           // per entry
+    int32_t *cat;            // per kept novel: 0 known junctions, 1 known splice sites, 2 a novel splice site
+    uint8_t *kind;           // per junction of a kept novel, the same three
+};
+
+__global__ __launch_bounds__(64 * kFcWaves) void k_filter_class(FcArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * kFcWaves + (threadIdx.x >> 6);
+    if (g >= a.n_gene) return;
+    const int e0 = a.e_off[g], e1 = a.e_off[g + 1];
+    const int l0 = a.g_line0[g], nl = a.g_line1[g] - l0;
+    const int2 *mj = a.pool + a.l_j_off[l0];  // every model junction of the gene
+    const int nmj = a.l_j_off[l0 + nl] - a.l_j_off[l0];
+    const int d = a.delta;
+    for (int e = e0; e < e1; e++) {
+        const int2 *ej = a.pool + a.e_j_off[e];
+        const int nj = a.e_nj[e];
+        bool keep = true;
+        if (!a.e_known[e]) {
+            // isPartOfLonger: the lanes take the transcripts kept so far, then the model lines of the gene
+            const int nc = (e - e0) + nl;
+            for (int c0 = 0; c0 < nc && keep; c0 += 64) {
+                const int c = c0 + lane;
+                bool hit = false;
+                if (c < e - e0) {
+                    if (a.keep[e0 + c])  // (c & 63) == lane: this lane stored that flag itself, below
+                        hit = all_include(ej, nj, a.pool + a.e_j_off[e0 + c], a.e_nj[e0 + c], d);
+                } else if (c < nc) {
+                    const int l = l0 + (c - (e - e0));
+                    hit = all_include(ej, nj, a.pool + a.l_j_off[l], a.l_j_off[l + 1] - a.l_j_off[l], d);
+                }
+                if (__any(hit)) keep = false;
+            }
+        }
+        // keep is wave-uniform (__any).  The flag of entry e is stored by the lane that reads it back for the later entries (candidate c
+        // goes to lane c & 63), so every flag a lane loads is one it stored itself: program order, no fence and no atomics
+        if (lane == ((e - e0) & 63)) a.keep[e] = keep ? 1 : 0;
+        if (keep && !a.e_known[e]) {
+            // noveltyDetector: known junction (isIn with DELTA), else both ends exact members of the model's splice sites, else novel
+            int worst = 0;
+            for (int k = lane; k < nj; k += 64) {
+                const int2 j = ej[k];
+                int kd = 0;
+                if (!is_in(j, mj, nmj, d)) {
+                    bool sx = false, sy = false;
+                    for (int i = 0; i < nmj; i++) {
+                        sx |= mj[i].x == j.x || mj[i].y == j.x;
+                        sy |= mj[i].x == j.y || mj[i].y == j.y;
+                    }
+                    kd = sx && sy ? 1 : 2;
+                }
+                a.kind[a.e_k_off[e] + k] = (uint8_t)kd;
+                worst = max(worst, kd);
+            }
+            for (int o = 32; o > 0; o >>= 1) worst = max(worst, __shfl_xor(worst, o));
+            if (lane == 0) a.cat[e] = worst;
+        }
+    }
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------------
+using lr::Aux;
+using lr::drop_minus1;
+using lr::jint;
+using lr::jsplit;
+
+struct Line {  // one refFlat line kept by the model
+    std::string gene, tx;
+    int32_t tx_start, tx_end, cds_start, cds_end;
+    std::vector<int32_t> xs, xe;  // exon starts (as written, 0-based) and ends
+};
+
+struct Model {
+    std::vector<Line> lines;  // gene-major: genes in order of their first line, lines of a gene in file order
+    std::vector<std::string> genes;
+    std::unordered_map<std::string, int32_t> gene_id;
+    std::vector<int32_t> gene_line_off;  // n_gene + 1
+    std::vector<int32_t> l_j_off{0};     // n_line + 1
+    std::vector<int2> tj;
+    std::unordered_map<std::string, int32_t> select;  // gene \t tx -> the last line
+};
+
+int parse_model(const char *text, size_t n, Model &M) {
+    std::vector<Line> lines;
+    std::vector<int32_t> line_gene;
+    size_t b = 0;
+    int64_t lineno = 0;
+    while (b < n) {
+        size_t e = b;
+        while (e < n && text[e] != '\n') e++;
+        std::string_view line(text + b, e - b);
+        if (!line.empty() && line.back() == '\r') line.remove_suffix(1);
+        b = e + 1;
+        lineno++;
+        auto f = jsplit(line, '\t');
+        auto fail = [&](const std::string &why) {
+            set_error("CollapseModel: REFFLAT line " + std::to_string(lineno) + ": " + why);
+            return SMI_ERR_INVALID;
+        };
+        if (f.size() < 11) return fail("has " + std::to_string(f.size()) + " fields, at least 11 are needed");
+        if (f[3] != "+" && f[3] != "-" && f[3] != ".") return fail("field 4 is no strand (+, - or .)");
+        Line L;
+        int32_t v[5];
+        for (int k = 4; k <= 8; k++)
+            if (!jint(f[k], v[k - 4])) return fail("field " + std::to_string(k + 1) + " is not an integer");
+        for (int k = 9; k <= 10; k++) {
+            std::string_view s = f[k];
+            while (!s.empty() && s.back() == ',') s.remove_suffix(1);
+            for (auto t : jsplit(s, ',')) {
+                int32_t x;
+                if (!jint(t, x)) return fail("field " + std::to_string(k + 1) + " is not a list of integers");
+                (k == 9 ? L.xs : L.xe).push_back(x);
+            }
+        }
+        if (L.xe.size() < L.xs.size()) return fail("fewer exon ends than exon starts");
+        int64_t bases = 0;
+        for (size_t i = 0; i < L.xs.size(); i++) bases += (int64_t)L.xe[i] - L.xs[i];
+        if ((int32_t)bases == 0) continue;
+        L.gene = std::string(f[0]);
+        L.tx = std::string(f[1]);
+        L.tx_start = v[0];
+        L.tx_end = v[1];
+        L.cds_start = v[2];
+        L.cds_end = v[3];
+        L.xe.resize(L.xs.size());
+        auto git = M.gene_id.emplace(L.gene, (int32_t)M.genes.size());
+        if (git.second) M.genes.push_back(L.gene);
+        line_gene.push_back(git.first->second);
+        lines.push_back(std::move(L));
+    }
+    std::vector<int32_t> ord(lines.size());
+    for (size_t i = 0; i < ord.size(); i++) ord[i] = (int32_t)i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return line_gene[x] < line_gene[y]; });
+    M.gene_line_off.assign(M.genes.size() + 1, 0);
+    for (int32_t g : line_gene) M.gene_line_off[g + 1]++;
+    for (size_t g = 0; g < M.genes.size(); g++) M.gene_line_off[g + 1] += M.gene_line_off[g];
+    for (int32_t i : ord) {
+        Line &L = lines[i];
+        for (size_t k = 1; k < L.xs.size(); k++) M.tj.push_back(make_int2(L.xe[k - 1], L.xs[k] + 1));
+        M.l_j_off.push_back((int32_t)M.tj.size());
+        M.select[L.gene + "\t" + L.tx] = (int32_t)M.lines.size();  // the last line wins
+        M.lines.push_back(std::move(L));
+    }
+    return SMI_OK;
+}
+
+enum Outcome : uint8_t { kKept, kNull, kMapq0, kChimeric, kLowRn, kNotListed, kNoGene, kError };
+
+struct Parsed {
+    Outcome what = kError;
+    std::string_view name, bc, gene, it;
+    bool has_it = false;
+    int32_t tx_start = 0, tx_end = 0;
+    std::vector<int2> junc;
+    std::string err;
+};
+
+struct TagSet {
+    uint16_t cell, umi, gene, iso, rn, de, df;
+};
+
+}  // namespace
+}  // namespace smi
+
+using namespace smi;
+
+struct smi_collapse {
+    smi_ctx *ctx = nullptr;
+    smi_collapse_config cfg = {};
+    TagSet tags = {};
+    Model M;
+    std::unordered_map<std::string, int32_t> listed;  // the cell list
+    std::vector<std::string> refs;
+    // kept records in file order
+    std::unordered_map<std::string, int32_t> gene_id, cell_id;
+    std::vector<std::string> genes;
+    std::vector<int32_t> r_gene, r_line, r_cell, r_ref, r_start, r_end, r_j_off{0};
+    std::vector<uint8_t> r_neg;
+    std::vector<int2> rj;
+    int64_t counts[SMI_COLLAPSE_COUNTS] = {};
+    std::string out[SMI_COLLAPSE_OUTPUTS];
+    std::string error_read;
+    int64_t error_record = -1;
+    int64_t seen = 0;
+    bool ran = false, failed = false;
+    // K-COLLAPSE's input and result, kept for smi_collapse_host_loop
+    std::vector<int32_t> k_cg_off, k_u_j_off, k_u_founder;
+    std::vector<int2> k_uj;
+};
+
+namespace smi {
+namespace {
+
+void parse_record(const uint8_t *bam, const smi_bam_record &r, const smi_collapse &h, Parsed &out) {
+    const TagSet &tg = h.tags;
+    out.name = std::string_view((const char *)bam + r.name_off, r.l_read_name ? r.l_read_name - 1 : 0);
+    const uint8_t *p = bam + r.aux_off, *end = p + r.aux_len;
+    Aux cell, umi, gene, iso, rn, de, df;
+    while (p < end) {
+        size_t n;
+        if (lr::aux_size(p, end, &n)) {
+            out.err = "malformed attributes";
+            return;
+        }
+        const uint16_t t = (uint16_t)(p[0] | p[1] << 8);
+        const Aux a{p, n};
+        if (t == tg.cell) cell = a;  // (a repeated tag keeps its last value, as htsjdk reads it)
+        if (t == tg.umi) umi = a;
+        if (t == tg.gene) gene = a;
+        if (t == tg.iso) iso = a;
+        if (t == tg.rn) rn = a;
+        if (t == tg.de) de = a;
+        if (t == tg.df) df = a;
+        p += n;
+    }
+    auto bad = [&](const Aux &a) {
+        out.err = std::string("attribute ") + (char)a.p[0] + (char)a.p[1] + " of type " + (char)a.p[2] + " is not the type CollapseModel reads";
+    };
+    auto zstr = [&](const Aux &a, std::string_view &v) {
+        if (!a.p) return true;
+        if (a.p[2] != 'Z') {
+            bad(a);
+            return false;
+        }
+        v = std::string_view((const char *)a.p + 3, a.n - 4);
+        return true;
+    };
+    std::string_view umi_v;
+    int64_t rnv = 1;
+    // loader L157-161: the casts come before anything else, for every record
+    if (!zstr(cell, out.bc) || !zstr(umi, umi_v) || !zstr(gene, out.gene) || !zstr(iso, out.it)) return;
+    out.has_it = iso.p != nullptr;
+    if (rn.p && !lr::aux_integer(rn, rnv)) {
+        bad(rn);
+        return;
+    }
+    if (!cell.p || (r.flag & 4) || r.ref_id < 0) {  // fromSAMRecord L80 (and a record on no sequence is in no query)
+        out.what = kNull;
+        return;
+    }
+    for (const Aux *a : {&de, &df}) {  // L92
+        if (!a->p) continue;
+        if (a->p[2] != 'f') {
+            bad(*a);
+            return;
+        }
+        break;
+    }
+    if (r.n_cigar == 0) {
+        out.err = "no CIGAR";
+        return;
+    }
+    uint32_t c0, c1;
+    std::memcpy(&c0, bam + r.cigar_off, 4);
+    std::memcpy(&c1, bam + r.cigar_off + 4 * ((size_t)r.n_cigar - 1), 4);
+    if (!lr::walk_junctions(bam, r, out.junc)) {  // the walk runs before the filter
+        out.err = "the CIGAR walk runs past the alignment blocks";
+        return;
+    }
+    int64_t ref_len = 0;
+    for (int k = 0; k < r.n_cigar; k++) {
+        uint32_t c;
+        std::memcpy(&c, bam + r.cigar_off + 4ull * k, 4);
+        const uint32_t op = c & 15;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += c >> 4;
+    }
+    out.tx_start = r.pos + 1;                  // getAlignmentStart
+    out.tx_end = (int32_t)(r.pos + ref_len);   // getAlignmentEnd
+    // loader L167-170
+    if (r.mapq == 0) out.what = kMapq0;
+    else if (lr::chimeric(c0, c1, h.cfg.max_clip)) out.what = kChimeric;
+    else if (rnv < h.cfg.rn_min) out.what = kLowRn;
+    else if (!h.listed.count(std::string(out.bc))) out.what = kNotListed;
+    else if (!gene.p || out.gene.empty() || out.gene == "undef") out.what = kNoGene;
+    else out.what = kKept;
+}
+
+void append_int(std::string &s, int64_t v) { s += std::to_string(v); }
+
+}  // namespace
+}  // namespace smi
+
+extern "C" int smi_collapse_default_config(smi_collapse_config *cfg) {
+    if (!cfg) {
+        set_error("smi_collapse_default_config: null argument");
+        return SMI_ERR_INVALID;
+    }
+    *cfg = {};
+    std::memcpy(cfg->cell_tag, "BC", 3);
+    std::memcpy(cfg->umi_tag, "U8", 3);
+    std::memcpy(cfg->gene_tag, "IG", 3);
+    std::memcpy(cfg->iso_tag, "IT", 3);
+    std::memcpy(cfg->rn_tag, "RN", 3);
+    cfg->max_clip = 150;
+    cfg->delta = 2;
+    cfg->min_evidence = 2;
+    cfg->rn_min = 1;
+    cfg->n_threads = 20;
+    cfg->lds_junc = kLdsJunc;
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_create(smi_ctx *ctx, const smi_collapse_config *cfg, const char *refflat, size_t n_refflat, const char *csv, size_t n_csv,
+                                   smi_collapse **out) {
+    if (!ctx || !cfg || !out || (n_refflat && !refflat) || (n_csv && !csv)) {
+        set_error("smi_collapse_create: null argument");
+        return SMI_ERR_INVALID;
+    }
+    *out = nullptr;
+    const char *tags[] = {cfg->cell_tag, cfg->umi_tag, cfg->gene_tag, cfg->iso_tag, cfg->rn_tag};
+    const char *what[] = {"CELLTAG", "UMITAG", "GENETAG", "ISOFORMTAG", "RNTAG"};
+    for (int i = 0; i < 5; i++)
+        if (!lr::valid_tag(tags[i])) {
+            set_error(std::string(what[i]) + " must be two characters");
+            return SMI_ERR_INVALID;
+        }
+    // (a DELTA below 0 is taken as the reference takes it: isIn never holds, so nothing joins, nothing is contained and no junction is known)
+    if (cfg->lds_junc < 1 || cfg->lds_junc > kLdsJunc) {
+        set_error("smi_collapse_config.lds_junc must be 1 .. " + std::to_string(kLdsJunc));
+        return SMI_ERR_INVALID;
+    }
+    smi_collapse *h = new smi_collapse();
+    h->ctx = ctx;
+    h->cfg = *cfg;
+    h->cfg.n_threads = std::max(1, std::min(cfg->n_threads, 256));
+    h->tags = TagSet{lr::tag16(cfg->cell_tag), lr::tag16(cfg->umi_tag), lr::tag16(cfg->gene_tag), lr::tag16(cfg->iso_tag), lr::tag16(cfg->rn_tag),
+                     lr::tag16("de"), lr::tag16("df")};
+    if (int rc = parse_model(refflat, n_refflat, h->M)) {
+        delete h;
+        return rc;
+    }
+    size_t b = 0;  // CellList: every line (readLine: \n, \r\n or \r) with "-1" removed
+    while (b < n_csv) {
+        size_t e = b;
+        while (e < n_csv && csv[e] != '\n' && csv[e] != '\r') e++;
+        h->listed.emplace(drop_minus1(std::string_view(csv + b, e - b)), 0);
+        if (e < n_csv && csv[e] == '\r' && e + 1 < n_csv && csv[e + 1] == '\n') e++;
+        b = e + 1;
+    }
+    h->counts[SMI_COL_CELLS] = (int64_t)h->listed.size();
+    h->counts[SMI_COL_MODEL_GENES] = (int64_t)h->M.genes.size();
+    h->counts[SMI_COL_MODEL_TRANSCRIPTS] = (int64_t)h->M.lines.size();
+    *out = h;
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_free(smi_collapse *h) {
+    delete h;
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_set_references(smi_collapse *h, const char *const *ref_names, int32_t n_refs) {
+    if (!h || n_refs < 0 || (n_refs && !ref_names)) {
+        set_error("smi_collapse_set_references: null argument");
+        return SMI_ERR_INVALID;
+    }
+    h->refs.clear();
+    for (int32_t i = 0; i < n_refs; i++) h->refs.emplace_back(ref_names[i] ? ref_names[i] : "");
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_error_read(const smi_collapse *h, char *name, size_t cap, int64_t *record) {
+    if (!h || !record || (cap && !name)) {
+        set_error("smi_collapse_error_read: null argument");
+        return SMI_ERR_INVALID;
+    }
+    *record = h->error_record;
+    if (cap) {
+        const size_t k = std::min(cap - 1, h->error_read.size());
+        std::memcpy(name, h->error_read.data(), k);
+        name[k] = 0;
+    }
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_counts(const smi_collapse *h, int64_t *counts) {
+    if (!h || !counts) {
+        set_error("smi_collapse_counts: null argument");
+        return SMI_ERR_INVALID;
+    }
+    std::memcpy(counts, h->counts, sizeof h->counts);
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_output(const smi_collapse *h, int32_t which, uint8_t *out, size_t cap, size_t *n_out) {
+    if (!h || !n_out || which < 0 || which >= SMI_COLLAPSE_OUTPUTS) {
+        set_error("smi_collapse_output: bad argument");
+        return SMI_ERR_INVALID;
+    }
+    const std::string &s = h->out[which];
+    *n_out = s.size();
+    if (!out) return SMI_OK;
+    if (cap < s.size()) return 1;
+    std::memcpy(out, s.data(), s.size());
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_add_segment(smi_collapse *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n) {
+    if (!h || n < 0 || (n && (!bam || !recs))) {
+        set_error("smi_collapse_add_segment: null argument");
+        return SMI_ERR_INVALID;
+    }
+    if (h->ran || h->failed) {
+        set_error(h->ran ? "smi_collapse_add_segment: the model was already collapsed (smi_collapse_run)"
+                         : "smi_collapse_add_segment: an earlier segment failed");
+        return SMI_ERR_STATE;
+    }
+    for (int32_t i = 0; i < n; i++) {
+        const smi_bam_record &r = recs[i];
+        if (r.name_off + r.l_read_name > n_bam || r.cigar_off + 4ull * r.n_cigar > n_bam || r.aux_off + r.aux_len > n_bam) {
+            set_error("smi_collapse_add_segment: record " + std::to_string(i) + " lies outside the segment");
+            return SMI_ERR_INVALID;
+        }
+    }
+    std::vector<Parsed> parsed(n);
+    const int nt = std::max(1, std::min<int>(h->cfg.n_threads, (n + 4095) / 4096));
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; t++)
+        th.emplace_back([&, t] {
+            for (int32_t i = (int32_t)((int64_t)n * t / nt); i < (int32_t)((int64_t)n * (t + 1) / nt); i++)
+                parse_record(bam, recs[i], *h, parsed[i]);
+        });
+    for (auto &x : th) x.join();
+    auto fail = [&](int32_t i, const std::string &why) {
+        h->failed = true;
+        h->error_read = std::string(parsed[i].name);
+        h->error_record = h->seen + i;
+        set_error("CollapseModel: read " + h->error_read + ": " + why);
+        return SMI_ERR_INVALID;
+    };
+    // the first failing record in file order is the one named: the lookups of the kept records are part of the same pass
+    std::vector<int32_t> line(n, -1);
+    for (int32_t i = 0; i < n; i++) {
+        const Parsed &p = parsed[i];
+        if (p.what == kError) return fail(i, p.err);
+        if (p.what != kKept || (p.has_it && p.it == "undef")) continue;
+        auto it = p.has_it ? h->M.select.find(std::string(p.gene) + "\t" + std::string(p.it)) : h->M.select.end();
+        if (it == h->M.select.end())  // refmodel.select gives null: the reference fails on it later (L196 or initialize)
+            return fail(i, p.has_it ? "transcript " + std::string(p.it) + " of the ISOFORMTAG is no transcript of gene " + std::string(p.gene) + " in the REFFLAT"
+                                    : "no ISOFORMTAG attribute");
+        line[i] = it->second;
+    }
+    // records and junctions are numbered in int32 from here on (the offsets below, the kernels' indices, the hipcub calls): refuse what
+    // does not fit where it accumulates, as mtx::matrix does for its codes
+    size_t add_rec = 0, add_junc = 0;
+    for (int32_t i = 0; i < n; i++)
+        if (parsed[i].what == kKept) {
+            add_rec++;
+            add_junc += parsed[i].junc.size();
+        }
+    if (h->r_gene.size() + add_rec > (size_t)INT32_MAX || h->rj.size() + add_junc > (size_t)INT32_MAX) {
+        h->failed = true;
+        set_error("CollapseModel: more than 2^31 - 1 evidence records or junctions in one run");
+        return SMI_ERR_INVALID;
+    }
+    int64_t *c = h->counts;
+    for (int32_t i = 0; i < n; i++) {
+        const Parsed &p = parsed[i];
+        c[SMI_COL_RECORDS]++;
+        if (p.what != kKept) {
+            c[p.what == kNull ? SMI_COL_NULL : p.what == kMapq0 ? SMI_COL_MAPQ0 : p.what == kChimeric ? SMI_COL_CHIMERIC
+              : p.what == kLowRn ? SMI_COL_LOW_RN : p.what == kNotListed ? SMI_COL_NOT_LISTED : SMI_COL_NO_GENE]++;
+            continue;
+        }
+        c[SMI_COL_KEPT]++;
+        auto git = h->gene_id.emplace(std::string(p.gene), (int32_t)h->genes.size());
+        if (git.second) h->genes.emplace_back(p.gene);
+        auto cit = h->cell_id.emplace(drop_minus1(p.bc), (int32_t)h->cell_id.size());
+        h->r_gene.push_back(git.first->second);
+        h->r_line.push_back(line[i]);
+        h->r_cell.push_back(cit.first->second);
+        h->r_ref.push_back(recs[i].ref_id);
+        h->r_start.push_back(p.tx_start);
+        h->r_end.push_back(p.tx_end);
+        h->r_neg.push_back((recs[i].flag & 16) ? 1 : 0);
+        h->rj.insert(h->rj.end(), p.junc.begin(), p.junc.end());
+        h->r_j_off.push_back((int32_t)h->rj.size());
+    }
+    h->seen += n;
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_run(smi_collapse *h, float *stage_ms) {
+    if (!h) {
+        set_error("smi_collapse_run: null argument");
+        return SMI_ERR_INVALID;
+    }
+    float ms[SMI_COLLAPSE_STAGES] = {};
+    if (stage_ms) std::memset(stage_ms, 0, sizeof(ms));
+    if (h->ran || h->failed) {
+        set_error(h->ran ? "smi_collapse_run: already run" : "smi_collapse_run: a segment failed");
+        return SMI_ERR_STATE;
+    }
+    h->ran = true;
+    SMI_HIP(hipSetDevice(h->ctx->device));
+    hipStream_t s = h->ctx->stream;
+    const Model &M = h->M;
+    int64_t *c = h->counts;
+    const int32_t delta = h->cfg.delta;
+    const size_t nk = h->r_gene.size();
+    if (h->rj.size() + M.tj.size() > (size_t)INT32_MAX) {
+        set_error("CollapseModel: more than 2^31 - 1 junctions in one run");
+        return SMI_ERR_INVALID;
+    }
+    // genes in byte order of their name; evidence order = reference-dictionary order, then file order
+    const int32_t nG = (int32_t)h->genes.size();
+    std::vector<int32_t> gord(nG), grank(nG);
+    for (int32_t i = 0; i < nG; i++) gord[i] = i;
+    std::sort(gord.begin(), gord.end(), [&](int32_t x, int32_t y) { return h->genes[x] < h->genes[y]; });
+    for (int32_t i = 0; i < nG; i++) grank[gord[i]] = i;
+    std::vector<int32_t> ev(nk);
+    for (size_t i = 0; i < nk; i++) ev[i] = (int32_t)i;
+    std::stable_sort(ev.begin(), ev.end(), [&](int32_t x, int32_t y) { return h->r_ref[x] < h->r_ref[y]; });
+    // per evidence record (numbered in evidence order): gene, known slot or undef
+    std::vector<int32_t> e_gene(nk), rec_slot(nk, -1), rec_u(nk, -1), tx_start(nk), tx_end(nk), cell(nk);
+    std::vector<std::vector<int32_t>> gene_slots(nG), gene_undef(nG);
+    std::vector<int32_t> slot_line;
+    std::unordered_map<uint64_t, int32_t> slot_of;
+    for (size_t k = 0; k < nk; k++) {
+        const int32_t i = ev[k], g = grank[h->r_gene[i]];
+        e_gene[k] = g;
+        tx_start[k] = h->r_start[i];
+        tx_end[k] = h->r_end[i];
+        cell[k] = h->r_cell[i];
+        if (h->r_line[i] < 0) {
+            gene_undef[g].push_back((int32_t)k);
+        } else {
+            auto it = slot_of.emplace((uint64_t)(uint32_t)g << 32 | (uint32_t)h->r_line[i], (int32_t)slot_line.size());
+            if (it.second) {
+                slot_line.push_back(h->r_line[i]);
+                gene_slots[g].push_back(it.first->second);
+            }
+            rec_slot[k] = it.first->second;
+        }
+    }
+    const int32_t n_slots = (int32_t)slot_line.size();
+    // the undef lists, gene by gene
+    std::vector<int32_t> cg_gene, cg_off{0}, u_rec, u_cg, u_j_off{0};
+    std::vector<int2> uj;
+    for (int32_t g = 0; g < nG; g++) {
+        if (gene_undef[g].empty()) continue;
+        for (int32_t k : gene_undef[g]) {
+            rec_u[k] = (int32_t)u_rec.size();
+            u_rec.push_back(k);
+            u_cg.push_back((int32_t)cg_gene.size());
+            const int32_t i = ev[k];
+            uj.insert(uj.end(), h->rj.begin() + h->r_j_off[i], h->rj.begin() + h->r_j_off[i + 1]);
+            u_j_off.push_back((int32_t)uj.size());
+            c[SMI_COL_MONOEXON] += h->r_j_off[i + 1] == h->r_j_off[i];
+            c[SMI_COL_LONG_LISTS] += h->r_j_off[i + 1] - h->r_j_off[i] > h->cfg.lds_junc;
+        }
+        cg_gene.push_back(g);
+        cg_off.push_back((int32_t)u_rec.size());
+        c[SMI_COL_MAX_UNDEF] = std::max<int64_t>(c[SMI_COL_MAX_UNDEF], (int64_t)gene_undef[g].size());
+    }
+    const int32_t nCG = (int32_t)cg_gene.size(), nU = (int32_t)u_rec.size();
+    c[SMI_COL_GENES] = nG;
+    c[SMI_COL_UNDEF_RECORDS] = nU;
+    int rc = 0;
+    Events evt;
+    // K-COLLAPSE
+    std::vector<int32_t> u_founder(nU, -1), cg_nf(nCG, 0), cg_base(nCG + 1, 0);
+    DevBuf<int32_t> d_cgo, d_ujo, d_uf, d_nf, d_base;
+    DevBuf<int2> d_uj;
+    if ((rc = d_cgo.put(cg_off, s)) || (rc = d_ujo.put(u_j_off, s)) || (rc = d_uj.put(uj, s)) || (rc = d_uf.alloc(nU)) || (rc = d_nf.alloc(nCG + 1)) ||
+        (rc = d_base.alloc(nCG + 1)))
+        return rc;
+    SMI_HIP(hipMemsetAsync(d_nf.p, 0, (size_t)(nCG + 1) * 4, s));
+    if (nCG) {
+        ColArgs a = {d_cgo.p, d_ujo.p, d_uj.p, delta, h->cfg.lds_junc, d_uf.p, d_nf.p};
+        if ((rc = evt.begin(s))) return rc;
+        hipLaunchKernelGGL(k_collapse, dim3((unsigned)nCG), dim3(kColThreads), 0, s, a);
+        SMI_HIP(hipGetLastError());
+        if ((rc = evt.end(s, &ms[0]))) return rc;
+    }
+    // K-COLSTAT: the scan of the founder counts (the Novel.<n> numbers), then the statistics per transcript
+    {
+        DevBuf<uint8_t> d_tmp;
+        size_t tmp = 0;
+        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_nf.p, d_base.p, nCG + 1, s));
+        if ((rc = d_tmp.alloc(tmp))) return rc;
+        if ((rc = evt.begin(s))) return rc;
+        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp, d_nf.p, d_base.p, nCG + 1, s));
+        if ((rc = evt.end(s, &ms[1]))) return rc;
+        SMI_HIP(hipMemcpy(cg_base.data(), d_base.p, (size_t)(nCG + 1) * 4, hipMemcpyDeviceToHost));
+        if (nCG) SMI_HIP(hipMemcpy(cg_nf.data(), d_nf.p, (size_t)nCG * 4, hipMemcpyDeviceToHost));
+        if (nU) SMI_HIP(hipMemcpy(u_founder.data(), d_uf.p, (size_t)nU * 4, hipMemcpyDeviceToHost));
+    }
+    const int32_t n_founders = cg_base[nCG], nT = n_slots + n_founders;
+    c[SMI_COL_FOUNDERS] = n_founders;
+    for (int32_t x : cg_nf) c[SMI_COL_MAX_FOUNDERS] = std::max<int64_t>(c[SMI_COL_MAX_FOUNDERS], x);
+    std::vector<int32_t> t_count(nT), t_min(nT), t_max(nT), t_last(nT), t_cells(nT);
+    if (nk && nT) {
+        DevBuf<int32_t> d_slot, d_ru, d_ucg, d_ts, d_te, d_cell, d_cnt, d_min, d_max, d_last, d_cells;
+        DevBuf<uint64_t> d_code, d_sorted, d_unique;
+        DevBuf<uint32_t> d_rl;
+        DevBuf<int64_t> d_nrun;
+        DevBuf<uint8_t> d_tmp;
+        if ((rc = d_slot.put(rec_slot, s)) || (rc = d_ru.put(rec_u, s)) || (rc = d_ucg.put(u_cg, s)) || (rc = d_ts.put(tx_start, s)) ||
+            (rc = d_te.put(tx_end, s)) || (rc = d_cell.put(cell, s)) || (rc = d_cnt.alloc(nT)) || (rc = d_min.alloc(nT)) || (rc = d_max.alloc(nT)) ||
+            (rc = d_last.alloc(nT)) || (rc = d_cells.alloc(nT)) || (rc = d_code.alloc(nk)) || (rc = d_sorted.alloc(nk)) || (rc = d_unique.alloc(nk)) ||
+            (rc = d_rl.alloc(nk)) || (rc = d_nrun.alloc(1)))
+            return rc;
+        size_t t1 = 0, t2 = 0;
+        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, d_code.p, d_sorted.p, (int)nk, 0, 64, s));
+        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, d_sorted.p, d_unique.p, d_rl.p, d_nrun.p, (int)nk, s));
+        if ((rc = d_tmp.alloc(std::max(t1, t2)))) return rc;
+        StatArgs a = {d_slot.p, d_ru.p, d_ucg.p, d_uf.p, d_base.p, d_ts.p, d_te.p, d_cell.p, (int32_t)nk, n_slots,
+                      d_cnt.p, d_min.p, d_max.p, d_last.p, d_code.p};
+        if ((rc = evt.begin(s))) return rc;
+        hipLaunchKernelGGL(k_colstat_init, dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, s, d_cnt.p, d_min.p, d_max.p, d_last.p, d_cells.p, nT);
+        hipLaunchKernelGGL(k_colstat, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, a);
+        SMI_HIP(hipGetLastError());
+        size_t tmp = std::max(t1, t2);
+        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(d_tmp.p, tmp, d_code.p, d_sorted.p, (int)nk, 0, 64, s));
+        tmp = std::max(t1, t2);
+        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(d_tmp.p, tmp, d_sorted.p, d_unique.p, d_rl.p, d_nrun.p, (int)nk, s));
+        hipLaunchKernelGGL(k_colstat_cells, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, d_unique.p, d_nrun.p, d_cells.p);
+        SMI_HIP(hipGetLastError());
+        if ((rc = evt.end(s, &ms[1]))) return rc;
+        SMI_HIP(hipMemcpy(t_count.data(), d_cnt.p, (size_t)nT * 4, hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(t_min.data(), d_min.p, (size_t)nT * 4, hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(t_max.data(), d_max.p, (size_t)nT * 4, hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(t_last.data(), d_last.p, (size_t)nT * 4, hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(t_cells.data(), d_cells.p, (size_t)nT * 4, hipMemcpyDeviceToHost));
+    }
+    // the founding record of every founder: the first record of its ordinal
+    std::vector<int32_t> f_u(n_founders, -1);
+    for (int32_t u = 0; u < nU; u++)
+        if (u_founder[u] >= 0) {
+            int32_t &f = f_u[cg_base[u_cg[u]] + u_founder[u]];
+            if (f < 0) f = u;
+        }
+    // per gene: the known transcripts in order of their first evidence, then the founders of MINEVIDENCE records in creation order
+    // (collapser L211-230); Collections.sort by exon count, descending and stable (filter L247)
+    struct Entry {
+        int32_t t, nex;  // transcript (slot, or n_slots + founder), exons
+    };
+    std::vector<int32_t> e_off{0}, e_t, e_j_off, e_nj, e_k_off, g_line0(nG, 0), g_line1(nG, 0);
+    std::vector<uint8_t> e_known;
+    const int32_t n_mj = (int32_t)M.tj.size();
+    int32_t n_kind = 0;
+    {
+        std::vector<int32_t> cg_of(nG, -1);
+        for (int32_t q = 0; q < nCG; q++) cg_of[cg_gene[q]] = q;
+        std::vector<Entry> lst;
+        for (int32_t g = 0; g < nG; g++) {
+            lst.clear();
+            for (int32_t sl : gene_slots[g]) lst.push_back({sl, (int32_t)M.lines[slot_line[sl]].xs.size()});
+            if (cg_of[g] >= 0)
+                for (int32_t f = cg_base[cg_of[g]]; f < cg_base[cg_of[g] + 1]; f++)
+                    if (t_count[n_slots + f] >= h->cfg.min_evidence) {
+                        lst.push_back({n_slots + f, u_j_off[f_u[f] + 1] - u_j_off[f_u[f]] + 1});
+                        c[SMI_COL_NOVEL_EVIDENCED]++;
+                    }
+            std::stable_sort(lst.begin(), lst.end(), [](const Entry &x, const Entry &y) { return x.nex > y.nex; });
+            for (const Entry &e : lst) {
+                const bool known = e.t < n_slots;
+                e_t.push_back(e.t);
+                e_known.push_back(known);
+                if (known) {
+                    e_j_off.push_back(M.l_j_off[slot_line[e.t]]);
+                    e_nj.push_back(M.l_j_off[slot_line[e.t] + 1] - M.l_j_off[slot_line[e.t]]);
+                    e_k_off.push_back(0);
+                } else {
+                    const int32_t u = f_u[e.t - n_slots];
+                    e_j_off.push_back(n_mj + u_j_off[u]);
+                    e_nj.push_back(u_j_off[u + 1] - u_j_off[u]);
+                    e_k_off.push_back(n_kind);
+                    n_kind += e_nj.back();
+                }
+            }
+            e_off.push_back((int32_t)e_t.size());
+            auto mit = M.gene_id.find(h->genes[gord[g]]);
+            if (mit != M.gene_id.end()) {
+                g_line0[g] = M.gene_line_off[mit->second];
+                g_line1[g] = M.gene_line_off[mit->second + 1];
+            }
+        }
+    }
+    const int32_t nE = (int32_t)e_t.size();
+    std::vector<int32_t> keep(nE, 0), cat(nE, 0);
+    std::vector<uint8_t> kind(n_kind, 0);
+    if (nE) {
+        std::vector<int2> pool(M.tj);
+        pool.insert(pool.end(), uj.begin(), uj.end());
+        DevBuf<int32_t> d_eo, d_ejo, d_enj, d_eko, d_l0, d_l1, d_ljo, d_keep, d_cat;
+        DevBuf<uint8_t> d_ek, d_kind;
+        DevBuf<int2> d_pool;
+        if ((rc = d_eo.put(e_off, s)) || (rc = d_ejo.put(e_j_off, s)) || (rc = d_enj.put(e_nj, s)) || (rc = d_ek.put(e_known, s)) ||
+            (rc = d_eko.put(e_k_off, s)) || (rc = d_l0.put(g_line0, s)) || (rc = d_l1.put(g_line1, s)) || (rc = d_ljo.put(M.l_j_off, s)) ||
+            (rc = d_pool.put(pool, s)) || (rc = d_keep.alloc(nE)) || (rc = d_cat.alloc(nE)) || (rc = d_kind.alloc(n_kind)))
+            return rc;
+        SMI_HIP(hipMemsetAsync(d_keep.p, 0, (size_t)nE * 4, s));
+        SMI_HIP(hipMemsetAsync(d_cat.p, 0, (size_t)nE * 4, s));
+        FcArgs a = {d_eo.p, d_ejo.p, d_enj.p, d_ek.p, d_eko.p, d_l0.p, d_l1.p, d_ljo.p, d_pool.p, nG, delta, d_keep.p, d_cat.p, d_kind.p};
+        if ((rc = evt.begin(s))) return rc;
+        hipLaunchKernelGGL(k_filter_class, dim3((unsigned)((nG + kFcWaves - 1) / kFcWaves)), dim3(64 * kFcWaves), 0, s, a);
+        SMI_HIP(hipGetLastError());
+        if ((rc = evt.end(s, &ms[2]))) return rc;
+        SMI_HIP(hipMemcpy(keep.data(), d_keep.p, (size_t)nE * 4, hipMemcpyDeviceToHost));
+        SMI_HIP(hipMemcpy(cat.data(), d_cat.p, (size_t)nE * 4, hipMemcpyDeviceToHost));
+        if (n_kind) SMI_HIP(hipMemcpy(kind.data(), d_kind.p, (size_t)n_kind, hipMemcpyDeviceToHost));
+    }
+    // exportFiles: genes in byte order, a gene's transcripts in the filter's order
+    static const char *kSub[] = {"combination_of_known_junctions", "combination_of_known_splicesites", "at_least_one_novel_splicesite"};
+    static const char *kCol[] = {"#9dd122", "#c594e1", "#e65802"};
+    std::string &txt = h->out[SMI_COL_OUT_TXT], &flat = h->out[SMI_COL_OUT_REFFLAT], &flatv = h->out[SMI_COL_OUT_FINAL_REFFLAT];
+    std::string &gff = h->out[SMI_COL_OUT_GFF], &gffv = h->out[SMI_COL_OUT_FINAL_GFF];
+    txt = "geneId\ttranscriptId\tchrom\tstrand\ttxStart\ttxEnd\texons\tUMIs\tCells\tcategorie\tsubcategorie\tnovelJunctions"
+          "\tnovelJunctions_reads\tis_valid_allNovelJunctions\tdist_cage\tis_valid_cage\tdist_polya\tis_valid_polya\tis_valid\n";
+    std::vector<int32_t> xs, xe;
+    std::string one_flat, one_gff;
+    for (int32_t g = 0; g < nG; g++) {
+        const std::string &gname = h->genes[gord[g]];
+        for (int32_t e = e_off[g]; e < e_off[g + 1]; e++) {
+            if (!keep[e]) {
+                c[SMI_COL_NOVEL_FILTERED]++;
+                continue;
+            }
+            const int32_t t = e_t[e];
+            const bool known = e_known[e];
+            const int32_t last = ev[t_last[t]];  // chromosome and strand of the LAST evidence record, for known transcripts too
+            const std::string chrom = h->r_ref[last] < (int32_t)h->refs.size() ? h->refs[h->r_ref[last]] : std::string("*");
+            const char *strand = h->r_neg[last] ? "-" : "+";
+            std::string tname, categorie, sub, color, nov;
+            int32_t s0, s1, c0, c1;
+            xs.clear();
+            xe.clear();
+            if (known) {
+                const Line &L = M.lines[slot_line[t]];
+                tname = L.tx;
+                categorie = "full_splice_match";
+                sub = "gencode";
+                color = "#014e8e";
+                s0 = L.tx_start;
+                s1 = L.tx_end;
+                c0 = L.cds_start;
+                c1 = L.cds_end;
+                for (size_t k = 0; k < L.xs.size(); k++) {
+                    xs.push_back(L.xs[k] + 1);
+                    xe.push_back(L.xe[k]);
+                }
+                c[SMI_COL_GENCODE]++;
+                c[SMI_COL_GENCODE_EV] += t_count[t];
+            } else {
+                const int32_t f = t - n_slots, u = f_u[f];
+                tname = "Novel." + std::to_string(f + 1);
+                categorie = cat[e] == 2 ? "novel_not_in_catalog" : "novel_in_catalog";
+                sub = kSub[cat[e]];
+                color = kCol[cat[e]];
+                s0 = c0 = t_min[t];
+                s1 = c1 = t_max[t];
+                const int2 *j = uj.data() + u_j_off[u];
+                const int32_t nj = e_nj[e];
+                xs.push_back(s0);
+                for (int32_t k = 0; k < nj; k++) {
+                    xe.push_back(j[k].x);
+                    xs.push_back(j[k].y);
+                    if (kind[e_k_off[e] + k]) nov += (nov.empty() ? "" : ",") + std::to_string(j[k].x) + "-" + std::to_string(j[k].y);
+                }
+                xe.push_back(s1);
+                c[SMI_COL_CKJ + 2 * cat[e]]++;
+                c[SMI_COL_CKJ_EV + 2 * cat[e]] += t_count[t];
+            }
+            if (nov.empty()) nov = "-";
+            c[SMI_COL_ISOFORMS]++;
+            c[SMI_COL_EVIDENCES] += t_count[t];
+            const std::string umis = std::to_string(t_count[t]), cells = std::to_string(t_cells[t]);
+            const std::string head = gname + "\t" + tname + "\t" + chrom + "\t" + strand + "\t" + std::to_string(s0) + "\t" + std::to_string(s1) + "\t";
+            txt += head + std::to_string(xs.size()) + "\t" + umis + "\t" + cells + "\t" + categorie + "\t" + sub + "\t" + nov +
+                   "\t0\tfalse\t0\tfalse\t0\tfalse\tfalse\n";
+            one_flat = head + std::to_string(c0) + "\t" + std::to_string(c1) + "\t" + std::to_string(xs.size()) + "\t";
+            for (int32_t x : xs) {
+                append_int(one_flat, (int64_t)x - 1);
+                one_flat += ',';
+            }
+            one_flat += '\t';
+            for (int32_t x : xe) {
+                append_int(one_flat, x);
+                one_flat += ',';
+            }
+            one_flat += '\n';
+            const std::string ids = "gene_id \"" + gname + "\"; transcript_id \"" + tname + "\";";
+            one_gff = chrom + "\tsicelore\ttranscript\t" + std::to_string(s0) + "\t" + std::to_string(s1) + "\t.\t" + strand + "\t.\t" + ids +
+                      " category \"" + categorie + "\"; subcategory \"" + sub + "\"; UMIs \"" + umis + "\"; Cells \"" + cells + "\"; novelJunctions \"" +
+                      nov + "\"; supportingReads \"0\"; CAGEdist \"0\"; POLYAdist \"0\"; color \"" + color + "\";\n";
+            for (size_t k = 0; k < xs.size(); k++)
+                one_gff += chrom + "\tsicelore\texon\t" + std::to_string(xs[k]) + "\t" + std::to_string(xe[k]) + "\t.\t" + strand + "\t.\t" + ids + "\n";
+            flat += one_flat;
+            gff += one_gff;
+            if (known) {  // no novel is valid without the validator
+                flatv += one_flat;
+                gffv += one_gff;
+            }
+        }
+    }
+    h->k_cg_off = std::move(cg_off);
+    h->k_u_j_off = std::move(u_j_off);
+    h->k_u_founder = std::move(u_founder);
+    h->k_uj = std::move(uj);
+    if (stage_ms) std::memcpy(stage_ms, ms, sizeof(ms));
+    return SMI_OK;
+}
+
+// collapse() L639-671 as the reference runs it: one thread, record by record against the founders so far
+extern "C" int smi_collapse_host_loop(const smi_collapse *h, double *seconds, int64_t *mismatches) {
+    if (!h || !seconds || !mismatches) {
+        set_error("smi_collapse_host_loop: null argument");
+        return SMI_ERR_INVALID;
+    }
+    if (!h->ran) {
+        set_error("smi_collapse_host_loop: smi_collapse_run comes first");
+        return SMI_ERR_STATE;
+    }
+    const int32_t d = h->cfg.delta;
+    const int2 *uj = h->k_uj.data();
+    const int32_t *joff = h->k_u_j_off.data();
+    auto is_in = [&](int2 j, const int2 *l, int n) {
+        bool b = false;
+        for (int i = 0; i < n; i++)
+            if (std::abs(l[i].x - j.x) <= d && std::abs(l[i].y - j.y) <= d) b = true;
+        return b;
+    };
+    std::vector<int32_t> got(h->k_u_founder.size(), -1), founders;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t g = 0; g + 1 < h->k_cg_off.size(); g++) {
+        founders.clear();
+        for (int32_t u = h->k_cg_off[g]; u < h->k_cg_off[g + 1]; u++) {
+            const int nj = joff[u + 1] - joff[u];
+            bool seen = false;
+            for (size_t f = 0; f < founders.size(); f++) {
+                const int32_t fu = founders[f];
+                bool same = nj > 0 && joff[fu + 1] - joff[fu] == nj;
+                for (int k = 0; same && k < nj; k++) same = is_in(uj[joff[fu] + k], uj + joff[u], nj);
+                if (same && !seen) {
+                    got[u] = (int32_t)f;
+                    seen = true;
+                }
+            }
+            if (!seen && nj > 0) {
+                got[u] = (int32_t)founders.size();
+                founders.push_back(u);
+            }
+        }
+    }
+    *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    *mismatches = 0;
+    for (size_t u = 0; u < got.size(); u++) *mismatches += got[u] != h->k_u_founder[u];
+    return SMI_OK;
+}

@@ -76,6 +76,8 @@ EXPORTS = [
     "smi_dedup_counts", "smi_dedup_stage_ms", "smi_dedup_error_line", "smi_dedup_free",
     "smi_moltag_default_config", "smi_moltag_create", "smi_moltag_segment", "smi_moltag_counts", "smi_moltag_error_read", "smi_moltag_stage_ms",
     "smi_moltag_free",
+    "smi_collapse_default_config", "smi_collapse_create", "smi_collapse_set_references", "smi_collapse_add_segment", "smi_collapse_run",
+    "smi_collapse_output", "smi_collapse_counts", "smi_collapse_error_read", "smi_collapse_free", "smi_collapse_host_loop",
 ]
 
 
@@ -286,6 +288,16 @@ def load_library():
     lib.smi_moltag_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
     lib.smi_moltag_stage_ms.argtypes = [vp, vp]
     lib.smi_moltag_free.argtypes = [vp]
+    lib.smi_collapse_default_config.argtypes = [vp]
+    lib.smi_collapse_create.argtypes = [vp, vp, vp, sz, vp, sz, ctypes.POINTER(vp)]
+    lib.smi_collapse_set_references.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32]
+    lib.smi_collapse_add_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32]
+    lib.smi_collapse_run.argtypes = [vp, vp]
+    lib.smi_collapse_output.argtypes = [vp, ctypes.c_int32, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_collapse_counts.argtypes = [vp, vp]
+    lib.smi_collapse_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_collapse_free.argtypes = [vp]
+    lib.smi_collapse_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     explicit = {"smi_last_error", "smi_version", "smi_read_planes_words", "smi_packed_planes_words", "smi_record_flags"}  # restype set above (char*, size_t)
@@ -886,6 +898,107 @@ class Snp:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.smi_snp_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class CollapseConfig(ctypes.Structure):
+    """smi_collapse_config"""
+    _fields_ = [("cell_tag", ctypes.c_char * 4), ("umi_tag", ctypes.c_char * 4), ("gene_tag", ctypes.c_char * 4), ("iso_tag", ctypes.c_char * 4),
+                ("rn_tag", ctypes.c_char * 4), ("max_clip", ctypes.c_int32), ("delta", ctypes.c_int32), ("min_evidence", ctypes.c_int32),
+                ("rn_min", ctypes.c_int32), ("n_threads", ctypes.c_int32), ("lds_junc", ctypes.c_int32)]
+
+
+# smi_collapse_counts, in SMI_COL_* order
+COLLAPSE_COUNTS = ("records", "kept", "null", "mapq0", "chimeric", "low_rn", "not_listed", "no_gene", "cells", "model_genes", "model_transcripts",
+                   "genes", "undef_records", "monoexon", "founders", "novel_evidenced", "novel_filtered", "isoforms", "evidences", "gencode",
+                   "gencode_ev", "ckj", "ckj_ev", "cks", "cks_ev", "nss", "nss_ev", "long_lists", "max_undef", "max_founders")
+# smi_collapse_output, in SMI_COL_OUT_* order: the file name suffixes (PREFIX.d<DELTA>.rn<RNMIN>.e<MINEVIDENCE><suffix>)
+COLLAPSE_OUTPUTS = (".txt", ".refflat.txt", ".final.refflat.txt", ".gff", ".final.gff")
+
+
+class Collapse:
+    """CollapseModel (smi_collapse_*): the refFlat and cell-list texts and the BAM's reference names, then BAM segments in; the five output
+    texts out.  Keywords: the fields of smi_collapse_config (tags as two-character strings).  A record the loader fails on raises SmiError;
+    error_read then holds (read name, record index)."""
+
+    def __init__(self, ctx, refflat, csv, ref_names, **kw):
+        self._lib = load_library()
+        cfg = CollapseConfig()
+        self._lib.smi_collapse_default_config(ctypes.byref(cfg))
+        for k, v in kw.items():
+            if k in ISOFORM_TAGS + ("iso_tag",):
+                b = str(v).encode()
+                if len(b) != 2:
+                    raise SmiError(f"{k}: a tag is two characters")
+                setattr(cfg, k, b)
+            elif k in ("max_clip", "delta", "min_evidence", "rn_min", "n_threads", "lds_junc"):
+                setattr(cfg, k, int(v))
+            else:
+                raise ValueError(f"unknown smi_collapse_config field {k!r}")
+        rf = np.frombuffer(bytes(refflat), dtype=np.uint8)
+        cs = np.frombuffer(bytes(csv), dtype=np.uint8)
+        self._h = ctypes.c_void_p()
+        if self._lib.smi_collapse_create(ctx._h, ctypes.byref(cfg), _ptr(rf) if rf.size else None, rf.size, _ptr(cs) if cs.size else None, cs.size,
+                                         ctypes.byref(self._h)):
+            self._h = None
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        names = [str(r).rstrip("\0").encode("latin-1") for r in ref_names]
+        arr = (ctypes.c_char_p * max(len(names), 1))(*names)
+        if self._lib.smi_collapse_set_references(self._h, arr, len(names)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._ctx = ctx
+        self.error_read = None
+        self.stage_ms = dict(collapse=0.0, colstat=0.0, filter_class=0.0)
+
+    def add_segment(self, bam, recs):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
+        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
+            raise ValueError("bam: a contiguous 1-D uint8 array")
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != BAM_RECORD_DTYPE:
+            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
+        if self._lib.smi_collapse_add_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)):
+            msg = self._lib.smi_last_error().decode(errors="replace")
+            name = ctypes.create_string_buffer(256)
+            rec = ctypes.c_int64(-1)
+            self._lib.smi_collapse_error_read(self._h, name, 256, ctypes.byref(rec))
+            if rec.value >= 0:
+                self.error_read = (name.value.decode(errors="replace"), rec.value)
+            raise SmiError(msg)
+
+    def run(self):
+        """K-COLLAPSE, K-COLSTAT, K-FILTER / K-CLASS -> {file name suffix: bytes}"""
+        ms = np.zeros(3, dtype=np.float32)
+        if self._lib.smi_collapse_run(self._h, _ptr(ms)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self.stage_ms = dict(collapse=float(ms[0]), colstat=float(ms[1]), filter_class=float(ms[2]))
+        outs = {}
+        for i, name in enumerate(COLLAPSE_OUTPUTS):
+            n = ctypes.c_size_t(0)
+            self._lib.smi_collapse_output(self._h, i, None, 0, ctypes.byref(n))
+            out = np.zeros(max(n.value, 1), dtype=np.uint8)
+            if self._lib.smi_collapse_output(self._h, i, _ptr(out), out.size, ctypes.byref(n)):
+                raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+            outs[name] = out[:n.value].tobytes()
+        return outs
+
+    def counts(self):
+        c = np.zeros(len(COLLAPSE_COUNTS), dtype=np.int64)
+        self._lib.smi_collapse_counts(self._h, _ptr(c))
+        return dict(zip(COLLAPSE_COUNTS, (int(x) for x in c)))
+
+    def host_loop(self):
+        """after run(): the reference's single-thread collapse() on the same arrays -> (seconds, records whose founder differs from K-COLLAPSE's)"""
+        sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
+        if self._lib.smi_collapse_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        return sec.value, bad.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.smi_collapse_free(self._h)
             self._h = None
 
     __del__ = close

@@ -36,9 +36,9 @@ def main():
     used = synth.pick_used(wl, 5000, seed=2)
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
-            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag}
+            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -581,9 +581,9 @@ def leg_consensus(pkg, synth, ctx, dev, wl, used, res):
     res["consensus"] = out
 
 
-def _isoform_fixture(n_genes, n_recs, n_cells, seed=41, molecule_names=False):
+def _isoform_fixture(n_genes, n_recs, n_cells, seed=41, molecule_names=False, minus1=True):
     """a seeded refFlat (n_genes genes of 1..19 transcripts, 1..40 exons each) and a BAM of n_recs records: molecules of 1..3 reads, each
-    read spliced along one transcript with junction ends moved by up to 3 bases"""
+    read spliced along one transcript with junction ends moved by up to 3 bases; minus1: the barcodes carry 10x's "-1", in the BAM and the list"""
     import struct
 
     from sicelore_amd import lib
@@ -611,7 +611,7 @@ def _isoform_fixture(n_genes, n_recs, n_cells, seed=41, molecule_names=False):
     while k < n_recs:
         g = int(rng.integers(n_genes))
         ex = genes[g][int(rng.integers(len(genes[g])))]
-        cell, umi = b"CELL%05d-1" % int(rng.integers(n_cells)), b"U%09d" % m
+        cell, umi = b"CELL%05d" % int(rng.integers(n_cells)) + (b"-1" if minus1 else b""), b"U%09d" % m
         aux_m = b"BCZ" + cell + b"\0" + b"U8Z" + umi + b"\0" + b"GEZ" + b"GENE%d" % g + b"\0"
         for _r in range(int(rng.integers(1, 4))):
             cig, cur, p1 = [], None, ex[0][0] + 1
@@ -635,7 +635,7 @@ def _isoform_fixture(n_genes, n_recs, n_cells, seed=41, molecule_names=False):
         m += 1
     head = b"BAM\1" + struct.pack("<I", 0) + struct.pack("<I", 1) + struct.pack("<I", 5) + b"chr1\0" + struct.pack("<I", 2 ** 31 - 1)
     bam = np.frombuffer(head + b"".join(recs), dtype=np.uint8)
-    csv = "".join(f"CELL{c:05d}-1\n" for c in range(n_cells))
+    csv = "".join(f"CELL{c:05d}{'-1' if minus1 else ''}\n" for c in range(n_cells))
     return "".join(lines), csv, lib.bgzf_deflate(bam, level=1, n_threads=16), k, m
 
 
@@ -711,6 +711,44 @@ def leg_moltag(pkg, synth, ctx, dev, wl, used, res):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     res["moltag"] = out
+
+
+def leg_collapse(pkg, synth, ctx, dev, wl, used, res):
+    """K-COLLAPSE / K-COLSTAT / K-FILTER / K-CLASS (`CollapseModel`): the isoform leg's fixture (SMI_MB_COL_GENES genes, 20,000;
+    SMI_MB_COL_RECS records, 2,000,000) run through `IsoformMatrix ISOBAM=true`, then CollapseModel file to file on that ISOBAM: device ms
+    per stage (HIP events), seconds in parse, in the device calls and in file writes, wall seconds, and beside K-COLLAPSE the wall time of the
+    reference's single-thread collapse() loop on the same arrays (smi_collapse_host_loop), with the records on which the two differ (0)."""
+    import shutil
+    import tempfile
+
+    iso = importlib.import_module(graft.PKG_NAME + ".isoformmatrix")
+    col = importlib.import_module(graft.PKG_NAME + ".collapsemodel")
+    n_genes = int(os.environ.get("SMI_MB_COL_GENES", "20000"))
+    n_recs = int(os.environ.get("SMI_MB_COL_RECS", "2000000"))
+    t0 = time.perf_counter()
+    ref, csv, z, n_rec, n_mol = _isoform_fixture(n_genes, n_recs, 5000, minus1=False)   # ISOBAM and CollapseModel look the RAW barcode up (8d, 8h)
+    out = {"genes": n_genes, "records": n_rec, "molecules_generated": n_mol, "cells": 5000, "fixture_s": time.perf_counter() - t0}
+    d = tempfile.mkdtemp(prefix="collapse_")
+    try:
+        z.tofile(os.path.join(d, "in.bam"))
+        with open(os.path.join(d, "r.refFlat"), "w") as f:
+            f.write(ref)
+        with open(os.path.join(d, "c.csv"), "w") as f:
+            f.write(csv)
+        t0 = time.perf_counter()
+        iso.isoform_matrix(ctx, os.path.join(d, "in.bam"), os.path.join(d, "r.refFlat"), os.path.join(d, "c.csv"), d, n_threads=16, isobam=True)
+        out["isobam_s"] = time.perf_counter() - t0
+        info = col.collapse_model(ctx, os.path.join(d, "sicelore_isobam.bam"), os.path.join(d, "r.refFlat"), os.path.join(d, "c.csv"), d,
+                                  n_threads=16, host_loop=True)
+        lib = importlib.import_module(graft.PKG_NAME + ".lib")
+        out["file_to_file"] = dict({k: info[k] for k in lib.COLLAPSE_COUNTS}, stage_ms=info["stage_ms"], seconds=info["seconds"],
+                                   wall_s=info["wall_s"], bytes_written=info["bytes_written"], records_per_s=info["records"] / info["wall_s"])
+        out["k_collapse_device_s"] = info["stage_ms"]["collapse"] / 1e3
+        out["host_collapse_loop_wall_s"] = info["host_loop_s"]
+        out["host_loop_mismatches"] = info["host_loop_mismatches"]
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    res["collapse"] = out
 
 
 def _snp_fixture(n_recs, n_lines, n_cells, seed=51):

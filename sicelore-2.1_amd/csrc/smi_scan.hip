@@ -77,7 +77,7 @@ struct ScanParams {
     uint32_t tso_nib[2];  // 4-bit codes of the read scan's TSO (generic kernels; the shipped kernels carry tso4() as constants)
     int tso_window, tso_max_mm, tso_min_consec, tso_min_two;  // 90, 5, 8, 12
     __host__ __device__ __forceinline__ uint32_t t4(int i) const { return (tso_nib[i >> 3] >> ((i & 7) * 4)) & 15u; }
-    int finder_bits;     // host side only: the bit-parallel polyT finder applies (polya_len 15, thresholds 12 / 10, window <= 160) -- otherwise the generic kernels run
+    int finder_bits;     // host side only: the bit-parallel polyT finder applies (polya_len 15, thresholds 12 / 10, window <= kFinderMaxWindow) -- otherwise the generic kernels run
     int ablate;          // measurement only (SMI_SCAN_ABLATE): 1 no TSO alignments, 2 no adapter alignments, 4 no polyT finder, 8 no TSO gates, 16 no TSO pre-filter (results unchanged), 32 finder: first loop only, 64 no adapter gates, 128 no folds
 };
 
@@ -214,27 +214,46 @@ __device__ __forceinline__ uint64_t mask64(const uint64_t *m, int tid, int p) {
     if (sh) r |= b << (64 - sh);
     return r;
 }
-__device__ __forceinline__ bool find_polyt_bits(const uint32_t *planes, uint64_t *go_lds, int tid, const ScanParams &P, const uint32_t (&tw)[8], int &begin1,
-                                                int &end1) {
+// The words a window of at most kFinderMaxWindow positions can reach (launch_scan sends longer windows to the generic kernels):
+//   entry(pos), go(p)    pos, p < window                          words 0 .. kFinderPosWords - 1
+//   >= 12 / >= 10 masks  read one position further on (pos + 1)   the same words, and position kFinderMaxWindow alone: bit 0 of the next word,
+//                                                                  which is one popcount of the exact-T bits [window, window + 15)
+//   five-counts c5       at q, q + 5, q + 10 for q < window       one more word, of which bits 0 .. 9 are read: they need T bits 0 .. 13 of that word only
+//   walk back            endpos = start + 14 <= window + 13        words 0 .. kFinderBackWords - 1
+// (the forward steps behind the walk back go on to n - 1 = window + 24 through get64 on the planes, which reads all seven words)
+// smi_scan_device accepts window + polya_len + 10 <= 175 only, i.e. windows up to 150 for the 15-base polyT this finder is built for: the part of
+// these words that serves windows 151 .. 160 (the top ten bits of the fifth position word and the popcount for position 160) is reached by no
+// caller today.  The bound stays the finder's own, so that the scan's check can move without touching it.
+constexpr int kFinderMaxWindow = 160;
+constexpr int kFinderPosWords = kFinderMaxWindow / 32;               // 5
+constexpr int kFinderC5Words = kFinderPosWords + 1;                  // 6
+constexpr int kFinderBackWords = (kFinderMaxWindow + 13) / 32 + 1;   // 6
+constexpr int kFinderTWords = kFinderBackWords > kFinderC5Words ? kFinderBackWords : kFinderC5Words;  // exact-T words the finder is handed
+static_assert(kFinderMaxWindow % 32 == 0, "position kFinderMaxWindow is taken as bit 0 of a word of its own");
+static_assert(kFinderMaxWindow - 1 + 10 + 4 < 32 * kFinderC5Words, "the last five-count word is built without the T word behind it");
+static_assert(kFinderMaxWindow + 15 <= 32 * kFinderTWords && kFinderTWords <= kLdsWords && kFinderMaxWindow + 15 + 10 <= 32 * kLdsWords,
+              "the finder's window leaves the staged planes");
+__device__ __forceinline__ bool find_polyt_bits(const uint32_t *planes, uint64_t *go_lds, int tid, const ScanParams &P, const uint32_t (&tw)[kFinderTWords],
+                                                int &begin1, int &end1) {
     constexpr int ML = 15;
     const int n = P.window + ML + 10;
-    // T's in [q, q + 5) for every q: planes c5[0..2], seven words (the eighth reads as 0)
-    uint32_t c5[3][8];
+    // T's in [q, q + 5) for every q: planes c5[0..2]
+    uint32_t c5[3][kFinderC5Words];
 #pragma unroll
-    for (int k = 0; k < 7; k++) {
-        const uint32_t s1 = __builtin_amdgcn_alignbit(tw[k + 1], tw[k], 1), s2 = __builtin_amdgcn_alignbit(tw[k + 1], tw[k], 2),
-                       s3 = __builtin_amdgcn_alignbit(tw[k + 1], tw[k], 3), s4 = __builtin_amdgcn_alignbit(tw[k + 1], tw[k], 4);
+    for (int k = 0; k < kFinderC5Words; k++) {
+        const uint32_t up = k + 1 < kFinderC5Words ? tw[k + 1] : 0u;
+        const uint32_t s1 = __builtin_amdgcn_alignbit(up, tw[k], 1), s2 = __builtin_amdgcn_alignbit(up, tw[k], 2),
+                       s3 = __builtin_amdgcn_alignbit(up, tw[k], 3), s4 = __builtin_amdgcn_alignbit(up, tw[k], 4);
         uint32_t x, k1, k2;
         full_add(tw[k], s1, s2, x, k1);
         full_add(x, s3, s4, c5[0][k], k2);
         c5[1][k] = k1 ^ k2;
         c5[2][k] = k1 & k2;
     }
-    c5[0][7] = c5[1][7] = c5[2][7] = 0u;
-    // T's in [q, q + 15) = the three five-counts at q, q + 5, q + 10: >= 12 and >= 10 as masks, six words (+ a zero word)
-    uint32_t ge12[7], ge10[7];
+    // T's in [q, q + 15) = the three five-counts at q, q + 5, q + 10: >= 12 and >= 10 as masks
+    uint32_t ge12[kFinderPosWords + 1], ge10[kFinderPosWords + 1];
 #pragma unroll
-    for (int k = 0; k < 6; k++) {
+    for (int k = 0; k < kFinderPosWords; k++) {
         uint32_t b[3], c[3];
 #pragma unroll
         for (int j = 0; j < 3; j++) {
@@ -252,12 +271,18 @@ __device__ __forceinline__ bool find_polyt_bits(const uint32_t *planes, uint64_t
         ge12[k] = r3 & r2;
         ge10[k] = r3 & (r2 | r1);
     }
-    ge12[6] = ge10[6] = 0u;
+    {
+        const int top = __popc(tw[kFinderPosWords] & ((1u << ML) - 1u));  // position kFinderMaxWindow: T's in its fifteen bases
+        ge12[kFinderPosWords] = top >= 12 ? 1u : 0u;
+        ge10[kFinderPosWords] = top >= 10 ? 1u : 0u;
+    }
     // entry positions; the extension's probe mask goes to LDS (it is read at run-time offsets)
     int first = -1;
     uint32_t gom[6];
+    gom[5] = 0u;
+    static_assert(kFinderPosWords == 5, "gom[] is three 64-bit slots of the candidate-mask area");
 #pragma unroll
-    for (int k = 5; k >= 0; k--) {
+    for (int k = kFinderPosWords - 1; k >= 0; k--) {
         const int keep = P.window - 32 * k;  // positions below `window` (uniform)
         const uint32_t below = keep >= 32 ? 0xFFFFFFFFu : (keep <= 0 ? 0u : ((1u << keep) - 1u));
         const uint32_t entry = __builtin_amdgcn_alignbit(ge12[k + 1], ge12[k], 1) & tw[k] & (c5[2][k] | (c5[1][k] & c5[0][k])) & below;
@@ -289,7 +314,7 @@ __device__ __forceinline__ bool find_polyt_bits(const uint32_t *planes, uint64_t
         int e = 4;
         bool found = false;
 #pragma unroll
-        for (int k = 5; k >= 0; k--) {
+        for (int k = kFinderBackWords - 1; k >= 0; k--) {
             const uint32_t lo = k ? tw[k - 1] : 0u;
             const uint32_t l1 = __builtin_amdgcn_alignbit(tw[k], lo, 31), l2 = __builtin_amdgcn_alignbit(tw[k], lo, 30), l3 = __builtin_amdgcn_alignbit(tw[k], lo, 29),
                            l4 = __builtin_amdgcn_alignbit(tw[k], lo, 28);
@@ -456,10 +481,9 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                 // (the empty asm keeps the loads, and with them the branch-free front of the finder, INSIDE this branch: hoisted above it -- the compiler
                 // did -- they run for every wave of the 5' --noPolyARequired kernel, which never takes the branch: 1.44 -> 1.63 ms per 10 M reads)
                 asm volatile("" ::: "memory");
-                uint32_t tw[8];
+                uint32_t tw[kFinderTWords];
 #pragma unroll
-                for (int w = 0; w < kLdsWords; w++) tw[w] = planes[(3 * kLdsWords + w) * kBlock + tid] & ~planes[w * kBlock + tid];
-                tw[7] = 0u;
+                for (int w = 0; w < kFinderTWords; w++) tw[w] = planes[(3 * kLdsWords + w) * kBlock + tid] & ~planes[w * kBlock + tid];
                 has_t = find_polyt_bits(planes, cmask, tid, P, tw, pb, pe);
             } else
                 has_t = find_polyt(planes, tid, P, pb, pe);
@@ -468,14 +492,40 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
         // 5' barcoding scans an end when the polyT was found at the OTHER end (or no polyA is asked for):
         // PolyATadapterAnalyzer_5pBCUMI.java:L51-68
         const bool scan5 = FP && active && long_enough && (P.dont_polya || __shfl_xor((int)has_t, 1));
-        if (FP ? scan5 : has_t) {
-            // 3': positions 1 .. min(pe - AD, pe - 12)  (seqTilPolyAend has length pe; L49-61, AdapterTSOanalyzer L87)
-            // 5': positions 1 .. AdapterSearchWindow of the first window + AD + maxMM + 5 bases
-            const int last = FP ? P.window5 : min(pe - AD, pe - 12);
+        // 3': positions 1 .. min(pe - AD, pe - 12)  (seqTilPolyAend has length pe; L49-61, AdapterTSOanalyzer L87)
+        // 5': positions 1 .. AdapterSearchWindow of the first window + AD + maxMM + 5 bases
+        const int last = FP ? P.window5 : min(pe - AD, pe - 12);
+        auto ad_code = [&](int i) { return SHIP ? shipped_a4<AD>(i) : P.a4(i); };
+        bool gated = false;
+        if (SHIP && !FP) {
+            // The 3' scan gates an end only when its polyT was found, which in almost every read is ONE end of the two: half the lanes of each
+            // gate64 sit idle, and the second chunk runs in nearly every wave (some lane's `last` passes 64).  When no read of the wave has a
+            // polyT on both ends, the idle lane of each pair gates the second chunk of its partner's column while the partner gates the first:
+            // one gate64 for both chunks.  The mask goes back through one 64-bit exchange; the owner cuts it at its own `last`.  A wave with a
+            // read that has both takes the path below.
+            const bool o_has = (bool)__shfl_xor((int)has_t, 1);
+            const int o_last = __shfl_xor(last, 1);
+            if (__ballot(has_t && o_has) == 0) {  // wave-uniform
+                gated = true;
+                // bits left to gate in this lane's chunk: the owner's first 64 positions, the partner's 64 behind them
+                const int left = has_t ? last : (o_has ? o_last - 64 : 0);
+                uint64_t g = 0;
+                wave_sync();  // the partner's columns were staged by the partner
+                // (the second chunk is the first one two plane words further on: the bit offsets inside gate64 stay compile-time constants)
+                if (left > 0 && !SMI_ABLATED(64)) g = gate64<AD>(planes + (has_t ? 0 : 2 * kBlock), has_t ? tid : tid ^ 1, 0, ad_code);
+                const uint64_t og = __shfl_xor((unsigned long long)g, 1);
+                if (has_t) {
+                    am[0] = keep_low(g, last);
+                    am[1] = keep_low(og, last - 64);
+                    if (last > 128 && !SMI_ABLATED(64)) am[2] = keep_low(gate64<AD>(planes, tid, 128, ad_code), last - 128);  // (the few ends whose polyT ends beyond position 138)
+                }
+            }
+        }
+        if (!gated && (FP ? scan5 : has_t)) {
 #pragma unroll
             for (int ch = 0; ch < 3; ch++)
                 if (last > ch * 64 && !SMI_ABLATED(64))  // (the third chunk is needed by the few ends whose polyT ends beyond position 138: most waves skip it)
-                    am[ch] = keep_low(gate64<AD>(planes, tid, ch * 64, [&](int i) { return SHIP ? shipped_a4<AD>(i) : P.a4(i); }), last - ch * 64);
+                    am[ch] = keep_low(gate64<AD>(planes, tid, ch * 64, ad_code), last - ch * 64);
         }
         const int n_ad = __popcll(am[0]) + __popcll(am[1]) + __popcll(am[2]);
         const int lane = tid & 63, wbase = tid & ~63;  // this wave's lanes are wbase .. wbase+63
@@ -518,6 +568,8 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                             tm[ch] = keep_low(gate64<16>(planes, tid, ch * 64, [&](int i) { return P.t4(i); }), P.tso_window - ch * 64);
                     }
                 }
+                int n_ts = __popcll(tm[0]) + __popcll(tm[1]), off_ts = 0;
+                bool numbered = false;  // wave-uniform
                 if (SHIP && !SMI_ABLATED(16)) {
                     // Exact pre-filter of the ISOLATED TSO candidates.  A candidate's alignment matters in two ways only: it may be
                     // accepted (Math.round(ne) <= 5, AdapterTSOanalyzer L96-104), or its error count makes the scan jump over the next
@@ -548,12 +600,24 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                         shi |= b;
                     }
                     const uint64_t iso0 = tm[0] & ~slo, iso1 = tm[1] & ~shi;
-                    int tot_iso;
-                    const int off_iso = wave_exscan(__popcll(iso0) + __popcll(iso1), lane, tot_iso);
-                    if (tot_iso) {  // wave-uniform
+                    // The pre-filter is there so that a wave's candidates fit fewer alignment rounds, and it drops isolated candidates only: when
+                    // even without all of them the wave needs as many rounds of 64 as with them (in a quarter of the waves everything gated
+                    // fits one round as it is), it is ~ 500 instructions for nothing, and the wave aligns every gated candidate as the generic
+                    // kernels do.  One prefix sum numbers both sets: gated counts in the low half (<= 90 per end, so <= 64 * 90 = 5,760 < 65,536 per wave: the
+                    // low half never carries into the high one), isolated ones in the high half.
+                    static_assert(64 * 90 < (1 << 16), "the gated counts of a wave must fit the low half of the packed prefix sum");
+                    int tot2;
+                    const int off2 = wave_exscan(n_ts | ((__popcll(iso0) + __popcll(iso1)) << 16), lane, tot2);
+                    tot2 = __builtin_amdgcn_readfirstlane(tot2);
+                    const int tot_iso = tot2 >> 16;
+                    total = tot2 & 0xFFFF;
+                    off_ts = off2 & 0xFFFF;
+                    numbered = true;
+                    if (tot_iso && ((total + 63) >> 6) > ((total - tot_iso + 63) >> 6)) {  // wave-uniform
+                        numbered = false;
                         cmask[0 * kBlock + tid] = iso0;
                         cmask[1 * kBlock + tid] = iso1;
-                        coff[tid] = (uint32_t)off_iso;
+                        coff[tid] = (uint32_t)(off2 >> 16);
                         uint32_t *drop = ent + tid * 5;  // three words of dropped positions per end
                         drop[0] = drop[1] = drop[2] = 0u;
                         wave_sync();
@@ -583,10 +647,11 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                         tm[0] &= ~((uint64_t)drop[0] | ((uint64_t)drop[1] << 32));
                         tm[1] &= ~(uint64_t)drop[2];
                         wave_sync();  // cmask / coff / ent are written again below
+                        n_ts = __popcll(tm[0]) + __popcll(tm[1]);
                     }
                 }
-                const int n_ts = __popcll(tm[0]) + __popcll(tm[1]);
-                no = (uint32_t)n_ts | ((uint32_t)wave_exscan(n_ts, lane, total) << 8);
+                if (!numbered) off_ts = wave_exscan(n_ts, lane, total);
+                no = (uint32_t)n_ts | ((uint32_t)off_ts << 8);
                 cmask[0 * kBlock + tid] = tm[0];
                 cmask[1 * kBlock + tid] = tm[1];
                 cmask[2 * kBlock + tid] = 0ull;
@@ -946,7 +1011,7 @@ int launch_scan(smi_ctx *ctx, const uint32_t *d_ends, const int32_t *d_len, cons
     P.tso_min_two = tso_given ? cfg->tso_min_two_best : 12;
     // the kernels of the shipped adapters carry the bit-parallel finder, built for the shipped window length and the thresholds the shipped fractions give;
     // SMI_SCAN_FINDER_LOOP: cross-check switch (the generic kernels, which keep the loop)
-    P.finder_bits = cfg->polya_len == 15 && P.thr_first == 12 && P.thr_adv == 10 && cfg->window_polya >= 1 && cfg->window_polya <= 160 && !std::getenv("SMI_SCAN_FINDER_LOOP");
+    P.finder_bits = cfg->polya_len == 15 && P.thr_first == 12 && P.thr_adv == 10 && cfg->window_polya >= 1 && cfg->window_polya <= kFinderMaxWindow && !std::getenv("SMI_SCAN_FINDER_LOOP");
     // SMI_SCAN_ABLATE switches parts of the kernel off to time them (tools/gpu_scan_ablate.sh): the results are wrong by construction, so
     // only a measurement build (make MEASURE=1 -> -DSMI_MEASURE) honours it; the shipped library refuses to run with it set
     const char *abl = std::getenv("SMI_SCAN_ABLATE");

@@ -1098,7 +1098,7 @@ int smi_moltag_free(smi_moltag *h);
  *   the order of each molecule's first kept record (the reference: hash order); kernel_ms (may be NULL): K-POA device time.  A molecule
  *   K-POA cannot hold in cfg.scratch_bytes fails the call with its name (BC-UMI-n).
  * smi_consensus_fastq: out == NULL -> size only; cap too small -> returns 1.  smi_consensus_counts: SMI_CONSENSUS_COUNTS entries, SMI_CC_*. */
-#define SMI_CONSENSUS_COUNTS 13
+#define SMI_CONSENSUS_COUNTS 15
 #define SMI_CC_RECORDS 0        /* Total SAMrecords */
 #define SMI_CC_VALID 1          /* SAMrecords valid */
 #define SMI_CC_UNVALID 2        /* SAMrecords unvalid */
@@ -1112,6 +1112,8 @@ int smi_moltag_free(smi_moltag *h);
 #define SMI_CC_MOLECULES 10     /* Total molecules */
 #define SMI_CC_POA_MOLECULES 11 /* molecules of 3 or more selected reads (K-POA) */
 #define SMI_CC_POA_RERUN 12     /* of those, run again in a slot of their worst case (smi_poa_batch's *n_rerun) */
+#define SMI_CC_POA_LAUNCHES 13  /* K-POA launches of the run (SMI_POA_STAT_LAUNCHES) */
+#define SMI_CC_POA_SLOT_REUSE 14 /* molecules that ran in a slot another had used, a lower bound (SMI_POA_STAT_SLOT_REUSE) */
 typedef struct {
     char cell_tag[4], umi_tag[4], gene_tag[4], tso_end_tag[4];  /* CELLTAG UMITAG GENETAG TSOENDTAG: two characters + NUL */
     char polya_start_tag[4], cdna_tag[4], us_tag[4], rn_tag[4]; /* POLYASTARTTAG CDNATAG USTAG RNTAG */
@@ -1143,6 +1145,17 @@ int smi_consensus_free(smi_consensus *h);
  * Host arrays; synchronous. */
 int smi_poa_batch(smi_ctx *ctx, const uint8_t *seqs, const uint64_t *read_off, const int32_t *mol_off, int32_t n_mol, int32_t max_ps,
                   size_t scratch_bytes, uint8_t *cons, uint8_t *qv, int32_t *cons_len, float *kernel_ms, int32_t *n_rerun);
+/* smi_poa_batch_ex: smi_poa_batch + the launch statistics of the call (stats may be NULL; SMI_POA_STATS entries, host arithmetic, zero on
+ * an error before the first launch).  A launch runs a group of molecules on `waves` persistent wavefronts, each in its own slot of the
+ * scratch arena, which is not cleared between molecules: waves = min(scratch budget / slot size, 8 x compute units, molecules of the group). */
+#define SMI_POA_STATS 4
+#define SMI_POA_STAT_LAUNCHES 0       /* kernel launches (both passes) */
+#define SMI_POA_STAT_WAVES 1          /* wavefronts, summed over the launches */
+#define SMI_POA_STAT_SLOT_REUSE 2     /* sum over launches of max(0, molecules of the launch - waves): a lower bound on the molecules
+                                         that ran in a slot another molecule had used before */
+#define SMI_POA_STAT_MAX_SLOT_BYTES 3 /* the largest slot of any launch */
+int smi_poa_batch_ex(smi_ctx *ctx, const uint8_t *seqs, const uint64_t *read_off, const int32_t *mol_off, int32_t n_mol, int32_t max_ps,
+                     size_t scratch_bytes, uint8_t *cons, uint8_t *qv, int32_t *cons_len, float *kernel_ms, int32_t *n_rerun, int64_t *stats);
 
 /* ---- IsoformMatrix (K-ISO + K-MTX, smi_isoform.hip) -----------------------------------------------------------------------------------
  * IsoformMatrix.process (IsoformMatrix.java:L93-160), METHOD=STRICT, DESIGN.md section 8d.

@@ -43,8 +43,11 @@ constexpr int kNeg = -1000000000;                                               
 constexpr int kGraphInts = 16;  // int arrays of node_cap entries in a slot (nodes 11, edges 5)
 constexpr int kStOverflow = 1, kStCycle = 2;
 // DP rows are stored as int16 when every read of the launch has at most kNarrowMaxLen bases, else as int32.  The cells the recurrences and
-// the traceback read are exact in int16: H and the values along a traceback lie in [0, 5 n] <= 30000, F >= min(g, q) = -10 (H >= 0),
-// and only E can go lower (down to g + (n - 1) e); E is clamped at kStoreMin16 when stored, which no comparison with a value > 0 sees
+// the traceback read are exact in int16.  The bound that matters is the upper one: a local alignment of n read bases scores at most 5 n, so
+// H <= 5 n <= 30000.  Below, nothing goes under -10: H' >= 0, so F >= min(g, q), and E is g (q) plus a prefix maximum of
+// H'[k] + (j - 1 - k) e over k = 0 .. j - 1 that contains k = j - 1, hence E1 >= g and E2 >= q.  The clamp at kStoreMin16 in store_e is therefore
+// never reached; it is kept as it was (tests/test_poa_edges_cpu.py asserts both lower bounds on the model, test_poa_edges_gpu.py runs a
+// 6,000 x 6,000 alignment whose H reaches exactly 30000)
 constexpr int kNarrowMaxLen = 6000;
 constexpr int kStoreMin16 = -30000;
 
@@ -486,11 +489,13 @@ struct Events {  // the two timing events of a launch, destroyed on every way ou
 // K-POA over a batch: host arrays in, consensus bases and per-base counts out (offsets of the molecules' reads).  Pass 1 gives each molecule a
 // slot of its estimate; a molecule whose graph outgrows it, or whose estimate does not fit the budget, is run again in pass 2 in a slot of its
 // worst case.  A molecule whose worst case does not fit the budget fails the call: *bad = its index in the batch and *why says why (on any
-// other error *bad = -1 and the error text is set).  *n_rerun = molecules run in pass 2.
+// other error *bad = -1 and the error text is set).  *n_rerun = molecules run in pass 2.  stats (may be null): SMI_POA_STATS entries,
+// host arithmetic over the launches made.
 int poa_batch(smi_ctx *ctx, const uint8_t *seq, const uint64_t *read_off, const int32_t *mol_off, int32_t n_mol, size_t budget, uint8_t *cons,
-              uint32_t *same, int32_t *cons_len, float *kernel_ms, int32_t *n_rerun, int32_t *bad, std::string *why) {
+              uint32_t *same, int32_t *cons_len, float *kernel_ms, int32_t *n_rerun, int32_t *bad, std::string *why, int64_t *stats) {
     if (kernel_ms) *kernel_ms = 0.f;
     if (n_rerun) *n_rerun = 0;
+    if (stats) std::fill(stats, stats + SMI_POA_STATS, (int64_t)0);
     *bad = -1;
     if (n_mol <= 0) return SMI_OK;
     SMI_HIP(hipSetDevice(ctx->device));
@@ -594,6 +599,12 @@ int poa_batch(smi_ctx *ctx, const uint8_t *seq, const uint64_t *read_off, const 
                 set_error("smi_poa_batch: device allocation of " + std::to_string(((size_t)waves * slot) >> 20) + " MiB of POA scratch failed");
                 return rc;
             }
+            if (stats) {
+                stats[SMI_POA_STAT_LAUNCHES]++;
+                stats[SMI_POA_STAT_WAVES] += waves;
+                stats[SMI_POA_STAT_SLOT_REUSE] += std::max<int64_t>(0, (int64_t)(g1 - g0) - waves);
+                stats[SMI_POA_STAT_MAX_SLOT_BYTES] = std::max<int64_t>(stats[SMI_POA_STAT_MAX_SLOT_BYTES], (int64_t)slot);
+            }
             SMI_HIP(hipMemcpyAsync(d_order.p, todo.data() + g0, (g1 - g0) * 4, hipMemcpyHostToDevice, st));
             SMI_HIP(hipMemsetAsync(d_counter.p, 0, 4, st));
             PoaArgs a;
@@ -659,8 +670,10 @@ uint8_t qv_byte(uint32_t same, uint32_t rows, int max_ps) {
 
 using namespace smi;
 
-extern "C" int smi_poa_batch(smi_ctx *ctx, const uint8_t *seqs, const uint64_t *read_off, const int32_t *mol_off, int32_t n_mol, int32_t max_ps,
-                             size_t scratch_bytes, uint8_t *cons, uint8_t *qv, int32_t *cons_len, float *kernel_ms, int32_t *n_rerun) {
+extern "C" int smi_poa_batch_ex(smi_ctx *ctx, const uint8_t *seqs, const uint64_t *read_off, const int32_t *mol_off, int32_t n_mol, int32_t max_ps,
+                                size_t scratch_bytes, uint8_t *cons, uint8_t *qv, int32_t *cons_len, float *kernel_ms, int32_t *n_rerun,
+                                int64_t *stats) {
+    if (stats) std::fill(stats, stats + SMI_POA_STATS, (int64_t)0);
     if (!ctx || !read_off || !mol_off || n_mol < 0 || (n_mol && (!cons || !qv || !cons_len))) {
         set_error("smi_poa_batch: null argument");
         return SMI_ERR_INVALID;
@@ -689,7 +702,8 @@ extern "C" int smi_poa_batch(smi_ctx *ctx, const uint8_t *seqs, const uint64_t *
     std::vector<uint32_t> same(std::max<uint64_t>(total, 1));
     int32_t bad = -1;
     std::string why;
-    const int rc = poa_batch(ctx, seqs, read_off, mol_off, n_mol, scratch_bytes, cons, same.data(), cons_len, kernel_ms, n_rerun, &bad, &why);
+    const int rc = poa_batch(ctx, seqs, read_off, mol_off, n_mol, scratch_bytes, cons, same.data(), cons_len, kernel_ms, n_rerun, &bad, &why,
+                             stats);
     if (rc) {
         if (bad >= 0) set_error("smi_poa_batch: molecule " + std::to_string(bad) + " (" + why + ")");
         return rc;
@@ -700,6 +714,11 @@ extern "C" int smi_poa_batch(smi_ctx *ctx, const uint8_t *seqs, const uint64_t *
         for (int i = 0; i < cons_len[m]; i++) qv[o + i] = qv_byte(same[o + i], rows, max_ps);
     }
     return SMI_OK;
+}
+
+extern "C" int smi_poa_batch(smi_ctx *ctx, const uint8_t *seqs, const uint64_t *read_off, const int32_t *mol_off, int32_t n_mol, int32_t max_ps,
+                             size_t scratch_bytes, uint8_t *cons, uint8_t *qv, int32_t *cons_len, float *kernel_ms, int32_t *n_rerun) {
+    return smi_poa_batch_ex(ctx, seqs, read_off, mol_off, n_mol, max_ps, scratch_bytes, cons, qv, cons_len, kernel_ms, n_rerun, nullptr);
 }
 
 // ---- the record parser, molecules and the FASTQ (host) ---------------------------------------------------------------------------------
@@ -1063,9 +1082,10 @@ extern "C" int smi_consensus_run(smi_consensus *h, float *kernel_ms) {
     std::vector<int32_t> clen(poa_mols.size());
     if (!poa_mols.empty()) {
         int32_t bad = -1, n_rerun = 0;
+        int64_t stats[SMI_POA_STATS];
         std::string why;
         const int rc = poa_batch(h->ctx, (const uint8_t *)seqs.data(), roff.data(), moff.data(), (int32_t)poa_mols.size(), (size_t)h->cfg.scratch_bytes,
-                                 cons.data(), same.data(), clen.data(), kernel_ms, &n_rerun, &bad, &why);
+                                 cons.data(), same.data(), clen.data(), kernel_ms, &n_rerun, &bad, &why, stats);
         if (rc) {
             if (bad >= 0) {  // the batch index back to the molecule's name
                 const int32_t m = poa_mols[bad];
@@ -1077,6 +1097,8 @@ extern "C" int smi_consensus_run(smi_consensus *h, float *kernel_ms) {
             return rc;
         }
         c[SMI_CC_POA_RERUN] = n_rerun;
+        c[SMI_CC_POA_LAUNCHES] = stats[SMI_POA_STAT_LAUNCHES];
+        c[SMI_CC_POA_SLOT_REUSE] = stats[SMI_POA_STAT_SLOT_REUSE];
     }
     // the FASTQ: @BC-UMI-n / cons / + / qv per molecule (Consensus.toFastq L233)
     std::string &fq = h->fastq;

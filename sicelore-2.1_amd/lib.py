@@ -67,7 +67,7 @@ EXPORTS = [
     "smi_bam_write_default_config", "smi_bam_write_batch", "smi_bam_chunk_inputs", "smi_bam_name_seen", "smi_name_set_create", "smi_name_set_free", "smi_name_set_seen",
     "smi_tagbam_default_config", "smi_tagbam_create", "smi_tagbam_free", "smi_tagbam_records", "smi_tagbam_segment", "smi_tagbam_stage_ms",
     "smi_consensus_default_config", "smi_consensus_create", "smi_consensus_add_segment", "smi_consensus_run", "smi_consensus_fastq",
-    "smi_consensus_counts", "smi_consensus_free", "smi_poa_batch",
+    "smi_consensus_counts", "smi_consensus_free", "smi_poa_batch", "smi_poa_batch_ex",
     "smi_isoform_default_config", "smi_isoform_create", "smi_isoform_add_segment", "smi_isoform_run", "smi_isoform_output",
     "smi_isoform_counts", "smi_isoform_free", "smi_isoform_isobam",
     "smi_snp_default_config", "smi_snp_create", "smi_snp_add_segment", "smi_snp_run", "smi_snp_output", "smi_snp_counts",
@@ -300,6 +300,7 @@ def load_library():
     lib.smi_collapse_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
+    lib.smi_poa_batch_ex.argtypes = lib.smi_poa_batch.argtypes + [vp]
     explicit = {"smi_last_error", "smi_version", "smi_read_planes_words", "smi_packed_planes_words", "smi_record_flags"}  # restype set above (char*, size_t)
     for name in EXPORTS:
         if name not in explicit:
@@ -649,7 +650,7 @@ class ConsensusConfig(ctypes.Structure):
 
 # smi_consensus_counts, in SMI_CC_* order
 CONSENSUS_COUNTS = ("records", "valid", "unvalid", "mapqv0", "no_gene", "no_umi", "chimeria", "null", "reads", "reads_multi", "molecules",
-                    "poa_molecules", "poa_rerun")
+                    "poa_molecules", "poa_rerun", "poa_launches", "poa_slot_reuse")
 CONSENSUS_TAGS = ("cell_tag", "umi_tag", "gene_tag", "tso_end_tag", "polya_start_tag", "cdna_tag", "us_tag", "rn_tag")
 
 
@@ -1184,9 +1185,14 @@ class MolTag:
     __del__ = close
 
 
-def poa_batch(ctx, seqs, read_off, mol_off, max_ps=20, scratch_bytes=0):
+# smi_poa_batch_ex's statistics, in SMI_POA_STAT_* order
+POA_STATS = ("launches", "waves", "slot_reuse", "max_slot_bytes")
+
+
+def poa_batch(ctx, seqs, read_off, mol_off, max_ps=20, scratch_bytes=0, stats=False):
     """K-POA alone (smi_poa_batch).  seqs: uint8 bases of all reads back to back; read_off: uint64 [n_reads + 1]; mol_off: int32 [n_mol + 1],
-    both starting at 0 -> (list of consensus bytes, list of QV bytes, device ms, molecules run again in a slot of their worst case)"""
+    both starting at 0 -> (list of consensus bytes, list of QV bytes, device ms, molecules run again in a slot of their worst case); with
+    stats=True a fifth element, the dict of the call's launch statistics (POA_STATS, smi_poa_batch_ex)"""
     lib = load_library()
     seqs = np.ascontiguousarray(seqs)
     read_off = np.ascontiguousarray(read_off)
@@ -1202,14 +1208,18 @@ def poa_batch(ctx, seqs, read_off, mol_off, max_ps=20, scratch_bytes=0):
     qv = np.zeros_like(cons)
     clen = np.zeros(max(n_mol, 1), dtype=np.int32)
     ms, rerun = ctypes.c_float(0.0), ctypes.c_int32(0)
-    if lib.smi_poa_batch(ctx._h, _ptr(seqs) if seqs.size else None, _ptr(read_off), _ptr(mol_off), n_mol, int(max_ps), int(scratch_bytes),
-                         _ptr(cons), _ptr(qv), _ptr(clen), ctypes.byref(ms), ctypes.byref(rerun)):
+    st = np.zeros(len(POA_STATS), dtype=np.int64)
+    args = (ctx._h, _ptr(seqs) if seqs.size else None, _ptr(read_off), _ptr(mol_off), n_mol, int(max_ps), int(scratch_bytes), _ptr(cons), _ptr(qv),
+            _ptr(clen), ctypes.byref(ms), ctypes.byref(rerun))
+    if lib.smi_poa_batch_ex(*args, _ptr(st)) if stats else lib.smi_poa_batch(*args):
         raise SmiError(lib.smi_last_error().decode())
     outs, qvs = [], []
     for m in range(n_mol):
         o, n = int(read_off[mol_off[m]]), int(clen[m])
         outs.append(cons[o:o + n].tobytes())
         qvs.append(qv[o:o + n].tobytes())
+    if stats:
+        return outs, qvs, float(ms.value), int(rerun.value), dict(zip(POA_STATS, (int(x) for x in st)))
     return outs, qvs, float(ms.value), int(rerun.value)
 
 

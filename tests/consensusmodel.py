@@ -79,19 +79,23 @@ class Graph:
         return [self.e_from[e] for e in self.ins[v]]
 
 
-def align(graph, read):
-    """read (bytes) against the graph -> aligned node per read position (-1: not aligned), rules 1 and 3-6"""
+def align(graph, read, out=None, dtype=np.int64):
+    """read (bytes) against the graph -> aligned node per read position (-1: not aligned), rules 1 and 3-6.  out: a dict that receives
+    `best` (H of the end cell, 0 when nothing aligns), `e1_min` / `e2_min` (the smallest E1 / E2 of the alignment, None without a DP);
+    dtype: the matrices' type (int32 holds every value: |H'[k] - k e| <= 5 n + 6 n)"""
     n, N = len(read), len(graph.base)
     aln = [-1] * n
+    if out is not None:
+        out.update(best=0, e1_min=None, e2_min=None)
     if n == 0 or N == 0:
         return aln
     order = graph.topo()
     rank = [0] * N
     for i, v in enumerate(order):
         rank[v] = i
-    rd = np.frombuffer(read, dtype=np.uint8).astype(np.int64)
-    jj = np.arange(1, n + 1, dtype=np.int64)
-    H, F1, F2, E1, E2 = (np.zeros((N, n), dtype=np.int64) for _ in range(5))
+    rd = np.frombuffer(read, dtype=np.uint8).astype(dtype)
+    jj = np.arange(1, n + 1, dtype=dtype)
+    H, F1, F2, E1, E2 = (np.zeros((N, n), dtype=dtype) for _ in range(5))
     preds = [graph.preds(v) for v in range(N)]
     best, bv, bj = 0, -1, -1
     for v in order:
@@ -99,11 +103,11 @@ def align(graph, read):
         ps = preds[v]
         if not ps:
             M = sc.copy()
-            f1 = np.full(n, G, dtype=np.int64)
-            f2 = np.full(n, Q, dtype=np.int64)
+            f1 = np.full(n, G, dtype=dtype)
+            f2 = np.full(n, Q, dtype=dtype)
         else:
             hp = H[ps]
-            hs = np.concatenate([np.zeros((len(ps), 1), dtype=np.int64), hp[:, :-1]], axis=1)
+            hs = np.concatenate([np.zeros((len(ps), 1), dtype=dtype), hp[:, :-1]], axis=1)
             M = hs.max(axis=0) + sc
             f1 = np.maximum(hp + G, F1[ps] + E).max(axis=0)
             f2 = np.maximum(hp + Q, F2[ps] + C).max(axis=0)
@@ -116,6 +120,8 @@ def align(graph, read):
         m = int(h.max())
         if m > best:
             best, bv, bj = m, v, int(np.argmax(h)) + 1
+    if out is not None:
+        out.update(best=best, e1_min=int(E1.min()), e2_min=int(E2.min()))
     if best <= 0:
         return aln
 
@@ -238,11 +244,11 @@ def consensus(graph):
     return bytes(graph.base[v] for v in path), [graph.count[v] for v in path]
 
 
-def poa(reads):
+def poa(reads, dtype=np.int64):
     """reads (bytes, selection order) -> (consensus bases, per-base counts)"""
     g = Graph()
     for r in reads:
-        add_read(g, r, align(g, r))
+        add_read(g, r, align(g, r, dtype=dtype))
     return consensus(g)
 
 

@@ -1414,6 +1414,72 @@ int smi_collapse_free(smi_collapse *h);
  * (the baseline tools/microbench.py reports beside K-COLLAPSE) and the number of undef records whose founder differs from the device's (0) */
 int smi_collapse_host_loop(const smi_collapse *h, double *seconds, int64_t *mismatches);
 
+/* ---- FusionDetector (K-FUS-INSERT, K-FUS-READ, K-FUS-MOL, K-FUS-GENES, smi_fusion.hip) ---------------------------------------------------
+ * FusionDetector.doWork (FusionDetector.java:L54-113), DESIGN.md section 8i: the molecules of a tagged BAM with exactly two gene names,
+ * counted per cell.  The parameters of L63-67 are fixed: tags BC U8 GE RN, MAXCLIP 10000, LongreadParser(INPUT, false, false, true, false).
+ * smi_fusion_default_config: table_log2 0, 4 loader threads, budget_bytes 0.
+ * smi_fusion_create: the CSV cell list (CellList.java:L15-27, "-1" removed).
+ * smi_fusion_add_segment: records of an inflated BAM segment (smi_bam_index_records) through LongreadRecord.fromSAMRecord L71-184 and
+ * LongreadParser.parseSAMRecord L96-115 on host threads; of every kept record the read name, barcode, UMI (or that it has none), rn, de and
+ * the fields of GE.split(",") (Longread.addRecord L40-54) are appended to pools that live across segments.  A record the reference's parse
+ * loop dies on (an attribute of another type than it casts, a CIGAR the exon walk runs off, a mapped record without CIGAR) fails the call;
+ * smi_last_error and smi_fusion_error_read name the first such read in file order (record: its index over all segments) and the handle
+ * takes no more input.  More than 2^31 - 1 kept records or gene fields are refused by the segment that would pass it.
+ * smi_fusion_run: on the device, keyed by the strings' bytes: the reads of LongreadParser L61-79 (THashMap by name), the molecules of
+ * MoleculeDataset(LongreadParser) L60-98 with Molecule.addLongread L127-135, the distinct gene names of every molecule, the selection of
+ * FusionDetector.java L76-92 with the order of a two-element java.util.HashSet, the cell list's membership; then the row labels
+ * (L82-85), K-MTX (Matrix.addMolecule L62-105, writeIsoformMatrix L158-223 with model == null) and the molinfos text.  Cells and rows are
+ * in byte order, molinfos in (cell, UMI) byte order.  stage_ms (may be NULL): SMI_FUSION_STAGES device times: K-FUS-INSERT (the four
+ * tables), K-FUS-READ, K-FUS-MOL, K-FUS-GENES, K-MTX's sort, K-MTX's renderer.
+ * smi_fusion_output: text of SMI_FUS_OUT_*; out == NULL -> size only; cap too small -> returns 1.
+ * smi_fusion_counts: SMI_FUSION_COUNTS entries, SMI_FUS_*. */
+#define SMI_FUS_RECORDS 0         /* Total SAMrecords */
+#define SMI_FUS_VALID 1           /* SAMrecords valid */
+#define SMI_FUS_UNVALID 2         /* SAMrecords unvalid */
+#define SMI_FUS_MAPQV0 3          /* SAMrecords mapqv=0 (secondary or supplementary) */
+#define SMI_FUS_NO_GENE 4         /* SAMrecords no gene */
+#define SMI_FUS_NO_UMI 5          /* SAMrecords no UMI: 0, a UMI is not mandatory here */
+#define SMI_FUS_CHIMERIA 6        /* SAMrecords chimeria */
+#define SMI_FUS_NULL 7            /* no BC, or unmapped (part of unvalid) */
+#define SMI_FUS_READS 8           /* Total reads */
+#define SMI_FUS_READS_MULTI 9     /* Total reads multiSAM */
+#define SMI_FUS_MOLECULES 10      /* Total molecules */
+#define SMI_FUS_MOLECULE_READS 11 /* Total molecule reads */
+#define SMI_FUS_MULTI_IG 12       /* Total molecule multiIG */
+#define SMI_FUS_CELLS 13          /* Cells detected */
+#define SMI_FUS_GENE_FIELDS 14    /* gene fields of the kept records */
+#define SMI_FUS_GENES 15          /* distinct gene names */
+#define SMI_FUS_COUNTED 16        /* molecules counted: a listed cell, a UMI, two gene names */
+#define SMI_FUS_ROWS 17           /* matrix rows: distinct keys */
+#define SMI_FUS_RENDER_BLOCKS 18  /* row blocks K-MTX rendered */
+#define SMI_FUS_PROBE_STEPS 19    /* K-FUS-INSERT: slots passed over, all tables (depends on the race for the slots) */
+#define SMI_FUS_WRAPS 20          /* K-FUS-INSERT: probe chains that went past the end of a table (the same) */
+#define SMI_FUSION_COUNTS 21
+#define SMI_FUS_OUT_MATRIX 0
+#define SMI_FUS_OUT_METRICS 1
+#define SMI_FUS_OUT_MOLINFOS 2
+#define SMI_FUSION_OUTPUTS 3
+#define SMI_FUSION_STAGES 6
+typedef struct {
+    int32_t table_log2;    /* K-FUS-INSERT: every table has 2^table_log2 slots (1 .. 31; fewer slots than keys fails smi_fusion_run);
+                              0 (default): the power of two >= 2 x keys */
+    int32_t n_threads;     /* host loader threads */
+    int64_t budget_bytes;  /* K-MTX device memory per row block (0: 1 GiB) */
+} smi_fusion_config;
+typedef struct smi_fusion smi_fusion;
+int smi_fusion_default_config(smi_fusion_config *cfg);
+int smi_fusion_create(smi_ctx *ctx, const smi_fusion_config *cfg, const char *csv, size_t n_csv, smi_fusion **out);
+int smi_fusion_add_segment(smi_fusion *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n);
+int smi_fusion_run(smi_fusion *h, float *stage_ms);
+int smi_fusion_output(const smi_fusion *h, int32_t which, uint8_t *out, size_t cap, size_t *n_out);
+int smi_fusion_counts(const smi_fusion *h, int64_t *counts);
+int smi_fusion_error_read(const smi_fusion *h, char *name, size_t cap, int64_t *record);
+int smi_fusion_free(smi_fusion *h);
+/* after smi_fusion_run: the reference's loops as it runs them (LongreadParser L61-79, MoleculeDataset L69-84, FusionDetector L76-92), one
+ * host thread with ordinary hash maps over the same pools: its wall time (the baseline tools/microbench.py reports beside the device's
+ * grouping) and the number of molecules whose gene count, pair of names or selection differs from the device's (0) */
+int smi_fusion_host_loop(const smi_fusion *h, double *seconds, int64_t *mismatches);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

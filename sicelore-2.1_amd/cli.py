@@ -8,6 +8,7 @@
     java -jar [-Xmx..] Sicelore-2.1.jar ComputeConsensus -I <bam> -O <fastq> [-T n] [-CELLTAG BC] ... [-MAXREADS 20] [-MINPS 3] [-MAXPS 20]   (or I=<bam> O=<fastq> ...)
     java -jar [-Xmx..] Sicelore-2.1.jar SNPMatrix I=<bam> CSV=<barcodes> SNP=<sites.csv> O=<dir> [PREFIX=snp] [MINRN=0] [MINQV=0] [CELLTAG=BC] [UMITAG=U8] [RNTAG=RN] ...
     java -jar [-Xmx..] Sicelore-2.1.jar CollapseModel I=<isobam> CSV=<barcodes> REFFLAT=<refFlat> OUTDIR=<dir> [PREFIX=CollapseModel] [DELTA=2] [MINEVIDENCE=2] [RNMIN=1] ...   (or -I <isobam> ...)
+    java -jar [-Xmx..] Sicelore-2.1.jar FusionDetector I=<bam> CSV=<barcodes> O=<dir> [PREFIX=fusion]                                                  (or -I <bam> ...)
     java -jar [-Xmx..] Sicelore-2.1.jar DeduplicateMolecule -I <fastq|fasta> -O <fastq|fasta> [-SELECT true] [-TSO seq] [-MAXPOS 100]                  (or I=<..> O=<..> ...)
 
 become   python sicelore-2.1_amd scanfastq ... / assignumis ... / tagbamwithread ... / ComputeConsensus ...   (the directory is runnable: __main__.py; a `java` wrapper that drops
@@ -761,6 +762,36 @@ def collapsemodel(argv):
     return 0
 
 
+# FusionDetector (FusionDetector.java:L35-42): Picard's option names -> (None, kind, default).  The tags and MAXCLIP are constants of
+# the program (L63-67), not options.
+FD_OPTIONS = {
+    "I": (None, "path", None), "CSV": (None, "path", None), "O": (None, "path", None), "PREFIX": (None, "str", "fusion"),
+    "VALIDATION_STRINGENCY": (None, "stringency", "STRICT"),
+}
+FD_LONG = {"INPUT": "I", "OUTPUT": "O"}
+
+
+def fusiondetector(argv):
+    """FusionDetector.doWork (L54-113).  VALIDATION_STRINGENCY is accepted and changes nothing."""
+    o = _picard_parse(argv, "FusionDetector", FD_OPTIONS, FD_LONG)
+    need = [k for k in ("I", "CSV", "O") if k not in o]
+    if need:
+        raise CliError(f"sub-command FusionDetector: missing required option(s) {', '.join(need)}")
+    for k in ("I", "CSV"):                                                  # IOUtil.assertFileIsReadable (L56-57)
+        if not os.path.isfile(o[k]):
+            raise CliError(f"FusionDetector: {k}={o[k]}: no such file")
+    if not os.path.isdir(o["O"]):
+        raise CliError(f"FusionDetector: O={o['O']}: no such directory")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise CliError("FusionDetector runs in one process on one GPU in this build: start it without torchrun")
+    from .fusiondetector import fusion_detector
+    ctx = _context()
+    info = fusion_detector(ctx, o["I"], o["CSV"], o["O"], prefix=o.get("PREFIX", "fusion"), n_threads=_ncpu({}), log=sys.stderr)
+    print(f"DONE -- {info['valid']} of {info['records']} records, {info['molecules']} molecules, {info['counted']} of them support "
+          f"{info['rows']} fusions", file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
@@ -792,7 +823,9 @@ def main(argv=None):
             return addgenenametag(rest)
         if sub == "CollapseModel":
             return collapsemodel(rest)
-        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus, DeduplicateMolecule, AddBamMoleculeTags, AddGeneNameTag, IsoformMatrix, SNPMatrix and CollapseModel (mergestats, parseillumina: "
+        if sub == "FusionDetector":
+            return fusiondetector(rest)
+        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus, DeduplicateMolecule, AddBamMoleculeTags, AddGeneNameTag, IsoformMatrix, SNPMatrix, CollapseModel and FusionDetector (mergestats, parseillumina: "
                        "SURVEY 2, out of scope)")
     except CliError as e:
         print(f"ERROR: {e}", file=sys.stderr)

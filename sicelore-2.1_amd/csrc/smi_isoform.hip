@@ -218,6 +218,7 @@ __global__ __launch_bounds__(64 * kIsoWaves) void k_iso(IsoArgs a) {
 // ---- host parsing -----------------------------------------------------------------------------------------------------------------------
 using lr::Aux;
 using lr::drop_minus1;
+using lr::java_float;
 using lr::jint;
 using lr::jsplit;
 using lr::walk_junctions;
@@ -323,41 +324,6 @@ void parse_record(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg,
         return;
     }
     out.what = kKept;
-}
-
-// Float.toString: the shortest decimal that reads back as the float; d.ddd in [1e-3, 1e7), else d.dddE<exp>
-std::string java_float(float x) {
-    if (std::isnan(x)) return "NaN";
-    if (std::isinf(x)) return x > 0 ? "Infinity" : "-Infinity";
-    if (x == 0) return std::signbit(x) ? "-0.0" : "0.0";
-    char buf[64];
-    auto r = std::to_chars(buf, buf + sizeof(buf), x, std::chars_format::scientific);
-    std::string sci(buf, r.ptr);
-    std::string sign;
-    if (sci[0] == '-') {
-        sign = "-";
-        sci.erase(0, 1);
-    }
-    const size_t ep = sci.find('e');
-    const int exp = std::stoi(sci.substr(ep + 1));
-    std::string dig;
-    for (size_t i = 0; i < ep; i++)
-        if (sci[i] != '.') dig += sci[i];
-    const float ax = std::fabs(x);
-    std::string out;
-    if (ax >= 1e-3f && ax < 1e7f) {
-        if (exp >= 0) {
-            std::string ip = dig.substr(0, std::min<size_t>(dig.size(), exp + 1));
-            while ((int)ip.size() < exp + 1) ip += '0';
-            std::string fp = (int)dig.size() > exp + 1 ? dig.substr(exp + 1) : "0";
-            out = ip + "." + fp;
-        } else {
-            out = "0." + std::string(-exp - 1, '0') + dig;
-        }
-    } else {
-        out = dig.substr(0, 1) + "." + (dig.size() > 1 ? dig.substr(1) : "0") + "E" + std::to_string(exp);
-    }
-    return sign + out;
 }
 
 struct Model {

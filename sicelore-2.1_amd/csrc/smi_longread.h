@@ -1,8 +1,11 @@
 // smi_longread.h -- the attribute helpers of the LongreadRecord.fromSAMRecord parsers (ComputeConsensus in smi_consensus.hip,
-// IsoformMatrix in smi_isoform.hip, SNPMatrix in smi_snp.hip), its CIGAR walk and the Java text rules they share: host only.
+// IsoformMatrix in smi_isoform.hip, SNPMatrix in smi_snp.hip), its CIGAR walk and the Java text rules they share
+// (FusionDetector in smi_fusion.hip reads them too): host only.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <charconv>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -127,6 +130,41 @@ inline bool jint(std::string_view s, int32_t &v) {
     if (x > 2147483647ll || x < -2147483648ll) return false;
     v = (int32_t)x;
     return true;
+}
+
+// Float.toString: the shortest decimal that reads back as the float; d.ddd in [1e-3, 1e7), else d.dddE<exp>
+inline std::string java_float(float x) {
+    if (std::isnan(x)) return "NaN";
+    if (std::isinf(x)) return x > 0 ? "Infinity" : "-Infinity";
+    if (x == 0) return std::signbit(x) ? "-0.0" : "0.0";
+    char buf[64];
+    auto r = std::to_chars(buf, buf + sizeof(buf), x, std::chars_format::scientific);
+    std::string sci(buf, r.ptr);
+    std::string sign;
+    if (sci[0] == '-') {
+        sign = "-";
+        sci.erase(0, 1);
+    }
+    const size_t ep = sci.find('e');
+    const int exp = std::stoi(sci.substr(ep + 1));
+    std::string dig;
+    for (size_t i = 0; i < ep; i++)
+        if (sci[i] != '.') dig += sci[i];
+    const float ax = std::fabs(x);
+    std::string out;
+    if (ax >= 1e-3f && ax < 1e7f) {
+        if (exp >= 0) {
+            std::string ip = dig.substr(0, std::min<size_t>(dig.size(), exp + 1));
+            while ((int)ip.size() < exp + 1) ip += '0';
+            std::string fp = (int)dig.size() > exp + 1 ? dig.substr(exp + 1) : "0";
+            out = ip + "." + fp;
+        } else {
+            out = "0." + std::string(-exp - 1, '0') + dig;
+        }
+    } else {
+        out = dig.substr(0, 1) + "." + (dig.size() > 1 ? dig.substr(1) : "0") + "E" + std::to_string(exp);
+    }
+    return sign + out;
 }
 
 // LongreadRecord.fromSAMRecord L120-150, literally: the walk over cigar.replaceAll("[0-9]+[IS]", "") split into cigartype ("[0-9]+") and

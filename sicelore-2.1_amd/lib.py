@@ -78,6 +78,8 @@ EXPORTS = [
     "smi_moltag_free",
     "smi_collapse_default_config", "smi_collapse_create", "smi_collapse_set_references", "smi_collapse_add_segment", "smi_collapse_run",
     "smi_collapse_output", "smi_collapse_counts", "smi_collapse_error_read", "smi_collapse_free", "smi_collapse_host_loop",
+    "smi_fusion_default_config", "smi_fusion_create", "smi_fusion_add_segment", "smi_fusion_run", "smi_fusion_output", "smi_fusion_counts",
+    "smi_fusion_error_read", "smi_fusion_free", "smi_fusion_host_loop",
 ]
 
 
@@ -298,6 +300,15 @@ def load_library():
     lib.smi_collapse_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
     lib.smi_collapse_free.argtypes = [vp]
     lib.smi_collapse_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_fusion_default_config.argtypes = [vp]
+    lib.smi_fusion_create.argtypes = [vp, vp, vp, sz, ctypes.POINTER(vp)]
+    lib.smi_fusion_add_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32]
+    lib.smi_fusion_run.argtypes = [vp, vp]
+    lib.smi_fusion_output.argtypes = [vp, ctypes.c_int32, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_fusion_counts.argtypes = [vp, vp]
+    lib.smi_fusion_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_fusion_free.argtypes = [vp]
+    lib.smi_fusion_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     lib.smi_poa_batch_ex.argtypes = lib.smi_poa_batch.argtypes + [vp]
@@ -1000,6 +1011,92 @@ class Collapse:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.smi_collapse_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class FusionConfig(ctypes.Structure):
+    """smi_fusion_config"""
+    _fields_ = [("table_log2", ctypes.c_int32), ("n_threads", ctypes.c_int32), ("budget_bytes", ctypes.c_int64)]
+
+
+# smi_fusion_counts, in SMI_FUS_* order
+FUSION_COUNTS = ("records", "valid", "unvalid", "mapqv0", "no_gene", "no_umi", "chimeria", "null", "reads", "reads_multi", "molecules",
+                 "molecule_reads", "multi_ig", "cells", "gene_fields", "genes", "counted", "rows", "render_blocks", "probe_steps", "wraps")
+# smi_fusion_output, in SMI_FUS_OUT_* order: the file name suffixes (PREFIX<suffix>, FusionDetector.java:L107-109)
+FUSION_OUTPUTS = ("_fusmatrix.txt", "_fusmetrics.txt", "_fusmolinfos.txt")
+FUSION_STAGES = ("insert", "read", "mol", "genes", "mtx_sort", "mtx_render")
+
+
+class Fusion:
+    """FusionDetector (smi_fusion_*): the cell-list text, then BAM segments in; the three output texts out.  Keywords: the fields of
+    smi_fusion_config.  A record the parser fails on raises SmiError; error_read then holds (read name, record index)."""
+
+    def __init__(self, ctx, csv, **kw):
+        self._lib = load_library()
+        cfg = FusionConfig()
+        self._lib.smi_fusion_default_config(ctypes.byref(cfg))
+        for k, v in kw.items():
+            if k not in ("table_log2", "n_threads", "budget_bytes"):
+                raise ValueError(f"unknown smi_fusion_config field {k!r}")
+            setattr(cfg, k, int(v))
+        cs = np.frombuffer(bytes(csv), dtype=np.uint8)
+        self._h = ctypes.c_void_p()
+        if self._lib.smi_fusion_create(ctx._h, ctypes.byref(cfg), _ptr(cs) if cs.size else None, cs.size, ctypes.byref(self._h)):
+            self._h = None
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._ctx = ctx
+        self.error_read = None
+        self.stage_ms = dict.fromkeys(FUSION_STAGES, 0.0)
+
+    def add_segment(self, bam, recs):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
+        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
+            raise ValueError("bam: a contiguous 1-D uint8 array")
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != BAM_RECORD_DTYPE:
+            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
+        if self._lib.smi_fusion_add_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)):
+            msg = self._lib.smi_last_error().decode(errors="replace")
+            name = ctypes.create_string_buffer(256)
+            rec = ctypes.c_int64(-1)
+            self._lib.smi_fusion_error_read(self._h, name, 256, ctypes.byref(rec))
+            if rec.value >= 0:
+                self.error_read = (name.value.decode(errors="replace"), rec.value)
+            raise SmiError(msg)
+
+    def run(self):
+        """K-FUS-INSERT, K-FUS-READ, K-FUS-MOL, K-FUS-GENES, K-MTX -> {file name suffix: bytes}"""
+        ms = np.zeros(len(FUSION_STAGES), dtype=np.float32)
+        if self._lib.smi_fusion_run(self._h, _ptr(ms)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self.stage_ms = dict(zip(FUSION_STAGES, (float(x) for x in ms)))
+        outs = {}
+        for i, name in enumerate(FUSION_OUTPUTS):
+            n = ctypes.c_size_t(0)
+            self._lib.smi_fusion_output(self._h, i, None, 0, ctypes.byref(n))
+            out = np.zeros(max(n.value, 1), dtype=np.uint8)
+            if self._lib.smi_fusion_output(self._h, i, _ptr(out), out.size, ctypes.byref(n)):
+                raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+            outs[name] = out[:n.value].tobytes()
+        return outs
+
+    def counts(self):
+        c = np.zeros(len(FUSION_COUNTS), dtype=np.int64)
+        self._lib.smi_fusion_counts(self._h, _ptr(c))
+        return dict(zip(FUSION_COUNTS, (int(x) for x in c)))
+
+    def host_loop(self):
+        """after run(): the reference's single-thread loops over the same pools -> (seconds, molecules that differ from the device's)"""
+        sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
+        if self._lib.smi_fusion_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        return sec.value, bad.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.smi_fusion_free(self._h)
             self._h = None
 
     __del__ = close

@@ -36,9 +36,9 @@ def main():
     used = synth.pick_used(wl, 5000, seed=2)
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
-            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse}
+            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse, "fusion": leg_fusion}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -749,6 +749,77 @@ def leg_collapse(pkg, synth, ctx, dev, wl, used, res):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     res["collapse"] = out
+
+
+def _fusion_fixture(n_recs, n_cells, n_genes, seed=61):
+    """a seeded tagged BAM of n_recs records as the plumbing of step 6 leaves it: molecules of 1..3 reads of 1..2 records (the second one
+    supplementary, now and then without UMI), barcodes with 10x's "-1", GE of one gene or, for about a tenth of the molecules, of a second
+    gene on some records (a handful of recurrent pairs among them), RN on a third of the records, de on all -> (cell list, BGZF bytes,
+    records, molecules)"""
+    import struct
+
+    from sicelore_amd import lib
+
+    rng = np.random.default_rng(seed)
+    recurrent = [(b"BCR", b"ABL1"), (b"EML4", b"ALK"), (b"TMPRSS2", b"ERG"), (b"KIF5B", b"RET")]
+    recs, k, m = [], 0, 0
+    cig = struct.pack("<3I", 40 << 4 | 4, 900 << 4 | 0, 60 << 4 | 4)
+    while k < n_recs:
+        cell, umi = b"CELL%05d-1" % int(rng.integers(n_cells)), b"U%09d" % m
+        g0 = b"GENE%d" % int(rng.integers(n_genes))
+        p = rng.random()
+        g1 = None if p < 0.9 else b"GENE%d" % int(rng.integers(n_genes))
+        if p > 0.98:
+            g0, g1 = recurrent[int(rng.integers(len(recurrent)))]
+        for _r in range(int(rng.integers(1, 4))):
+            name = b"r%09d\0" % k
+            for j in range(int(rng.integers(1, 3))):
+                ge = g0 if g1 is None or (j == 0 and rng.random() < 0.5) else g1 if rng.random() < 0.5 else g0 + b"," + g1
+                aux = b"BCZ" + cell + b"\0" + (b"" if j and rng.random() < 0.3 else b"U8Z" + umi + b"\0") + b"GEZ" + ge + b"\0"
+                if rng.random() < 0.33:
+                    aux += b"RNC" + bytes([int(rng.integers(1, 9))])
+                aux += b"def" + struct.pack("<f", float(rng.integers(0, 50)) / 500)
+                body = struct.pack("<iiBBHHHiiii", 0, int(rng.integers(10_000, 100_000_000)), len(name), 60, 4680, 3, 0x800 if j else 0, 0, -1, -1, 0) + name + cig + aux
+                recs.append(struct.pack("<I", len(body)) + body)
+                k += 1
+        m += 1
+    head = b"BAM\1" + struct.pack("<I", 0) + struct.pack("<I", 1) + struct.pack("<I", 5) + b"chr1\0" + struct.pack("<I", 2 ** 31 - 1)
+    bam = np.frombuffer(head + b"".join(recs), dtype=np.uint8)
+    csv = "".join(f"CELL{c:05d}-1\n" for c in range(n_cells))
+    return csv, lib.bgzf_deflate(bam, level=1, n_threads=16), k, m
+
+
+def leg_fusion(pkg, synth, ctx, dev, wl, used, res):
+    """K-FUS-INSERT / K-FUS-READ / K-FUS-MOL / K-FUS-GENES + K-MTX (`FusionDetector`): a seeded tagged BAM of SMI_MB_FUS_RECS records
+    (500,000: the clipped reads are a small share of a run), 5,000 cells, SMI_MB_FUS_GENES gene names (20,000), file to file: device ms per
+    stage (HIP events), seconds in parse, in the device calls and in file writes, wall seconds, and beside the device's grouping the wall
+    time of the reference's single-thread loops over the same pools (smi_fusion_host_loop), with the molecules on which the two differ (0)."""
+    import shutil
+    import tempfile
+
+    fus = importlib.import_module(graft.PKG_NAME + ".fusiondetector")
+    lib = importlib.import_module(graft.PKG_NAME + ".lib")
+    n_recs = int(os.environ.get("SMI_MB_FUS_RECS", "500000"))
+    n_genes = int(os.environ.get("SMI_MB_FUS_GENES", "20000"))
+    t0 = time.perf_counter()
+    csv, z, n_rec, n_mol = _fusion_fixture(n_recs, 5000, n_genes)
+    out = {"records": n_rec, "molecules_generated": n_mol, "cells": 5000, "gene_names": n_genes, "fixture_s": time.perf_counter() - t0}
+    d = tempfile.mkdtemp(prefix="fusion_")
+    try:
+        z.tofile(os.path.join(d, "in.bam"))
+        with open(os.path.join(d, "c.csv"), "w") as f:
+            f.write(csv)
+        fus.fusion_detector(ctx, os.path.join(d, "in.bam"), os.path.join(d, "c.csv"), d, n_threads=16)          # the first run loads the code objects
+        info = fus.fusion_detector(ctx, os.path.join(d, "in.bam"), os.path.join(d, "c.csv"), d, n_threads=16, host_loop=True)
+        out["file_to_file"] = dict({k: info[k] for k in lib.FUSION_COUNTS}, stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"],
+                                   bytes_written=info["bytes_written"], records_per_s=info["records"] / info["wall_s"])
+        out["device_grouping_s"] = sum(info["stage_ms"][k] for k in ("insert", "read", "mol", "genes")) / 1e3
+        out["host_loop_wall_s"] = info["host_loop_s"]
+        out["host_loop_mismatches"] = info["host_loop_mismatches"]
+        out["top_fusions"] = sorted(info["fusions"], key=lambda kv: -kv[1])[:4]
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    res["fusion"] = out
 
 
 def _snp_fixture(n_recs, n_lines, n_cells, seed=51):

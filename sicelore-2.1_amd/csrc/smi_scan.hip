@@ -421,16 +421,63 @@ struct Entry {
     uint32_t b;  // consec | best_two << 8 | pos << 16
 };
 
-// wave-wide exclusive prefix sum of one int per lane; returns the wave total through `total`
+// Two variant switches for counter runs and cross-checks (make VARIANT=... EXTRA=-D...=1), never set in the shipped library:
+//   SMI_SCAN_SHFL_SCAN     the wave prefix sum through six __shfl_up steps (ds_bpermute) instead of DPP
+//   SMI_SCAN_QUEUE_SEARCH  every candidate lane searches its owner (binary search over the offsets, a walk over the masks) instead of
+//                          the owners pushing (lane, position) into the candidates' slots
+#ifndef SMI_SCAN_SHFL_SCAN
+#define SMI_SCAN_SHFL_SCAN 0
+#endif
+#ifndef SMI_SCAN_QUEUE_SEARCH
+#define SMI_SCAN_QUEUE_SEARCH 0
+#endif
+
+// wave-wide exclusive prefix sum of one int per lane; returns the wave total (wave-uniform) through `total`.  Called with all 64 lanes active.
 __device__ __forceinline__ int wave_exscan(int v, int lane, int &total) {
     int inc = v;
+#if SMI_SCAN_SHFL_SCAN
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const int y = __shfl_up(inc, o);
         if (lane >= o) inc += y;
     }
-    total = __shfl(inc, 63);
+    total = __builtin_amdgcn_readfirstlane(__shfl(inc, 63));
+#else
+    // DPP: a Hillis-Steele sum inside each row of 16 lanes (row_shr:1/2/4/8, lanes without a source add 0), then lane 15 of a row into the
+    // row behind it (row_bcast:15 on rows 1 and 3) and lane 31 into rows 2 and 3 (row_bcast:31): eight VALU operations, no LDS crossbar
+    (void)lane;
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);   // row_shr:1
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);   // row_shr:2
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);   // row_shr:4
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, true);   // row_shr:8
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);  // row_bcast:15 row_mask:0xa
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);  // row_bcast:31 row_mask:0xc
+    total = __builtin_amdgcn_readlane(inc, 63);
+#endif
     return inc - v;
+}
+
+// Owner push of the candidate queue.  The candidates of a wave are numbered off + k for the k-th set bit of the owner's masks (chunk order, then
+// bit order), and round `base` aligns the numbers [base, base + 64) on lanes 0 .. 63.  An owner whose numbers [off, off + n) meet the round walks
+// its set bits and writes `lane | value << 8` into the slot of each of those candidates (slots = the wave's 64 words of `coff`); the candidate
+// lane reads one word.  `mask_of(ch)` hands over the owner's mask of chunk ch, `value(ch, bit)` what the candidate needs (<= 255: the shift by 8
+// leaves the lane bits alone).  -> nothing; the caller puts wave_sync() between this and the candidates' read.
+template <int CH, typename M, typename V>
+__device__ __forceinline__ void queue_push(uint32_t *slots, int lane, int off, int n, int base, M mask_of, V value) {
+    const int f0 = max(off, base), f1 = min(off + n, base + 64);
+    if (f0 < f1) {
+        int idx = off;
+#pragma unroll
+        for (int ch = 0; ch < CH; ch++) {
+            uint64_t m = mask_of(ch);
+            while (m != 0ull && idx < f1) {
+                const int bit = __builtin_ctzll(m);
+                m &= m - 1;
+                if (idx >= f0) slots[idx - base] = (uint32_t)lane | ((uint32_t)value(ch, bit) << 8);
+                idx++;
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -570,7 +617,7 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                 }
                 int n_ts = __popcll(tm[0]) + __popcll(tm[1]), off_ts = 0;
                 bool numbered = false;  // wave-uniform
-                if (SHIP && !SMI_ABLATED(16)) {
+                if (SHIP && !FP && !SMI_ABLATED(16)) {  // (the 5' analyzer has no TSO candidates: a DPP sum of zeros is not folded away as the shuffles were)
                     // Exact pre-filter of the ISOLATED TSO candidates.  A candidate's alignment matters in two ways only: it may be
                     // accepted (Math.round(ne) <= 5, AdapterTSOanalyzer L96-104), or its error count makes the scan jump over the next
                     // candidates (delta = round(ne - 5) - 1 <= 26: an alignment of two 16-mers has at most 32 columns).  A candidate
@@ -607,22 +654,39 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                     // low half never carries into the high one), isolated ones in the high half.
                     static_assert(64 * 90 < (1 << 16), "the gated counts of a wave must fit the low half of the packed prefix sum");
                     int tot2;
-                    const int off2 = wave_exscan(n_ts | ((__popcll(iso0) + __popcll(iso1)) << 16), lane, tot2);
-                    tot2 = __builtin_amdgcn_readfirstlane(tot2);
+                    const int n_iso = __popcll(iso0) + __popcll(iso1);
+                    const int off2 = wave_exscan(n_ts | (n_iso << 16), lane, tot2);
                     const int tot_iso = tot2 >> 16;
                     total = tot2 & 0xFFFF;
                     off_ts = off2 & 0xFFFF;
                     numbered = true;
                     if (tot_iso && ((total + 63) >> 6) > ((total - tot_iso + 63) >> 6)) {  // wave-uniform
                         numbered = false;
+#if SMI_SCAN_QUEUE_SEARCH
                         cmask[0 * kBlock + tid] = iso0;
                         cmask[1 * kBlock + tid] = iso1;
                         coff[tid] = (uint32_t)(off2 >> 16);
+#endif
                         uint32_t *drop = ent + tid * 5;  // three words of dropped positions per end
                         drop[0] = drop[1] = drop[2] = 0u;
                         wave_sync();
                         for (int base = 0; base < tot_iso; base += 64) {
                             const int en = base + lane;
+#if !SMI_SCAN_QUEUE_SEARCH
+                            // the isolated masks are in registers: the owners push (lane, bit) straight from them
+                            queue_push<2>(coff + wbase, lane, off2 >> 16, n_iso, base, [&](int ch) { return ch ? iso1 : iso0; },
+                                          [](int ch, int bit) { return ch * 64 + bit; });
+                            wave_sync();
+                            if (en < tot_iso) {
+                                const uint32_t slot = coff[tid];
+                                const int owner = wbase + (int)(slot & 63u);
+                                const int bit = (int)(slot >> 8);  // scan position - 1
+                                uint32_t V[4];
+#pragma unroll
+                                for (int c = 0; c < 4; c++) V[c] = __brev(get32(planes + c * kLdsWords * kBlock, owner, bit)) >> 16;
+                                if (myers_bound_tso16(V, 5) > 5) atomicOr(&ent[owner * 5 + (bit >> 5)], 1u << (bit & 31));
+                            }
+#else
                             if (en < tot_iso) {
                                 int lo = 0, hi = 64;
                                 while (hi - lo > 1) {
@@ -642,6 +706,7 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                                 for (int c = 0; c < 4; c++) V[c] = __brev(get32(planes + c * kLdsWords * kBlock, owner, bit)) >> 16;
                                 if (myers_bound_tso16(V, 5) > 5) atomicOr(&ent[owner * 5 + (bit >> 5)], 1u << (bit & 31));
                             }
+#endif
                         }
                         wave_sync();
                         tm[0] &= ~((uint64_t)drop[0] | ((uint64_t)drop[1] << 32));
@@ -650,19 +715,37 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                         n_ts = __popcll(tm[0]) + __popcll(tm[1]);
                     }
                 }
-                if (!numbered) off_ts = wave_exscan(n_ts, lane, total);
+                if (FP)
+                    total = 0;  // no TSO scan, no candidates: nothing to number
+                else if (!numbered)
+                    off_ts = wave_exscan(n_ts, lane, total);
                 no = (uint32_t)n_ts | ((uint32_t)off_ts << 8);
                 cmask[0 * kBlock + tid] = tm[0];
                 cmask[1 * kBlock + tid] = tm[1];
                 cmask[2 * kBlock + tid] = 0ull;
             }
+            const int my_off = (int)(no >> 8), my_n = (int)(no & 0xFFu);
+#if SMI_SCAN_QUEUE_SEARCH
             coff[tid] = no >> 8;
             wave_sync();
             const uint32_t *offs = coff;
-            const int my_off = (int)(no >> 8), my_n = (int)(no & 0xFFu);
+#endif
             for (int base = 0; base < total; base += 64) {
                 const int en = base + lane;
+#if !SMI_SCAN_QUEUE_SEARCH
+                // the owners of this round's candidates push (lane, scan position) into the candidates' slots, from their own column of the
+                // masks (a lane reads back what it wrote itself; nothing of the masks stays in registers across the alignments).  The previous
+                // round's slots were read before the wave_sync() behind its alignments.
+                queue_push<3>(coff + wbase, lane, my_off, my_n, base, [&](int ch) { return cmask[ch * kBlock + tid]; },
+                              [](int ch, int bit) { return ch * 64 + bit + 1; });
+                wave_sync();
+#endif
                 if (en < total) {
+#if !SMI_SCAN_QUEUE_SEARCH
+                    const uint32_t slot = coff[tid];
+                    const int owner = wbase + (int)(slot & 63u);
+                    const int pos = (int)(slot >> 8);
+#else
                     // owner: last lane of this wave with offs[lane] <= en
                     int lo = 0, hi = 64;
                     while (hi - lo > 1) {
@@ -684,6 +767,7 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                         }
                         k -= c;
                     }
+#endif
                     AlnStats st;
                     st.ne = 9.0f, st.end5 = st.endn = 0.0f, st.nmis = 9, st.ins = st.del = st.consec = st.best_two = 0, st.term6 = false;
                     // the column masks of the alignment are the four base planes of the read slice, selected per pattern

@@ -503,7 +503,7 @@ extern "C" int smi_collapse_create(smi_ctx *ctx, const smi_collapse_config *cfg,
     const char *tags[] = {cfg->cell_tag, cfg->umi_tag, cfg->gene_tag, cfg->iso_tag, cfg->rn_tag};
     const char *what[] = {"CELLTAG", "UMITAG", "GENETAG", "ISOFORMTAG", "RNTAG"};
     for (int i = 0; i < 5; i++)
-        if (!lr::valid_tag(tags[i])) {
+        if (!valid_tag(tags[i])) {
             set_error(std::string(what[i]) + " must be two characters");
             return SMI_ERR_INVALID;
         }

@@ -738,7 +738,6 @@ using lr::Aux;
 using lr::aux_size;
 using lr::float_less;
 using lr::tag16;
-using lr::valid_tag;
 
 struct TagSet {
     uint16_t cell, umi, gene, te, ps, cs, us, rn, de, df;

@@ -13,6 +13,9 @@ namespace smi {
 void set_error(const std::string &msg);
 int hip_fail(hipError_t e, const char *what);
 
+// a SAM tag as the programs take it from their command lines: two printable characters
+inline int valid_tag(const char *t) { return t[0] > ' ' && t[0] <= '~' && t[1] > ' ' && t[1] <= '~' && t[2] == 0; }
+
 // smi_tagbam.hip: K-TAG-ASM over n records already on the device, each record i rewritten with two Z attributes tag_a / tag_b whose payloads
 // are d_text[d_a_start[k] ..+ d_a_len[k]) and d_text[d_b_start[k] ..+ d_b_len[k]) for k = d_entry[i] (k < 0: the record is dropped), under
 // htsjdk's attribute rules -> the records back to back in out (host).  ms (may be NULL): device time added.  Synchronous on s.

@@ -82,7 +82,6 @@ inline bool float_less(float a, float b) {  // Float.compare(a, b) < 0
 }
 
 inline uint16_t tag16(const char *t) { return (uint16_t)((uint8_t)t[0] | (uint8_t)t[1] << 8); }
-inline int valid_tag(const char *t) { return t[0] > ' ' && t[0] <= '~' && t[1] > ' ' && t[1] <= '~' && t[2] == 0; }
 
 // LongreadRecord L108-112: the first or the last CIGAR operation is S or H and longer than MAXCLIP
 inline bool chimeric(uint32_t first, uint32_t last, int32_t max_clip) {

@@ -11,24 +11,22 @@
 //           ordinals INTERGENIC < INTRONIC < UTR < CODING are also the score order -- so maxima of interval tests give the same value.
 //           Records that keep two or more genes are flagged: the ORDER of the names in their value is the reference's HashSet iteration
 //           order, which the host's smi_gene_tag_chunk models (gene_tag_chunk_opt is called on exactly those records).
-//   K-EDIT  one wavefront per record, SIZE launch + exclusive scan + WRITE launch like K-TAG-ASM (smi_tagbam.hip), with an edit list per
-//           record: set Z from a device byte pool / set integer in htsjdk's smallest type / remove, applied in order on the attribute list
-//           K-TAG writes (ordered by binary tag, a repeated tag keeping its last value, integers re-typed, H as B:c: pinned by
-//           tests/golden/ref_exec_auxorder.json).  The attribute walk and copy loops restate K-TAG-ASM's: that kernel is left untouched.
-#include <hipcub/hipcub.hpp>
-
+//   K-EDIT  one wavefront per record: k_aux_rewrite<WRITE, EditSource> of smi_auxedit.h, the attribute rewrite shared with K-TAG-ASM
+//           (smi_tagbam.hip), as SIZE + exclusive scan + WRITE through an AuxRewriter.  EditSource keeps every record and applies an edit
+//           list per record behind its own attributes: set Z from a device byte pool / set integer in htsjdk's smallest type / remove,
+//           in order.
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "smi_auxedit.h"
 #include "smi_internal.h"
 
 namespace smi {
 namespace {
 
-constexpr int kMaxFields = SMI_TAGBAM_MAX_ATTRS;
-constexpr int kEditWaves = 4;  // waves per block of K-EDIT and K-GENE
+constexpr int kGeneWaves = 4;  // waves per block of K-GENE
 constexpr int kEdits = 3;      // edits per record
 constexpr unsigned long long kNoRecord = ~0ull;
 
@@ -51,237 +49,40 @@ struct GeneRes {
     uint16_t pad;
 };
 
-// ---- the attribute list (restated from smi_tagbam.hip) -----------------------------------------------------------------------------------
-struct Field {
-    uint16_t key;  // binary tag: second char << 8 | first char
-    uint8_t kind;  // 0 verbatim (src: type byte .. end), 1 integer (ival), 2 H -> B:c (src: the hex digits), 3 Z from the byte pool
-    uint8_t type;  // output type of an integer
-    uint32_t len;  // kind 0: bytes behind the tag; 2: hex digits; 3: payload bytes
-    uint64_t src;  // kind 0 / 2: offset in the BAM stream; 3: offset in the pool
-    int64_t ival;
-    uint64_t out;  // offset of the field in the output record (WRITE)
+// what K-EDIT applies behind a record's own attributes: its edits in order (SAMRecord.setAttribute in call order: a later edit of a tag wins)
+struct EditSource {
+    const Edit *edits;    // kEdits per record
+    const uint8_t *pool;  // the SET_Z payloads
+    struct Tail {
+        const Edit *ed;
+        __device__ uint32_t put(Field *f, int &n) const {
+            for (int k = 0; k < kEdits; k++) {
+                const Edit e = ed[k];
+                if (e.kind == EDIT_NONE) continue;
+                if (e.kind == EDIT_REMOVE) {
+                    remove_field(f, n, e.key);
+                    continue;
+                }
+                Field s = {};
+                s.key = e.key;
+                if (e.kind == EDIT_SET_Z) {
+                    s.kind = 3;
+                    s.len = e.len;
+                    s.src = e.src;
+                } else {
+                    s.kind = 1;
+                    s.ival = e.val;
+                    s.type = int_type(e.val);
+                }
+                if (!put_field(f, n, s)) return SMI_TAG_TOO_MANY_ATTRS;
+            }
+            return 0;
+        }
+    };
+    __device__ bool keeps(size_t) const { return true; }
+    __device__ Tail tail(size_t i) const { return {edits + (size_t)kEdits * i}; }
+    __device__ const uint8_t *payload() const { return pool; }
 };
-
-__device__ __forceinline__ uint32_t field_bytes(const Field &f) {
-    switch (f.kind) {
-        case 1: return 3u + (f.type == 'c' || f.type == 'C' ? 1u : f.type == 's' || f.type == 'S' ? 2u : 4u);
-        case 2: return 8u + f.len / 2;
-        case 3: return 4u + f.len;
-        default: return 2u + f.len;
-    }
-}
-__device__ __forceinline__ uint8_t int_type(int64_t v) {  // BinaryTagCodec.getIntegerType
-    if (v >= -128 && v <= 127) return 'c';
-    if (v >= 0 && v <= 255) return 'C';
-    if (v >= -32768 && v <= 32767) return 's';
-    if (v >= 0 && v <= 65535) return 'S';
-    if (v >= -2147483648ll && v <= 2147483647ll) return 'i';
-    return 'I';
-}
-__device__ __forceinline__ int hex_val(uint8_t c) {
-    if (c >= '0' && c <= '9') return c - '0';
-    c |= 0x20;
-    if (c >= 'a' && c <= 'f') return c - 'a' + 10;
-    return -1;
-}
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
-
-__device__ bool put_field(Field *f, int &n, const Field &x) {  // insert or replace; false: more than kMaxFields attributes
-    for (int j = 0; j < n; j++)
-        if (f[j].key == x.key) {
-            f[j] = x;
-            return true;
-        }
-    if (n >= kMaxFields) return false;
-    f[n++] = x;
-    return true;
-}
-
-// lane 0: the attribute list of record rec after the edits ed[0 .. kEdits), in f[0 .. n), sorted by binary tag; SMI_TAG_* error bits
-__device__ uint32_t parse_fields(const uint8_t *__restrict__ bam, const smi_bam_record &rec, const Edit *__restrict__ ed, Field *f, int &n) {
-    n = 0;
-    const uint64_t end = rec.aux_off + rec.aux_len;
-    uint64_t p = rec.aux_off;
-    while (p < end) {
-        if (p + 3 > end) return SMI_TAG_BAD_AUX;
-        Field x = {};
-        x.key = (uint16_t)(bam[p + 1] << 8 | bam[p]);
-        const uint8_t ty = bam[p + 2];
-        const uint64_t v = p + 3;
-        uint64_t q;
-        switch (ty) {
-            case 'A': q = v + 1; break;
-            case 'f': q = v + 4; break;
-            case 'c': case 'C': case 's': case 'S': case 'i': case 'I': {
-                const uint32_t w = ty == 'c' || ty == 'C' ? 1 : ty == 's' || ty == 'S' ? 2 : 4;
-                q = v + w;
-                if (q > end) return SMI_TAG_BAD_AUX;
-                const uint32_t raw = w == 1 ? bam[v] : w == 2 ? (uint32_t)(bam[v] | bam[v + 1] << 8) : ld_u32(bam + v);
-                x.kind = 1;
-                x.ival = ty == 'c' ? (int64_t)(int8_t)raw : ty == 's' ? (int64_t)(int16_t)raw : ty == 'i' ? (int64_t)(int32_t)raw : (int64_t)raw;
-                x.type = int_type(x.ival);
-                break;
-            }
-            case 'Z': case 'H': {
-                q = v;
-                while (q < end && bam[q]) q++;
-                if (q >= end) return SMI_TAG_BAD_AUX;
-                if (ty == 'H') {
-                    const uint32_t digits = (uint32_t)(q - v);
-                    if (digits & 1u) return SMI_TAG_BAD_HEX;
-                    for (uint64_t k = v; k < q; k++)
-                        if (hex_val(bam[k]) < 0) return SMI_TAG_BAD_HEX;
-                    x.kind = 2;
-                    x.src = v;
-                    x.len = digits;
-                }
-                q++;
-                break;
-            }
-            case 'B': {
-                if (v + 5 > end) return SMI_TAG_BAD_AUX;
-                const uint8_t sub = bam[v];
-                const uint32_t w = sub == 'c' || sub == 'C' ? 1 : sub == 's' || sub == 'S' ? 2 : sub == 'i' || sub == 'I' || sub == 'f' ? 4 : 0;
-                if (!w) return SMI_TAG_BAD_AUX;
-                q = v + 5 + (uint64_t)w * ld_u32(bam + v + 1);
-                break;
-            }
-            default: return SMI_TAG_BAD_AUX;
-        }
-        if (q > end) return SMI_TAG_BAD_AUX;
-        if (x.kind == 0) {
-            x.src = p + 2;
-            x.len = (uint32_t)(q - p - 2);
-        }
-        if (!put_field(f, n, x)) return SMI_TAG_TOO_MANY_ATTRS;
-        p = q;
-    }
-    for (int k = 0; k < kEdits; k++) {  // SAMRecord.setAttribute in call order: a later edit of a tag wins
-        const Edit e = ed[k];
-        if (e.kind == EDIT_NONE) continue;
-        if (e.kind == EDIT_REMOVE) {  // setAttribute(tag, null): an absent tag is a no-op
-            for (int j = 0; j < n; j++)
-                if (f[j].key == e.key) {
-                    for (int m = j + 1; m < n; m++) f[m - 1] = f[m];
-                    n--;
-                    break;
-                }
-            continue;
-        }
-        Field s = {};
-        s.key = e.key;
-        if (e.kind == EDIT_SET_Z) {
-            s.kind = 3;
-            s.len = e.len;
-            s.src = e.src;
-        } else {
-            s.kind = 1;
-            s.ival = e.val;
-            s.type = int_type(e.val);
-        }
-        if (!put_field(f, n, s)) return SMI_TAG_TOO_MANY_ATTRS;
-    }
-    for (int i = 1; i < n; i++) {  // insertion sort by binary tag (keys are distinct)
-        const Field x = f[i];
-        int j = i - 1;
-        while (j >= 0 && f[j].key > x.key) {
-            f[j + 1] = f[j];
-            j--;
-        }
-        f[j + 1] = x;
-    }
-    return 0;
-}
-
-template <bool WRITE>
-__global__ __launch_bounds__(64 * kEditWaves) void k_edit(const uint8_t *__restrict__ bam, const smi_bam_record *__restrict__ recs, size_t n,
-                                                          const Edit *__restrict__ edits, const uint8_t *__restrict__ pool,
-                                                          uint64_t *__restrict__ size, const uint64_t *__restrict__ off, uint8_t *__restrict__ out,
-                                                          uint64_t out_cap, uint32_t *__restrict__ err) {
-    __shared__ Field fields[kEditWaves][kMaxFields];
-    __shared__ int n_fields[kEditWaves];
-    __shared__ uint32_t bad[kEditWaves];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const size_t i = blockIdx.x * (size_t)kEditWaves + wv;
-    if (i >= n) return;
-    const smi_bam_record rec = recs[i];
-    Field *f = fields[wv];
-    if (lane == 0) {
-        int nf = 0;
-        uint32_t b = parse_fields(bam, rec, edits + (size_t)kEdits * i, f, nf);
-        uint64_t o = rec.aux_off - rec.rec_off;  // block_size word + fixed part + name + CIGAR + sequence + qualities
-        for (int j = 0; j < nf; j++) {
-            f[j].out = o;
-            o += field_bytes(f[j]);
-        }
-        if (!WRITE) {
-            size[i] = b ? 0 : o;
-            if (b) atomicOr(err, b);
-        } else if (!b && off[i] + o > out_cap) {
-            b = SMI_TAG_OVERFLOW;  // (cannot happen with the sizes of the SIZE pass; never written past the buffer)
-            atomicOr(err, b);
-        }
-        n_fields[wv] = nf;
-        bad[wv] = b;
-    }
-    if (!WRITE) return;
-    wave_sync();
-    if (bad[wv]) return;
-    const int nf = n_fields[wv];
-    uint8_t *dst = out + off[i];
-    const uint64_t fixed = rec.aux_off - rec.rec_off - 4;
-    const uint64_t total = nf ? f[nf - 1].out + field_bytes(f[nf - 1]) : fixed + 4;
-    if (lane == 0) {
-        const uint32_t bs = (uint32_t)(total - 4);
-        dst[0] = (uint8_t)bs;
-        dst[1] = (uint8_t)(bs >> 8);
-        dst[2] = (uint8_t)(bs >> 16);
-        dst[3] = (uint8_t)(bs >> 24);
-    }
-    for (uint64_t k = lane; k < fixed; k += 64) dst[4 + k] = bam[rec.rec_off + 4 + k];
-    for (int j = 0; j < nf; j++) {
-        const Field x = f[j];
-        uint8_t *d = dst + x.out;
-        if (lane == 0) {
-            d[0] = (uint8_t)x.key;
-            d[1] = (uint8_t)(x.key >> 8);
-        }
-        switch (x.kind) {
-            case 0:
-                for (uint32_t k = lane; k < x.len; k += 64) d[2 + k] = bam[x.src + k];
-                break;
-            case 1:
-                if (lane == 0) {
-                    d[2] = x.type;
-                    const uint32_t w = x.type == 'c' || x.type == 'C' ? 1 : x.type == 's' || x.type == 'S' ? 2 : 4;
-                    const uint64_t u = (uint64_t)x.ival;
-                    for (uint32_t k = 0; k < w; k++) d[3 + k] = (uint8_t)(u >> (8 * k));
-                }
-                break;
-            case 2: {
-                const uint32_t nb = x.len / 2;
-                if (lane == 0) {
-                    d[2] = 'B';
-                    d[3] = 'c';
-                    d[4] = (uint8_t)nb;
-                    d[5] = (uint8_t)(nb >> 8);
-                    d[6] = (uint8_t)(nb >> 16);
-                    d[7] = (uint8_t)(nb >> 24);
-                }
-                for (uint32_t k = lane; k < nb; k += 64)
-                    d[8 + k] = (uint8_t)(hex_val(bam[x.src + 2 * k]) << 4 | hex_val(bam[x.src + 2 * k + 1]));
-                break;
-            }
-            default:
-                if (lane == 0) {
-                    d[2] = 'Z';
-                    d[3 + x.len] = 0;  // a payload of length 0 is the empty string
-                }
-                for (uint32_t k = lane; k < x.len; k += 64) d[3 + k] = pool[x.src + k];
-                break;
-        }
-    }
-}
 
 // ---- K-NAME ----------------------------------------------------------------------------------------------------------------------------
 // String.split(one literal character) of s[0 .. len): the number of pieces (trailing empty pieces dropped, leading and inner ones kept, a
@@ -397,9 +198,9 @@ __device__ __forceinline__ void cigar_round(const GeneArgs &a, const smi_bam_rec
     round_end = ref_base + (int64_t)__shfl((long long)ir, 63);
 }
 
-__global__ __launch_bounds__(64 * kEditWaves) void k_gene(GeneArgs a) {
+__global__ __launch_bounds__(64 * kGeneWaves) void k_gene(GeneArgs a) {
     const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * kEditWaves + (threadIdx.x >> 6);
+    const int i = blockIdx.x * kGeneWaves + (threadIdx.x >> 6);
     if (i >= a.n) return;
     const smi_bam_record r = a.recs[i];
     Edit *ed = a.edits + (size_t)kEdits * i;
@@ -535,32 +336,12 @@ __global__ void k_gene_multi(const MultiPatch *__restrict__ p, int n, uint32_t g
     ed[2] = {(uint16_t)strand_key, EDIT_SET_Z, 0, x.gs_len, x.gs_off, 0};
 }
 
-unsigned blocks_for(size_t n, unsigned per) { return (unsigned)std::max<size_t>(1, (n + per - 1) / per); }
-int valid_tag(const char *t) { return t[0] > ' ' && t[0] <= '~' && t[1] > ' ' && t[1] <= '~' && t[2] == 0; }
-uint32_t tag_key(const char *t) { return (uint32_t)(uint8_t)t[1] << 8 | (uint8_t)t[0]; }
-
-template <class T>
-int grow(T **p, size_t &cap, size_t want) {  // device buffer of at least `want` elements (contents not kept)
-    if (want <= cap && *p) return SMI_OK;
-    if (*p) SMI_HIP(hipFree(*p));
-    *p = nullptr;
-    cap = 0;
-    const size_t n = std::max<size_t>(want + want / 4, 1024);
-    SMI_HIP(hipMalloc((void **)p, n * sizeof(T)));
-    cap = n;
-    return SMI_OK;
-}
 template <class T>
 int upload(T **p, const std::vector<T> &v) {
     SMI_HIP(hipMalloc((void **)p, std::max<size_t>(v.size(), 1) * sizeof(T)));
     if (!v.empty()) SMI_HIP(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return SMI_OK;
 }
-float elapsed(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
-}
-
 const char *const kFnName[4] = {"INTERGENIC", "INTRONIC", "UTR", "CODING"};
 
 }  // namespace
@@ -591,13 +372,9 @@ struct smi_moltag {
     smi_bam_record *d_recs = nullptr;
     Edit *d_edits = nullptr;
     GeneRes *d_res = nullptr;
-    uint64_t *d_size = nullptr, *d_off = nullptr;
-    size_t rec_cap = 0;
-    void *d_cub = nullptr;
-    size_t cub_cap = 0;
-    uint8_t *d_out = nullptr;
-    size_t out_cap = 0;
-    unsigned long long *d_words = nullptr;  // [0] first error record, [1] tagged records, [2] K-EDIT error bits
+    size_t recs_cap = 0, res_cap = 0, edits_cap = 0;
+    AuxRewriter rw;                         // K-EDIT: SIZE + scan, WRITE
+    unsigned long long *d_words = nullptr;  // [0] first error record, [1] tagged records
     std::vector<GeneRes> res;
     // the segment the last call sized and did not write: the next call with the same arguments writes it
     const uint8_t *last_bam = nullptr;
@@ -608,7 +385,7 @@ struct smi_moltag {
     int64_t counts[SMI_MOLTAG_COUNTS] = {};
     std::string error_read;
     int64_t error_record = -1;
-    hipEvent_t ev[5] = {};
+    hipEvent_t ev[2] = {};
     float ms[SMI_MOLTAG_STAGES] = {};
 };
 
@@ -616,7 +393,7 @@ namespace {
 
 void moltag_release(smi_moltag *h) {
     void *bufs[] = {h->d_contig_off, h->d_g_start, h->d_g_end, h->d_g_runmax, h->d_g_tx_off, h->d_tx, h->d_t_ex_off, h->d_exons, h->d_g_neg, h->d_name_off,
-                    h->d_pool, h->d_patch, h->d_bam, h->d_recs, h->d_edits, h->d_res, h->d_size, h->d_off, h->d_cub, h->d_out, h->d_words};
+                    h->d_pool, h->d_patch, h->d_bam, h->d_recs, h->d_edits, h->d_res, h->d_words};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev)
@@ -633,11 +410,7 @@ int pool_to_device(smi_moltag *h, hipStream_t s) {
     return SMI_OK;
 }
 
-std::string edit_error_text(uint32_t err) {
-    return std::string("smi_moltag_segment: a record's attributes cannot be rewritten:") + (err & SMI_TAG_BAD_AUX ? " malformed or unknown attribute type;" : "") +
-           (err & SMI_TAG_BAD_HEX ? " H attribute that is not hex;" : "") +
-           (err & SMI_TAG_TOO_MANY_ATTRS ? " more than " + std::to_string(kMaxFields) + " attributes;" : std::string());
-}
+EditSource edit_source(const smi_moltag *h) { return {h->d_edits, h->cfg.program == SMI_MOLTAG_GENE ? h->d_pool : h->d_bam}; }
 
 }  // namespace
 
@@ -699,7 +472,7 @@ extern "C" int smi_moltag_create(smi_ctx *ctx, const smi_moltag_config *cfg, con
         if (e__ != hipSuccess) return fail(hip_fail(e__, "hipEventCreate"));
     }
     {
-        hipError_t e__ = hipMalloc((void **)&h->d_words, 3 * sizeof(unsigned long long));
+        hipError_t e__ = hipMalloc((void **)&h->d_words, 2 * sizeof(unsigned long long));
         if (e__ != hipSuccess) return fail(hip_fail(e__, "hipMalloc"));
     }
     if (gene) {
@@ -804,26 +577,14 @@ extern "C" int smi_moltag_segment(smi_moltag *h, const uint8_t *bam, size_t n_ba
                 return SMI_ERR_INVALID;
             }
         }
-        size_t cub = 0;
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub, (uint64_t *)nullptr, (uint64_t *)nullptr, n + 1, s));
         if (int rc = grow(&h->d_bam, h->bam_cap, n_bam + 1)) return rc;
-        if ((size_t)n + 1 > h->rec_cap || !h->d_recs) {
-            size_t c0 = h->rec_cap, c1 = h->rec_cap, c2 = h->rec_cap, c3 = h->rec_cap, c4 = h->rec_cap;
-            size_t ce = h->rec_cap * kEdits;
-            if (int rc = grow(&h->d_recs, c0, (size_t)n + 1)) return rc;
-            if (int rc = grow(&h->d_res, c1, (size_t)n + 1)) return rc;
-            if (int rc = grow(&h->d_size, c2, (size_t)n + 1)) return rc;
-            if (int rc = grow(&h->d_off, c3, (size_t)n + 1)) return rc;
-            if (int rc = grow(&h->d_edits, ce, ((size_t)n + 1) * kEdits)) return rc;
-            c4 = ce / kEdits;
-            h->rec_cap = std::min(std::min(std::min(c0, c1), std::min(c2, c3)), c4);
-        }
-        if (int rc = grow((uint8_t **)&h->d_cub, h->cub_cap, cub)) return rc;
+        if (int rc = grow(&h->d_recs, h->recs_cap, (size_t)n + 1)) return rc;
+        if (int rc = grow(&h->d_res, h->res_cap, (size_t)n + 1)) return rc;
+        if (int rc = grow(&h->d_edits, h->edits_cap, ((size_t)n + 1) * kEdits)) return rc;
         if (n_bam) SMI_HIP(hipMemcpyAsync(h->d_bam, bam, n_bam, hipMemcpyHostToDevice, s));
         if (n) SMI_HIP(hipMemcpyAsync(h->d_recs, recs, (size_t)n * sizeof(smi_bam_record), hipMemcpyHostToDevice, s));
         SMI_HIP(hipMemsetAsync(h->d_words, 0xFF, 8, s));
-        SMI_HIP(hipMemsetAsync(h->d_words + 1, 0, 16, s));
-        SMI_HIP(hipMemsetAsync(h->d_size + n, 0, 8, s));
+        SMI_HIP(hipMemsetAsync(h->d_words + 1, 0, 8, s));
         SMI_HIP(hipEventRecord(h->ev[0], s));
         if (n && !gene)
             hipLaunchKernelGGL(k_name, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const uint8_t *)h->d_bam, (const smi_bam_record *)h->d_recs, (size_t)n,
@@ -859,7 +620,7 @@ extern "C" int smi_moltag_segment(smi_moltag *h, const uint8_t *bam, size_t n_ba
             a.edits = h->d_edits;
             a.res = h->d_res;
             a.err_rec = h->d_words;
-            hipLaunchKernelGGL(k_gene, dim3(blocks_for(n, kEditWaves)), dim3(64 * kEditWaves), 0, s, a);
+            hipLaunchKernelGGL(k_gene, dim3(blocks_for(n, kGeneWaves)), dim3(64 * kGeneWaves), 0, s, a);
         }
         SMI_HIP(hipGetLastError());
         SMI_HIP(hipEventRecord(h->ev[1], s));
@@ -947,23 +708,7 @@ extern "C" int smi_moltag_segment(smi_moltag *h, const uint8_t *bam, size_t n_ba
                 SMI_HIP(hipStreamSynchronize(s));  // patch is read by the copy above
             }
         }
-        SMI_HIP(hipEventRecord(h->ev[2], s));
-        if (n)
-            hipLaunchKernelGGL(k_edit<false>, dim3(blocks_for(n, kEditWaves)), dim3(64 * kEditWaves), 0, s, (const uint8_t *)h->d_bam,
-                               (const smi_bam_record *)h->d_recs, (size_t)n, (const Edit *)h->d_edits, (const uint8_t *)(gene ? h->d_pool : h->d_bam), h->d_size,
-                               (const uint64_t *)nullptr, (uint8_t *)nullptr, (uint64_t)0, (uint32_t *)(h->d_words + 2));
-        SMI_HIP(hipGetLastError());
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(h->d_cub, cub, h->d_size, h->d_off, n + 1, s));
-        SMI_HIP(hipEventRecord(h->ev[3], s));
-        unsigned long long err = 0;
-        SMI_HIP(hipMemcpyAsync(&total, h->d_off + n, 8, hipMemcpyDeviceToHost, s));
-        SMI_HIP(hipMemcpyAsync(&err, h->d_words + 2, 8, hipMemcpyDeviceToHost, s));
-        SMI_HIP(hipStreamSynchronize(s));
-        h->ms[2] = elapsed(h->ev[2], h->ev[3]);
-        if (err) {
-            set_error(edit_error_text((uint32_t)err));
-            return SMI_ERR_INVALID;
-        }
+        if (int rc = h->rw.size("smi_moltag_segment: ", s, h->d_bam, h->d_recs, (size_t)n, edit_source(h), &total, &h->ms[2])) return rc;
     }
     *n_out = total;
     if (!out || cap < total) {  // sizes only: the segment stays on the device for the next call with the same arguments
@@ -975,21 +720,5 @@ extern "C" int smi_moltag_segment(smi_moltag *h, const uint8_t *bam, size_t n_ba
         return out ? 1 : SMI_OK;
     }
     if (!total) return SMI_OK;
-    if (int rc = grow(&h->d_out, h->out_cap, total)) return rc;
-    SMI_HIP(hipEventRecord(h->ev[3], s));
-    hipLaunchKernelGGL(k_edit<true>, dim3(blocks_for(n, kEditWaves)), dim3(64 * kEditWaves), 0, s, (const uint8_t *)h->d_bam,
-                       (const smi_bam_record *)h->d_recs, (size_t)n, (const Edit *)h->d_edits, (const uint8_t *)(gene ? h->d_pool : h->d_bam),
-                       (uint64_t *)nullptr, (const uint64_t *)h->d_off, h->d_out, (uint64_t)h->out_cap, (uint32_t *)(h->d_words + 2));
-    SMI_HIP(hipGetLastError());
-    SMI_HIP(hipEventRecord(h->ev[4], s));
-    unsigned long long err = 0;
-    SMI_HIP(hipMemcpyAsync(&err, h->d_words + 2, 8, hipMemcpyDeviceToHost, s));
-    SMI_HIP(hipMemcpyAsync(out, h->d_out, total, hipMemcpyDeviceToHost, s));
-    SMI_HIP(hipStreamSynchronize(s));
-    h->ms[3] = elapsed(h->ev[3], h->ev[4]);
-    if (err) {
-        set_error("smi_moltag_segment: the output buffer of the device was too small for a record (internal error)");
-        return SMI_ERR_INVALID;
-    }
-    return SMI_OK;
+    return h->rw.write("smi_moltag_segment: ", s, h->d_bam, h->d_recs, (size_t)n, edit_source(h), total, out, &h->ms[3]);
 }

@@ -417,7 +417,7 @@ extern "C" int smi_snp_create(smi_ctx *ctx, const smi_snp_config *cfg, const cha
     const char *tags[] = {cfg->cell_tag, cfg->umi_tag, cfg->gene_tag, cfg->rn_tag};
     const char *what[] = {"CELLTAG", "UMITAG", "GENETAG", "RNTAG"};
     for (int i = 0; i < 4; i++)
-        if (!lr::valid_tag(tags[i])) {
+        if (!valid_tag(tags[i])) {
             set_error(std::string(what[i]) + " must be two characters");
             return SMI_ERR_INVALID;
         }

@@ -11,19 +11,17 @@
 //               the highest index (the last record) wins whatever order the threads arrive in
 //   K-TAG-PROBE one thread per BAM record: UNMAPPED (reference index -1), the FASTQ record, or MISSING; every tag hit is confirmed
 //               byte for byte
-//   K-TAG-ASM   one wavefront per BAM record, in two instantiations: SIZE (lane 0 parses the attributes and sizes the record) and
-//               WRITE (lane 0 parses into LDS; the wavefront copies the fixed part, the attributes and the two Z payloads straight from
-//               the FASTQ text into the output at the offset of the exclusive scan of the sizes)
-// The attribute list is what htsjdk writes after setAttribute (BinaryTagCodec.readTags L271-305 + SAMBinaryTagAndValue.insert L207-228,
-// pinned by tests/golden/ref_exec_auxorder.json): ordered by binary tag, a repeated tag keeping its last value, integers in the smallest
-// type (getIntegerType L153-180), H read back as a byte array (B:c).
-#include <hipcub/hipcub.hpp>
-
+//   K-TAG-ASM   one wavefront per BAM record: k_aux_rewrite<WRITE, TagSource> of smi_auxedit.h, the attribute rewrite shared with K-EDIT
+//               (smi_moltag.hip), as SIZE + exclusive scan + WRITE through an AuxRewriter.  TagSource drops the records K-TAG-PROBE did not
+//               find (before their attributes are read) and puts two Z fields behind the others, their payloads copied straight from the
+//               FASTQ text.  tag_assemble_z2 runs the same kernel for IsoformMatrix's ISOBAM (smi_isoform.hip).
+// The attribute rules (htsjdk's, pinned by tests/golden/ref_exec_auxorder.json) are stated in smi_auxedit.h.
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "smi_auxedit.h"
 #include "smi_internal.h"
 
 namespace smi {
@@ -31,8 +29,6 @@ namespace {
 
 constexpr uint64_t kEmpty = ~0ull;          // no valid entry: record indices stay below 2^31
 constexpr int32_t kMissing = -1, kUnmapped = -2;
-constexpr int kMaxFields = SMI_TAGBAM_MAX_ATTRS;
-constexpr int kAsmWaves = 4;                // waves per block of K-TAG-ASM
 
 __device__ __forceinline__ uint64_t mix64(uint64_t h) {  // splitmix64's finaliser
     h ^= h >> 30;
@@ -116,237 +112,26 @@ __global__ void k_tag_probe(const uint8_t *__restrict__ bam, const smi_bam_recor
     res[i] = found;
 }
 
-// one attribute of the written record
-struct Field {
-    uint16_t key;    // binary tag: second char << 8 | first char (SAMTag.makeBinaryTag L124-127)
-    uint8_t kind;    // 0 verbatim (src: type byte .. end), 1 integer (ival), 2 H -> B:c (src: the hex digits), 3 Z from the FASTQ text
-    uint8_t type;    // output type of an integer
-    uint32_t len;    // kind 0: bytes behind the tag; 2: hex digits; 3: payload bytes
-    uint64_t src;    // kind 0 / 2: offset in the BAM stream; 3: offset in the FASTQ text
-    int64_t ival;
-    uint64_t out;    // offset of the field in the output record (WRITE)
+// what K-TAG-ASM puts behind a record's own attributes: two Z fields whose payloads lie in the resident text (the second one optional)
+struct TagSource {
+    const int32_t *res;  // per record: the entry of its payloads, or negative: the record is dropped
+    const uint8_t *text;
+    const uint64_t *a_start, *b_start;
+    const uint32_t *a_len, *b_len;
+    uint32_t a_key, b_key;
+    int with_b;
+    struct Tail {
+        Field a, b;
+        bool with_b;
+        __device__ uint32_t put(Field *f, int &n) const { return put_field(f, n, a) && (!with_b || put_field(f, n, b)) ? 0 : SMI_TAG_TOO_MANY_ATTRS; }
+    };
+    __device__ bool keeps(size_t i) const { return res[i] >= 0; }
+    __device__ Tail tail(size_t i) const {
+        const int32_t k = res[i];
+        return {{(uint16_t)a_key, 3, 0, a_len[k], a_start[k], 0, 0}, {(uint16_t)b_key, 3, 0, b_len[k], b_start[k], 0, 0}, with_b != 0};
+    }
+    __device__ const uint8_t *payload() const { return text; }
 };
-
-__device__ __forceinline__ uint32_t field_bytes(const Field &f) {
-    switch (f.kind) {
-        case 1: return 3u + (f.type == 'c' || f.type == 'C' ? 1u : f.type == 's' || f.type == 'S' ? 2u : 4u);
-        case 2: return 8u + f.len / 2;
-        case 3: return 4u + f.len;
-        default: return 2u + f.len;
-    }
-}
-__device__ __forceinline__ uint8_t int_type(int64_t v) {  // BinaryTagCodec.getIntegerType
-    if (v >= -128 && v <= 127) return 'c';
-    if (v >= 0 && v <= 255) return 'C';
-    if (v >= -32768 && v <= 32767) return 's';
-    if (v >= 0 && v <= 65535) return 'S';
-    if (v >= -2147483648ll && v <= 2147483647ll) return 'i';
-    return 'I';
-}
-__device__ __forceinline__ int hex_val(uint8_t c) {
-    if (c >= '0' && c <= '9') return c - '0';
-    c |= 0x20;
-    if (c >= 'a' && c <= 'f') return c - 'a' + 10;
-    return -1;
-}
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
-
-// insert or replace (a repeated tag keeps its last value); false: more than kMaxFields attributes
-__device__ bool put_field(Field *f, int &n, const Field &x) {
-    for (int j = 0; j < n; j++)
-        if (f[j].key == x.key) {
-            f[j] = x;
-            return true;
-        }
-    if (n >= kMaxFields) return false;
-    f[n++] = x;
-    return true;
-}
-
-// lane 0: the attribute list of record rec as written, in f[0 .. n), sorted by binary tag; returns SMI_TAG_* error bits (0 = fine)
-__device__ uint32_t parse_fields(const uint8_t *__restrict__ bam, const smi_bam_record &rec, const uint8_t *__restrict__ text, uint64_t seq_start,
-                                 uint64_t qual_start, uint32_t seq_len, uint32_t qual_len, uint32_t read_key, uint32_t qv_key, bool with_qv, Field *f,
-                                 int &n) {
-    n = 0;
-    const uint64_t end = rec.aux_off + rec.aux_len;
-    uint64_t p = rec.aux_off;
-    while (p < end) {
-        if (p + 3 > end) return SMI_TAG_BAD_AUX;
-        Field x = {};
-        x.key = (uint16_t)(bam[p + 1] << 8 | bam[p]);
-        const uint8_t ty = bam[p + 2];
-        const uint64_t v = p + 3;
-        uint64_t q;
-        switch (ty) {
-            case 'A': q = v + 1; break;
-            case 'f': q = v + 4; break;
-            case 'c': case 'C': case 's': case 'S': case 'i': case 'I': {
-                const uint32_t w = ty == 'c' || ty == 'C' ? 1 : ty == 's' || ty == 'S' ? 2 : 4;
-                q = v + w;
-                if (q > end) return SMI_TAG_BAD_AUX;
-                const uint32_t raw = w == 1 ? bam[v] : w == 2 ? (uint32_t)(bam[v] | bam[v + 1] << 8) : ld_u32(bam + v);
-                x.kind = 1;
-                x.ival = ty == 'c' ? (int64_t)(int8_t)raw : ty == 's' ? (int64_t)(int16_t)raw : ty == 'i' ? (int64_t)(int32_t)raw : (int64_t)raw;
-                x.type = int_type(x.ival);
-                break;
-            }
-            case 'Z': case 'H': {
-                q = v;
-                while (q < end && bam[q]) q++;
-                if (q >= end) return SMI_TAG_BAD_AUX;
-                if (ty == 'H') {
-                    const uint32_t digits = (uint32_t)(q - v);
-                    if (digits & 1u) return SMI_TAG_BAD_HEX;
-                    for (uint64_t k = v; k < q; k++)
-                        if (hex_val(bam[k]) < 0) return SMI_TAG_BAD_HEX;
-                    x.kind = 2;
-                    x.src = v;
-                    x.len = digits;
-                }
-                q++;
-                break;
-            }
-            case 'B': {
-                if (v + 5 > end) return SMI_TAG_BAD_AUX;
-                const uint8_t sub = bam[v];
-                const uint32_t w = sub == 'c' || sub == 'C' ? 1 : sub == 's' || sub == 'S' ? 2 : sub == 'i' || sub == 'I' || sub == 'f' ? 4 : 0;
-                if (!w) return SMI_TAG_BAD_AUX;
-                q = v + 5 + (uint64_t)w * ld_u32(bam + v + 1);
-                break;
-            }
-            default: return SMI_TAG_BAD_AUX;
-        }
-        if (q > end) return SMI_TAG_BAD_AUX;
-        if (x.kind == 0) {
-            x.src = p + 2;
-            x.len = (uint32_t)(q - p - 2);
-        }
-        if (!put_field(f, n, x)) return SMI_TAG_TOO_MANY_ATTRS;
-        p = q;
-    }
-    Field s = {};
-    s.kind = 3;
-    s.len = seq_len;
-    s.key = (uint16_t)read_key;
-    s.src = seq_start;
-    if (!put_field(f, n, s)) return SMI_TAG_TOO_MANY_ATTRS;
-    if (with_qv) {
-        s.key = (uint16_t)qv_key;
-        s.src = qual_start;
-        s.len = qual_len;
-        if (!put_field(f, n, s)) return SMI_TAG_TOO_MANY_ATTRS;
-    }
-    for (int i = 1; i < n; i++) {  // insertion sort by binary tag (keys are distinct)
-        const Field x = f[i];
-        int j = i - 1;
-        while (j >= 0 && f[j].key > x.key) {
-            f[j + 1] = f[j];
-            j--;
-        }
-        f[j + 1] = x;
-    }
-    return 0;
-}
-
-template <bool WRITE>
-__global__ __launch_bounds__(64 * kAsmWaves) void k_tag_asm(const uint8_t *__restrict__ bam, const smi_bam_record *__restrict__ recs, size_t n,
-                                                             const int32_t *__restrict__ res, const uint8_t *__restrict__ text,
-                                                             const uint64_t *__restrict__ seq_start, const uint32_t *__restrict__ seq_len,
-                                                             const uint64_t *__restrict__ qual_start, const uint32_t *__restrict__ qual_len,
-                                                             uint32_t read_key, uint32_t qv_key, int with_qv,
-                                                             uint64_t *__restrict__ size, const uint64_t *__restrict__ off, uint8_t *__restrict__ out,
-                                                             uint64_t out_cap, uint32_t *__restrict__ err) {
-    __shared__ Field fields[kAsmWaves][kMaxFields];
-    __shared__ int n_fields[kAsmWaves];
-    __shared__ uint32_t bad[kAsmWaves];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const size_t i = blockIdx.x * (size_t)kAsmWaves + wv;
-    if (i >= n) return;
-    const int32_t fq = res[i];
-    if (fq < 0) {
-        if (!WRITE && lane == 0) size[i] = 0;  // dropped
-        return;
-    }
-    const smi_bam_record rec = recs[i];
-    Field *f = fields[wv];
-    if (lane == 0) {
-        int nf = 0;
-        uint32_t b = parse_fields(bam, rec, text, seq_start[fq], qual_start[fq], seq_len[fq], qual_len[fq], read_key, qv_key, with_qv != 0, f, nf);
-        uint64_t o = rec.aux_off - rec.rec_off;  // block_size word + fixed part + name + CIGAR + sequence + qualities
-        for (int j = 0; j < nf; j++) {
-            f[j].out = o;
-            o += field_bytes(f[j]);
-        }
-        if (!WRITE) {
-            size[i] = b ? 0 : o;
-            if (b) atomicOr(err, b);
-        } else if (!b && off[i] + o > out_cap) {
-            b = SMI_TAG_OVERFLOW;  // (cannot happen with the sizes of the SIZE pass; never written past the buffer)
-            atomicOr(err, b);
-        }
-        n_fields[wv] = nf;
-        bad[wv] = b;
-    }
-    if (!WRITE) return;
-    wave_sync();
-    if (bad[wv]) return;
-    const int nf = n_fields[wv];
-    uint8_t *dst = out + off[i];
-    const uint64_t fixed = rec.aux_off - rec.rec_off - 4;
-    const uint64_t total = nf ? f[nf - 1].out + field_bytes(f[nf - 1]) : fixed + 4;
-    if (lane == 0) {
-        const uint32_t bs = (uint32_t)(total - 4);
-        dst[0] = (uint8_t)bs;
-        dst[1] = (uint8_t)(bs >> 8);
-        dst[2] = (uint8_t)(bs >> 16);
-        dst[3] = (uint8_t)(bs >> 24);
-    }
-    for (uint64_t k = lane; k < fixed; k += 64) dst[4 + k] = bam[rec.rec_off + 4 + k];
-    for (int j = 0; j < nf; j++) {
-        const Field x = f[j];
-        uint8_t *d = dst + x.out;
-        if (lane == 0) {
-            d[0] = (uint8_t)x.key;
-            d[1] = (uint8_t)(x.key >> 8);
-        }
-        switch (x.kind) {
-            case 0:
-                for (uint32_t k = lane; k < x.len; k += 64) d[2 + k] = bam[x.src + k];
-                break;
-            case 1:
-                if (lane == 0) {
-                    d[2] = x.type;
-                    const uint32_t w = x.type == 'c' || x.type == 'C' ? 1 : x.type == 's' || x.type == 'S' ? 2 : 4;
-                    const uint64_t u = (uint64_t)x.ival;
-                    for (uint32_t k = 0; k < w; k++) d[3 + k] = (uint8_t)(u >> (8 * k));
-                }
-                break;
-            case 2: {
-                const uint32_t nb = x.len / 2;
-                if (lane == 0) {
-                    d[2] = 'B';
-                    d[3] = 'c';
-                    d[4] = (uint8_t)nb;
-                    d[5] = (uint8_t)(nb >> 8);
-                    d[6] = (uint8_t)(nb >> 16);
-                    d[7] = (uint8_t)(nb >> 24);
-                }
-                for (uint32_t k = lane; k < nb; k += 64)
-                    d[8 + k] = (uint8_t)(hex_val(bam[x.src + 2 * k]) << 4 | hex_val(bam[x.src + 2 * k + 1]));
-                break;
-            }
-            default:
-                if (lane == 0) {
-                    d[2] = 'Z';
-                    d[3 + x.len] = 0;
-                }
-                for (uint32_t k = lane; k < x.len; k += 64) d[3 + k] = text[x.src + k];
-                break;
-        }
-    }
-}
-
-unsigned blocks_for(size_t n, unsigned per) { return (unsigned)std::max<size_t>(1, (n + per - 1) / per); }
 
 }  // namespace
 
@@ -356,70 +141,16 @@ int tag_assemble_z2(hipStream_t s, const uint8_t *d_bam, const smi_bam_record *d
                     const char *tag_b, std::vector<uint8_t> &out, float *ms) {
     out.clear();
     if (!n) return SMI_OK;
-    const uint32_t ka = (uint32_t)(uint8_t)tag_a[1] << 8 | (uint8_t)tag_a[0], kb = (uint32_t)(uint8_t)tag_b[1] << 8 | (uint8_t)tag_b[0];
-    uint64_t *d_size = nullptr, *d_off = nullptr;
-    uint32_t *d_err = nullptr;
-    void *d_cub = nullptr;
-    uint8_t *d_out = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = SMI_OK;
-    auto fin = [&](int r) {
-        for (void *p : {(void *)d_size, (void *)d_off, (void *)d_err, d_cub, (void *)d_out})
-            if (p) (void)hipFree(p);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        return r;
-    };
-#define SMI_Z2(call)                                          \
-    do {                                                      \
-        hipError_t e__ = (call);                              \
-        if (e__ != hipSuccess) return fin(hip_fail(e__, #call)); \
-    } while (0)
-    size_t cub = 0;
-    SMI_Z2(hipcub::DeviceScan::ExclusiveSum(nullptr, cub, (uint64_t *)nullptr, (uint64_t *)nullptr, n + 1, s));
-    SMI_Z2(hipMalloc((void **)&d_size, (n + 1) * 8));
-    SMI_Z2(hipMalloc((void **)&d_off, (n + 1) * 8));
-    SMI_Z2(hipMalloc((void **)&d_err, 4));
-    SMI_Z2(hipMalloc(&d_cub, std::max<size_t>(cub, 1)));
-    SMI_Z2(hipEventCreate(&e0));
-    SMI_Z2(hipEventCreate(&e1));
-    SMI_Z2(hipMemsetAsync(d_err, 0, 4, s));
-    SMI_Z2(hipMemsetAsync(d_size + n, 0, 8, s));
-    SMI_Z2(hipEventRecord(e0, s));
-    hipLaunchKernelGGL(k_tag_asm<false>, dim3(blocks_for(n, kAsmWaves)), dim3(64 * kAsmWaves), 0, s, d_bam, d_recs, n, d_entry, d_text, d_a_start,
-                       d_a_len, d_b_start, d_b_len, ka, kb, 1, d_size, (const uint64_t *)nullptr, (uint8_t *)nullptr, (uint64_t)0, d_err);
-    SMI_Z2(hipGetLastError());
-    SMI_Z2(hipcub::DeviceScan::ExclusiveSum(d_cub, cub, d_size, d_off, n + 1, s));
+    const TagSource src = {d_entry, d_text, d_a_start, d_b_start, d_a_len, d_b_len, tag_key(tag_a), tag_key(tag_b), 1};
+    AuxRewriter rw;
     uint64_t total = 0;
-    uint32_t err = 0;
-    SMI_Z2(hipMemcpyAsync(&total, d_off + n, 8, hipMemcpyDeviceToHost, s));
-    SMI_Z2(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s));
-    SMI_Z2(hipStreamSynchronize(s));
-    if (err) {
-        set_error(std::string("a record's attributes cannot be rewritten:") + (err & SMI_TAG_BAD_AUX ? " malformed or unknown attribute type;" : "") +
-                  (err & SMI_TAG_BAD_HEX ? " H attribute that is not hex;" : "") +
-                  (err & SMI_TAG_TOO_MANY_ATTRS ? " more than " + std::to_string(kMaxFields) + " attributes;" : std::string()));
-        return fin(SMI_ERR_INVALID);
-    }
-    SMI_Z2(hipMalloc((void **)&d_out, std::max<uint64_t>(total, 1)));
-    hipLaunchKernelGGL(k_tag_asm<true>, dim3(blocks_for(n, kAsmWaves)), dim3(64 * kAsmWaves), 0, s, d_bam, d_recs, n, d_entry, d_text, d_a_start,
-                       d_a_len, d_b_start, d_b_len, ka, kb, 1, (uint64_t *)nullptr, (const uint64_t *)d_off, d_out, (uint64_t)total, d_err);
-    SMI_Z2(hipGetLastError());
-    SMI_Z2(hipEventRecord(e1, s));
+    float t_size = 0.f, t_write = 0.f;
+    if (int rc = rw.size("", s, d_bam, d_recs, n, src, &total, &t_size)) return rc;
     out.resize(total);
-    SMI_Z2(hipMemcpyAsync(out.data(), d_out, total, hipMemcpyDeviceToHost, s));
-    SMI_Z2(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s));
-    SMI_Z2(hipStreamSynchronize(s));
-#undef SMI_Z2
-    if (ms) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) *ms += t;
-    }
-    if (err) {
-        set_error("the output buffer of the device was too small for a record (internal error)");
-        rc = SMI_ERR_INVALID;
-    }
-    return fin(rc);
+    if (total)
+        if (int rc = rw.write("", s, d_bam, d_recs, n, src, total, out.data(), &t_write)) return rc;
+    if (ms) *ms += t_size + t_write;
+    return SMI_OK;
 }
 
 }  // namespace smi
@@ -441,13 +172,8 @@ struct smi_tagbam {
     size_t bam_cap = 0;
     smi_bam_record *d_recs = nullptr;
     int32_t *d_res = nullptr;
-    uint64_t *d_size = nullptr, *d_off = nullptr;
-    size_t rec_cap = 0;
-    void *d_cub = nullptr;
-    size_t cub_cap = 0;
-    uint8_t *d_out = nullptr;
-    size_t out_cap = 0;
-    uint32_t *d_err = nullptr;
+    size_t recs_cap = 0, res_cap = 0;
+    AuxRewriter rw;  // K-TAG-ASM: SIZE + scan, WRITE
     std::vector<int32_t> res;
     // the segment the last call sized and did not write (out too small / NULL): the next call with the same arguments writes it
     const uint8_t *last_bam = nullptr;
@@ -455,7 +181,7 @@ struct smi_tagbam {
     size_t last_n_bam = 0;
     int32_t last_n = -1;
     uint64_t last_total = 0;
-    hipEvent_t ev[6] = {};
+    hipEvent_t ev[4] = {};
     float ms[SMI_TAGBAM_STAGES] = {};
 };
 
@@ -463,7 +189,7 @@ namespace {
 
 void tagbam_release(smi_tagbam *h) {
     void *bufs[] = {h->d_text, h->d_line_start, h->d_name_start, h->d_seq_start, h->d_qual_start, h->d_offsets, h->d_name_len, h->d_seq_len,
-                    h->d_key_len, h->d_table, h->d_bam, h->d_recs, h->d_res, h->d_size, h->d_off, h->d_cub, h->d_out, h->d_err};
+                    h->d_key_len, h->d_table, h->d_bam, h->d_recs, h->d_res};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev)
@@ -471,25 +197,10 @@ void tagbam_release(smi_tagbam *h) {
     delete h;
 }
 
-int valid_tag(const char *t) { return t[0] > ' ' && t[0] <= '~' && t[1] > ' ' && t[1] <= '~' && t[2] == 0; }
-
-uint32_t tag_key(const char *t) { return (uint32_t)(uint8_t)t[1] << 8 | (uint8_t)t[0]; }
-
-template <class T>
-int grow(T **p, size_t &cap, size_t want) {  // device buffer of at least `want` elements (contents not kept)
-    if (want <= cap && *p) return SMI_OK;
-    if (*p) SMI_HIP(hipFree(*p));
-    *p = nullptr;
-    cap = 0;
-    const size_t n = std::max<size_t>(want + want / 4, 1024);
-    SMI_HIP(hipMalloc((void **)p, n * sizeof(T)));
-    cap = n;
-    return SMI_OK;
-}
-
-float elapsed(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
+// the read (and QV) attribute of the record whose FASTQ entry K-TAG-PROBE found
+TagSource tag_source(const smi_tagbam *h) {
+    return {h->d_res, h->d_text, h->d_seq_start, h->d_qual_start, h->d_seq_len, h->d_seq_len, tag_key(h->cfg.read_tag), tag_key(h->cfg.qv_tag),
+            h->cfg.with_qv};
 }
 
 }  // namespace
@@ -618,7 +329,6 @@ extern "C" int smi_tagbam_create(smi_ctx *ctx, const uint8_t *fastq_text, size_t
     TAG_HIP(hipStreamSynchronize(s));
     h->ms[0] = elapsed(h->ev[0], h->ev[1]);
     h->ms[1] = elapsed(h->ev[1], h->ev[2]);
-    TAG_HIP(hipMalloc(&h->d_err, 4));
 #undef TAG_HIP
     *out = h;
     return SMI_OK;
@@ -676,23 +386,11 @@ extern "C" int smi_tagbam_segment(smi_tagbam *h, const uint8_t *bam, size_t n_ba
                 return SMI_ERR_INVALID;
             }
         }
-        size_t cub = 0;
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub, (uint64_t *)nullptr, (uint64_t *)nullptr, n + 1, s));
         if (int rc = grow(&h->d_bam, h->bam_cap, n_bam + 1)) return rc;
-        size_t c0 = h->rec_cap, c1 = h->rec_cap, c2 = h->rec_cap, c3 = h->rec_cap;
-        if ((size_t)n + 1 > h->rec_cap || !h->d_recs) {
-            if (int rc = grow(&h->d_recs, c0, (size_t)n + 1)) return rc;
-            if (int rc = grow(&h->d_res, c1, (size_t)n + 1)) return rc;
-            if (int rc = grow(&h->d_size, c2, (size_t)n + 1)) return rc;
-            if (int rc = grow(&h->d_off, c3, (size_t)n + 1)) return rc;
-            h->rec_cap = std::min(std::min(c0, c1), std::min(c2, c3));
-        }
-        if (int rc = grow((uint8_t **)&h->d_cub, h->cub_cap, cub)) return rc;
+        if (int rc = grow(&h->d_recs, h->recs_cap, (size_t)n + 1)) return rc;
+        if (int rc = grow(&h->d_res, h->res_cap, (size_t)n + 1)) return rc;
         if (n_bam) SMI_HIP(hipMemcpyAsync(h->d_bam, bam, n_bam, hipMemcpyHostToDevice, s));
         if (n) SMI_HIP(hipMemcpyAsync(h->d_recs, recs, (size_t)n * sizeof(smi_bam_record), hipMemcpyHostToDevice, s));
-        SMI_HIP(hipMemsetAsync(h->d_err, 0, 4, s));
-        SMI_HIP(hipMemsetAsync(h->d_size + n, 0, 8, s));
-        const uint32_t rk = tag_key(h->cfg.read_tag), qk = tag_key(h->cfg.qv_tag);
         SMI_HIP(hipEventRecord(h->ev[2], s));
         if (n)
             hipLaunchKernelGGL(k_tag_probe, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const uint8_t *)h->d_bam, (const smi_bam_record *)h->d_recs,
@@ -700,29 +398,12 @@ extern "C" int smi_tagbam_segment(smi_tagbam *h, const uint8_t *bam, size_t n_ba
                                (const uint64_t *)h->d_table, h->mask, h->hash_mask, h->d_res);
         SMI_HIP(hipGetLastError());
         SMI_HIP(hipEventRecord(h->ev[3], s));
-        if (n)
-            hipLaunchKernelGGL(k_tag_asm<false>, dim3(blocks_for(n, kAsmWaves)), dim3(64 * kAsmWaves), 0, s, (const uint8_t *)h->d_bam,
-                               (const smi_bam_record *)h->d_recs, (size_t)n, (const int32_t *)h->d_res, (const uint8_t *)h->d_text,
-                               (const uint64_t *)h->d_seq_start, (const uint32_t *)h->d_seq_len, (const uint64_t *)h->d_qual_start,
-                               (const uint32_t *)h->d_seq_len, rk, qk,
-                               h->cfg.with_qv, h->d_size, (const uint64_t *)nullptr, (uint8_t *)nullptr, (uint64_t)0, h->d_err);
-        SMI_HIP(hipGetLastError());
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(h->d_cub, cub, h->d_size, h->d_off, n + 1, s));
-        SMI_HIP(hipEventRecord(h->ev[4], s));
         h->res.resize((size_t)n + 1);
-        uint32_t err = 0;
-        if (n) SMI_HIP(hipMemcpyAsync(h->res.data(), h->d_res, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        SMI_HIP(hipMemcpyAsync(&total, h->d_off + n, 8, hipMemcpyDeviceToHost, s));
-        SMI_HIP(hipMemcpyAsync(&err, h->d_err, 4, hipMemcpyDeviceToHost, s));
-        SMI_HIP(hipStreamSynchronize(s));
+        const int rc = h->rw.size("smi_tagbam_segment: ", s, h->d_bam, h->d_recs, (size_t)n, tag_source(h), &total, &h->ms[3], [&] {
+            return n ? hipMemcpyAsync(h->res.data(), h->d_res, (size_t)n * 4, hipMemcpyDeviceToHost, s) : hipSuccess;  // read back on size()'s wait
+        });
         h->ms[2] = elapsed(h->ev[2], h->ev[3]);
-        h->ms[3] = elapsed(h->ev[3], h->ev[4]);
-        if (err) {
-            set_error(std::string("smi_tagbam_segment: a record's attributes cannot be rewritten:") +
-                      (err & SMI_TAG_BAD_AUX ? " malformed or unknown attribute type;" : "") + (err & SMI_TAG_BAD_HEX ? " H attribute that is not hex;" : "") +
-                      (err & SMI_TAG_TOO_MANY_ATTRS ? " more than " + std::to_string(kMaxFields) + " attributes;" : std::string()));
-            return SMI_ERR_INVALID;
-        }
+        if (rc) return rc;
     }
     int32_t nm = 0, nu = 0;
     for (int32_t i = 0; i < n; i++) {
@@ -743,23 +424,5 @@ extern "C" int smi_tagbam_segment(smi_tagbam *h, const uint8_t *bam, size_t n_ba
         return out ? 1 : SMI_OK;
     }
     if (!total) return SMI_OK;
-    if (int rc = grow(&h->d_out, h->out_cap, total)) return rc;
-    SMI_HIP(hipEventRecord(h->ev[4], s));
-    hipLaunchKernelGGL(k_tag_asm<true>, dim3(blocks_for(n, kAsmWaves)), dim3(64 * kAsmWaves), 0, s, (const uint8_t *)h->d_bam,
-                       (const smi_bam_record *)h->d_recs, (size_t)n, (const int32_t *)h->d_res, (const uint8_t *)h->d_text,
-                       (const uint64_t *)h->d_seq_start, (const uint32_t *)h->d_seq_len, (const uint64_t *)h->d_qual_start, (const uint32_t *)h->d_seq_len,
-                       tag_key(h->cfg.read_tag),
-                       tag_key(h->cfg.qv_tag), h->cfg.with_qv, (uint64_t *)nullptr, (const uint64_t *)h->d_off, h->d_out, (uint64_t)h->out_cap, h->d_err);
-    SMI_HIP(hipGetLastError());
-    SMI_HIP(hipEventRecord(h->ev[5], s));
-    uint32_t err = 0;
-    SMI_HIP(hipMemcpyAsync(&err, h->d_err, 4, hipMemcpyDeviceToHost, s));
-    SMI_HIP(hipMemcpyAsync(out, h->d_out, total, hipMemcpyDeviceToHost, s));
-    SMI_HIP(hipStreamSynchronize(s));
-    h->ms[4] = elapsed(h->ev[4], h->ev[5]);
-    if (err) {
-        set_error("smi_tagbam_segment: the output buffer of the device was too small for a record (internal error)");
-        return SMI_ERR_INVALID;
-    }
-    return SMI_OK;
+    return h->rw.write("smi_tagbam_segment: ", s, h->d_bam, h->d_recs, (size_t)n, tag_source(h), total, out, &h->ms[4]);
 }

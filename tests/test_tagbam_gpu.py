@@ -25,6 +25,13 @@ def tb(pkg):
     return importlib.import_module("sicelore_amd.tagbamwithread")
 
 
+@pytest.fixture(scope="module")
+def lib(pkg):
+    import importlib
+
+    return importlib.import_module("sicelore_amd.lib")
+
+
 def _rec(name, flag=0, ref=0, pos=10, aux=b"", seq="ACGTACGT"):
     return bammodel.bam_record(name, flag, ref, pos, 60, [("M", len(seq))], seq, aux=aux)
 
@@ -148,6 +155,83 @@ def test_segment_size_only_call_then_write(pkg, gpu_ctx):
     assert bam[:start].tobytes() + out.tobytes() == want and len(missing) == len(miss) and unmapped == 2
     assert set(t.stage_ms()) == {"key", "build", "probe", "size", "assemble"}
     t.close()
+
+
+# ---- K-TAG-ASM through lib.TagBam.segment: what the rewrite shared with K-EDIT (smi_auxedit.h) must keep ----------------------------------
+FASTQ_AB = tm.fastq_text([("a", "ACGT", "IIII"), ("b", "GG", "##")])
+
+
+def _attrs(n, first=0):
+    """n distinct one-byte integer attributes (lower-case tags: none is US or QS)"""
+    return b"".join(tm.aux_int("%c%c" % (ord("a") + k // 26, ord("a") + k % 26), "C", k % 200) for k in range(first, first + n))
+
+
+def _segment(lib, ctx, records, qv="QS", fastq=FASTQ_AB):
+    """records through one TagBam.segment -> (what the model writes for them, the records written, missing, unmapped, stage ms)"""
+    bam = np.frombuffer(bammodel.bam_bytes(HEAD_TEXT, REFS, records), dtype=np.uint8).copy()
+    _t, _r, start = lib.bam_header(bam)
+    recs, _end = lib.bam_index_records(bam, start, cap=len(records) + 1)
+    assert len(recs) == len(records)
+    t = lib.TagBam(ctx, fastq, "US", qv)
+    try:
+        out, missing, unmapped = t.segment(bam, recs)
+        want = tm.tag_bam(fastq, bam.tobytes(), "US", qv)[0][start:]      # (behind the call: the model has no limit and no error of its own)
+        return want, out.tobytes(), list(missing), unmapped, t.stage_ms()
+    finally:
+        t.close()
+
+
+@pytest.mark.parametrize("qv, n_in", [("QS", 62), (None, 63)])
+def test_attribute_limit_is_reached_with_the_new_tags(lib, gpu_ctx, qv, n_in):
+    """64 attributes are written, the 65th is the error -- counted after US (and QS) are added"""
+    plain = _rec("b", aux=tm.aux_int("NM", "i", 2))
+    want, got, _m, _u, _ms = _segment(lib, gpu_ctx, [plain, _rec("a", aux=_attrs(n_in)), plain], qv)
+    assert got == want
+    with pytest.raises(lib.SmiError, match="smi_tagbam_segment: a record's attributes cannot be rewritten: more than 64 attributes;"):
+        _segment(lib, gpu_ctx, [plain, _rec("a", aux=_attrs(n_in + 1)), plain], qv)
+
+
+def test_attribute_limit_counts_a_tag_once(lib, gpu_ctx):
+    """stale US / QS among 64 inputs are replaced, not added; a tag repeated in the input counts once"""
+    stale = _attrs(31) + tm.aux_z("US", "stale") + _attrs(31, first=31) + tm.aux_z("QS", "old")
+    repeated = _attrs(62) + _attrs(62) + tm.aux_int("aa", "i", -70000)       # 125 fields, 62 tags
+    want, got, _m, _u, _ms = _segment(lib, gpu_ctx, [_rec("a", aux=stale), _rec("b", aux=repeated)])
+    assert got == want
+    with pytest.raises(lib.SmiError, match="more than 64 attributes"):
+        _segment(lib, gpu_ctx, [_rec("b", aux=_attrs(63) + _attrs(63))])
+
+
+@pytest.mark.parametrize("aux", [_attrs(70), tm.aux_h("XH", "abc")], ids=["70_attributes", "odd_hex"])
+def test_a_dropped_record_is_never_parsed(lib, gpu_ctx, aux):
+    """a record without a reference and one whose name the FASTQ lacks are dropped before their attributes are looked at: attributes that
+    would be an error in a written record are none here"""
+    good = _rec("a", aux=tm.aux_z("US", "stale") + tm.aux_int("NM", "i", 2))
+    records = [good, _rec("a", flag=4, ref=-1, pos=-1, aux=aux), _rec("b"), _rec("absent", aux=aux), good]
+    want, got, missing, unmapped, _ms = _segment(lib, gpu_ctx, records)
+    assert got == want and missing == [3] and unmapped == 1
+    assert len(bammodel.parse_bam(bammodel.bam_bytes(HEAD_TEXT, REFS, []) + got)[2]) == 3
+    with pytest.raises(lib.SmiError, match="cannot be rewritten"):            # the same attributes on a record that is written
+        _segment(lib, gpu_ctx, [good, _rec("b", aux=aux)])
+
+
+def test_all_records_dropped_and_empty_segment(lib, gpu_ctx):
+    """nothing to write: total 0 and no WRITE launch (its stage time stays 0); n == 0 through the two-call protocol"""
+    want, got, missing, unmapped, ms = _segment(lib, gpu_ctx, [_rec("a", flag=4, ref=-1, pos=-1), _rec("absent"), _rec("b", ref=-1)])
+    assert want == b"" and got == b"" and missing == [1] and unmapped == 2 and ms["assemble"] == 0.0 and ms["size"] > 0.0
+    want, got, missing, unmapped, ms = _segment(lib, gpu_ctx, [])
+    assert want == b"" and got == b"" and missing == [] and unmapped == 0 and ms["assemble"] == 0.0
+    import ctypes
+
+    t = lib.TagBam(gpu_ctx, FASTQ_AB, "US", "QS")
+    try:
+        n_out, n_miss, n_unm = ctypes.c_size_t(7), ctypes.c_int32(7), ctypes.c_int32(7)
+        buf = np.zeros(16, dtype=np.uint8)
+        for out, cap in ((None, 0), (buf.ctypes.data, buf.size)):              # sizes first, then the same arguments with a buffer
+            assert t._lib.smi_tagbam_segment(t._h, None, 0, None, 0, out, cap, ctypes.byref(n_out), None, ctypes.byref(n_miss), ctypes.byref(n_unm)) == 0
+            assert (n_out.value, n_miss.value, n_unm.value) == (0, 0, 0)
+        assert t.stage_ms()["assemble"] == 0.0
+    finally:
+        t.close()
 
 
 # sicelore-nf/main.nf:116, verbatim

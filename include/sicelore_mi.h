@@ -1333,8 +1333,8 @@ int smi_dedup_error_line(const smi_dedup *h, int64_t *line);
 int smi_dedup_free(smi_dedup *h);
 
 /* ---- CollapseModel (K-COLLAPSE, K-COLSTAT, K-FILTER / K-CLASS, smi_collapse.hip) --------------------------------------------------------
- * CollapseModel.process (CollapseModel.java:L151-193) without the validator, DESIGN.md section 8h: novel isoforms from the IT = undef records
- * of an ISOBAM.
+ * CollapseModel.process (CollapseModel.java:L151-193), DESIGN.md section 8h (the validator: smi_collapse_validate_*, below): novel isoforms
+ * from the IT = undef records of an ISOBAM.
  * smi_collapse_default_config: the defaults of CollapseModel.java:L28-57 (MINEVIDENCE 2, GENETAG IG).
  * smi_collapse_create: the refFlat text (UCSCRefFlatParser(File) L48-80 over TranscriptRecord.fromRefFlat L92-164; a line of fewer than 11
  * fields, with a bad integer or strand fails the call naming the line) and the CSV cell list (CellList.java:L15-27, "-1" removed).
@@ -1413,6 +1413,56 @@ int smi_collapse_free(smi_collapse *h);
 /* after smi_collapse_run: collapse() L639-671 as the reference runs it, one host thread over the arrays K-COLLAPSE was given: its wall time
  * (the baseline tools/microbench.py reports beside K-COLLAPSE) and the number of undef records whose founder differs from the device's (0) */
 int smi_collapse_host_loop(const smi_collapse *h, double *seconds, int64_t *mismatches);
+
+/* ---- the validator of CollapseModel (K-JSUP, smi_collapse.hip) ---------------------------------------------------------------------------
+ * UCSCRefFlatParser.validator L279-366 over BEDParser (BEDParser.java L27-119), run by CollapseModel.process L166-171 when CAGE, POLYA and
+ * SHORT all exist; DESIGN.md section 8h.  The three calls come after smi_collapse_run, in this order, once.
+ * smi_collapse_validate_begin: the CAGE and POLYA texts through BEDCodec(StartOffset.ZERO).decode (htsjdk-4.1.3, BEDCodec L82-198: blank,
+ * "#", "track" and "browser" lines and lines of fewer than two tokens give no feature; tokens split on a tab or a run of spaces; start
+ * token 2, end token 3 or the start, strand the first character of token 6; a score Float.parseFloat refuses ends the line's parse with
+ * strand NONE); a line the reference's constructor would stop at (L57: a start, end or block column that is no integer, fewer block sizes or
+ * starts than blocks, a colour of fewer than three parts or outside 0 .. 255) fails the call naming it ("CAGE line N" / "POLYA line N"), and
+ * so does a start or end beyond +-2^30.  getDistanceCage L68-91 / getDistancePolyA L97-119 for every transcript smi_collapse_run printed
+ * (two binary searches per transcript over the features of its chromosome and strand; equal distances go to the earlier line), the cut-offs
+ * of validator L306-308.  short_ref_names: the @SQ names of SHORT in dictionary order; a chromosome SHORT does not name has support 0
+ * (BAMFileReader answers reference index -1 with an empty iterator).  The distinct (reference of SHORT, donor, acceptor) of all
+ * novelJunctions go into a table on the device of 2^table_log2 slots, or with table_log2 == 0 the power of two that is at least twice
+ * their number (at least 16); a table of fewer slots than keys is refused.
+ * smi_collapse_validate_segment: one inflated segment of SHORT with its smi_bam_index_records index; K-JSUP counts, per key, the records
+ * whose alignment blocks (SAMUtils.getAlignmentBlocks L726-762) have that boundary exactly (validator L325-339, isIn with delta 0).  No
+ * flag but 0x4 and no mapping quality is looked at; a record with flag 0x4 supports nothing.  The CIGAR is the one in the record's fixed
+ * part: a CG attribute is not read, as smi_longread.h does not read it.
+ * smi_collapse_validate_end: the counters back, junctionReads / is_valid_junction / is_valid per transcript (L310-361), and the five texts
+ * rendered again: smi_collapse_output then returns the validated ones.  stage_ms (may be NULL): K-JSUP's device time over all segments.
+ * smi_collapse_validate_counts: SMI_COLLAPSE_VALIDATE_COUNTS entries, SMI_CVAL_*; those up to SMI_CVAL_NSS_EV are the valid_set column of
+ * statistics L568-591 and hold the known transcripts alone until smi_collapse_validate_end. */
+#define SMI_CVAL_ISOFORMS 0          /* valid set: known transcripts and novels with is_valid, then their UMIs */
+#define SMI_CVAL_EVIDENCES 1
+#define SMI_CVAL_GENCODE 2
+#define SMI_CVAL_GENCODE_EV 3
+#define SMI_CVAL_CKJ 4
+#define SMI_CVAL_CKJ_EV 5
+#define SMI_CVAL_CKS 6
+#define SMI_CVAL_CKS_EV 7
+#define SMI_CVAL_NSS 8
+#define SMI_CVAL_NSS_EV 9
+#define SMI_CVAL_SHORT_RECORDS 10    /* records of SHORT seen */
+#define SMI_CVAL_SHORT_BOUNDARIES 11 /* block boundaries looked up: of records without flag 0x4 on a reference that carries a key, a
+                                         boundary equal to the record's previous one not counted */
+#define SMI_CVAL_JUNCTION_KEYS 12    /* distinct (reference of SHORT, donor, acceptor) */
+#define SMI_CVAL_JUNCTION_HITS 13    /* look-ups that hit: the sum of the supports over the keys */
+#define SMI_CVAL_TABLE_SLOTS 14
+#define SMI_CVAL_CAGE_REFERENCES 15  /* BEDParser's message: [references=N,entries=M] */
+#define SMI_CVAL_CAGE_ENTRIES 16
+#define SMI_CVAL_POLYA_REFERENCES 17
+#define SMI_CVAL_POLYA_ENTRIES 18
+#define SMI_COLLAPSE_VALIDATE_COUNTS 19
+int smi_collapse_validate_begin(smi_collapse *h, const char *cage, size_t n_cage, const char *polya, size_t n_polya,
+                                const char *const *short_ref_names, int32_t n_refs, int32_t cage_co, int32_t polya_co, int32_t junc_co,
+                                int32_t table_log2);
+int smi_collapse_validate_segment(smi_collapse *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n);
+int smi_collapse_validate_end(smi_collapse *h, float *stage_ms);
+int smi_collapse_validate_counts(const smi_collapse *h, int64_t *counts);
 
 /* ---- FusionDetector (K-FUS-INSERT, K-FUS-READ, K-FUS-MOL, K-FUS-GENES, smi_fusion.hip) ---------------------------------------------------
  * FusionDetector.doWork (FusionDetector.java:L54-113), DESIGN.md section 8i: the molecules of a tagged BAM with exactly two gene names,

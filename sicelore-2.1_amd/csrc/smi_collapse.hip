@@ -20,13 +20,17 @@
 // K-FILTER / K-CLASS: one wavefront per gene: filter L243-263 with isPartOfLonger L429-460 over the list the host sorted (Collections.sort
 //   by TranscriptRecord.compareTo L85-90, stable), and noveltyDetector L379-427 for every novel it keeps.
 // Host again: statistics L535-592 as counters, exportFiles L595-637 over printLegendTxt / printTxt / printRefflat / printGff
-//   (TranscriptRecord.java L248-327).
+//   (TranscriptRecord.java L248-327): one renderer over the kept transcripts.
+// The validator (validator L279-366 over BEDParser.java, smi_collapse_validate_*): the BED texts and both distances per transcript on the
+//   host; K-JSUP: one lane per record of the short-read BAM, every alignment-block boundary looked up in a device table of the novel
+//   junctions; then the validator's fields per transcript and the five texts again.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <chrono>
 #include <climits>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <string_view>
 #include <thread>
@@ -251,6 +255,80 @@ __global__ __launch_bounds__(64 * kFcWaves) void k_filter_class(FcArgs a) {
     }
 }
 
+// K-JSUP: the junction support of UCSCRefFlatParser.validator L321-345 for every novel junction at once.  One lane per record of SHORT: the
+// alignment blocks of SAMRecord.getAlignmentBlocks (M / = / X, zero-length ones included; I / S move the read, D / N the reference, H / P
+// nothing) are walked keeping the previous block's end, and every boundary (last base of the previous block, first base of the next,
+// 1-based) that differs from the lane's previous one is looked up in the table of (SHORT reference id, donor, acceptor) keys: open
+// addressing, linear probing, wrapping.  A hit is one atomic add whose result nobody reads.  The keys never change while the kernel runs,
+// so they are read with plain loads; the counters live in an array of their own.  A record with flag 0x4 supports nothing.
+__host__ __device__ __forceinline__ uint32_t jsup_hash(int32_t ref, int32_t donor, int32_t acceptor) {
+    uint32_t h = (uint32_t)ref * 0x9E3779B1u ^ (uint32_t)donor * 0x85EBCA77u ^ (uint32_t)acceptor * 0xC2B2AE3Du;
+    h ^= h >> 15;
+    h *= 0x2C1B3C6Du;
+    return h ^ h >> 12;
+}
+
+struct JsupArgs {
+    const uint8_t *bam;
+    const uint64_t *rec_off;    // n: offset of the record's block_size word
+    int32_t n, n_ref;
+    const uint8_t *ref_keys;    // n_ref: 1 = some key lies on this reference of SHORT
+    const int4 *keys;           // mask + 1 slots: (reference, donor, acceptor, 0); reference -1 = empty
+    uint32_t mask;
+    uint32_t *count;            // mask + 1
+    unsigned long long *boundaries;
+};
+
+__global__ __launch_bounds__(256) void k_jsup(JsupArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t looked = 0;
+    if (i < a.n) {
+        const uint8_t *r = a.bam + a.rec_off[i];
+        int32_t ref, pos;
+        uint32_t w;
+        __builtin_memcpy(&ref, r + 4, 4);
+        __builtin_memcpy(&pos, r + 8, 4);
+        __builtin_memcpy(&w, r + 16, 4);  // n_cigar_op, flag
+        const uint32_t n_op = w & 0xffff;
+        if (n_op >= 2 && !(w >> 16 & 4) && (uint32_t)ref < (uint32_t)a.n_ref && a.ref_keys[ref]) {
+            const uint8_t *cg = r + 36 + r[12];
+            uint32_t at = (uint32_t)pos + 1;  // the reference base the next operation starts on (int arithmetic, as the reference's)
+            uint32_t prev_end = 0, last_d = 0, last_a = 0;
+            bool block = false, have_last = false;
+            for (uint32_t k = 0; k < n_op; k++) {
+                uint32_t c;
+                __builtin_memcpy(&c, cg + 4 * k, 4);
+                const uint32_t op = c & 15, len = c >> 4;
+                if (op == 0 || op == 7 || op == 8) {
+                    if (block && !(have_last && last_d == prev_end && last_a == at)) {
+                        last_d = prev_end;
+                        last_a = at;
+                        have_last = true;
+                        looked++;
+                        uint32_t s = jsup_hash(ref, (int32_t)last_d, (int32_t)last_a) & a.mask;
+                        for (uint32_t step = 0; step <= a.mask; step++) {
+                            const int4 e = a.keys[s];
+                            if (e.x < 0) break;
+                            if (e.x == ref && e.y == (int32_t)last_d && e.z == (int32_t)last_a) {
+                                atomicAdd(&a.count[s], 1u);
+                                break;
+                            }
+                            s = (s + 1) & a.mask;
+                        }
+                    }
+                    prev_end = at + len - 1;
+                    block = true;
+                    at += len;
+                } else if (op == 2 || op == 3) {
+                    at += len;
+                }
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) looked += __shfl_xor(looked, o);
+    if ((threadIdx.x & 63) == 0 && looked) atomicAdd(a.boundaries, (unsigned long long)looked);
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
 using lr::Aux;
 using lr::drop_minus1;
@@ -352,6 +430,45 @@ struct TagSet {
     uint16_t cell, umi, gene, iso, rn, de, df;
 };
 
+// one transcript of the output, as exportFiles prints it
+struct OutTx {
+    int32_t gene;  // index into smi_collapse::genes
+    std::string tname, chrom;
+    bool neg, known;
+    int32_t cat;  // of a novel: 0 known junctions, 1 known splice sites, 2 a novel splice site
+    int32_t s0, s1, c0, c1, umis, cells;
+    std::vector<int32_t> xs, xe;
+    std::vector<int2> nov;  // novelJunctions
+    // the validator's fields, TranscriptRecord's defaults (L46-52) until smi_collapse_validate_end sets them
+    int32_t junction_reads = 0, dist_cage = 0, dist_polya = 0;
+    bool v_junction = false, v_cage = false, v_polya = false, valid = false;
+};
+
+// BEDParser: per chromosome and strand the features' pp (start for +, end for -), sorted, the smallest line per equal pp
+struct BedSide {
+    std::vector<int32_t> pp, idx;
+};
+struct Bed {
+    std::unordered_map<std::string, BedSide> side[2];  // + / -
+    int64_t references = 0, entries = 0;
+};
+
+struct Validator {
+    Bed cage, polya;
+    int32_t cage_co = 50, polya_co = 50, junc_co = 1;
+    std::vector<int4> keys;                     // the table as uploaded
+    std::vector<int32_t> tx_k_off{0}, tx_slot;  // per output transcript: the slots of its novel junctions, -1 = chromosome not in SHORT
+    std::vector<uint8_t> ref_keys;
+    DevBuf<int4> d_keys;
+    DevBuf<uint32_t> d_count;
+    DevBuf<uint8_t> d_ref_keys;
+    DevBuf<unsigned long long> d_bound;
+    uint32_t mask = 0;
+    int32_t n_ref = 0;
+    float ms = 0.f;
+    bool ended = false;
+};
+
 }  // namespace
 }  // namespace smi
 
@@ -379,6 +496,9 @@ struct smi_collapse {
     // K-COLLAPSE's input and result, kept for smi_collapse_host_loop
     std::vector<int32_t> k_cg_off, k_u_j_off, k_u_founder;
     std::vector<int2> k_uj;
+    std::vector<OutTx> txs;  // what smi_collapse_run kept, in output order
+    std::unique_ptr<Validator> val;
+    int64_t vcounts[SMI_COLLAPSE_VALIDATE_COUNTS] = {};
 };
 
 namespace smi {
@@ -469,6 +589,209 @@ void parse_record(const uint8_t *bam, const smi_bam_record &r, const smi_collaps
 }
 
 void append_int(std::string &s, int64_t v) { s += std::to_string(v); }
+
+// Float.parseFloat as BEDCodec L161 calls it, for the decimal forms: white space trimmed, a sign, "NaN", "Infinity", or digits with an
+// optional point, an optional exponent and an optional f / F / d / D.  (A hexadecimal floating literal is taken as malformed here.)
+bool java_float_ok(std::string_view s) {
+    while (!s.empty() && (unsigned char)s.front() <= ' ') s.remove_prefix(1);
+    while (!s.empty() && (unsigned char)s.back() <= ' ') s.remove_suffix(1);
+    if (!s.empty() && (s[0] == '+' || s[0] == '-')) s.remove_prefix(1);
+    if (s == "NaN" || s == "Infinity") return true;
+    size_t i = 0, digits = 0;
+    while (i < s.size() && s[i] >= '0' && s[i] <= '9') i++, digits++;
+    if (i < s.size() && s[i] == '.') {
+        i++;
+        while (i < s.size() && s[i] >= '0' && s[i] <= '9') i++, digits++;
+    }
+    if (!digits) return false;
+    if (i < s.size() && (s[i] == 'e' || s[i] == 'E')) {
+        i++;
+        if (i < s.size() && (s[i] == '+' || s[i] == '-')) i++;
+        size_t ed = 0;
+        while (i < s.size() && s[i] >= '0' && s[i] <= '9') i++, ed++;
+        if (!ed) return false;
+    }
+    if (i < s.size() && (s[i] == 'f' || s[i] == 'F' || s[i] == 'd' || s[i] == 'D')) i++;
+    return i == s.size();
+}
+
+// BEDParser(File) L27-60 over BEDCodec(StartOffset.ZERO).decode, line by line as AsciiLineReader cuts them (\n, \r\n or \r)
+int parse_bed(const char *text, size_t n, const char *what, Bed &B) {
+    std::unordered_map<std::string, int> chroms;
+    size_t b = 0;
+    int64_t lineno = 0;
+    int32_t idx = 0;
+    while (b < n) {
+        size_t e = b;
+        while (e < n && text[e] != '\n' && text[e] != '\r') e++;
+        const std::string_view line(text + b, e - b);
+        if (e < n && text[e] == '\r' && e + 1 < n && text[e + 1] == '\n') e++;
+        b = e + 1;
+        lineno++;
+        auto fail = [&](const std::string &why) {
+            set_error(std::string("CollapseModel: ") + what + " line " + std::to_string(lineno) + ": " + why);
+            return SMI_ERR_INVALID;
+        };
+        bool blank = true;
+        for (char ch : line) blank &= (unsigned char)ch <= ' ';
+        if (blank || line[0] == '#' || line.substr(0, 5) == "track" || line.substr(0, 7) == "browser") continue;
+        std::vector<std::string_view> tk;  // Pattern "\t|( +)", split(line, -1)
+        size_t t0 = 0;
+        for (size_t i = 0; i < line.size();) {
+            if (line[i] != '\t' && line[i] != ' ') {
+                i++;
+                continue;
+            }
+            tk.push_back(line.substr(t0, i - t0));
+            if (line[i] == '\t') i++;
+            else
+                while (i < line.size() && line[i] == ' ') i++;
+            t0 = i;
+        }
+        tk.push_back(line.substr(t0));
+        if (tk.size() < 2) continue;
+        int32_t start, end;
+        if (!jint(tk[1], start)) return fail("the start is not an integer");
+        end = start;
+        if (tk.size() > 2 && !jint(tk[2], end)) return fail("the end is not an integer");
+        if (std::abs((int64_t)start) > (1 << 30) || std::abs((int64_t)end) > (1 << 30)) return fail("a start or end beyond 2^30");
+        int strand = -1;  // NONE
+        const bool scored = tk.size() <= 4 || java_float_ok(tk[4]);  // a NumberFormatException returns the feature as it is (L163-168)
+        if (scored) {
+            if (tk.size() > 5) {
+                std::string_view st = tk[5];
+                while (!st.empty() && (unsigned char)st.front() <= ' ') st.remove_prefix(1);
+                strand = st.empty() ? -1 : st[0] == '+' ? 0 : st[0] == '-' ? 1 : -1;
+            }
+            if (tk.size() > 8 && tk[8].find(',') != std::string_view::npos) {  // ParsingUtils.parseColor L369-374
+                const auto rgb = jsplit(tk[8], ',');
+                int32_t v[3];
+                bool number = true;
+                for (size_t k = 0; k < 3 && number; k++) {
+                    if (k >= rgb.size()) return fail("a colour of fewer than three parts");
+                    number = jint(rgb[k], v[k]);  // a NumberFormatException gives black
+                }
+                if (number && (v[0] < 0 || v[0] > 255 || v[1] < 0 || v[1] > 255 || v[2] < 0 || v[2] > 255))
+                    return fail("a colour part outside 0 .. 255");
+            }
+            if (tk.size() > 11) {  // createExons L209-231
+                int32_t x, count;
+                if (!jint(tk[6], x) || !jint(tk[7], x)) return fail("thickStart or thickEnd is not an integer");
+                if (!jint(tk[9], count) || count < 0) return fail("the block count is not a count");
+                for (int c = 11; c >= 10; c--) {
+                    const auto parts = jsplit(tk[c], ',');
+                    for (int32_t k = 0; k < count; k++)
+                        if ((size_t)k >= parts.size() || !jint(parts[k], x)) return fail("fewer block sizes or starts than blocks, or one that is no integer");
+                }
+            }
+        }
+        const std::string chr(tk[0]);
+        chroms.emplace(chr, 0);
+        if (strand >= 0) {
+            BedSide &S = B.side[strand][chr];
+            S.pp.push_back(strand ? end : start);
+            S.idx.push_back(idx);
+        }
+        idx++;
+    }
+    B.references = (int64_t)chroms.size();
+    B.entries = idx;
+    for (auto &side : B.side)
+        for (auto &kv : side) {
+            BedSide &S = kv.second;
+            std::vector<int32_t> ord(S.pp.size());
+            for (size_t i = 0; i < ord.size(); i++) ord[i] = (int32_t)i;
+            std::sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return S.pp[x] != S.pp[y] ? S.pp[x] < S.pp[y] : S.idx[x] < S.idx[y]; });
+            BedSide T;
+            for (int32_t o : ord)
+                if (T.pp.empty() || T.pp.back() != S.pp[o]) {  // the smallest line of an equal pp
+                    T.pp.push_back(S.pp[o]);
+                    T.idx.push_back(S.idx[o]);
+                }
+            S = std::move(T);
+        }
+    return SMI_OK;
+}
+
+// getDistanceCage L68-91 = getDistancePolyA L97-119: the first feature in file order of the smallest |pos - pp|
+int32_t bed_distance(const Bed &B, const std::string &chrom, bool neg, int32_t pos) {
+    int64_t min = INT32_MAX, minabs = INT32_MAX;
+    const auto it = B.side[neg].find(chrom);
+    if (it != B.side[neg].end()) {
+        const BedSide &S = it->second;
+        const size_t r = std::lower_bound(S.pp.begin(), S.pp.end(), pos) - S.pp.begin();
+        int32_t best = -1;
+        for (size_t k = r ? r - 1 : r; k <= r && k < S.pp.size(); k++) {
+            const int64_t d = (int64_t)pos - S.pp[k], ad = d < 0 ? -d : d;
+            if (ad < minabs || (best >= 0 && ad == minabs && S.idx[k] < best)) {
+                min = d;
+                minabs = ad;
+                best = S.idx[k];
+            }
+        }
+    }
+    return (int32_t)(neg ? min : -min);
+}
+
+// exportFiles L595-637 over printLegendTxt / printTxt / printRefflat / printGff (TranscriptRecord.java L248-327), and the valid set of
+// statistics L568-576: the known transcripts and the novels with is_valid
+void render(smi_collapse *h) {
+    static const char *kSub[] = {"combination_of_known_junctions", "combination_of_known_splicesites", "at_least_one_novel_splicesite"};
+    static const char *kCol[] = {"#9dd122", "#c594e1", "#e65802"};
+    std::string &txt = h->out[SMI_COL_OUT_TXT], &flat = h->out[SMI_COL_OUT_REFFLAT], &flatv = h->out[SMI_COL_OUT_FINAL_REFFLAT];
+    std::string &gff = h->out[SMI_COL_OUT_GFF], &gffv = h->out[SMI_COL_OUT_FINAL_GFF];
+    for (std::string &o : h->out) o.clear();
+    txt = "geneId\ttranscriptId\tchrom\tstrand\ttxStart\ttxEnd\texons\tUMIs\tCells\tcategorie\tsubcategorie\tnovelJunctions"
+          "\tnovelJunctions_reads\tis_valid_allNovelJunctions\tdist_cage\tis_valid_cage\tdist_polya\tis_valid_polya\tis_valid\n";
+    int64_t *v = h->vcounts;
+    for (int k = SMI_CVAL_ISOFORMS; k <= SMI_CVAL_NSS_EV; k++) v[k] = 0;
+    auto tf = [](bool b) { return b ? "true" : "false"; };
+    std::string one_flat, one_gff;
+    for (const OutTx &t : h->txs) {
+        const std::string &gname = h->genes[t.gene];
+        const char *strand = t.neg ? "-" : "+";
+        const std::string categorie = t.known ? "full_splice_match" : t.cat == 2 ? "novel_not_in_catalog" : "novel_in_catalog";
+        const std::string sub = t.known ? "gencode" : kSub[t.cat];
+        const std::string color = t.known ? "#014e8e" : kCol[t.cat];
+        std::string nov;
+        for (const int2 &j : t.nov) nov += (nov.empty() ? "" : ",") + std::to_string(j.x) + "-" + std::to_string(j.y);
+        if (nov.empty()) nov = "-";
+        const std::string umis = std::to_string(t.umis), cells = std::to_string(t.cells);
+        const std::string head = gname + "\t" + t.tname + "\t" + t.chrom + "\t" + strand + "\t" + std::to_string(t.s0) + "\t" + std::to_string(t.s1) + "\t";
+        txt += head + std::to_string(t.xs.size()) + "\t" + umis + "\t" + cells + "\t" + categorie + "\t" + sub + "\t" + nov + "\t" +
+               std::to_string(t.junction_reads) + "\t" + tf(t.v_junction) + "\t" + std::to_string(t.dist_cage) + "\t" + tf(t.v_cage) + "\t" +
+               std::to_string(t.dist_polya) + "\t" + tf(t.v_polya) + "\t" + tf(t.valid) + "\n";
+        one_flat = head + std::to_string(t.c0) + "\t" + std::to_string(t.c1) + "\t" + std::to_string(t.xs.size()) + "\t";
+        for (int32_t x : t.xs) {
+            append_int(one_flat, (int64_t)x - 1);
+            one_flat += ',';
+        }
+        one_flat += '\t';
+        for (int32_t x : t.xe) {
+            append_int(one_flat, x);
+            one_flat += ',';
+        }
+        one_flat += '\n';
+        const std::string ids = "gene_id \"" + gname + "\"; transcript_id \"" + t.tname + "\";";
+        one_gff = t.chrom + "\tsicelore\ttranscript\t" + std::to_string(t.s0) + "\t" + std::to_string(t.s1) + "\t.\t" + strand + "\t.\t" + ids +
+                  " category \"" + categorie + "\"; subcategory \"" + sub + "\"; UMIs \"" + umis + "\"; Cells \"" + cells + "\"; novelJunctions \"" +
+                  nov + "\"; supportingReads \"" + std::to_string(t.junction_reads) + "\"; CAGEdist \"" + std::to_string(t.dist_cage) +
+                  "\"; POLYAdist \"" + std::to_string(t.dist_polya) + "\"; color \"" + color + "\";\n";
+        for (size_t k = 0; k < t.xs.size(); k++)
+            one_gff += t.chrom + "\tsicelore\texon\t" + std::to_string(t.xs[k]) + "\t" + std::to_string(t.xe[k]) + "\t.\t" + strand + "\t.\t" + ids + "\n";
+        flat += one_flat;
+        gff += one_gff;
+        if (t.known || t.valid) {
+            flatv += one_flat;
+            gffv += one_gff;
+            const int k = t.known ? SMI_CVAL_GENCODE : SMI_CVAL_CKJ + 2 * t.cat;
+            v[SMI_CVAL_ISOFORMS]++;
+            v[SMI_CVAL_EVIDENCES] += t.umis;
+            v[k]++;
+            v[k + 1] += t.umis;
+        }
+    }
+}
 
 }  // namespace
 }  // namespace smi
@@ -895,104 +1218,243 @@ extern "C" int smi_collapse_run(smi_collapse *h, float *stage_ms) {
         SMI_HIP(hipMemcpy(cat.data(), d_cat.p, (size_t)nE * 4, hipMemcpyDeviceToHost));
         if (n_kind) SMI_HIP(hipMemcpy(kind.data(), d_kind.p, (size_t)n_kind, hipMemcpyDeviceToHost));
     }
-    // exportFiles: genes in byte order, a gene's transcripts in the filter's order
-    static const char *kSub[] = {"combination_of_known_junctions", "combination_of_known_splicesites", "at_least_one_novel_splicesite"};
-    static const char *kCol[] = {"#9dd122", "#c594e1", "#e65802"};
-    std::string &txt = h->out[SMI_COL_OUT_TXT], &flat = h->out[SMI_COL_OUT_REFFLAT], &flatv = h->out[SMI_COL_OUT_FINAL_REFFLAT];
-    std::string &gff = h->out[SMI_COL_OUT_GFF], &gffv = h->out[SMI_COL_OUT_FINAL_GFF];
-    txt = "geneId\ttranscriptId\tchrom\tstrand\ttxStart\ttxEnd\texons\tUMIs\tCells\tcategorie\tsubcategorie\tnovelJunctions"
-          "\tnovelJunctions_reads\tis_valid_allNovelJunctions\tdist_cage\tis_valid_cage\tdist_polya\tis_valid_polya\tis_valid\n";
-    std::vector<int32_t> xs, xe;
-    std::string one_flat, one_gff;
+    // the transcripts exportFiles prints: genes in byte order, a gene's transcripts in the filter's order
     for (int32_t g = 0; g < nG; g++) {
-        const std::string &gname = h->genes[gord[g]];
         for (int32_t e = e_off[g]; e < e_off[g + 1]; e++) {
             if (!keep[e]) {
                 c[SMI_COL_NOVEL_FILTERED]++;
                 continue;
             }
             const int32_t t = e_t[e];
-            const bool known = e_known[e];
             const int32_t last = ev[t_last[t]];  // chromosome and strand of the LAST evidence record, for known transcripts too
-            const std::string chrom = h->r_ref[last] < (int32_t)h->refs.size() ? h->refs[h->r_ref[last]] : std::string("*");
-            const char *strand = h->r_neg[last] ? "-" : "+";
-            std::string tname, categorie, sub, color, nov;
-            int32_t s0, s1, c0, c1;
-            xs.clear();
-            xe.clear();
-            if (known) {
+            OutTx o;
+            o.gene = gord[g];
+            o.known = e_known[e];
+            o.chrom = h->r_ref[last] < (int32_t)h->refs.size() ? h->refs[h->r_ref[last]] : std::string("*");
+            o.neg = h->r_neg[last];
+            o.cat = 0;
+            if (o.known) {
                 const Line &L = M.lines[slot_line[t]];
-                tname = L.tx;
-                categorie = "full_splice_match";
-                sub = "gencode";
-                color = "#014e8e";
-                s0 = L.tx_start;
-                s1 = L.tx_end;
-                c0 = L.cds_start;
-                c1 = L.cds_end;
+                o.tname = L.tx;
+                o.s0 = L.tx_start;
+                o.s1 = L.tx_end;
+                o.c0 = L.cds_start;
+                o.c1 = L.cds_end;
                 for (size_t k = 0; k < L.xs.size(); k++) {
-                    xs.push_back(L.xs[k] + 1);
-                    xe.push_back(L.xe[k]);
+                    o.xs.push_back(L.xs[k] + 1);
+                    o.xe.push_back(L.xe[k]);
                 }
                 c[SMI_COL_GENCODE]++;
                 c[SMI_COL_GENCODE_EV] += t_count[t];
             } else {
                 const int32_t f = t - n_slots, u = f_u[f];
-                tname = "Novel." + std::to_string(f + 1);
-                categorie = cat[e] == 2 ? "novel_not_in_catalog" : "novel_in_catalog";
-                sub = kSub[cat[e]];
-                color = kCol[cat[e]];
-                s0 = c0 = t_min[t];
-                s1 = c1 = t_max[t];
+                o.tname = "Novel." + std::to_string(f + 1);
+                o.cat = cat[e];
+                o.s0 = o.c0 = t_min[t];
+                o.s1 = o.c1 = t_max[t];
                 const int2 *j = uj.data() + u_j_off[u];
                 const int32_t nj = e_nj[e];
-                xs.push_back(s0);
+                o.xs.push_back(o.s0);
                 for (int32_t k = 0; k < nj; k++) {
-                    xe.push_back(j[k].x);
-                    xs.push_back(j[k].y);
-                    if (kind[e_k_off[e] + k]) nov += (nov.empty() ? "" : ",") + std::to_string(j[k].x) + "-" + std::to_string(j[k].y);
+                    o.xe.push_back(j[k].x);
+                    o.xs.push_back(j[k].y);
+                    if (kind[e_k_off[e] + k]) o.nov.push_back(j[k]);
                 }
-                xe.push_back(s1);
+                o.xe.push_back(o.s1);
                 c[SMI_COL_CKJ + 2 * cat[e]]++;
                 c[SMI_COL_CKJ_EV + 2 * cat[e]] += t_count[t];
             }
-            if (nov.empty()) nov = "-";
             c[SMI_COL_ISOFORMS]++;
             c[SMI_COL_EVIDENCES] += t_count[t];
-            const std::string umis = std::to_string(t_count[t]), cells = std::to_string(t_cells[t]);
-            const std::string head = gname + "\t" + tname + "\t" + chrom + "\t" + strand + "\t" + std::to_string(s0) + "\t" + std::to_string(s1) + "\t";
-            txt += head + std::to_string(xs.size()) + "\t" + umis + "\t" + cells + "\t" + categorie + "\t" + sub + "\t" + nov +
-                   "\t0\tfalse\t0\tfalse\t0\tfalse\tfalse\n";
-            one_flat = head + std::to_string(c0) + "\t" + std::to_string(c1) + "\t" + std::to_string(xs.size()) + "\t";
-            for (int32_t x : xs) {
-                append_int(one_flat, (int64_t)x - 1);
-                one_flat += ',';
-            }
-            one_flat += '\t';
-            for (int32_t x : xe) {
-                append_int(one_flat, x);
-                one_flat += ',';
-            }
-            one_flat += '\n';
-            const std::string ids = "gene_id \"" + gname + "\"; transcript_id \"" + tname + "\";";
-            one_gff = chrom + "\tsicelore\ttranscript\t" + std::to_string(s0) + "\t" + std::to_string(s1) + "\t.\t" + strand + "\t.\t" + ids +
-                      " category \"" + categorie + "\"; subcategory \"" + sub + "\"; UMIs \"" + umis + "\"; Cells \"" + cells + "\"; novelJunctions \"" +
-                      nov + "\"; supportingReads \"0\"; CAGEdist \"0\"; POLYAdist \"0\"; color \"" + color + "\";\n";
-            for (size_t k = 0; k < xs.size(); k++)
-                one_gff += chrom + "\tsicelore\texon\t" + std::to_string(xs[k]) + "\t" + std::to_string(xe[k]) + "\t.\t" + strand + "\t.\t" + ids + "\n";
-            flat += one_flat;
-            gff += one_gff;
-            if (known) {  // no novel is valid without the validator
-                flatv += one_flat;
-                gffv += one_gff;
-            }
+            o.umis = t_count[t];
+            o.cells = t_cells[t];
+            h->txs.push_back(std::move(o));
         }
     }
+    render(h);  // no novel is valid without the validator (smi_collapse_validate_*)
     h->k_cg_off = std::move(cg_off);
     h->k_u_j_off = std::move(u_j_off);
     h->k_u_founder = std::move(u_founder);
     h->k_uj = std::move(uj);
     if (stage_ms) std::memcpy(stage_ms, ms, sizeof(ms));
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_validate_begin(smi_collapse *h, const char *cage, size_t n_cage, const char *polya, size_t n_polya,
+                                           const char *const *short_ref_names, int32_t n_refs, int32_t cage_co, int32_t polya_co, int32_t junc_co,
+                                           int32_t table_log2) {
+    if (!h || (n_cage && !cage) || (n_polya && !polya) || n_refs < 0 || (n_refs && !short_ref_names)) {
+        set_error("smi_collapse_validate_begin: null argument");
+        return SMI_ERR_INVALID;
+    }
+    if (!h->ran || h->failed || h->val) {
+        set_error(h->val ? "smi_collapse_validate_begin: already called" : "smi_collapse_validate_begin: smi_collapse_run comes first");
+        return SMI_ERR_STATE;
+    }
+    if (table_log2 < 0 || table_log2 > 30) {
+        set_error("smi_collapse_validate_begin: table_log2 must be 0 .. 30");
+        return SMI_ERR_INVALID;
+    }
+    auto V = std::make_unique<Validator>();
+    V->cage_co = cage_co;
+    V->polya_co = polya_co;
+    V->junc_co = junc_co;
+    int rc;
+    if ((rc = parse_bed(cage, n_cage, "CAGE", V->cage)) || (rc = parse_bed(polya, n_polya, "POLYA", V->polya))) return rc;
+    std::unordered_map<std::string, int32_t> short_id;
+    for (int32_t i = 0; i < n_refs; i++) short_id.emplace(short_ref_names[i] ? short_ref_names[i] : "", i);
+    V->n_ref = n_refs;
+    V->ref_keys.assign(std::max(n_refs, 1), 0);
+    // validator L299-308: the distances of every transcript, known ones included; L310-316: its keys
+    struct Key {
+        int32_t ref, donor, acceptor;
+    };
+    std::vector<Key> keys;
+    std::unordered_map<std::string, int32_t> key_id;
+    std::vector<int32_t> tx_key;
+    for (OutTx &t : h->txs) {
+        t.dist_cage = bed_distance(V->cage, t.chrom, t.neg, t.neg ? t.s1 : t.s0);
+        t.dist_polya = bed_distance(V->polya, t.chrom, t.neg, t.neg ? t.s0 : t.s1);
+        t.v_cage = std::abs((int64_t)t.dist_cage) <= cage_co;
+        t.v_polya = std::abs((int64_t)t.dist_polya) <= polya_co;
+        const auto sit = short_id.find(t.chrom);
+        for (const int2 &j : t.nov) {
+            if (sit == short_id.end()) {
+                tx_key.push_back(-1);
+                continue;
+            }
+            const Key k{sit->second, j.x, j.y};
+            const auto kit = key_id.emplace(std::string((const char *)&k, sizeof k), (int32_t)keys.size());
+            if (kit.second) keys.push_back(k);
+            tx_key.push_back(kit.first->second);
+        }
+        V->tx_k_off.push_back((int32_t)tx_key.size());
+    }
+    uint64_t size = 16;
+    if (table_log2) size = 1ull << table_log2;
+    else
+        while (size < 2 * (uint64_t)keys.size()) size <<= 1;
+    if (size < keys.size() || size > (1ull << 30)) {
+        set_error("CollapseModel: a junction table of " + std::to_string(size) + " slots does not hold the " + std::to_string(keys.size()) +
+                  " novel junctions to validate");
+        return SMI_ERR_INVALID;
+    }
+    V->mask = (uint32_t)(size - 1);
+    V->keys.assign(size, make_int4(-1, 0, 0, 0));
+    std::vector<int32_t> key_slot(keys.size());
+    for (size_t i = 0; i < keys.size(); i++) {
+        uint32_t s = jsup_hash(keys[i].ref, keys[i].donor, keys[i].acceptor) & V->mask;
+        while (V->keys[s].x >= 0) s = (s + 1) & V->mask;  // (the table holds every key: a free slot exists)
+        V->keys[s] = make_int4(keys[i].ref, keys[i].donor, keys[i].acceptor, 0);
+        key_slot[i] = (int32_t)s;
+        V->ref_keys[keys[i].ref] = 1;
+    }
+    for (int32_t k : tx_key) V->tx_slot.push_back(k < 0 ? -1 : key_slot[k]);
+    SMI_HIP(hipSetDevice(h->ctx->device));
+    hipStream_t s = h->ctx->stream;
+    if ((rc = V->d_keys.put(V->keys, s)) || (rc = V->d_ref_keys.put(V->ref_keys, s)) || (rc = V->d_count.alloc(size)) || (rc = V->d_bound.alloc(1)))
+        return rc;
+    SMI_HIP(hipMemsetAsync(V->d_count.p, 0, size * sizeof(uint32_t), s));
+    SMI_HIP(hipMemsetAsync(V->d_bound.p, 0, sizeof(unsigned long long), s));
+    SMI_HIP(hipStreamSynchronize(s));
+    int64_t *v = h->vcounts;
+    v[SMI_CVAL_JUNCTION_KEYS] = (int64_t)keys.size();
+    v[SMI_CVAL_TABLE_SLOTS] = (int64_t)size;
+    v[SMI_CVAL_CAGE_REFERENCES] = V->cage.references;
+    v[SMI_CVAL_CAGE_ENTRIES] = V->cage.entries;
+    v[SMI_CVAL_POLYA_REFERENCES] = V->polya.references;
+    v[SMI_CVAL_POLYA_ENTRIES] = V->polya.entries;
+    h->val = std::move(V);
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_validate_segment(smi_collapse *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n) {
+    if (!h || n < 0 || (n && (!bam || !recs))) {
+        set_error("smi_collapse_validate_segment: null argument");
+        return SMI_ERR_INVALID;
+    }
+    if (!h->val || h->val->ended) {
+        set_error("smi_collapse_validate_segment: between smi_collapse_validate_begin and smi_collapse_validate_end");
+        return SMI_ERR_STATE;
+    }
+    Validator &V = *h->val;
+    // K-JSUP reads the fixed part and the CIGAR from the segment's own bytes: both inside the segment, by those bytes
+    std::vector<uint64_t> off(n);
+    for (int32_t i = 0; i < n; i++) {
+        const uint64_t o = recs[i].rec_off;
+        bool ok = o <= n_bam && n_bam - o >= 36;
+        if (ok) {
+            uint16_t n_op;
+            std::memcpy(&n_op, bam + o + 16, 2);
+            ok = n_bam - o - 36 >= (uint64_t)bam[o + 12] + 4ull * n_op;
+        }
+        if (!ok) {
+            set_error("smi_collapse_validate_segment: record " + std::to_string(i) + " lies outside the segment");
+            return SMI_ERR_INVALID;
+        }
+        off[i] = o;
+    }
+    h->vcounts[SMI_CVAL_SHORT_RECORDS] += n;
+    if (n == 0 || h->vcounts[SMI_CVAL_JUNCTION_KEYS] == 0) return SMI_OK;
+    SMI_HIP(hipSetDevice(h->ctx->device));
+    hipStream_t s = h->ctx->stream;
+    DevBuf<uint8_t> d_bam;
+    DevBuf<uint64_t> d_off;
+    int rc;
+    if ((rc = d_bam.alloc(n_bam)) || (rc = d_off.put(off, s))) return rc;
+    SMI_HIP(hipMemcpyAsync(d_bam.p, bam, n_bam, hipMemcpyHostToDevice, s));
+    JsupArgs a = {d_bam.p, d_off.p, n, V.n_ref, V.d_ref_keys.p, V.d_keys.p, V.mask, V.d_count.p, V.d_bound.p};
+    Events evt;
+    if ((rc = evt.begin(s))) return rc;
+    hipLaunchKernelGGL(k_jsup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    SMI_HIP(hipGetLastError());
+    if ((rc = evt.end(s, &V.ms))) return rc;
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_validate_end(smi_collapse *h, float *stage_ms) {
+    if (!h) {
+        set_error("smi_collapse_validate_end: null argument");
+        return SMI_ERR_INVALID;
+    }
+    if (stage_ms) *stage_ms = 0.f;
+    if (!h->val || h->val->ended) {
+        set_error(h->val ? "smi_collapse_validate_end: already called" : "smi_collapse_validate_end: smi_collapse_validate_begin comes first");
+        return SMI_ERR_STATE;
+    }
+    Validator &V = *h->val;
+    V.ended = true;
+    SMI_HIP(hipSetDevice(h->ctx->device));
+    std::vector<uint32_t> count(V.keys.size());
+    unsigned long long bound = 0;
+    SMI_HIP(hipMemcpy(count.data(), V.d_count.p, count.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SMI_HIP(hipMemcpy(&bound, V.d_bound.p, sizeof bound, hipMemcpyDeviceToHost));
+    h->vcounts[SMI_CVAL_SHORT_BOUNDARIES] = (int64_t)bound;
+    for (uint32_t x : count) h->vcounts[SMI_CVAL_JUNCTION_HITS] += x;
+    for (size_t i = 0; i < h->txs.size(); i++) {  // validator L310-361
+        OutTx &t = h->txs[i];
+        uint32_t total = 0;
+        bool ok = true;
+        for (int32_t k = V.tx_k_off[i]; k < V.tx_k_off[i + 1]; k++) {
+            const int32_t support = V.tx_slot[k] < 0 ? 0 : (int32_t)count[V.tx_slot[k]];
+            total += (uint32_t)support;
+            ok &= support >= V.junc_co;
+        }
+        t.junction_reads = (int32_t)total;
+        t.v_junction = ok;
+        t.valid = t.v_cage && t.v_polya && ok;
+    }
+    render(h);
+    if (stage_ms) *stage_ms = V.ms;
+    return SMI_OK;
+}
+
+extern "C" int smi_collapse_validate_counts(const smi_collapse *h, int64_t *counts) {
+    if (!h || !counts) {
+        set_error("smi_collapse_validate_counts: null argument");
+        return SMI_ERR_INVALID;
+    }
+    std::memcpy(counts, h->vcounts, sizeof h->vcounts);
     return SMI_OK;
 }
 

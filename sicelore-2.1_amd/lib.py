@@ -78,6 +78,7 @@ EXPORTS = [
     "smi_moltag_free",
     "smi_collapse_default_config", "smi_collapse_create", "smi_collapse_set_references", "smi_collapse_add_segment", "smi_collapse_run",
     "smi_collapse_output", "smi_collapse_counts", "smi_collapse_error_read", "smi_collapse_free", "smi_collapse_host_loop",
+    "smi_collapse_validate_begin", "smi_collapse_validate_segment", "smi_collapse_validate_end", "smi_collapse_validate_counts",
     "smi_fusion_default_config", "smi_fusion_create", "smi_fusion_add_segment", "smi_fusion_run", "smi_fusion_output", "smi_fusion_counts",
     "smi_fusion_error_read", "smi_fusion_free", "smi_fusion_host_loop",
 ]
@@ -300,6 +301,11 @@ def load_library():
     lib.smi_collapse_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
     lib.smi_collapse_free.argtypes = [vp]
     lib.smi_collapse_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_collapse_validate_begin.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_int32, ctypes.c_int32]
+    lib.smi_collapse_validate_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32]
+    lib.smi_collapse_validate_end.argtypes = [vp, vp]
+    lib.smi_collapse_validate_counts.argtypes = [vp, vp]
     lib.smi_fusion_default_config.argtypes = [vp]
     lib.smi_fusion_create.argtypes = [vp, vp, vp, sz, ctypes.POINTER(vp)]
     lib.smi_fusion_add_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32]
@@ -928,12 +934,17 @@ COLLAPSE_COUNTS = ("records", "kept", "null", "mapq0", "chimeric", "low_rn", "no
                    "gencode_ev", "ckj", "ckj_ev", "cks", "cks_ev", "nss", "nss_ev", "long_lists", "max_undef", "max_founders")
 # smi_collapse_output, in SMI_COL_OUT_* order: the file name suffixes (PREFIX.d<DELTA>.rn<RNMIN>.e<MINEVIDENCE><suffix>)
 COLLAPSE_OUTPUTS = (".txt", ".refflat.txt", ".final.refflat.txt", ".gff", ".final.gff")
+# smi_collapse_validate_counts, in SMI_CVAL_* order
+COLLAPSE_VALIDATE_COUNTS = ("valid_isoforms", "valid_evidences", "gencode_valid", "gencode_valid_ev", "ckj_valid", "ckj_valid_ev", "cks_valid",
+                            "cks_valid_ev", "nss_valid", "nss_valid_ev", "short_records", "short_boundaries", "junction_keys", "junction_hits",
+                            "table_slots", "cage_references", "cage_entries", "polya_references", "polya_entries")
 
 
 class Collapse:
     """CollapseModel (smi_collapse_*): the refFlat and cell-list texts and the BAM's reference names, then BAM segments in; the five output
     texts out.  Keywords: the fields of smi_collapse_config (tags as two-character strings).  A record the loader fails on raises SmiError;
-    error_read then holds (read name, record index)."""
+    error_read then holds (read name, record index).  After run(), validate_begin / validate_segment / validate_end run the validator over
+    CAGE, POLYA and the segments of SHORT, and validate_end returns the five texts with its results."""
 
     def __init__(self, ctx, refflat, csv, ref_names, **kw):
         self._lib = load_library()
@@ -986,6 +997,9 @@ class Collapse:
         if self._lib.smi_collapse_run(self._h, _ptr(ms)):
             raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
         self.stage_ms = dict(collapse=float(ms[0]), colstat=float(ms[1]), filter_class=float(ms[2]))
+        return self._outputs()
+
+    def _outputs(self):
         outs = {}
         for i, name in enumerate(COLLAPSE_OUTPUTS):
             n = ctypes.c_size_t(0)
@@ -1000,6 +1014,42 @@ class Collapse:
         c = np.zeros(len(COLLAPSE_COUNTS), dtype=np.int64)
         self._lib.smi_collapse_counts(self._h, _ptr(c))
         return dict(zip(COLLAPSE_COUNTS, (int(x) for x in c)))
+
+    def validate_begin(self, cage, polya, short_ref_names, cage_co=50, polya_co=50, junc_co=1, table_log2=0):
+        """after run(): the CAGE and POLYA texts, the @SQ names of SHORT and the three cut-offs of UCSCRefFlatParser.validator; the distances
+        of every transcript and the device table of the novel junctions (table_log2: its size, for tests).  A BED line the reference's
+        parser stops at raises SmiError naming it."""
+        cg = np.frombuffer(bytes(cage), dtype=np.uint8)
+        pa = np.frombuffer(bytes(polya), dtype=np.uint8)
+        names = [str(r).rstrip("\0").encode("latin-1") for r in short_ref_names]
+        arr = (ctypes.c_char_p * max(len(names), 1))(*names)
+        if self._lib.smi_collapse_validate_begin(self._h, _ptr(cg) if cg.size else None, cg.size, _ptr(pa) if pa.size else None, pa.size, arr,
+                                                 len(names), int(cage_co), int(polya_co), int(junc_co), int(table_log2)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+
+    def validate_segment(self, bam, recs):
+        """one inflated segment of SHORT and the BAM_RECORD_DTYPE entries of the records in it: K-JSUP"""
+        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
+            raise ValueError("bam: a contiguous 1-D uint8 array")
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != BAM_RECORD_DTYPE:
+            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
+        if self._lib.smi_collapse_validate_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None,
+                                                   int(recs.size)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+
+    def validate_end(self):
+        """the supports back, the validator's fields per transcript -> {file name suffix: bytes}, validated"""
+        ms = np.zeros(1, dtype=np.float32)
+        if self._lib.smi_collapse_validate_end(self._h, _ptr(ms)):
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self.stage_ms["jsup"] = float(ms[0])
+        return self._outputs()
+
+    def validate_counts(self):
+        c = np.zeros(len(COLLAPSE_VALIDATE_COUNTS), dtype=np.int64)
+        self._lib.smi_collapse_validate_counts(self._h, _ptr(c))
+        return dict(zip(COLLAPSE_VALIDATE_COUNTS, (int(x) for x in c)))
 
     def host_loop(self):
         """after run(): the reference's single-thread collapse() on the same arrays -> (seconds, records whose founder differs from K-COLLAPSE's)"""

@@ -4,6 +4,7 @@ K-SCAN pass 1 (complete adapter + quality filter) + histogram, K-UMI.  Prints on
 import importlib
 import json
 import os
+import struct
 import sys
 import time
 
@@ -36,9 +37,9 @@ def main():
     used = synth.pick_used(wl, 5000, seed=2)
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
-            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse, "fusion": leg_fusion}
+            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse, "fusion": leg_fusion, "validator": leg_validator}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -749,6 +750,125 @@ def leg_collapse(pkg, synth, ctx, dev, wl, used, res):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     res["collapse"] = out
+
+
+def _short_fixture(junctions, n_recs, span, seed=71, spliced_share=0.2):
+    """a seeded SHORT of n_recs 100-base records on chr1, a fifth of them spliced over `junctions` ((donor, acceptor) rows): a third of the
+    junctions supported exactly, a third off by one, a third by a junction nearby; groups of four unspliced records and a spliced one
+    -> (BGZF bytes, records, spliced records)"""
+    from sicelore_amd import lib
+
+    rng = np.random.default_rng(seed)
+    fixed = [("block_size", "<u4"), ("ref_id", "<i4"), ("pos", "<i4"), ("l_read_name", "u1"), ("mapq", "u1"), ("bin", "<u2"), ("n_cigar", "<u2"),
+             ("flag", "<u2"), ("l_seq", "<i4"), ("next_ref", "<i4"), ("next_pos", "<i4"), ("tlen", "<i4"), ("name", "S11")]
+    tail = [("seq", "u1", (50,)), ("qual", "u1", (100,))]
+    plain = np.dtype(fixed + [("cigar", "<u4", (1,))] + tail)
+    splic = np.dtype(fixed + [("cigar", "<u4", (3,))] + tail)
+    n_grp = n_recs // 5
+    grp = np.zeros(n_grp, dtype=np.dtype([("u", plain, (4,)), ("s", splic)]))
+    for part, dt, n_op in ((grp["u"], plain, 1), (grp["s"], splic, 3)):
+        part["block_size"] = dt.itemsize - 4
+        part["l_read_name"], part["mapq"], part["bin"], part["n_cigar"], part["l_seq"] = 11, 60, 4680, n_op, 100
+        part["next_ref"] = part["next_pos"] = -1
+        part["seq"], part["qual"] = 0x11, 30
+    ids = np.arange(n_grp * 5, dtype=np.int64).reshape(n_grp, 5)
+    grp["u"]["name"] = np.char.add("u", np.char.zfill(ids[:, :4].astype("U9"), 9)).astype("S11")
+    grp["s"]["name"] = np.char.add("s", np.char.zfill(ids[:, 4].astype("U9"), 9)).astype("S11")
+    grp["u"]["pos"] = rng.integers(10_000, span, size=(n_grp, 4))
+    grp["u"]["cigar"][..., 0] = 100 << 4
+    grp["u"]["flag"] = 16 * rng.integers(0, 2, size=(n_grp, 4))
+    k = rng.integers(0, len(junctions), size=n_grp)
+    d, a = junctions[k, 0].copy(), junctions[k, 1].copy()
+    side, step = rng.integers(0, 2, size=n_grp), rng.choice((-1, 1), size=n_grp)
+    off = k % 3 == 1
+    d[off & (side == 0)] += step[off & (side == 0)]
+    a[off & (side == 1)] += step[off & (side == 1)]
+    d[k % 3 == 2] += 7
+    a[k % 3 == 2] += 9
+    left = rng.integers(10, 91, size=n_grp)
+    grp["s"]["pos"] = d - left
+    grp["s"]["cigar"][:, 0] = left << 4
+    grp["s"]["cigar"][:, 1] = np.maximum(a - d - 1, 0) << 4 | 3
+    grp["s"]["cigar"][:, 2] = (100 - left) << 4
+    grp["s"]["flag"] = rng.choice((0, 16, 0x100, 0x400), size=n_grp)
+    head = b"BAM\1" + struct.pack("<I", 0) + struct.pack("<I", 1) + struct.pack("<I", 5) + b"chr1\0" + struct.pack("<I", 2 ** 31 - 1)
+    bam = np.concatenate([np.frombuffer(head, dtype=np.uint8), grp.view(np.uint8)])
+    return lib.bgzf_deflate(bam, level=1, n_threads=16), n_grp * 5, n_grp
+
+
+def leg_validator(pkg, synth, ctx, dev, wl, used, res):
+    """K-JSUP (the validator of `CollapseModel`): the collapse leg's fixture (SMI_MB_VAL_GENES genes, 20,000; SMI_MB_VAL_RECS records,
+    2,000,000) through `IsoformMatrix ISOBAM=true` and CollapseModel; then a seeded SHORT of SMI_MB_VAL_SHORT 100-base records (3,000,000, a
+    fifth spliced over the novel junctions that run printed) and two BED files of one feature per 50th transcript end, through
+    smi_collapse_validate_*: K-JSUP device ms (HIP events, summed over segments), seconds waiting for inflate + index (the reader thread
+    works one segment ahead), in upload + kernel (validate_segment) and in read-back + rendering (validate_end)."""
+    import shutil
+    import tempfile
+
+    iso = importlib.import_module(graft.PKG_NAME + ".isoformmatrix")
+    lib = importlib.import_module(graft.PKG_NAME + ".lib")
+    n_genes = int(os.environ.get("SMI_MB_VAL_GENES", "20000"))
+    n_recs = int(os.environ.get("SMI_MB_VAL_RECS", "2000000"))
+    n_short = int(os.environ.get("SMI_MB_VAL_SHORT", "3000000"))
+    seg_bytes = int(os.environ.get("SMI_MB_VAL_SEGMENT", str(64 << 20)))
+    t0 = time.perf_counter()
+    ref, csv, z, n_rec, n_mol = _isoform_fixture(n_genes, n_recs, 5000, minus1=False)
+    out = {"genes": n_genes, "records": n_rec, "cells": 5000, "fixture_s": time.perf_counter() - t0}
+    print("validator: fixture built", file=sys.stderr, flush=True)
+    d = tempfile.mkdtemp(prefix="validator_")
+    h = None
+    try:
+        z.tofile(os.path.join(d, "in.bam"))
+        with open(os.path.join(d, "r.refFlat"), "w") as f:
+            f.write(ref)
+        with open(os.path.join(d, "c.csv"), "w") as f:
+            f.write(csv)
+        iso.isoform_matrix(ctx, os.path.join(d, "in.bam"), os.path.join(d, "r.refFlat"), os.path.join(d, "c.csv"), d, n_threads=16, isobam=True)
+        print("validator: ISOBAM written", file=sys.stderr, flush=True)
+        t0 = time.perf_counter()
+        for bam, recs, hdr in iso._segments(os.path.join(d, "sicelore_isobam.bam"), 256 << 20, 16):
+            if hdr is not None:
+                h = lib.Collapse(ctx, ref.encode(), csv.encode(), [r[0] for r in lib.bam_header(bam)[1]], n_threads=16)
+            if recs.size:
+                h.add_segment(bam, recs)
+        txt = h.run()[".txt"].decode()
+        out["collapse_s"] = time.perf_counter() - t0
+        rows = [ln.split("\t") for ln in txt.split("\n")[1:-1]]
+        junc = np.array(sorted(set(tuple(int(x) for x in j.split("-")) for r in rows if r[11] != "-" for j in r[11].split(","))), dtype=np.int64)
+        span = max(int(r[5]) for r in rows)
+        bed = ["".join(f"chr1\t{int(r[c]) + 20 * (i % 7 - 3)}\t{int(r[c]) + 60}\tf{i}\t0\t{r[3]}\n" for i, r in enumerate(rows) if i % 50 == 0)
+               for c in (4, 5)]
+        t0 = time.perf_counter()
+        zs, n_s, n_spl = _short_fixture(junc, n_short, span)
+        zs.tofile(os.path.join(d, "short.bam"))
+        out.update(transcripts=len(rows), novel_junctions=int(len(junc)), short_records=n_s, short_spliced=n_spl, short_bgzf_bytes=int(zs.size),
+                   short_fixture_s=time.perf_counter() - t0)
+        print("validator: SHORT written", file=sys.stderr, flush=True)
+        sec = dict(inflate_index_wait=0.0, upload_kernel=0.0, begin=0.0, end_render=0.0)
+        inflated = 0
+        t_all = t0 = time.perf_counter()
+        for bam, recs, hdr in iso._segments(os.path.join(d, "short.bam"), seg_bytes, 16):
+            sec["inflate_index_wait"] += time.perf_counter() - t0
+            if hdr is not None:
+                t0 = time.perf_counter()
+                h.validate_begin(bed[0].encode(), bed[1].encode(), [r[0] for r in lib.bam_header(bam)[1]])
+                sec["begin"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            if recs.size:
+                h.validate_segment(bam, recs)
+            sec["upload_kernel"] += time.perf_counter() - t0
+            inflated += int(bam.size)
+            t0 = time.perf_counter()
+        t0 = time.perf_counter()
+        outs = h.validate_end()
+        sec["end_render"] = time.perf_counter() - t0
+        out["validate"] = dict(h.validate_counts(), k_jsup_device_ms=h.stage_ms["jsup"], seconds=sec, wall_s=time.perf_counter() - t_all,
+                               segment_bytes=seg_bytes, inflated_bytes=inflated, text_bytes=sum(len(v) for v in outs.values()))
+    finally:
+        if h is not None:
+            h.close()
+        shutil.rmtree(d, ignore_errors=True)
+    res["validator"] = out
 
 
 def _fusion_fixture(n_recs, n_cells, n_genes, seed=61):

@@ -33,7 +33,6 @@
 #include <memory>
 #include <string>
 #include <string_view>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -330,7 +329,6 @@ __global__ __launch_bounds__(256) void k_jsup(JsupArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-using lr::Aux;
 using lr::drop_minus1;
 using lr::jint;
 using lr::jsplit;
@@ -415,21 +413,6 @@ int parse_model(const char *text, size_t n, Model &M) {
     return SMI_OK;
 }
 
-enum Outcome : uint8_t { kKept, kNull, kMapq0, kChimeric, kLowRn, kNotListed, kNoGene, kError };
-
-struct Parsed {
-    Outcome what = kError;
-    std::string_view name, bc, gene, it;
-    bool has_it = false;
-    int32_t tx_start = 0, tx_end = 0;
-    std::vector<int2> junc;
-    std::string err;
-};
-
-struct TagSet {
-    uint16_t cell, umi, gene, iso, rn, de, df;
-};
-
 // one transcript of the output, as exportFiles prints it
 struct OutTx {
     int32_t gene;  // index into smi_collapse::genes
@@ -477,7 +460,7 @@ using namespace smi;
 struct smi_collapse {
     smi_ctx *ctx = nullptr;
     smi_collapse_config cfg = {};
-    TagSet tags = {};
+    lr::TagSet tags;
     Model M;
     std::unordered_map<std::string, int32_t> listed;  // the cell list
     std::vector<std::string> refs;
@@ -503,90 +486,6 @@ struct smi_collapse {
 
 namespace smi {
 namespace {
-
-void parse_record(const uint8_t *bam, const smi_bam_record &r, const smi_collapse &h, Parsed &out) {
-    const TagSet &tg = h.tags;
-    out.name = std::string_view((const char *)bam + r.name_off, r.l_read_name ? r.l_read_name - 1 : 0);
-    const uint8_t *p = bam + r.aux_off, *end = p + r.aux_len;
-    Aux cell, umi, gene, iso, rn, de, df;
-    while (p < end) {
-        size_t n;
-        if (lr::aux_size(p, end, &n)) {
-            out.err = "malformed attributes";
-            return;
-        }
-        const uint16_t t = (uint16_t)(p[0] | p[1] << 8);
-        const Aux a{p, n};
-        if (t == tg.cell) cell = a;  // (a repeated tag keeps its last value, as htsjdk reads it)
-        if (t == tg.umi) umi = a;
-        if (t == tg.gene) gene = a;
-        if (t == tg.iso) iso = a;
-        if (t == tg.rn) rn = a;
-        if (t == tg.de) de = a;
-        if (t == tg.df) df = a;
-        p += n;
-    }
-    auto bad = [&](const Aux &a) {
-        out.err = std::string("attribute ") + (char)a.p[0] + (char)a.p[1] + " of type " + (char)a.p[2] + " is not the type CollapseModel reads";
-    };
-    auto zstr = [&](const Aux &a, std::string_view &v) {
-        if (!a.p) return true;
-        if (a.p[2] != 'Z') {
-            bad(a);
-            return false;
-        }
-        v = std::string_view((const char *)a.p + 3, a.n - 4);
-        return true;
-    };
-    std::string_view umi_v;
-    int64_t rnv = 1;
-    // loader L157-161: the casts come before anything else, for every record
-    if (!zstr(cell, out.bc) || !zstr(umi, umi_v) || !zstr(gene, out.gene) || !zstr(iso, out.it)) return;
-    out.has_it = iso.p != nullptr;
-    if (rn.p && !lr::aux_integer(rn, rnv)) {
-        bad(rn);
-        return;
-    }
-    if (!cell.p || (r.flag & 4) || r.ref_id < 0) {  // fromSAMRecord L80 (and a record on no sequence is in no query)
-        out.what = kNull;
-        return;
-    }
-    for (const Aux *a : {&de, &df}) {  // L92
-        if (!a->p) continue;
-        if (a->p[2] != 'f') {
-            bad(*a);
-            return;
-        }
-        break;
-    }
-    if (r.n_cigar == 0) {
-        out.err = "no CIGAR";
-        return;
-    }
-    uint32_t c0, c1;
-    std::memcpy(&c0, bam + r.cigar_off, 4);
-    std::memcpy(&c1, bam + r.cigar_off + 4 * ((size_t)r.n_cigar - 1), 4);
-    if (!lr::walk_junctions(bam, r, out.junc)) {  // the walk runs before the filter
-        out.err = "the CIGAR walk runs past the alignment blocks";
-        return;
-    }
-    int64_t ref_len = 0;
-    for (int k = 0; k < r.n_cigar; k++) {
-        uint32_t c;
-        std::memcpy(&c, bam + r.cigar_off + 4ull * k, 4);
-        const uint32_t op = c & 15;
-        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += c >> 4;
-    }
-    out.tx_start = r.pos + 1;                  // getAlignmentStart
-    out.tx_end = (int32_t)(r.pos + ref_len);   // getAlignmentEnd
-    // loader L167-170
-    if (r.mapq == 0) out.what = kMapq0;
-    else if (lr::chimeric(c0, c1, h.cfg.max_clip)) out.what = kChimeric;
-    else if (rnv < h.cfg.rn_min) out.what = kLowRn;
-    else if (!h.listed.count(std::string(out.bc))) out.what = kNotListed;
-    else if (!gene.p || out.gene.empty() || out.gene == "undef") out.what = kNoGene;
-    else out.what = kKept;
-}
 
 void append_int(std::string &s, int64_t v) { s += std::to_string(v); }
 
@@ -839,8 +738,7 @@ extern "C" int smi_collapse_create(smi_ctx *ctx, const smi_collapse_config *cfg,
     h->ctx = ctx;
     h->cfg = *cfg;
     h->cfg.n_threads = std::max(1, std::min(cfg->n_threads, 256));
-    h->tags = TagSet{lr::tag16(cfg->cell_tag), lr::tag16(cfg->umi_tag), lr::tag16(cfg->gene_tag), lr::tag16(cfg->iso_tag), lr::tag16(cfg->rn_tag),
-                     lr::tag16("de"), lr::tag16("df")};
+    h->tags.set(lr::kCell, cfg->cell_tag).set(lr::kUmi, cfg->umi_tag).set(lr::kGene, cfg->gene_tag).set(lr::kRn, cfg->rn_tag).set(lr::kIso, cfg->iso_tag);
     if (int rc = parse_model(refflat, n_refflat, h->M)) {
         delete h;
         return rc;
@@ -921,25 +819,19 @@ extern "C" int smi_collapse_add_segment(smi_collapse *h, const uint8_t *bam, siz
                          : "smi_collapse_add_segment: an earlier segment failed");
         return SMI_ERR_STATE;
     }
-    for (int32_t i = 0; i < n; i++) {
-        const smi_bam_record &r = recs[i];
-        if (r.name_off + r.l_read_name > n_bam || r.cigar_off + 4ull * r.n_cigar > n_bam || r.aux_off + r.aux_len > n_bam) {
-            set_error("smi_collapse_add_segment: record " + std::to_string(i) + " lies outside the segment");
-            return SMI_ERR_INVALID;
-        }
+    const auto listed = [&](std::string_view bc) { return h->listed.count(std::string(bc)) != 0; };
+    const lr::Segment seg = lr::read_segment("smi_collapse_add_segment", bam, n_bam, recs, n, h->cfg.n_threads,
+                                             [&](const uint8_t *b, const smi_bam_record &r, lr::Record &out, std::string &err) {
+                                                 lr::read_collapse(b, r, h->tags, h->cfg.max_clip, h->cfg.rn_min, listed, out, err);
+                                             });
+    if (!seg.refused.empty()) {
+        set_error(seg.refused);
+        return SMI_ERR_INVALID;
     }
-    std::vector<Parsed> parsed(n);
-    const int nt = std::max(1, std::min<int>(h->cfg.n_threads, (n + 4095) / 4096));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; t++)
-        th.emplace_back([&, t] {
-            for (int32_t i = (int32_t)((int64_t)n * t / nt); i < (int32_t)((int64_t)n * (t + 1) / nt); i++)
-                parse_record(bam, recs[i], *h, parsed[i]);
-        });
-    for (auto &x : th) x.join();
+    const lr::Records &parsed = seg.recs;
     auto fail = [&](int32_t i, const std::string &why) {
         h->failed = true;
-        h->error_read = std::string(parsed[i].name);
+        h->error_read = std::string(lr::read_name(bam, recs[i]));
         h->error_record = h->seen + i;
         set_error("CollapseModel: read " + h->error_read + ": " + why);
         return SMI_ERR_INVALID;
@@ -947,9 +839,9 @@ extern "C" int smi_collapse_add_segment(smi_collapse *h, const uint8_t *bam, siz
     // the first failing record in file order is the one named: the lookups of the kept records are part of the same pass
     std::vector<int32_t> line(n, -1);
     for (int32_t i = 0; i < n; i++) {
-        const Parsed &p = parsed[i];
-        if (p.what == kError) return fail(i, p.err);
-        if (p.what != kKept || (p.has_it && p.it == "undef")) continue;
+        const lr::Record &p = parsed[i];
+        if (i == seg.first_error) return fail(i, seg.error);
+        if (p.what != lr::kKept || (p.has_it && p.it == "undef")) continue;
         auto it = p.has_it ? h->M.select.find(std::string(p.gene) + "\t" + std::string(p.it)) : h->M.select.end();
         if (it == h->M.select.end())  // refmodel.select gives null: the reference fails on it later (L196 or initialize)
             return fail(i, p.has_it ? "transcript " + std::string(p.it) + " of the ISOFORMTAG is no transcript of gene " + std::string(p.gene) + " in the REFFLAT"
@@ -960,7 +852,7 @@ extern "C" int smi_collapse_add_segment(smi_collapse *h, const uint8_t *bam, siz
     // does not fit where it accumulates, as mtx::matrix does for its codes
     size_t add_rec = 0, add_junc = 0;
     for (int32_t i = 0; i < n; i++)
-        if (parsed[i].what == kKept) {
+        if (parsed[i].what == lr::kKept) {
             add_rec++;
             add_junc += parsed[i].junc.size();
         }
@@ -971,11 +863,11 @@ extern "C" int smi_collapse_add_segment(smi_collapse *h, const uint8_t *bam, siz
     }
     int64_t *c = h->counts;
     for (int32_t i = 0; i < n; i++) {
-        const Parsed &p = parsed[i];
+        const lr::Record &p = parsed[i];
         c[SMI_COL_RECORDS]++;
-        if (p.what != kKept) {
-            c[p.what == kNull ? SMI_COL_NULL : p.what == kMapq0 ? SMI_COL_MAPQ0 : p.what == kChimeric ? SMI_COL_CHIMERIC
-              : p.what == kLowRn ? SMI_COL_LOW_RN : p.what == kNotListed ? SMI_COL_NOT_LISTED : SMI_COL_NO_GENE]++;
+        if (p.what != lr::kKept) {
+            c[p.what == lr::kNull ? SMI_COL_NULL : p.what == lr::kMapq0 ? SMI_COL_MAPQ0 : p.what == lr::kChimeric ? SMI_COL_CHIMERIC
+              : p.what == lr::kLowRn ? SMI_COL_LOW_RN : p.what == lr::kNotListed ? SMI_COL_NOT_LISTED : SMI_COL_NO_GENE]++;
             continue;
         }
         c[SMI_COL_KEPT]++;

@@ -28,7 +28,6 @@
 #include <cstring>
 #include <string>
 #include <string_view>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -721,155 +720,13 @@ extern "C" int smi_poa_batch(smi_ctx *ctx, const uint8_t *seqs, const uint64_t *
     return smi_poa_batch_ex(ctx, seqs, read_off, mol_off, n_mol, max_ps, scratch_bytes, cons, qv, cons_len, kernel_ms, n_rerun, nullptr);
 }
 
-// ---- the record parser, molecules and the FASTQ (host) ---------------------------------------------------------------------------------
-namespace smi {
-namespace {
-
-enum Outcome : uint8_t { kKept, kNull, kChimeric, kNoUmi, kMapq0, kError };
-
-struct Parsed {
-    Outcome what = kError;
-    float de = 1.0f;
-    std::string_view name, bc, umi, cdna;  // views into the segment (bc: before the "-1" removal)
-    std::string err;
-};
-
-using lr::Aux;
-using lr::aux_size;
-using lr::float_less;
-using lr::tag16;
-
-struct TagSet {
-    uint16_t cell, umi, gene, te, ps, cs, us, rn, de, df;
-};
-
-void parse_record(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg, const smi_consensus_config &cfg, Parsed &out) {
-    out.name = std::string_view((const char *)bam + r.name_off, r.l_read_name ? r.l_read_name - 1 : 0);
-    const uint8_t *p = bam + r.aux_off, *end = p + r.aux_len;
-    Aux cell, umi, gene, te, ps, cs, us, rn, de, df;
-    while (p < end) {
-        size_t n;
-        if (aux_size(p, end, &n)) {
-            out.what = kError;
-            out.err = "malformed attributes";
-            return;
-        }
-        const uint16_t t = (uint16_t)(p[0] | p[1] << 8);
-        const Aux a{p, n};
-        if (t == tg.cell) cell = a;  // (a repeated tag keeps its last value, as htsjdk reads it)
-        if (t == tg.umi) umi = a;
-        if (t == tg.gene) gene = a;
-        if (t == tg.te) te = a;
-        if (t == tg.ps) ps = a;
-        if (t == tg.cs) cs = a;
-        if (t == tg.us) us = a;
-        if (t == tg.rn) rn = a;
-        if (t == tg.de) de = a;
-        if (t == tg.df) df = a;
-        p += n;
-    }
-    auto bad = [&](const Aux &a) {
-        out.what = kError;
-        out.err = std::string("attribute ") + (char)a.p[0] + (char)a.p[1] + " of type " + (char)a.p[2] + " is not the type ComputeConsensus reads";
-    };
-    auto zstr = [&](const Aux &a, std::string_view &v) {  // (String) getAttribute
-        if (!a.p) return true;
-        if (a.p[2] != 'Z') {
-            bad(a);
-            return false;
-        }
-        v = std::string_view((const char *)a.p + 3, a.n - 4);
-        return true;
-    };
-    auto integer = [&](const Aux &a, int64_t &v) {  // (Integer) getAttribute: htsjdk boxes c C s S i, and I up to 2^31 - 1, as Integer
-        if (!a.p || lr::aux_integer(a, v)) return true;
-        bad(a);
-        return false;
-    };
-    auto flt = [&](const Aux &a, bool &has, float &v) {
-        has = false;
-        if (!a.p) return true;
-        if (a.p[2] != 'f') {
-            bad(a);
-            return false;
-        }
-        std::memcpy(&v, a.p + 3, 4);
-        has = true;
-        return true;
-    };
-    std::string_view v_gene, v_cs, v_us;
-    // LongreadRecord.fromSAMRecord L75-81: gene, barcode and UMI are cast before anything is tested
-    if (!zstr(gene, v_gene) || !zstr(cell, out.bc) || !zstr(umi, out.umi)) return;
-    if (!cell.p || (r.flag & 4)) {
-        out.what = kNull;
-        return;
-    }
-    bool has;
-    float x;
-    if (!flt(de, has, x)) return;  // L92-94: de, else df, else 1
-    if (has) {
-        out.de = x;
-    } else {
-        if (!flt(df, has, x)) return;
-        out.de = has ? x : 1.0f;
-    }
-    int64_t iv = 1;
-    if (!integer(rn, iv)) return;  // L95 (not used further)
-    if (r.n_cigar == 0) {
-        out.what = kError;
-        out.err = "no CIGAR";
-        return;
-    }
-    uint32_t c0, c1;
-    std::memcpy(&c0, bam + r.cigar_off, 4);
-    std::memcpy(&c1, bam + r.cigar_off + 4 * ((size_t)r.n_cigar - 1), 4);
-    if (lr::chimeric(c0, c1, cfg.max_clip)) {  // L108-112
-        out.what = kChimeric;
-        return;
-    }
-    if (!zstr(cs, v_cs)) return;  // L116-135
-    if (cs.p) {
-        out.cdna = v_cs;
-    } else {
-        if (!zstr(us, v_us)) return;
-        if (!us.p) {
-            out.what = kError;
-            out.err = std::string("neither ") + cfg.cdna_tag + " nor " + cfg.us_tag;
-            return;
-        }
-        int64_t tso = 0, pa = 0;
-        if (!integer(te, tso) || !integer(ps, pa)) return;
-        const int64_t len = (int64_t)v_us.size();
-        const int64_t e = (pa != 0 && pa < len - 1) ? pa : len - 1;
-        if (tso < e) {
-            if (tso < 0) {
-                out.what = kError;
-                out.err = std::string(cfg.tso_end_tag) + " " + std::to_string(tso) + " is outside " + cfg.us_tag;  // String.substring throws
-                return;
-            }
-            out.cdna = v_us.substr((size_t)tso, (size_t)(e - tso));
-        } else {
-            out.cdna = v_us;
-        }
-    }
-    if (!umi.p) {  // LongreadParser L103
-        out.what = kNoUmi;
-        return;
-    }
-    if (!cfg.mapqv0 && r.mapq == 0 && (r.flag & 0x900)) {  // L105-112
-        out.what = kMapq0;
-        return;
-    }
-    out.what = kKept;
-}
-
-}  // namespace
-}  // namespace smi
+// ---- the records (lr::read_consensus in smi_longread.h), molecules and the FASTQ (host) -------------------------------------------------
+using smi::lr::float_less;
 
 struct smi_consensus {
     smi_ctx *ctx = nullptr;
     smi_consensus_config cfg = {};
-    TagSet tags = {};
+    lr::TagSet tags;
     // kept records in file order: their strings back to back in `text`
     std::string text;
     std::vector<uint64_t> name_off, bc_off, umi_off, cdna_off;  // each string: [off, off + len) with len in the *_len arrays
@@ -924,8 +781,8 @@ extern "C" int smi_consensus_create(smi_ctx *ctx, const smi_consensus_config *cf
     h->ctx = ctx;
     h->cfg = *cfg;
     h->cfg.n_threads = std::max(1, std::min(cfg->n_threads, 256));
-    h->tags = TagSet{tag16(cfg->cell_tag), tag16(cfg->umi_tag), tag16(cfg->gene_tag), tag16(cfg->tso_end_tag), tag16(cfg->polya_start_tag),
-                     tag16(cfg->cdna_tag), tag16(cfg->us_tag), tag16(cfg->rn_tag), tag16("de"), tag16("df")};
+    h->tags.set(lr::kCell, cfg->cell_tag).set(lr::kUmi, cfg->umi_tag).set(lr::kGene, cfg->gene_tag).set(lr::kRn, cfg->rn_tag);
+    h->tags.set(lr::kTe, cfg->tso_end_tag).set(lr::kPs, cfg->polya_start_tag).set(lr::kCs, cfg->cdna_tag).set(lr::kUs, cfg->us_tag);
     *out = h;
     return SMI_OK;
 }
@@ -944,36 +801,25 @@ extern "C" int smi_consensus_add_segment(smi_consensus *h, const uint8_t *bam, s
         set_error("smi_consensus_add_segment: the molecules were already built (smi_consensus_run)");
         return SMI_ERR_STATE;
     }
-    for (int32_t i = 0; i < n; i++) {
-        const smi_bam_record &r = recs[i];
-        if (r.name_off + r.l_read_name > n_bam || r.cigar_off + 4ull * r.n_cigar > n_bam || r.aux_off + r.aux_len > n_bam) {
-            set_error("smi_consensus_add_segment: record " + std::to_string(i) + " lies outside the segment");
-            return SMI_ERR_INVALID;
-        }
+    const lr::Segment seg = lr::read_segment("smi_consensus_add_segment", bam, n_bam, recs, n, h->cfg.n_threads,
+                                             [&](const uint8_t *b, const smi_bam_record &r, lr::Record &out, std::string &err) {
+                                                 lr::read_consensus(b, r, h->tags, h->cfg.max_clip, h->cfg.mapqv0, out, err);
+                                             });
+    if (!seg.refused.empty()) {
+        set_error(seg.refused);
+        return SMI_ERR_INVALID;
     }
-    std::vector<Parsed> parsed(n);
-    const int nt = std::max(1, std::min<int>(h->cfg.n_threads, (n + 4095) / 4096));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; t++)
-        th.emplace_back([&, t] {
-            for (int32_t i = (int32_t)((int64_t)n * t / nt); i < (int32_t)((int64_t)n * (t + 1) / nt); i++)
-                parse_record(bam, recs[i], h->tags, h->cfg, parsed[i]);
-        });
-    for (auto &x : th) x.join();
-    for (int32_t i = 0; i < n; i++) {
-        const Parsed &p = parsed[i];
-        if (p.what == kError) {
-            set_error("ComputeConsensus: read " + std::string(p.name) + ": " + p.err);
-            return SMI_ERR_INVALID;
-        }
+    if (seg.first_error >= 0) {
+        set_error("ComputeConsensus: read " + std::string(lr::read_name(bam, recs[seg.first_error])) + ": " + seg.error);
+        return SMI_ERR_INVALID;
     }
     int64_t *c = h->counts;
     for (int32_t i = 0; i < n; i++) {
-        const Parsed &p = parsed[i];
+        const lr::Record &p = seg.recs[i];
         c[SMI_CC_RECORDS]++;
-        if (p.what != kKept) {
+        if (p.what != lr::kKept) {
             c[SMI_CC_UNVALID]++;
-            c[p.what == kNull ? SMI_CC_NULL : p.what == kChimeric ? SMI_CC_CHIMERIA : p.what == kNoUmi ? SMI_CC_NO_UMI : SMI_CC_MAPQV0]++;
+            c[p.what == lr::kNull ? SMI_CC_NULL : p.what == lr::kChimeric ? SMI_CC_CHIMERIA : p.what == lr::kNoUmi ? SMI_CC_NO_UMI : SMI_CC_MAPQV0]++;
             continue;
         }
         c[SMI_CC_VALID]++;
@@ -982,10 +828,8 @@ extern "C" int smi_consensus_add_segment(smi_consensus *h, const uint8_t *bam, s
             len.push_back((uint32_t)s.size());
             h->text.append(s);
         };
-        put(p.name, h->name_off, h->name_len);
-        std::string bc(p.bc);  // String.replace("-1", "") (L83): every occurrence, left to right
-        for (size_t k = bc.find("-1"); k != std::string::npos; k = bc.find("-1", k)) bc.erase(k, 2);
-        put(bc, h->bc_off, h->bc_len);
+        put(lr::read_name(bam, recs[i]), h->name_off, h->name_len);
+        put(lr::drop_minus1(p.bc), h->bc_off, h->bc_len);  // L83
         put(p.umi, h->umi_off, h->umi_len);
         put(p.cdna, h->cdna_off, h->cdna_len);
         h->de.push_back(p.de);

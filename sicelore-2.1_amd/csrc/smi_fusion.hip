@@ -32,7 +32,6 @@
 #include <cstring>
 #include <string>
 #include <string_view>
-#include <thread>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -364,105 +363,6 @@ int sort_unique(hipStream_t s, Tmp &tmp, const uint64_t *in, uint64_t *sorted, u
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-using lr::Aux;
-
-enum Outcome : uint8_t { kKept, kNull, kChimeric, kNoGene, kMapq0, kError };
-
-struct Parsed {
-    Outcome what = kError;
-    float de = 1.0f;
-    int32_t rn = 1;
-    bool has_umi = false;
-    std::string_view name, bc, umi, gene;
-    std::string err;
-};
-
-// Java's "x".split(",") over a GE value that is neither null nor empty: trailing empty fields dropped, the others kept
-void split_genes(std::string_view s, std::vector<std::string_view> &out) {
-    out.clear();
-    size_t b = 0;
-    for (size_t i = 0; i <= s.size(); i++)
-        if (i == s.size() || s[i] == ',') {
-            out.push_back(s.substr(b, i - b));
-            b = i + 1;
-        }
-    while (!out.empty() && out.back().empty()) out.pop_back();
-}
-
-void parse_record(const uint8_t *bam, const smi_bam_record &r, Parsed &out) {
-    static const uint16_t kBC = lr::tag16("BC"), kU8 = lr::tag16("U8"), kGE = lr::tag16("GE"), kRN = lr::tag16("RN"), kDe = lr::tag16("de"),
-                          kDf = lr::tag16("df");
-    out.name = std::string_view((const char *)bam + r.name_off, r.l_read_name ? r.l_read_name - 1 : 0);
-    const uint8_t *p = bam + r.aux_off, *end = p + r.aux_len;
-    Aux cell, umi, gene, rn, de, df;
-    while (p < end) {
-        size_t n;
-        if (lr::aux_size(p, end, &n)) {
-            out.err = "malformed attributes";
-            return;
-        }
-        const uint16_t t = (uint16_t)(p[0] | p[1] << 8);
-        const Aux a{p, n};
-        if (t == kBC) cell = a;  // (a repeated tag keeps its last value, as htsjdk reads it)
-        if (t == kU8) umi = a;
-        if (t == kGE) gene = a;
-        if (t == kRN) rn = a;
-        if (t == kDe) de = a;
-        if (t == kDf) df = a;
-        p += n;
-    }
-    auto bad = [&](const Aux &a) {
-        out.err = std::string("attribute ") + (char)a.p[0] + (char)a.p[1] + " of type " + (char)a.p[2] + " is not the type FusionDetector reads";
-    };
-    auto zstr = [&](const Aux &a, std::string_view &v) {
-        if (!a.p) return true;
-        if (a.p[2] != 'Z') {
-            bad(a);
-            return false;
-        }
-        v = std::string_view((const char *)a.p + 3, a.n - 4);
-        return true;
-    };
-    if (!zstr(gene, out.gene) || !zstr(cell, out.bc) || !zstr(umi, out.umi)) return;  // fromSAMRecord L75-77: the casts come first
-    out.has_umi = umi.p != nullptr;
-    if (!cell.p || (r.flag & 4)) {  // L80
-        out.what = kNull;
-        return;
-    }
-    for (const Aux *a : {&de, &df}) {  // L92-94: de, else df, else 1
-        if (!a->p) continue;
-        if (a->p[2] != 'f') {
-            bad(*a);
-            return;
-        }
-        std::memcpy(&out.de, a->p + 3, 4);
-        break;
-    }
-    int64_t iv = 1;
-    if (rn.p && !lr::aux_integer(rn, iv)) {  // L95
-        bad(rn);
-        return;
-    }
-    out.rn = (int32_t)iv;
-    if (r.n_cigar == 0) {
-        out.err = "no CIGAR";
-        return;
-    }
-    uint32_t c0, c1;
-    std::memcpy(&c0, bam + r.cigar_off, 4);
-    std::memcpy(&c1, bam + r.cigar_off + 4 * ((size_t)r.n_cigar - 1), 4);
-    std::vector<int2> junc;
-    if (!lr::walk_junctions(bam, r, junc)) {  // L120-150: the walk runs for every record that is not null
-        out.err = "the CIGAR walk runs past the alignment blocks";
-        return;
-    }
-    // LongreadParser.parseSAMRecord L101-112 with is_gene_mandatory, !is_umi_mandatory, !keep_mapqv0
-    if (lr::chimeric(c0, c1, kMaxClip)) out.what = kChimeric;
-    else if (!gene.p || out.gene.empty() || out.gene == "undef") out.what = kNoGene;
-    else if (r.mapq == 0 && (r.flag & 0x900)) out.what = kMapq0;
-    else out.what = kKept;
-}
-
 // strings back to back: string i is pool[off[i] .. off[i + 1])
 struct Pool {
     std::vector<uint8_t> bytes;
@@ -603,35 +503,27 @@ extern "C" int smi_fusion_add_segment(smi_fusion *h, const uint8_t *bam, size_t 
         set_error(h->ran ? "smi_fusion_add_segment: the fusions were already detected (smi_fusion_run)" : "smi_fusion_add_segment: an earlier segment failed");
         return SMI_ERR_STATE;
     }
-    for (int32_t i = 0; i < n; i++) {
-        const smi_bam_record &r = recs[i];
-        if (r.name_off + r.l_read_name > n_bam || r.cigar_off + 4ull * r.n_cigar > n_bam || r.aux_off + r.aux_len > n_bam) {
-            set_error("smi_fusion_add_segment: record " + std::to_string(i) + " lies outside the segment");
-            return SMI_ERR_INVALID;
-        }
+    static const lr::TagSet tags = lr::TagSet().set(lr::kCell, "BC").set(lr::kUmi, "U8").set(lr::kGene, "GE").set(lr::kRn, "RN");  // L63-67
+    const lr::Segment seg = lr::read_segment("smi_fusion_add_segment", bam, n_bam, recs, n, h->cfg.n_threads,
+                                             [&](const uint8_t *b, const smi_bam_record &r, lr::Record &out, std::string &err) { lr::read_fusion(b, r, tags, kMaxClip, out, err); });
+    if (!seg.refused.empty()) {
+        set_error(seg.refused);
+        return SMI_ERR_INVALID;
     }
-    std::vector<Parsed> parsed(n);
-    const int nt = std::max(1, std::min<int>(h->cfg.n_threads, (n + 4095) / 4096));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; t++)
-        th.emplace_back([&, t] {
-            for (int32_t i = (int32_t)((int64_t)n * t / nt); i < (int32_t)((int64_t)n * (t + 1) / nt); i++) parse_record(bam, recs[i], parsed[i]);
-        });
-    for (auto &x : th) x.join();
-    // the first failing record in file order is the one named
+    if (seg.first_error >= 0) {
+        h->failed = true;
+        h->error_read = std::string(lr::read_name(bam, recs[seg.first_error]));
+        h->error_record = h->seen + seg.first_error;
+        set_error("FusionDetector: read " + h->error_read + ": " + seg.error);
+        return SMI_ERR_INVALID;
+    }
+    // GE.split(",") of Longread.addRecord L40-54.  jsplit("") is one empty field, which addRecord never sees: a kept record's gene is
+    // never empty (read_fusion tests no_gene).
     std::vector<std::string_view> fields;
     size_t add_rec = 0, add_fields = 0;
-    for (int32_t i = 0; i < n; i++) {
-        const Parsed &p = parsed[i];
-        if (p.what == kError) {
-            h->failed = true;
-            h->error_read = std::string(p.name);
-            h->error_record = h->seen + i;
-            set_error("FusionDetector: read " + h->error_read + ": " + p.err);
-            return SMI_ERR_INVALID;
-        }
-        if (p.what != kKept) continue;
-        split_genes(p.gene, fields);
+    for (const lr::Record &p : seg.recs) {
+        if (p.what != lr::kKept) continue;
+        lr::jsplit(p.gene, ',', fields);
         add_rec++;
         add_fields += fields.size();
     }
@@ -643,22 +535,22 @@ extern "C" int smi_fusion_add_segment(smi_fusion *h, const uint8_t *bam, size_t 
     }
     int64_t *c = h->counts;
     for (int32_t i = 0; i < n; i++) {
-        const Parsed &p = parsed[i];
+        const lr::Record &p = seg.recs[i];
         c[SMI_FUS_RECORDS]++;
-        if (p.what != kKept) {
+        if (p.what != lr::kKept) {
             c[SMI_FUS_UNVALID]++;
-            c[p.what == kNull ? SMI_FUS_NULL : p.what == kChimeric ? SMI_FUS_CHIMERIA : p.what == kNoGene ? SMI_FUS_NO_GENE : SMI_FUS_MAPQV0]++;
+            c[p.what == lr::kNull ? SMI_FUS_NULL : p.what == lr::kChimeric ? SMI_FUS_CHIMERIA : p.what == lr::kNoGene ? SMI_FUS_NO_GENE : SMI_FUS_MAPQV0]++;
             continue;
         }
         c[SMI_FUS_VALID]++;
         const int32_t r = (int32_t)h->names.size();
-        h->names.add(p.name);
+        h->names.add(lr::read_name(bam, recs[i]));
         h->bcs.add(lr::drop_minus1(p.bc));  // L83
         h->umis.add(p.has_umi ? p.umi : std::string_view());
         h->has_umi.push_back(p.has_umi);
         h->rn.push_back(p.rn);
         h->de.push_back(p.de);
-        split_genes(p.gene, fields);
+        lr::jsplit(p.gene, ',', fields);
         for (auto f : fields) {
             h->genes.add(f);
             h->f_rec.push_back(r);

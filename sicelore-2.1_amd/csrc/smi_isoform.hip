@@ -216,115 +216,10 @@ __global__ __launch_bounds__(64 * kIsoWaves) void k_iso(IsoArgs a) {
 
 
 // ---- host parsing -----------------------------------------------------------------------------------------------------------------------
-using lr::Aux;
 using lr::drop_minus1;
 using lr::java_float;
 using lr::jint;
 using lr::jsplit;
-using lr::walk_junctions;
-
-
-enum Outcome : uint8_t { kKept, kNull, kChimeric, kNoGene, kNoUmi, kMapq0, kError };
-
-struct Parsed {
-    Outcome what = kError;
-    float de = 1.0f;
-    int32_t rn = 1;
-    std::string_view name, bc, umi, gene;
-    std::vector<int2> junc;
-    std::string err;
-};
-
-struct TagSet {
-    uint16_t cell, umi, gene, rn, de, df;
-};
-
-void parse_record(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg, const smi_isoform_config &cfg, Parsed &out) {
-    out.name = std::string_view((const char *)bam + r.name_off, r.l_read_name ? r.l_read_name - 1 : 0);
-    const uint8_t *p = bam + r.aux_off, *end = p + r.aux_len;
-    Aux cell, umi, gene, rn, de, df;
-    while (p < end) {
-        size_t n;
-        if (lr::aux_size(p, end, &n)) {
-            out.what = kError;
-            out.err = "malformed attributes";
-            return;
-        }
-        const uint16_t t = (uint16_t)(p[0] | p[1] << 8);
-        const Aux a{p, n};
-        if (t == tg.cell) cell = a;  // (a repeated tag keeps its last value, as htsjdk reads it)
-        if (t == tg.umi) umi = a;
-        if (t == tg.gene) gene = a;
-        if (t == tg.rn) rn = a;
-        if (t == tg.de) de = a;
-        if (t == tg.df) df = a;
-        p += n;
-    }
-    auto bad = [&](const Aux &a) {
-        out.what = kError;
-        out.err = std::string("attribute ") + (char)a.p[0] + (char)a.p[1] + " of type " + (char)a.p[2] + " is not the type IsoformMatrix reads";
-    };
-    auto zstr = [&](const Aux &a, std::string_view &v) {
-        if (!a.p) return true;
-        if (a.p[2] != 'Z') {
-            bad(a);
-            return false;
-        }
-        v = std::string_view((const char *)a.p + 3, a.n - 4);
-        return true;
-    };
-    if (!zstr(gene, out.gene) || !zstr(cell, out.bc) || !zstr(umi, out.umi)) return;  // L75-77
-    if (!cell.p || (r.flag & 4)) {
-        out.what = kNull;
-        return;
-    }
-    for (const Aux *a : {&de, &df}) {  // L92-94: de, else df, else 1
-        if (!a->p) continue;
-        if (a->p[2] != 'f') {
-            bad(*a);
-            return;
-        }
-        std::memcpy(&out.de, a->p + 3, 4);
-        break;
-    }
-    int64_t iv = 1;
-    if (rn.p && !lr::aux_integer(rn, iv)) {  // L95
-        bad(rn);
-        return;
-    }
-    out.rn = (int32_t)iv;
-    if (r.n_cigar == 0) {
-        out.what = kError;
-        out.err = "no CIGAR";
-        return;
-    }
-    uint32_t c0, c1;
-    std::memcpy(&c0, bam + r.cigar_off, 4);
-    std::memcpy(&c1, bam + r.cigar_off + 4 * ((size_t)r.n_cigar - 1), 4);
-    const bool chim = lr::chimeric(c0, c1, cfg.max_clip);  // L108-112
-    if (!walk_junctions(bam, r, out.junc)) {                // (the walk runs for chimeric records too)
-        out.what = kError;
-        out.err = "the CIGAR walk runs past the alignment blocks";
-        return;
-    }
-    if (chim) {
-        out.what = kChimeric;
-        return;
-    }
-    if (!gene.p || out.gene.empty() || out.gene == "undef") {  // LongreadParser L101
-        out.what = kNoGene;
-        return;
-    }
-    if (!umi.p) {
-        out.what = kNoUmi;
-        return;
-    }
-    if (!cfg.mapqv0 && r.mapq == 0 && (r.flag & 0x900)) {
-        out.what = kMapq0;
-        return;
-    }
-    out.what = kKept;
-}
 
 struct Model {
     std::vector<std::string> genes;             // model genes in order of their first line
@@ -454,7 +349,7 @@ using namespace smi;
 struct smi_isoform {
     smi_ctx *ctx = nullptr;
     smi_isoform_config cfg = {};
-    TagSet tags = {};
+    lr::TagSet tags;
     Model M;
     std::vector<std::string> cells;  // byte order
     std::unordered_map<std::string, int32_t> cell_id;
@@ -533,8 +428,7 @@ extern "C" int smi_isoform_create(smi_ctx *ctx, const smi_isoform_config *cfg, c
     h->ctx = ctx;
     h->cfg = *cfg;
     h->cfg.n_threads = std::max(1, std::min(cfg->n_threads, 256));
-    h->tags = TagSet{lr::tag16(cfg->cell_tag), lr::tag16(cfg->umi_tag), lr::tag16(cfg->gene_tag), lr::tag16(cfg->rn_tag), lr::tag16("de"),
-                     lr::tag16("df")};
+    h->tags.set(lr::kCell, cfg->cell_tag).set(lr::kUmi, cfg->umi_tag).set(lr::kGene, cfg->gene_tag).set(lr::kRn, cfg->rn_tag);
     if (int rc = parse_model(refflat, n_refflat, h->M)) {
         delete h;
         return rc;
@@ -574,27 +468,18 @@ extern "C" int smi_isoform_add_segment(smi_isoform *h, const uint8_t *bam, size_
         set_error("smi_isoform_add_segment: the matrices were already built (smi_isoform_run)");
         return SMI_ERR_STATE;
     }
-    for (int32_t i = 0; i < n; i++) {
-        const smi_bam_record &r = recs[i];
-        if (r.name_off + r.l_read_name > n_bam || r.cigar_off + 4ull * r.n_cigar > n_bam || r.aux_off + r.aux_len > n_bam) {
-            set_error("smi_isoform_add_segment: record " + std::to_string(i) + " lies outside the segment");
-            return SMI_ERR_INVALID;
-        }
+    const lr::Segment seg = lr::read_segment("smi_isoform_add_segment", bam, n_bam, recs, n, h->cfg.n_threads,
+                                             [&](const uint8_t *b, const smi_bam_record &r, lr::Record &out, std::string &err) {
+                                                 lr::read_isoform(b, r, h->tags, h->cfg.max_clip, h->cfg.mapqv0, out, err);
+                                             });
+    if (!seg.refused.empty()) {
+        set_error(seg.refused);
+        return SMI_ERR_INVALID;
     }
-    std::vector<Parsed> parsed(n);
-    const int nt = std::max(1, std::min<int>(h->cfg.n_threads, (n + 4095) / 4096));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; t++)
-        th.emplace_back([&, t] {
-            for (int32_t i = (int32_t)((int64_t)n * t / nt); i < (int32_t)((int64_t)n * (t + 1) / nt); i++)
-                parse_record(bam, recs[i], h->tags, h->cfg, parsed[i]);
-        });
-    for (auto &x : th) x.join();
-    for (int32_t i = 0; i < n; i++)
-        if (parsed[i].what == kError) {
-            set_error("IsoformMatrix: read " + std::string(parsed[i].name) + ": " + parsed[i].err);
-            return SMI_ERR_INVALID;
-        }
+    if (seg.first_error >= 0) {
+        set_error("IsoformMatrix: read " + std::string(lr::read_name(bam, recs[seg.first_error])) + ": " + seg.error);
+        return SMI_ERR_INVALID;
+    }
     int64_t *c = h->counts;
     auto put = [&](std::string_view s, std::vector<uint64_t> &off, std::vector<uint32_t> &len) {
         off.push_back(h->text.size());
@@ -602,16 +487,16 @@ extern "C" int smi_isoform_add_segment(smi_isoform *h, const uint8_t *bam, size_
         h->text.append(s);
     };
     for (int32_t i = 0; i < n; i++) {
-        const Parsed &p = parsed[i];
+        const lr::Record &p = seg.recs[i];
         c[SMI_ISO_RECORDS]++;
-        if (p.what != kKept) {
+        if (p.what != lr::kKept) {
             c[SMI_ISO_UNVALID]++;
-            c[p.what == kNull ? SMI_ISO_NULL : p.what == kChimeric ? SMI_ISO_CHIMERIA : p.what == kNoGene ? SMI_ISO_NO_GENE
-                                                                     : p.what == kNoUmi ? SMI_ISO_NO_UMI : SMI_ISO_MAPQV0]++;
+            c[p.what == lr::kNull ? SMI_ISO_NULL : p.what == lr::kChimeric ? SMI_ISO_CHIMERIA : p.what == lr::kNoGene ? SMI_ISO_NO_GENE
+              : p.what == lr::kNoUmi ? SMI_ISO_NO_UMI : SMI_ISO_MAPQV0]++;
             continue;
         }
         c[SMI_ISO_VALID]++;
-        put(p.name, h->name_off, h->name_len);
+        put(lr::read_name(bam, recs[i]), h->name_off, h->name_len);
         put(drop_minus1(p.bc), h->bc_off, h->bc_len);
         put(p.umi, h->umi_off, h->umi_len);
         put(p.gene, h->gene_off, h->gene_len);
@@ -1024,6 +909,7 @@ extern "C" int smi_isoform_isobam(smi_isoform *h, const uint8_t *bam, size_t n_b
         // the lookup key: the raw CELLTAG and UMITAG strings ("null" when absent), as (String) r.getAttribute casts them
         std::vector<int32_t> entry(n > 0 ? n : 1, 0);
         std::vector<int32_t> bad(n > 0 ? n : 1, 0);
+        const uint16_t cell_tag = lr::tag16(h->cfg.cell_tag), umi_tag = lr::tag16(h->cfg.umi_tag);
         const int nt = std::max(1, std::min<int>(h->cfg.n_threads, (n + 4095) / 4096));
         std::vector<std::thread> th;
         for (int t = 0; t < nt; t++)
@@ -1039,8 +925,8 @@ extern "C" int smi_isoform_isobam(smi_isoform *h, const uint8_t *bam, size_t n_b
                             break;
                         }
                         const uint16_t tg = (uint16_t)(p[0] | p[1] << 8);
-                        if (tg == h->tags.cell) cell = lr::Aux{p, k};
-                        if (tg == h->tags.umi) umi = lr::Aux{p, k};
+                        if (tg == cell_tag) cell = lr::Aux{p, k};
+                        if (tg == umi_tag) umi = lr::Aux{p, k};
                         p += k;
                     }
                     if (bad[i]) continue;

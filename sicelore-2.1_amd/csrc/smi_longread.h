@@ -1,15 +1,20 @@
-// smi_longread.h -- the attribute helpers of the LongreadRecord.fromSAMRecord parsers (ComputeConsensus in smi_consensus.hip,
-// IsoformMatrix in smi_isoform.hip, SNPMatrix in smi_snp.hip), its CIGAR walk and the Java text rules they share
-// (FusionDetector in smi_fusion.hip reads them too): host only.
+// smi_longread.h -- LongreadRecord.fromSAMRecord and the LongreadParser filter, once, for the programs that read molecule records:
+// the attribute helpers, the CIGAR walk and the Java text rules (SNPMatrix in smi_snp.hip reads these too), the record reader (Reader),
+// the filters of IsoformMatrix, ComputeConsensus, CollapseModel and FusionDetector on top of it (read_isoform, read_consensus,
+// read_collapse, read_fusion) and the per-segment fan-out over host threads (read_segment).  Host only: no HIP call and no set_error,
+// so that a plain C++ compiler builds it (tools/asan/longread_host.cpp runs it on a CPU).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <charconv>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <new>
 #include <string>
 #include <string_view>
+#include <thread>
 #include <vector>
 
 #include "sicelore_mi.h"
@@ -95,9 +100,10 @@ inline std::string drop_minus1(std::string_view v) {  // String.replace("-1", ""
     return s;
 }
 
-// Java's String.split(regex) for a one-character separator: trailing empty strings removed
-inline std::vector<std::string_view> jsplit(std::string_view s, char sep) {
-    std::vector<std::string_view> out;
+// Java's String.split(regex) for a one-character separator: trailing empty strings removed.  Into `out`, for a caller that splits once
+// per record and keeps the vector's memory.
+inline void jsplit(std::string_view s, char sep, std::vector<std::string_view> &out) {
+    out.clear();
     size_t b = 0;
     for (size_t i = 0; i <= s.size(); i++)
         if (i == s.size() || s[i] == sep) {
@@ -106,6 +112,10 @@ inline std::vector<std::string_view> jsplit(std::string_view s, char sep) {
         }
     while (!out.empty() && out.back().empty()) out.pop_back();
     if (s.empty()) out.assign(1, std::string_view());  // "".split(x) = [""]
+}
+inline std::vector<std::string_view> jsplit(std::string_view s, char sep) {
+    std::vector<std::string_view> out;
+    jsplit(s, sep, out);
     return out;
 }
 
@@ -241,6 +251,296 @@ inline bool walk_junctions(const uint8_t *bam, const smi_bam_record &r, std::vec
     out.clear();
     for (size_t i = 1; i < xs.size(); i++) out.push_back(make_int2((int)xe[i - 1], (int)xs[i]));
     return true;
+}
+
+// ---- the record reader -------------------------------------------------------------------------------------------------------------------
+enum Tag { kCell, kUmi, kGene, kRn, kDe, kDf, kIso, kTe, kPs, kCs, kUs, kTags };
+
+// the attributes a program captures: de and df always, the others as it names them
+struct TagSet {
+    uint16_t id[kTags] = {};  // the captured ones, in the order they were set
+    uint8_t tag[kTags] = {};  // what id[i] is
+    int n = 0;
+    TagSet() {
+        set(kDe, "de");
+        set(kDf, "df");
+    }
+    TagSet &set(Tag k, const char *t) {
+        id[n] = tag16(t);
+        tag[n++] = (uint8_t)k;
+        return *this;
+    }
+    uint16_t of(Tag k) const {
+        for (int i = 0; i < n; i++)
+            if (tag[i] == k) return id[i];
+        return 0;
+    }
+    std::string text(Tag k) const { return std::string{(char)(of(k) & 255), (char)(of(k) >> 8)}; }
+};
+
+inline std::string_view read_name(const uint8_t *bam, const smi_bam_record &r) {
+    return std::string_view((const char *)bam + r.name_off, r.l_read_name ? r.l_read_name - 1 : 0);
+}
+
+enum Outcome : uint8_t { kKept, kNull, kChimeric, kNoGene, kNoUmi, kMapq0, kLowRn, kNotListed, kError };
+
+// what the four programs keep of a record, in two cache lines (the thread that appends the kept records reads what the workers wrote);
+// the views point into the segment (bc: before the "-1" removal); the read's name is read_name(bam, r)
+struct Record {
+    Outcome what = kError;
+    bool has_umi = false, has_it = false;
+    float de = 1.0f;
+    int32_t rn = 1;
+    int32_t tx_start = 0, tx_end = 0;  // getAlignmentStart, getAlignmentEnd
+    std::string_view bc, umi, gene, cdna, it;
+    std::vector<int2> junc;
+};
+
+// The steps of fromSAMRecord over one record.  Every step that can fail returns false with out.what = kError and the reason in err; a
+// filter calls them in its program's order and returns at the first false.
+struct Reader {
+    const uint8_t *bam;
+    const smi_bam_record &r;
+    const char *program;
+    Record &out;
+    std::string &err;
+    Aux aux[kTags];
+    uint32_t c0 = 0, c1 = 0;  // the first and the last CIGAR operation
+
+    Reader(const uint8_t *bam_, const smi_bam_record &r_, const char *program_, Record &out_, std::string &err_)
+        : bam(bam_), r(r_), program(program_), out(out_), err(err_) {
+        out.what = kError;
+    }
+    bool fail(std::string why) {
+        out.what = kError;
+        err = std::move(why);
+        return false;
+    }
+    bool bad(const Aux &a) {
+        return fail(std::string("attribute ") + (char)a.p[0] + (char)a.p[1] + " of type " + (char)a.p[2] + " is not the type " + program + " reads");
+    }
+    void is(Outcome o) { out.what = o; }
+    bool has(Tag k) const { return aux[k].p != nullptr; }
+
+    // the attribute walk: a repeated tag keeps its last value (and type), as htsjdk reads it
+    bool attributes(const TagSet &tg) {
+        const uint8_t *p = bam + r.aux_off, *end = p + r.aux_len;
+        while (p < end) {
+            size_t n;
+            if (aux_size(p, end, &n)) return fail("malformed attributes");
+            const uint16_t t = (uint16_t)(p[0] | p[1] << 8);
+            for (int k = 0; k < tg.n; k++)
+                if (t == tg.id[k]) aux[tg.tag[k]] = Aux{p, n};
+            p += n;
+        }
+        return true;
+    }
+    bool str(Tag k, std::string_view &v) {  // (String) getAttribute; absent: v stays
+        const Aux &a = aux[k];
+        if (!a.p) return true;
+        if (a.p[2] != 'Z') return bad(a);
+        v = std::string_view((const char *)a.p + 3, a.n - 4);
+        return true;
+    }
+    bool integer(Tag k, int64_t &v) {  // (Integer) getAttribute; absent: v stays
+        return !aux[k].p || aux_integer(aux[k], v) || bad(aux[k]);
+    }
+    bool rn() {  // L95
+        int64_t v = 1;
+        if (!integer(kRn, v)) return false;
+        out.rn = (int32_t)v;
+        return true;
+    }
+    bool de() {  // L92-94: de, else df, else 1; df is looked at only when de is absent
+        for (Tag k : {kDe, kDf}) {
+            if (!aux[k].p) continue;
+            if (aux[k].p[2] != 'f') return bad(aux[k]);
+            std::memcpy(&out.de, aux[k].p + 3, 4);
+            break;
+        }
+        return true;
+    }
+    bool null() const { return !aux[kCell].p || (r.flag & 4); }  // L80
+    bool cigar_ends() {
+        if (r.n_cigar == 0) return fail("no CIGAR");
+        std::memcpy(&c0, bam + r.cigar_off, 4);
+        std::memcpy(&c1, bam + r.cigar_off + 4 * ((size_t)r.n_cigar - 1), 4);
+        return true;
+    }
+    bool clipped(int32_t max_clip) const { return chimeric(c0, c1, max_clip); }  // L108-112
+    bool junctions(std::vector<int2> &junc) {                                    // L120-150
+        return walk_junctions(bam, r, junc) || fail("the CIGAR walk runs past the alignment blocks");
+    }
+    void alignment() {
+        int64_t ref_len = 0;
+        for (int k = 0; k < r.n_cigar; k++) {
+            uint32_t c;
+            std::memcpy(&c, bam + r.cigar_off + 4ull * k, 4);
+            const uint32_t op = c & 15;
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += c >> 4;
+        }
+        out.tx_start = r.pos + 1;
+        out.tx_end = (int32_t)(r.pos + ref_len);
+    }
+    bool no_gene() const { return !aux[kGene].p || out.gene.empty() || out.gene == "undef"; }  // LongreadParser L101
+    bool mapq0_secondary() const { return r.mapq == 0 && (r.flag & 0x900); }                   // LongreadParser L105-112
+};
+
+// ---- the four programs: the order of the casts and of the tests is each program's own ----------------------------------------------------
+
+// IsoformMatrix: tags cell, umi, gene, rn
+inline void read_isoform(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg, int32_t max_clip, bool mapqv0, Record &out,
+                         std::string &err) {
+    Reader rd(bam, r, "IsoformMatrix", out, err);
+    if (!rd.attributes(tg)) return;
+    if (!rd.str(kGene, out.gene) || !rd.str(kCell, out.bc) || !rd.str(kUmi, out.umi)) return;  // L75-77: the casts come first
+    if (rd.null()) return rd.is(kNull);
+    if (!rd.de() || !rd.rn()) return;
+    if (!rd.cigar_ends()) return;
+    if (!rd.junctions(out.junc)) return;  // (a failing walk is an error for a chimeric record too)
+    if (rd.clipped(max_clip)) return rd.is(kChimeric);
+    if (rd.no_gene()) return rd.is(kNoGene);
+    if (!rd.has(kUmi)) return rd.is(kNoUmi);
+    if (!mapqv0 && rd.mapq0_secondary()) return rd.is(kMapq0);
+    rd.is(kKept);
+}
+
+// ComputeConsensus: tags cell, umi, gene, rn, te, ps, cs, us.  The cDNA is cs, else us cut at te and ps (L116-135).
+inline void read_consensus(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg, int32_t max_clip, bool mapqv0, Record &out,
+                           std::string &err) {
+    Reader rd(bam, r, "ComputeConsensus", out, err);
+    if (!rd.attributes(tg)) return;
+    if (!rd.str(kGene, out.gene) || !rd.str(kCell, out.bc) || !rd.str(kUmi, out.umi)) return;  // L75-81: the casts come first
+    if (rd.null()) return rd.is(kNull);
+    if (!rd.de() || !rd.rn()) return;  // (rn is not used further)
+    if (!rd.cigar_ends()) return;
+    if (rd.clipped(max_clip)) return rd.is(kChimeric);  // before the cDNA is cut; the junction walk does not run
+    if (!rd.str(kCs, out.cdna)) return;
+    if (!rd.has(kCs)) {
+        std::string_view us;
+        if (!rd.str(kUs, us)) return;
+        if (!rd.has(kUs)) return (void)rd.fail("neither " + tg.text(kCs) + " nor " + tg.text(kUs));
+        int64_t tso = 0, pa = 0;
+        if (!rd.integer(kTe, tso) || !rd.integer(kPs, pa)) return;
+        const int64_t len = (int64_t)us.size();
+        const int64_t e = (pa != 0 && pa < len - 1) ? pa : len - 1;
+        if (tso < e && tso < 0) return (void)rd.fail(tg.text(kTe) + " " + std::to_string(tso) + " is outside " + tg.text(kUs));  // substring throws
+        out.cdna = tso < e ? us.substr((size_t)tso, (size_t)(e - tso)) : us;
+    }
+    if (!rd.has(kUmi)) return rd.is(kNoUmi);  // LongreadParser L103
+    if (!mapqv0 && rd.mapq0_secondary()) return rd.is(kMapq0);
+    rd.is(kKept);
+}
+
+// CollapseModel: tags cell, umi, gene, rn, iso.  listed(barcode): the cell list's contains().
+template <class Listed>
+inline void read_collapse(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg, int32_t max_clip, int32_t rn_min, Listed &&listed,
+                          Record &out, std::string &err) {
+    Reader rd(bam, r, "CollapseModel", out, err);
+    if (!rd.attributes(tg)) return;
+    // loader L157-161: every cast, RN's too, comes before anything else, for every record
+    std::string_view umi;  // (cast, not kept)
+    if (!rd.str(kCell, out.bc) || !rd.str(kUmi, umi) || !rd.str(kGene, out.gene) || !rd.str(kIso, out.it)) return;
+    out.has_it = rd.has(kIso);
+    if (!rd.rn()) return;
+    if (rd.null() || r.ref_id < 0) return rd.is(kNull);  // (a record on no sequence is in no query)
+    if (!rd.de()) return;
+    if (!rd.cigar_ends()) return;
+    if (!rd.junctions(out.junc)) return;  // the walk runs before the filter
+    rd.alignment();
+    // loader L167-170
+    if (r.mapq == 0) return rd.is(kMapq0);
+    if (rd.clipped(max_clip)) return rd.is(kChimeric);
+    if (out.rn < rn_min) return rd.is(kLowRn);
+    if (!listed(out.bc)) return rd.is(kNotListed);
+    if (rd.no_gene()) return rd.is(kNoGene);
+    rd.is(kKept);
+}
+
+// FusionDetector (FusionDetector.java L63-67): tags BC U8 GE RN, MAXCLIP 10000, gene mandatory, UMI not, mapq-0 records kept when primary
+inline void read_fusion(const uint8_t *bam, const smi_bam_record &r, const TagSet &tg, int32_t max_clip, Record &out, std::string &err) {
+    Reader rd(bam, r, "FusionDetector", out, err);
+    if (!rd.attributes(tg)) return;
+    if (!rd.str(kGene, out.gene) || !rd.str(kCell, out.bc) || !rd.str(kUmi, out.umi)) return;  // L75-77: the casts come first
+    out.has_umi = rd.has(kUmi);
+    if (rd.null()) return rd.is(kNull);
+    if (!rd.de() || !rd.rn()) return;
+    if (!rd.cigar_ends()) return;
+    std::vector<int2> junc;  // (not kept)
+    if (!rd.junctions(junc)) return;  // the walk runs for every record that is not null
+    if (rd.clipped(max_clip)) return rd.is(kChimeric);
+    if (rd.no_gene()) return rd.is(kNoGene);
+    if (rd.mapq0_secondary()) return rd.is(kMapq0);
+    rd.is(kKept);
+}
+
+// ---- one segment ----------------------------------------------------------------------------------------------------------------------
+// The records of a segment.  Each is constructed by the thread that reads it: the array's pages are then first touched by the workers and
+// not one after the other by the caller, which was close to half of a segment's time when the caller built a std::vector of them.
+class Records {
+    Record *p_ = nullptr;
+    size_t n_ = 0;
+
+   public:
+    Records() = default;
+    explicit Records(size_t n) : p_(n ? (Record *)::operator new(n * sizeof(Record)) : nullptr), n_(n) {}
+    Records(Records &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+    Records &operator=(Records &&o) noexcept {
+        std::swap(p_, o.p_), std::swap(n_, o.n_);
+        return *this;
+    }
+    ~Records() {  // (read_segment has constructed every one by the time it returns)
+        for (size_t i = 0; i < n_; i++) p_[i].~Record();
+        ::operator delete(p_);
+    }
+    Record *raw(size_t i) { return p_ + i; }
+    const Record &operator[](size_t i) const { return p_[i]; }
+    const Record *begin() const { return p_; }
+    const Record *end() const { return p_ + n_; }
+    size_t size() const { return n_; }
+};
+
+struct Segment {
+    Records recs;
+    int32_t first_error = -1;  // the first record in file order whose outcome is kError
+    std::string error;         // why that record failed
+    std::string refused;       // not empty: a record lies outside the segment and nothing was read
+};
+
+// read(bam, recs[i], out, err) for every record of the segment, on up to n_threads host threads; fn: the caller's name, for `refused`
+template <class Read>
+Segment read_segment(const char *fn, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n, int n_threads, Read &&read) {
+    Segment seg;
+    for (int32_t i = 0; i < n; i++) {
+        const smi_bam_record &r = recs[i];
+        if (r.name_off + r.l_read_name > n_bam || r.cigar_off + 4ull * r.n_cigar > n_bam || r.aux_off + r.aux_len > n_bam) {
+            seg.refused = std::string(fn) + ": record " + std::to_string(i) + " lies outside the segment";
+            return seg;
+        }
+    }
+    seg.recs = Records((size_t)n);
+    const int nt = std::max(1, std::min<int>(n_threads, (n + 4095) / 4096));
+    struct Failed {  // per thread: the first failing record of its slice
+        int32_t i = -1;
+        std::string why;
+    };
+    std::vector<Failed> failed(nt);
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; t++)
+        th.emplace_back([&, t] {
+            std::string err;
+            for (int32_t i = (int32_t)((int64_t)n * t / nt); i < (int32_t)((int64_t)n * (t + 1) / nt); i++) {
+                Record *out = new (seg.recs.raw(i)) Record;
+                read(bam, recs[i], *out, err);
+                if (out->what == kError && failed[t].i < 0) failed[t] = Failed{i, err};
+            }
+        });
+    for (auto &x : th) x.join();
+    for (int t = 0; t < nt && seg.first_error < 0; t++) {
+        seg.first_error = failed[t].i;
+        seg.error = std::move(failed[t].why);
+    }
+    return seg;
 }
 
 }  // namespace lr

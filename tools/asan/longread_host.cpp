@@ -1,0 +1,167 @@
+// The record reader of sicelore-2.1_amd/csrc/smi_longread.h on a CPU, as the library runs it: the filters of IsoformMatrix,
+// ComputeConsensus, CollapseModel and FusionDetector over every record of an inflated BAM, each through lr::read_segment.
+//   g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Isicelore-2.1_amd/csrc tools/asan/longread_host.cpp -lpthread
+//   longread_host in.bam settings.txt        (add -fsanitize=address,undefined to the g++ line for a sanitizer run)
+// settings.txt, one `key value` per line: the tags cell umi gene rn iso te ps cs us (two characters each), max_clip, mapqv0, rn_min,
+// threads, listed <barcode> (one line per cell of the list, "-1" removed as the handles do), outside <i> (record i's attributes are
+// moved behind the segment: what a caller's damaged index would hand over).
+// Output, per program: `<program> refused <text>`, or `<program> error <index> <read> <text>`, or `<program> counts k=v ...` followed
+// by one `<program> kept <read> <barcode, "-1" removed> <umi or *> <cdna or *> <junctions end-start,...>` per kept record.  Fields are
+// separated by tabs.
+// tests/test_longread_cpu.py builds and runs it and compares with the Python models.
+#include <cstdio>
+#include <fstream>
+#include <iterator>
+#include <sstream>
+#include <unordered_set>
+
+#include "smi_longread.h"
+
+using namespace smi;
+
+// the records of an inflated BAM; stops in front of a record that does not fit (a damaged file: the reader never sees it)
+static std::vector<smi_bam_record> index_records(const std::vector<uint8_t> &bam) {
+    std::vector<smi_bam_record> recs;
+    auto u32 = [&](size_t p) {
+        uint32_t v;
+        std::memcpy(&v, bam.data() + p, 4);
+        return v;
+    };
+    const size_t n = bam.size();
+    if (n < 12 || std::memcmp(bam.data(), "BAM\1", 4)) return recs;
+    size_t p = 8 + (size_t)u32(4);
+    if (p + 4 > n) return recs;
+    const uint32_t n_ref = u32(p);
+    p += 4;
+    for (uint32_t i = 0; i < n_ref; i++) {
+        if (p + 4 > n) return recs;
+        p += 8 + (size_t)u32(p);
+        if (p > n) return recs;
+    }
+    while (p + 36 <= n) {
+        const size_t len = u32(p);
+        if (len < 32 || len > n - p - 4) break;
+        smi_bam_record r = {};
+        const uint8_t *b = bam.data() + p + 4;
+        uint16_t n_cigar, flag;
+        int32_t l_seq;
+        std::memcpy(&r.ref_id, b, 4);
+        std::memcpy(&r.pos, b + 4, 4);
+        r.l_read_name = b[8];
+        r.mapq = b[9];
+        std::memcpy(&n_cigar, b + 12, 2);
+        std::memcpy(&flag, b + 14, 2);
+        std::memcpy(&l_seq, b + 16, 4);
+        if (l_seq < 0) break;
+        const size_t fixed = (size_t)r.l_read_name + 4 * (size_t)n_cigar + ((size_t)l_seq + 1) / 2 + (size_t)l_seq;
+        if (32 + fixed > len) break;
+        r.rec_off = p;
+        r.rec_len = (uint32_t)len + 4;
+        r.n_cigar = n_cigar;
+        r.flag = flag;
+        r.l_seq = l_seq;
+        r.name_off = p + 36;
+        r.cigar_off = r.name_off + r.l_read_name;
+        r.seq_off = r.cigar_off + 4 * (size_t)n_cigar;
+        r.qual_off = r.seq_off + ((size_t)l_seq + 1) / 2;
+        r.aux_off = r.qual_off + (size_t)l_seq;
+        r.aux_len = (uint32_t)(p + 4 + len - r.aux_off);
+        recs.push_back(r);
+        p += 4 + len;
+    }
+    return recs;
+}
+
+static const char *const kOutcome[] = {"kept", "null", "chimeric", "no_gene", "no_umi", "mapq0", "low_rn", "not_listed"};
+
+static void report(const char *program, const uint8_t *bam, const smi_bam_record *recs, const lr::Segment &seg) {
+    if (!seg.refused.empty()) {
+        std::printf("%s\trefused\t%s\n", program, seg.refused.c_str());
+        return;
+    }
+    if (seg.first_error >= 0) {
+        std::printf("%s\terror\t%d\t%s\t%s\n", program, seg.first_error, std::string(lr::read_name(bam, recs[seg.first_error])).c_str(),
+                    seg.error.c_str());
+        return;
+    }
+    int64_t c[lr::kError] = {};
+    for (const lr::Record &p : seg.recs) c[p.what]++;
+    std::printf("%s\tcounts\trecords=%zu", program, seg.recs.size());
+    for (int k = 0; k < lr::kError; k++) std::printf(" %s=%lld", kOutcome[k], (long long)c[k]);
+    std::printf("\n");
+    for (size_t i = 0; i < seg.recs.size(); i++)
+        if (const lr::Record &p = seg.recs[i]; p.what == lr::kKept) {
+            std::string junc;
+            for (const int2 &j : p.junc) junc += std::to_string(j.x) + "-" + std::to_string(j.y) + ",";
+            std::printf("%s\tkept\t%s\t%s\t%s\t%s\t%s\n", program, std::string(lr::read_name(bam, recs[i])).c_str(), lr::drop_minus1(p.bc).c_str(),
+                        p.umi.data() ? std::string(p.umi).c_str() : "*", p.cdna.data() ? std::string(p.cdna).c_str() : "*", junc.c_str());
+        }
+}
+
+int main(int argc, char **argv) {
+    if (argc != 3) {
+        std::fprintf(stderr, "usage: longread_host in.bam settings.txt\n");
+        return 2;
+    }
+    std::ifstream fb(argv[1], std::ios::binary), fs(argv[2]);
+    if (!fb || !fs) {
+        std::fprintf(stderr, "longread_host: cannot open the input\n");
+        return 2;
+    }
+    const std::vector<uint8_t> bam((std::istreambuf_iterator<char>(fb)), std::istreambuf_iterator<char>());
+    lr::TagSet tags;
+    int32_t max_clip = 150, rn_min = 1, mapqv0 = 0, threads = 4;
+    long outside = -1;
+    std::unordered_set<std::string> cells;
+    static const struct {
+        const char *key;
+        lr::Tag tag;
+    } kTagKeys[] = {{"cell", lr::kCell}, {"umi", lr::kUmi}, {"gene", lr::kGene}, {"rn", lr::kRn}, {"iso", lr::kIso},
+                    {"te", lr::kTe},     {"ps", lr::kPs},   {"cs", lr::kCs},     {"us", lr::kUs}};
+    for (std::string line; std::getline(fs, line);) {
+        std::istringstream in(line);
+        std::string key, value;
+        if (!(in >> key)) continue;
+        in >> value;  // (a listed barcode may be empty)
+        bool known = false;
+        for (const auto &t : kTagKeys)
+            if (key == t.key) {
+                if (value.size() != 2) {
+                    std::fprintf(stderr, "longread_host: %s must be two characters\n", key.c_str());
+                    return 2;
+                }
+                tags.set(t.tag, value.c_str());
+                known = true;
+            }
+        if (key == "listed") cells.insert(lr::drop_minus1(value));
+        else if (key == "max_clip") max_clip = std::atoi(value.c_str());
+        else if (key == "mapqv0") mapqv0 = std::atoi(value.c_str());
+        else if (key == "rn_min") rn_min = std::atoi(value.c_str());
+        else if (key == "threads") threads = std::atoi(value.c_str());
+        else if (key == "outside") outside = std::atol(value.c_str());
+        else if (!known) {
+            std::fprintf(stderr, "longread_host: unknown setting %s\n", key.c_str());
+            return 2;
+        }
+    }
+    std::vector<smi_bam_record> recs = index_records(bam);
+    if (outside >= 0 && (size_t)outside < recs.size()) recs[outside].aux_off = bam.size() - recs[outside].aux_len + 1;
+    const int32_t n = (int32_t)recs.size();
+    const lr::TagSet fusion_tags = lr::TagSet().set(lr::kCell, "BC").set(lr::kUmi, "U8").set(lr::kGene, "GE").set(lr::kRn, "RN");
+    const auto listed = [&](std::string_view bc) { return cells.count(std::string(bc)) != 0; };
+    report("isoform", bam.data(), recs.data(), lr::read_segment("smi_isoform_add_segment", bam.data(), bam.size(), recs.data(), n, threads,
+                                       [&](const uint8_t *b, const smi_bam_record &r, lr::Record &out, std::string &err) {
+                                           lr::read_isoform(b, r, tags, max_clip, mapqv0 != 0, out, err);
+                                       }));
+    report("consensus", bam.data(), recs.data(), lr::read_segment("smi_consensus_add_segment", bam.data(), bam.size(), recs.data(), n, threads,
+                                         [&](const uint8_t *b, const smi_bam_record &r, lr::Record &out, std::string &err) {
+                                             lr::read_consensus(b, r, tags, max_clip, mapqv0 != 0, out, err);
+                                         }));
+    report("collapse", bam.data(), recs.data(), lr::read_segment("smi_collapse_add_segment", bam.data(), bam.size(), recs.data(), n, threads,
+                                        [&](const uint8_t *b, const smi_bam_record &r, lr::Record &out, std::string &err) {
+                                            lr::read_collapse(b, r, tags, max_clip, rn_min, listed, out, err);
+                                        }));
+    report("fusion", bam.data(), recs.data(), lr::read_segment("smi_fusion_add_segment", bam.data(), bam.size(), recs.data(), n, threads,
+                                      [&](const uint8_t *b, const smi_bam_record &r, lr::Record &out, std::string &err) { lr::read_fusion(b, r, fusion_tags, 10000, out, err); }));
+    return 0;
+}

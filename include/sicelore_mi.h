@@ -815,6 +815,12 @@ int smi_assignumis_default_config(smi_assignumis_config *cfg);
 int smi_assignumis_chunk(smi_ctx *ctx, const char *names, const uint32_t *name_off, const uint16_t *flags, const int32_t *pos0,
                          const uint32_t *cigars, const uint32_t *cigar_off, int32_t n, const smi_assignumis_config *cfg,
                          smi_umi_tag *out, int32_t *n_done);
+/* which way the last chunk of this context (or lane) went: the host path is taken silently when a name is of a form K-UPARSE does not evaluate */
+#define SMI_AU_PATH_NONE 0        /* no chunk yet */
+#define SMI_AU_PATH_DEVICE 1      /* the device stage finished the chunk */
+#define SMI_AU_PATH_HOST_FORCED 2 /* the host path: SMI_AU_HOST was set */
+#define SMI_AU_PATH_HOST_NAMES 3  /* the host path: K-UPARSE reported a name it does not evaluate (errors of that path included) */
+int smi_assignumis_last_path(const smi_ctx *ctx, int32_t *path);
 
 /* ================================================================================================================
  * BAM ingest of `assignumis` (host): what BamReader (FJ!umifinder/bamreaders/BamReader.java:L82-158)

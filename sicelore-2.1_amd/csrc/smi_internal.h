@@ -211,6 +211,7 @@ struct smi_ctx {
     void *umi_dist = nullptr;      // K-UMI matrices of the device UMI stage (smi_assignumis_chunk), grow-only
     size_t umi_dist_bytes = 0;
     void *region_work = nullptr;      // host scratch of the region grouping (smi_cluster.hip), kept between calls
+    int32_t au_last_path = 0;         // SMI_AU_PATH_* of the last smi_assignumis_chunk of this context or lane (smi_assignumis_last_path)
     void *deflate_scratch = nullptr;  // K-DEFLATE: block slots, sizes, offsets, scan storage (grow-only)
     size_t deflate_scratch_bytes = 0;
     void *host_buf[HB_COUNT] = {};

@@ -58,7 +58,7 @@ __device__ __forceinline__ bool parse_int(const NameView &v, int a, int b, long 
     for (; i < b; i++) {
         const char c = v.at(i);
         if (c < '0' || c > '9') {
-            if (c == ' ' || c == '+' || c == '\t') *nonstd = true;  // strtol would have skipped / accepted these
+            if (c == ' ' || c == '+' || c == '\t') *nonstd = true;  // (a sign the host's parser reads, blanks it refuses: left to it)
             return false;
         }
         x = x * 10 + (c - '0');
@@ -271,7 +271,8 @@ __global__ __launch_bounds__(64) void k_umi_parse(const char *__restrict__ names
                         const float den = n_frac <= 0 ? 1.0f : n_frac == 1 ? 10.0f : n_frac == 2 ? 100.0f : 1000.0f;
                         P.q = __fdiv_rn((float)mant, den);
                     }
-                }
+                } else
+                    nonstd = true;  // (a longer text is still a Q= to the reference: left to the host)
             }
             // the read's own UMI window (umi_window of smi_worker.hip)
             if (has_bc && has_bc_end && p_x >= 0 && has_q) {

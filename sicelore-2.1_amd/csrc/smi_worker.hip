@@ -825,15 +825,24 @@ bool extract(const char *sub, size_t n, const char *tag, const char **val, size_
     return false;
 }
 
-bool to_int(const char *v, size_t n, long *out) {  // Integer.parseInt
-    if (n == 0 || n > 11) return false;
-    char buf[16];
-    std::memcpy(buf, v, n);
-    buf[n] = 0;
-    char *end = nullptr;
-    const long x = std::strtol(buf, &end, 10);
-    if (end != buf + n) return false;
-    *out = x;
+// Integer.parseInt: an optional sign, decimal digits, the value inside int.  Everything else -- blanks, other characters, a value out of range --
+// is a NumberFormatException there and no number here (strtol would skip blanks and hand back a long)
+bool to_int(const char *v, size_t n, long *out) {
+    size_t i = 0;
+    bool neg = false;
+    if (n && (v[0] == '-' || v[0] == '+')) {
+        neg = v[0] == '-';
+        i = 1;
+    }
+    if (i >= n) return false;
+    long x = 0;
+    for (; i < n; i++) {
+        if (v[i] < '0' || v[i] > '9') return false;
+        x = x * 10 + (v[i] - '0');
+        if (x > 2147483648L) return false;
+    }
+    if (x > 2147483647L + (neg ? 1 : 0)) return false;
+    *out = neg ? -x : x;
     return true;
 }
 
@@ -881,15 +890,11 @@ int parse_name(const char *name, size_t n, int bc_edit_limit, NameData &d) {
         d.x = v;
         d.x_len = l;
     }
-    if (extract(sub, sn, "Q=", &v, &l) && l < 30) {
-        char buf[32];
+    if (extract(sub, sn, "Q=", &v, &l)) {
         size_t k = 0;
-        while (k < l && v[k] != ' ') {
-            buf[k] = v[k];
-            k++;
-        }
-        buf[k] = 0;
-        d.q = std::strtof(buf, nullptr);  // Float.parseFloat
+        while (k < l && v[k] != ' ') k++;
+        const std::string text(v, k);                 // (of any length: the reference reads a Q= of 30 characters and more like any other)
+        d.q = std::strtof(text.c_str(), nullptr);  // Float.parseFloat
         d.has_q = k > 0;
     }
     return SMI_OK;
@@ -1187,6 +1192,16 @@ extern "C" int smi_umi_cluster_groups_device(smi_ctx *ctx, const uint8_t *d_dist
     return launch_umi_cluster(ctx, d_dist, d_mat_off, d_group_off, n_groups, d_mean_qv, *cfg, dev_max, d_out, d_skipped, static_cast<hipStream_t>(stream));
 }
 
+// which way the last chunk of this context went (SMI_AU_PATH_*): the fallback to the host path is otherwise invisible to the caller
+extern "C" int smi_assignumis_last_path(const smi_ctx *ctx, int32_t *path) {
+    if (!ctx || !path) {
+        set_error("smi_assignumis_last_path: null argument");
+        return SMI_ERR_INVALID;
+    }
+    *path = ctx->au_last_path;
+    return SMI_OK;
+}
+
 // `assignumis` for one chunk, the UMI stage on the device (smi_umi_stage.hip): K-UPARSE -> [host: region grouping] -> key sort ->
 // K-UMI -> K-UCLUST (groups of up to 100 reads; larger groups: their matrix comes back and ClusterOne_MyClustering runs on the host) ->
 // K-UTAG.  Same results as the host path, record by record (tests/test_umi_stage_gpu.py).
@@ -1207,7 +1222,10 @@ extern "C" int smi_assignumis_chunk(smi_ctx *ctx, const char *names, const uint3
     smi_umi_cluster_config cc;
     SMI_RC(smi_umi_cluster_default_config(&cc));
     if (cfg->cluster) cc = *cfg->cluster;
-    if (std::getenv("SMI_AU_HOST")) return assignumis_chunk_host(ctx, names, name_off, flags, pos0, cigars, cigar_off, n, cfg, out, n_done);
+    if (std::getenv("SMI_AU_HOST")) {
+        ctx->au_last_path = SMI_AU_PATH_HOST_FORCED;
+        return assignumis_chunk_host(ctx, names, name_off, flags, pos0, cigars, cigar_off, n, cfg, out, n_done);
+    }
     const bool timing = std::getenv("SMI_AU_TIMING") != nullptr;
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -1286,8 +1304,11 @@ extern "C" int smi_assignumis_chunk(smi_ctx *ctx, const char *names, const uint3
     SMI_HIP(hipMemcpyAsync(h_bits, d_rbits, n_words * 8, hipMemcpyDeviceToHost, s));
     SMI_HIP(hipStreamSynchronize(s));
     lap("parse+sort");
-    if (h_rcount[1])  // a name the device parser does not evaluate: the host path reads it itself (and reports AE= missing as the reference does)
+    if (h_rcount[1]) {  // a name the device parser does not evaluate: the host path reads it itself (and reports AE= missing as the reference does)
+        ctx->au_last_path = SMI_AU_PATH_HOST_NAMES;
         return assignumis_chunk_host(ctx, names, name_off, flags, pos0, cigars, cigar_off, n, cfg, out, n_done);
+    }
+    ctx->au_last_path = SMI_AU_PATH_DEVICE;
     SMI_RC(region_group_from_sorted(&ctx->region_work, h_keys, h_rcount[0], n, h_bits, cfg->max_dist, cfg->keep_data_end, h_region, n_done));
     lap("regions");
     SMI_HIP(hipMemcpyAsync(d_region, h_region, N * 4, hipMemcpyHostToDevice, s));

@@ -54,7 +54,7 @@ EXPORTS = [
     "smi_chimera_default_config", "smi_read_planes_words", "smi_pack_reads_device", "smi_chimera_device",
     "smi_split_offsets_device", "smi_chimera_fragment_name", "smi_umi_cluster_default_config", "smi_umi_cluster_groups",
     "smi_region_group", "smi_ref_position_at_read_position", "smi_scan_default_config_5p", "smi_chimera_default_config_5p", "smi_fastq_index_device", "smi_fastq_gather_device",
-    "smi_fastq_write_device", "smi_bgzf_uncompressed_size", "smi_bgzf_inflate", "smi_bam_header", "smi_bam_index_records", "smi_gz_inflate", "smi_bgzf_deflate", "smi_pass2_default_config", "smi_scanfastq_pass2_chunk", "smi_scanfastq_pass1_chunk", "smi_host_alloc", "smi_host_free", "smi_assignumis_default_config", "smi_assignumis_chunk", "smi_bc_counts_device", "smi_assigned_tsv", "smi_barcode_list_tsv", "smi_hist_allreduce", "smi_hist_allreduce_after", "smi_hist_allreduce_release", "smi_ctx_create_lane", "smi_ctx_lane_refresh", "smi_scan_batch", "smi_umi_dist_batch",
+    "smi_fastq_write_device", "smi_bgzf_uncompressed_size", "smi_bgzf_inflate", "smi_bam_header", "smi_bam_index_records", "smi_gz_inflate", "smi_bgzf_deflate", "smi_pass2_default_config", "smi_scanfastq_pass2_chunk", "smi_scanfastq_pass1_chunk", "smi_host_alloc", "smi_host_free", "smi_assignumis_default_config", "smi_assignumis_chunk", "smi_assignumis_last_path", "smi_bc_counts_device", "smi_assigned_tsv", "smi_barcode_list_tsv", "smi_hist_allreduce", "smi_hist_allreduce_after", "smi_hist_allreduce_release", "smi_ctx_create_lane", "smi_ctx_lane_refresh", "smi_scan_batch", "smi_umi_dist_batch",
     "smi_genes_load_refflat", "smi_genes_load_gtf", "smi_genes_free", "smi_genes_count", "smi_genes_dump", "smi_gene_tag_chunk", "smi_gene_tag_bam",
     "smi_pack_reads_text_device", "smi_pack_ends_text_device", "smi_frag_text_starts_device", "smi_fastq_write_text_device",
     "smi_fastq_index_host", "smi_pack_reads_host", "smi_pack_quals_host", "smi_scanfastq_pass2_packed", "smi_fastq_write_host",
@@ -156,6 +156,7 @@ def load_library():
     lib.smi_assigned_tsv.argtypes = [vp, vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
     lib.smi_assignumis_default_config.argtypes = [vp]
     lib.smi_assignumis_chunk.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int32)]
+    lib.smi_assignumis_last_path.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
     lib.smi_host_alloc.argtypes = [sz, ctypes.POINTER(vp)]
     lib.smi_host_free.argtypes = [vp]
     lib.smi_pass2_default_config.argtypes = [vp]
@@ -1575,6 +1576,8 @@ def ref_position_at_read_position_raw(cigar_u32, alignment_start, position):
 UMI_TAG_DTYPE = np.dtype([("region", "<i4"), ("center", "<i4"), ("u1", "i1"), ("u2", "i1"), ("flags", "u1"), ("reserved", "u1"),
                           ("u8", "S12"), ("u7", "S12")])
 UMI_HAS_BC, UMI_HAS_U7, UMI_CLUSTERED, UMI_SKIPPED = 1, 2, 4, 8
+# smi_assignumis_last_path: no chunk yet, the device stage, the host path under SMI_AU_HOST, the host path because of a name K-UPARSE does not evaluate
+AU_PATH_NONE, AU_PATH_DEVICE, AU_PATH_HOST_FORCED, AU_PATH_HOST_NAMES = 0, 1, 2, 3
 
 
 class AssignUmisConfig(ctypes.Structure):
@@ -2449,6 +2452,12 @@ class Context:
                                                    cbuf.ctypes.data, coff.ctypes.data, n, ctypes.byref(cfg), out.ctypes.data,
                                                    ctypes.byref(nd)))
         return out[:n], nd.value
+
+    def assignumis_last_path(self):
+        """which way the last assignumis_chunk of this context went: AU_PATH_NONE / _DEVICE / _HOST_FORCED / _HOST_NAMES"""
+        path = ctypes.c_int32(0)
+        self._check(self._lib.smi_assignumis_last_path(self._h, ctypes.byref(path)))
+        return path.value
 
     # ---- chimera splitter ----------------------------------------------------------------------------------
     def chimera_config(self, five_prime=False, knobs=None):

@@ -84,6 +84,9 @@ def test_host_entry_points_reject_bad_arguments(built):
     assert b"smi_region_group" in lib.smi_last_error()
     assert lib.smi_umi_cluster_groups(None, None, None, 3, None, None, None, None, 1) < 0
     assert lib.smi_chimera_fragment_name(b"r x", None, 0, None, 0) < 0
+    assert lib.smi_assignumis_last_path(None, None) < 0
+    assert b"smi_assignumis_last_path" in lib.smi_last_error()
+    assert (libmod.AU_PATH_NONE, libmod.AU_PATH_DEVICE, libmod.AU_PATH_HOST_FORCED, libmod.AU_PATH_HOST_NAMES) == (0, 1, 2, 3)
     assert libmod.region_group([], []) == ([], 0)
     out, sk = libmod.umi_cluster_groups(np.zeros(0, np.uint8), [0], [0], np.zeros(0, np.float32))
     assert out.size == 0 and sk.size == 0

@@ -126,13 +126,16 @@ def _chunk(pkg, synth, ctx, n_mol, copies, genes, seed, five=False):
     return names, flags, pos0, cigars
 
 
-def _both_paths(ctx, names, flags, pos0, cigars, **kw):
+def _both_paths(ctx, names, flags, pos0, cigars, path=1, **kw):
+    """path: the way the run without SMI_AU_HOST must have gone (smi_assignumis_last_path: 1 the device stage, 3 the host path because of a name)"""
     os.environ["SMI_AU_HOST"] = "1"
     try:
         host = ctx.assignumis_chunk(names, flags, pos0, cigars, **kw)
+        assert ctx.assignumis_last_path() == 2
     finally:
         del os.environ["SMI_AU_HOST"]
     dev = ctx.assignumis_chunk(names, flags, pos0, cigars, **kw)
+    assert ctx.assignumis_last_path() == path
     assert dev[1] == host[1]
     assert dev[0].tobytes() == host[0].tobytes()
     return dev
@@ -159,11 +162,12 @@ def test_chunk_with_unusual_names_takes_the_host_path(pkg, synth, gpu_ctx):
     odd = list(names)
     k = next(i for i, nm in enumerate(odd) if "_bc=" in nm)
     odd[k] = odd[k].replace("_bc=", "_bc=N", 1)                      # 17 characters
-    _both_paths(gpu_ctx, odd, flags, pos0, cigars)
+    _both_paths(gpu_ctx, odd, flags, pos0, cigars, path=3)
     odd = list(names)
     odd[k] = odd[k].replace("_Q=", "_Q=1e1", 1)
-    _both_paths(gpu_ctx, odd, flags, pos0, cigars)
+    _both_paths(gpu_ctx, odd, flags, pos0, cigars, path=3)
     bad = list(names)
     bad[k] = bad[k].replace("_AE=", "_AF=", 1)
     with pytest.raises(pkg.SmiError, match="AE="):
         gpu_ctx.assignumis_chunk(bad, flags, pos0, cigars)
+    assert gpu_ctx.assignumis_last_path() == 3

@@ -1356,6 +1356,48 @@ def gen_umi_3p_len10(g):
 def gen_umi_5p_len10(g):
     return gen_umi(g, True, 838, umi_len=10)
 
+
+def gen_umi_odd_names(g):
+    """FastqRecordExt.getScanDatFromReadName on names scanfastq never writes: number fields with signs, blanks, letters, values outside int; Q= in
+    forms Float.parseFloat reads or refuses; a name that ends with its marker.  What the product's name parsers do with such a name was decided by
+    these answers (tests/test_uparse_edges_gpu.py)"""
+    j = g.j
+    out = {"jar": "NanoporeBC_UMI_finder-2.1.jar", "sections": []}
+    base = "r1_FWD_PS=700_PE=730_AE=743_bc=ACGTACGTACGTACGT_ed=0_ed_sec=3_bcStart=742_bcEnd=727_X=" + "ACGT" * 10 + "ACG_Q=15.5_1a"
+    edits = [("AE=743", v) for v in ("AE=+743", "AE=-743", "AE=0743", "AE= 743", "AE=12x", "AE=2147483647", "AE=2147483648", "AE=3000000000", "AE=30000000743",
+                                     "AE=000000000743", "AE=-2147483648", "AE=-2147483649", "AF=743")]
+    edits += [("PS=700", v) for v in ("PS=+5", "PS= 5", "PS=12x", "PS=-0", "PS=2147483647", "PS=2147483648", "PS=-2147483648", "PS=3000000000")]
+    edits += [("_ed=0", v) for v in ("_ed=x", "_ed=+1", "_ed=3000000000")]
+    edits += [("bcEnd=727", v) for v in ("bcEnd=x", "bcEnd=99999999999", "bcEnd=-5", "bcEnd=2147483647")]
+    edits += [("Q=15.5", v) for v in ("Q=1e1", "Q=-1", "Q=.5", "Q=7.", "Q=007.25", "Q=1.2345", "Q=12345678", "Q=12." + "0" * 26, "Q=12." + "0" * 27, "Q=abc")]
+    for five_prime in (False, True):
+        side = UmiSide(g, five_prime)
+        s = g.section(("5-prime (-p)" if five_prime else "3-prime") + " assignumis: FastqRecordExt.getScanDatFromReadName(name) (L395-496) on one well-formed name "
+                      "with one field replaced: the parsed fields, or the exception the method leaves with", FQX, "getScanDatFromReadName")
+        s["five_prime"] = five_prime
+        for old, new in [(None, None)] + edits + [("tail", "r1_REV_")]:
+            nm = base if old is None else new if old == "tail" else base.replace(old, new)
+            assert old in (None, "tail") or nm != base
+            case = {"name": nm}
+            try:
+                sd = side.scan_data(nm)
+
+                def iv(o, k):
+                    v = None if o is None else o.f.get(k)
+                    if isinstance(v, JObject) and isinstance(v.native, tuple):   # java.util.Optional
+                        v = v.native[0]
+                    if isinstance(v, JObject) and "Optional" in v.cls:            # com.google.common.base.Optional
+                        v = j.call_virtual(v, "orNull", "()Ljava/lang/Object;")
+                    return None if v is None else (v.v if isinstance(v, JBox) else v)
+                ad, bcr, pa = sd.f["adapter_result"], sd.f["barcode_Result"], sd.f["polyA_Result"]
+                case.update({"adapter_end": iv(ad, "end"), "polya_start": iv(pa, "start"), "bc_ed": iv(bcr, "editDistance"), "bc_end": iv(bcr, "end"),
+                             "mean_qv": float(sd.f["mean_qv"].v)})
+            except JavaThrow as e:
+                case["throws"] = e.args[0] if e.args and isinstance(e.args[0], str) else str(e)
+            s["cases"].append(case)
+        out["sections"].append(g.finish(s))
+    return out
+
 # ---------------------------------------------------------------------------------------------------------------------
 # a-14: ChimeraFindernew.findSplitPositions on whole records (pass 2, before the scan)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -3045,7 +3087,7 @@ def gen_auxorder(g, seed=2222):
 
 SECTIONS = {"pass2t": gen_pass2t, "pass2k": gen_pass2k, "umi_3p_len10": gen_umi_3p_len10, "umi_5p_len10": gen_umi_5p_len10, "auxorder": gen_auxorder, "bamorder": gen_bamorder, "clusterpos": gen_clusterpos, "samtags": gen_samtags, "genecounts": gen_genecounts, "cluster_own": gen_cluster_own, "pass1": gen_pass1, "cluster": gen_cluster, "group": gen_group, "finalize": gen_finalize, "gene": gen_gene, "gene_gtf": gen_gene_gtf, "twobit": gen_twobit, "onebyte": gen_onebyte, "nw": gen_nw, "lev": gen_lev, "bcmatch": gen_bcmatch, "polyat": gen_polyat, "polyat_params": gen_polyat_params,
             "pass2_3p": gen_pass2_3p, "pass2_3p_ed2": gen_pass2_3p_ed2, "pass2_5p": gen_pass2_5p, "pass2_5p_polya": gen_pass2_5p_polya,
-            "umi_3p": gen_umi_3p, "umi_5p": gen_umi_5p, "chimera_3p": gen_chimera_3p, "stats_print": gen_stats_print,
+            "umi_3p": gen_umi_3p, "umi_5p": gen_umi_5p, "umi_odd_names": gen_umi_odd_names, "chimera_3p": gen_chimera_3p, "stats_print": gen_stats_print,
             "pass2w_3p": gen_pass2w_3p, "pass2w_3p_ed2": gen_pass2w_3p_ed2, "pass2w_5p": gen_pass2w_5p, "pass2w_5p_polya": gen_pass2w_5p_polya,
             "pass2x_3p": gen_pass2x_3p, "pass2x_5p": gen_pass2x_5p, "pass2p": gen_pass2p, "group2": gen_group2, "cluster_own2": gen_cluster_own2,
             "pass1_5p": lambda g: gen_pass1(g, 32, 1626, five_prime=True),

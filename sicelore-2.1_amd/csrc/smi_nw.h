@@ -9,6 +9,10 @@
 
 #include "smi_internal.h"
 
+#ifndef SMI_NW_CELL7
+#define SMI_NW_CELL7 0  // 1: the cell of 7 operations (see "Fill" below), for counter runs
+#endif
+
 namespace smi {
 
 // ---- Needleman-Wunsch with 2-bit moves in LDS and a walk from the end ---------------------------------------
@@ -27,12 +31,25 @@ struct AlnStats {
 
 // col[c] bit r = read base r of the slice matches pattern base c.
 //
-// Fill: one cell = 7 VALU ops.  A cell is kept as U = 4*score + 2 + 20*r (r = row): with the move as a 2-bit tag in
-// the low bits (3 diag match, 2 diag mismatch, 1 up, 0 left) one v_max3_i32 over
-//     diag' = U[r-1][c-1] + 41*m     up' = U[r-1][c] - 1     left' = U[r][c-1] - 22
-// yields 4*best + tag + 20*r -- the tag order IS the reference's tie order (diag >= up >= left) -- and
-// (v & ~3) | 2 is the stored cell again.  The tags of a row are shifted into one register (v_alignbit), the rows
-// stay in registers (row loop fully unrolled), so the walk needs no LDS.
+// Fill: one cell = 6 VALU ops.  A cell is kept as T = 4*score + 36*r + 20*c (r = row, c = column) with a zero tag field, and with
+// the move as a 2-bit tag in the low bits (3 diag mismatch, 2 diag match, 1 up, 0 left) one v_max3_i32 over
+//     diag' = T[r-1][c-1] + (39 << m)     up' = T[r-1][c] + 17     left' = T[r][c-1]
+// yields 4*best + tag + 36*r + 20*c -- the tag order IS the reference's tie order (diag >= up >= left) -- and v & ~3 is the
+// stored cell again:  v_bfe (m), v_lshl_add (diag'), v_add (up'), v_max3, v_and, v_alignbit (the tag into the row's word).
+//   Where the constants come from.  A predecessor enters the maximum as its stored value plus (4 * score change) + (its share of the
+//   skew 36*r + 20*c) + (its tag).  Left: -20 + 20 + 0 = 0, so it enters as it is stored.  Up: -20 + 36 + 1 = 17.  Diagonal: -20 + 56 + 3
+//   = 39 on a mismatch and +20 + 56 + 2 = 78 = 2 * 39 on a match, so the match bit selects a SHIFT of one constant (v_lshl_add_u32)
+//   where a multiple of it (v_mad) could not give the two cases different tags.  That is why match and mismatch carry the codes 2 and 3.
+//   Why six is the floor of this form.  Up and left are read from stored cells with one and the same tag field, and must enter the
+//   maximum with different tags: at most one of them is free, the other costs an add.  m, diag', the maximum, clearing the tag and
+//   keeping it are one operation each.
+//   Row 0 is not 0 but a negative multiple of 4 (kBias; column 0 is 20*r + kBias): the bias reaches neither a tag nor a comparison, and
+//   without it the compiler proves every cell non-negative and splits the maximum into v_max_i32 + v_max_u32, the seventh operation again.
+// The tags of a row are shifted into one register (v_alignbit), the rows stay in registers (row loop fully unrolled), so the walk
+// needs no LDS.
+// -DSMI_NW_CELL7=1 (make VARIANT=cell7 EXTRA=-DSMI_NW_CELL7=1) compiles the cell of 7 operations this one replaced, for counter runs:
+//   U = 4*score + 2 + 20*r, tags 3 match / 2 mismatch, diag' = U + 41*m (v_mad), up' = U - 1, left' = U - 22, stored as (v & ~3) | 2.
+// Same moves, same results; there is no run-time switch.
 // Walk: rows N..1 unrolled; inside a row only consecutive left moves loop.
 // kEnds: end5 / endn / term6 are wanted (the adapter fold); kRuns: consec / best_two are wanted (the TSO rules).  The walk
 // keeps only the bookkeeping of the statistics its caller reads.
@@ -52,9 +69,10 @@ __host__ __device__ constexpr int nw_band() {
 }
 
 // ---- the walk, bit-parallel ------------------------------------------------------------------------------------
-// The path from (N, N) back to (0, 0) is at most 2N steps; step t is recorded as two bits in two masks (T1 T0: 11 match, 10 mismatch,
-// 01 up = a base of the read against a template gap, 00 left = a read gap) and every statistic the reference reads off its alignment
-// strings is a popcount, a count of trailing / leading bits or a short loop over runs of those masks.  The walk itself is one
+// The path from (N, N) back to (0, 0) is at most 2N steps; step t is recorded as the two bits of its tag in two masks (T1 T0: 10 match,
+// 11 mismatch -- the other way round under SMI_NW_CELL7 --, 01 up = a base of the read against a template gap, 00 left = a read gap;
+// the rows only ask "diagonal" = T1 and "up" = T0 & ~T1, so match and mismatch are told apart once, at the end) and every statistic
+// the reference reads off its alignment strings is a popcount, a count of trailing / leading bits or a short loop over runs of those masks.  The walk itself is one
 // find-highest-bit per row: the left moves of a row are the zero tags between the current column and the next non-zero tag below
 // it, so a row costs the same whatever the number of its left moves, and the rows need no inner loop.  (Until round 5 every step went
 // through ~40 operations of bookkeeping, and a row with left moves ran them once per move for the whole wave.)
@@ -143,7 +161,12 @@ __device__ __forceinline__ void nw_walk_bits(const uint32_t (&mlo)[N], const uin
     T0 |= nw_lowmask<MW>(lead) << (t_end & (B - 1));
     t_end += lead + (cc >> 1);
     const MW valid = nw_lowmask<MW>(t_end);
-    const MW Mt = T0 & T1, I = T0 & ~T1, S = T1 & ~T0, D = valid & ~(T0 | T1), X = valid & ~Mt;
+#if SMI_NW_CELL7
+    const MW Mt = T0 & T1, S = T1 & ~T0;
+#else
+    const MW Mt = T1 & ~T0, S = T1 & T0;
+#endif
+    const MW I = T0 & ~T1, D = valid & ~(T0 | T1), X = valid & ~Mt;
     const int ins = nw_popc(I), sub = nw_popc(S), nx = nw_popc(X);
     const int trail = nw_ctz((MW)~D);  // read gaps at the end of the read (the start of the walk) are not deletions
     const int del = (int)(int8_t)(nw_popc(D) - trail);  // (byte arithmetic, L84)
@@ -196,30 +219,50 @@ __device__ __forceinline__ void nw_full(const uint32_t (&col)[N], int n_end, Aln
     uint32_t mlo[N], mhi[NHI > 0 ? N : 1];
     {
         int U[N + 1];
+#if SMI_NW_CELL7
+        constexpr int kUp = -1, kLeft = -22;
 #pragma unroll
         for (int c = 0; c <= N; c++) U[c] = -20 * c + 2;  // row 0 (columns beyond the band are never read)
+#else
+        constexpr int kBias = -(1 << 20), kUp = 17;  // (kBias: see "Fill" above; |4*score + 36*r + 20*c| < 2^12)
+#pragma unroll
+        for (int c = 0; c <= N; c++) U[c] = kBias;  // row 0: 4 * (-5c) + 20c = 0
+#endif
 #pragma unroll
         for (int r = 1; r <= N; r++) {
             const int clo = r - W > 1 ? r - W : 1, chi = r + W < N ? r + W : N;
             int diag = U[clo - 1];
+#if SMI_NW_CELL7
             if (r <= W) U[0] = 4 * r + 2;  // 4 * (-4r) + 2 + 20r
+#else
+            if (r <= W) U[0] = kBias + 20 * r;  // 4 * (-4r) + 36r
+#endif
             uint32_t lo = 0, hi = 0;
 #pragma unroll
             for (int c = clo; c <= chi; c++) {
-                int m, d;  // d = diag + 41 * match bit (asm: the compiler's own choice is and/cmp/cndmask/add)
+                int m, d;  // d = diag + (39 << match bit) (asm: the compiler's own choice is and/cmp/cndmask/add)
                 asm("v_bfe_u32 %0, %1, %2, 1" : "=v"(m) : "v"(col[c - 1]), "n"(r - 1));
+#if SMI_NW_CELL7
                 asm("v_mad_u32_u24 %0, %1, 41, %2" : "=v"(d) : "v"(m), "v"(diag));
+                const int left = U[c - 1] + kLeft;
+#else
+                asm("v_lshl_add_u32 %0, 39, %1, %2" : "=v"(d) : "v"(m), "v"(diag));
+                const int left = U[c - 1];
+#endif
                 int v;
                 if (c - r == W) {  // the cell above lies outside the band
-                    v = max(d, U[c - 1] - 22);
+                    v = max(d, left);
                 } else if (r - c == W) {  // the cell to the left lies outside the band
-                    v = max(d, U[c] - 1);
+                    v = max(d, U[c] + kUp);
                 } else {
-                    const int up = U[c] - 1, left = U[c - 1] - 22;
-                    v = max(max(d, up), left);
+                    v = max(max(d, U[c] + kUp), left);
                 }
                 diag = U[c];
+#if SMI_NW_CELL7
                 U[c] = (v & ~3) | 2;
+#else
+                U[c] = v & ~3;
+#endif
                 // {v, word} >> 2: the tag enters at the top.  Inline asm: as an intrinsic the chain is re-associated
                 // into 16 masks/shifts/ors per row and every v stays live until then
                 if (c <= 16)
@@ -266,11 +309,12 @@ __device__ __forceinline__ void nw_full(const uint32_t (&col)[N], int n_end, Aln
             int tag;
             do {
                 tag = (int)(((NHI > 0 && c > 16) ? (mhi[R - 1] >> (2 * (c - 17))) : (mlo[R - 1] >> (2 * (c - 1)))) & 3u);
-                const bool x = tag != 3;
+                constexpr int kTagMatch = SMI_NW_CELL7 ? 3 : 2, kTagMismatch = SMI_NW_CELL7 ? 2 : 3;
+                const bool x = tag != kTagMatch;
                 const bool read_gap = tag == 0;
                 ins += tag == 1;
                 del += read_gap;
-                sub += tag == 2;
+                sub += tag == kTagMismatch;
                 nx += x;
                 if (trailing && read_gap)
                     trail++;
@@ -341,42 +385,69 @@ __device__ __forceinline__ void nw_full(const uint32_t (&col)[N], int n_end, Aln
 // Error count only (Match.countErrorsInNeedleman = #x - 0.9f * leading template gaps), no moves kept: the two
 // statistics ride in the low bits of the cell, below the score and the move tag, where they cannot influence the
 // max (the three candidates of a cell always differ in (score, tag)).
-//   cell = (4*score + 2 + 20*r) << 11 | q << 5 | lead      q = 32 + #up - #match on the best path
-// On an N x N alignment #x = N + #up - #match (#up = #left, #diag = N - #up), so one counter is enough; 6 VALU ops
-// per cell.
+//   cell = (4*score + 36*r + 20*c) << 11 | q << 5 | lead      q = 2N - #mismatch - 2 * #match on the best path
+// The cell of nw_full under << 11, 5 VALU ops (no tag is kept): the diagonal's constant (39 << 11) - 32 takes 1 off q on a mismatch and,
+// shifted by the match bit, 2 on a match; up and left leave q alone.  On an N x N alignment #up = #left and #match + #mismatch = N - #up,
+// so q ends as #mismatch + 2 * #up = #x itself.  q >= 2N - 2 * min(r, c) >= 0 in every cell: no path borrows from the tag.
+// (SMI_NW_CELL7: cell = (4*score + 2 + 20*r) << 11 | q << 5 | lead, q = 32 + #up - #match, #x = N + q - 32; 6 VALU ops.)
 template <int N, int W = N>
 __device__ __forceinline__ float nw_errors(const uint32_t (&col)[N]) {
-    static_assert(N <= 27, "field widths: lead 5 bits, q 6 bits");
+    static_assert(N <= 27, "field widths: lead 5 bits, q 6 bits (2N <= 63)");
     constexpr int SH = 11;
-    const uint32_t kmatch = (41u << SH) - 32u;  // diag with a match: +41 in the tagged score, q - 1
     int U[N + 1];
+#if SMI_NW_CELL7
+    const uint32_t kmatch = (41u << SH) - 32u;  // diag with a match: +41 in the tagged score, q - 1
+    constexpr int kUp = -(1 << SH) + 32, kLeft = -(22 << SH);
 #pragma unroll
     for (int c = 0; c <= N; c++) U[c] = ((-20 * c + 2) << SH) + (32 << 5);
+#else
+    const uint32_t kmatch = (39u << SH) - 32u;  // diag: +39 and q - 1 on a mismatch, twice that on a match
+    constexpr int kBias = -(1 << (16 + SH)), kUp = 17 << SH;  // (kBias: as in nw_full; |4*score + 36*r + 20*c| < 2^12)
+#pragma unroll
+    for (int c = 0; c <= N; c++) U[c] = kBias + ((2 * N) << 5);
+#endif
 #pragma unroll
     for (int r = 1; r <= N; r++) {
         const int clo = r - W > 1 ? r - W : 1, chi = r + W < N ? r + W : N;  // the band of nw_full
         int diag = U[clo - 1];
+#if SMI_NW_CELL7
         if (r <= W) U[0] = ((4 * r + 2) << SH) + ((32 + r) << 5) + r;
+#else
+        if (r <= W) U[0] = kBias + ((20 * r) << SH) + ((2 * N) << 5) + r;
+#endif
 #pragma unroll
         for (int c = clo; c <= chi; c++) {
             int m, d;
             asm("v_bfe_u32 %0, %1, %2, 1" : "=v"(m) : "v"(col[c - 1]), "n"(r - 1));
+#if SMI_NW_CELL7
             asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(m), "s"(kmatch), "v"(diag));
+            const int left = U[c - 1] + kLeft;
+#else
+            asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(d) : "s"(kmatch), "v"(m), "v"(diag));
+            const int left = U[c - 1];
+#endif
             int v;
             if (c - r == W) {
-                v = max(d, U[c - 1] - (22 << SH));
+                v = max(d, left);
             } else if (r - c == W) {
-                v = max(d, U[c] - (1 << SH) + 32);
+                v = max(d, U[c] + kUp);
             } else {
-                const int up = U[c] - (1 << SH) + 32, left = U[c - 1] - (22 << SH);
-                v = max(max(d, up), left);
+                v = max(max(d, U[c] + kUp), left);
             }
             diag = U[c];
+#if SMI_NW_CELL7
             U[c] = (v & ~(3 << SH)) | (2 << SH);
+#else
+            U[c] = v & ~(3 << SH);
+#endif
         }
         __builtin_amdgcn_sched_barrier(0);
     }
+#if SMI_NW_CELL7
     const int lead = U[N] & 31, nx = N + ((U[N] >> 5) & 63) - 32;
+#else
+    const int lead = U[N] & 31, nx = (U[N] >> 5) & 63;
+#endif
     return __fsub_rn((float)nx, __fmul_rn(0.9f, (float)lead));
 }
 

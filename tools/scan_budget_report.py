@@ -38,10 +38,10 @@ out = {
                 "(the loops' branches)"},
     "reading": [
         "issue rate: %.0f G wave-instructions/s over the whole kernel = %.0f %% of the 601 G/s ceiling of 4-cycle forms" % (tot / ms(0) / 1e6, 100 * tot / ms(0) / 1e6 / 601.4),
-        "what an alignment needs: the fill is 7 operations per cell (bit extract, multiply-add, two subtractions, max3, and-or, tag shift) over the exact band "
-        "(smi_nw.h `Band`: 184 cells of 256 for the 16-base TSO, 44 of 100 for the 10-base adapter) = 1,290 + 310 per wave for one round of each; the candidates are what "
+        "what an alignment needs: the fill is 6 operations per cell (bit extract, shift-add by the match bit, one add, max3, and, tag shift; 7 under -DSMI_NW_CELL7=1) over the exact band "
+        "(smi_nw.h `Band`: 184 cells of 256 for the 16-base TSO, 44 of 100 for the 10-base adapter) for one round of each per wave; the candidates are what "
         "the reference's gate lets through minus the isolated ones under the Levenshtein bound (one round of each per wave: NOTES R5.13, R5.16); the walk is one "
-        "find-highest-bit per row.  No formulation of the cell with fewer than seven operations was found (DESIGN section 4)",
+        "find-highest-bit per row.  Six is the floor of a cell whose up and left neighbours are read from one stored value (smi_nw.h `Fill`, NOTES R6.25)",
         "with every scan off the kernel takes %.2f ms for %.0f M instructions: the time of moving 2.78 GB (ends in, records and windows out) -- the HBM floor of this "
         "launch; the scans hide it" % (ms(15), v(15) / 1e6)]}
 json.dump(out, open(dst, "w"), indent=1)

@@ -356,6 +356,18 @@ int smi_barcode_list_tsv(const uint64_t *keys, const uint32_t *counts, size_t n,
  * keys ascending as loaded; rows with equal counts by ascending key (the reference: HashMap order).  out == NULL: size only. */
 int smi_assigned_tsv(const uint64_t *keys, const uint32_t *counts, size_t n_keys, int max_ed, char *out, size_t cap,
                      size_t *n_out);
+/* The cell list from that table = SelectValidCellBarcode.doWork (org/ipmc/sicelore/programs/SelectValidCellBarcode.java:L39-92;
+ * quickrun-2.1.sh:45, sicelore-nf/main.nf:48).  tsv: the n bytes of BarcodesAssigned.tsv.  The first line is skipped; of every other line
+ * (ended by \n, \r\n or a lone \r) all ',' are removed, then it is split at tabs as String.split does; reads = field 1, ed0 = field 2,
+ * ed1 = field 3 by Integer.parseInt (an empty field 2 or 3 is 0, an ed1 of 0 becomes 1), fields past the fourth are ignored.  A row is
+ * kept when reads >= min_umi and (double)(ed0 / ed1) >= ed0ed1_ratio, the division being Java's int division.
+ * out: field 0 and \n of every kept row; removed: `<field 0> barcode removed\t\t[<line without commas>]\n` of every other row (the
+ * reference's log lines); *n_out / *n_removed: their sizes.  A NULL buffer is not written (both NULL: sizes only); a buffer that is too
+ * small fails the call.  counts[0] = data rows (Total cell barcodes), counts[1] = kept rows (Valid cell barcodes).
+ * A row the reference dies on (fewer than four fields, a field parseInt rejects): returns 2, *error_line = its 1-based line number,
+ * smi_last_error gives the reason, nothing is written.  Host only: no context, no device. */
+int smi_select_valid_cells(const char *tsv, size_t n, int32_t min_umi, double ed0ed1_ratio, char *out, size_t cap_out, size_t *n_out,
+                           char *removed, size_t cap_removed, size_t *n_removed, int64_t *counts, uint64_t *error_line);
 
 /* End of pass 1 on the host (no device work): low-count filter, collision merge, low-depth cut and rank of the
  * used-barcode list = UsedCellBCListGenerator$UsedBarcodesListData.finalizeData

@@ -5,6 +5,7 @@
     java -jar [-Xmx..] NanoporeBC_UMI_finder-2.1.jar assignumis --inFileNanopore <bam> -o <bam> [--annotationFile refFlat] [-v n] [-p] [-w] [-b ed] [-u ed] [-s]
     java -jar [-Xmx..] NanoporeBC_UMI_finder-2.1.jar tagbamwithread --inFastq <fastq[.gz]> --inBam <bam> --outBam <bam> --readTag XX [--qvTag YY]
 
+    java -jar [-Xmx..] Sicelore-2.1.jar SelectValidCellBarcode -I <BarcodesAssigned.tsv> -O <barcodes.csv> [-MINUMI 1] [-ED0ED1RATIO 1]              (or I=<tsv> O=<csv> ...; no GPU)
     java -jar [-Xmx..] Sicelore-2.1.jar ComputeConsensus -I <bam> -O <fastq> [-T n] [-CELLTAG BC] ... [-MAXREADS 20] [-MINPS 3] [-MAXPS 20]   (or I=<bam> O=<fastq> ...)
     java -jar [-Xmx..] Sicelore-2.1.jar SNPMatrix I=<bam> CSV=<barcodes> SNP=<sites.csv> O=<dir> [PREFIX=snp] [MINRN=0] [MINQV=0] [CELLTAG=BC] [UMITAG=U8] [RNTAG=RN] ...
     java -jar [-Xmx..] Sicelore-2.1.jar CollapseModel I=<isobam> CSV=<barcodes> REFFLAT=<refFlat> OUTDIR=<dir> [PREFIX=CollapseModel] [DELTA=2] [MINEVIDENCE=2] [RNMIN=1] ...   (or -I <isobam> ...)
@@ -12,7 +13,9 @@
     java -jar [-Xmx..] Sicelore-2.1.jar DeduplicateMolecule -I <fastq|fasta> -O <fastq|fasta> [-SELECT true] [-TSO seq] [-MAXPOS 100]                  (or I=<..> O=<..> ...)
 
 become   python sicelore-2.1_amd scanfastq ... / assignumis ... / tagbamwithread ... / ComputeConsensus ...   (the directory is runnable: __main__.py; a `java` wrapper that drops
-`-jar`, `-Xmx..` and the jar's name makes /root/reference/quickrun-2.1.sh:35,42 run unchanged, tests/test_cli_gpu.py does exactly that).
+`-jar`, `-Xmx..` and the jar's name makes /root/reference/quickrun-2.1.sh:35,42 run unchanged, tests/test_cli_gpu.py does exactly that; the four
+`java` lines of that script in order, 35, 42, 45 and 46: tests/test_quickrun_chain_gpu.py).  `-version` as the first argument (`java -version`
+through the wrapper) prints one line naming this build to stderr and returns 0.
 
 Reference units: option tables NanoporeReadScannerMain.cli_otions (NanoporeReadScannerMain.java:L336-469) and UmiFinderMain (L298-447);
 config discovery OneProgramMainBase.checkCfgFilePath (cwd, then the application's directory; -c names a file for assignumis);
@@ -27,6 +30,7 @@ product has no path for (Illumina-guided modes, the file watcher) are refused by
 """
 import gzip
 import os
+import re
 import sys
 import xml.etree.ElementTree as ET
 
@@ -491,6 +495,8 @@ CC_OPTIONS = {
     "VALIDATION_STRINGENCY": (None, "stringency", "STRICT"),
 }
 CC_LONG = {"INPUT": "I", "OUTPUT": "O", "nThreads": "T"}
+# the decimal texts Double.valueOf takes (the hexadecimal form is left out)
+_JAVA_DOUBLE = re.compile(r"[+-]?(NaN|Infinity|(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?[dDfF]?)")
 
 
 def _picard_parse(argv, prog, options, long_names):
@@ -520,6 +526,10 @@ def _picard_parse(argv, prog, options, long_names):
                 v = int(v)
             except ValueError:
                 raise CliError(f"sub-command {prog}: {name} {v!r} is not a number")
+        elif kind == "float":
+            if not _JAVA_DOUBLE.fullmatch(v):
+                raise CliError(f"sub-command {prog}: {name} {v!r} is not a number")
+            v = float(v.rstrip("dDfF").replace("Infinity", "inf"))
         elif kind == "bool":
             if v.lower() not in ("true", "false"):
                 raise CliError(f"sub-command {prog}: {name} takes true or false, not {v!r}")
@@ -792,11 +802,51 @@ def fusiondetector(argv):
     return 0
 
 
+# SelectValidCellBarcode (SelectValidCellBarcode.java:L25-32): Picard's option names -> (None, kind, default)
+SV_OPTIONS = {
+    "I": (None, "path", None), "O": (None, "path", None), "MINUMI": (None, "int", 1), "ED0ED1RATIO": (None, "float", 1.0),
+    "VALIDATION_STRINGENCY": (None, "stringency", "STRICT"),
+}
+SV_LONG = {"INPUT": "I", "OUTPUT": "O"}
+
+
+def selectvalidcellbarcode(argv):
+    """SelectValidCellBarcode.doWork (L39-92): host code only, no context and no GPU.  VALIDATION_STRINGENCY is accepted and changes nothing."""
+    o = _picard_parse(argv, "SelectValidCellBarcode", SV_OPTIONS, SV_LONG)
+    need = [k for k in ("I", "O") if k not in o]
+    if need:
+        raise CliError(f"sub-command SelectValidCellBarcode: missing required option(s) {', '.join(need)}")
+    if not os.path.isfile(o["I"]):                                          # IOUtil.assertFileIsReadable (L41)
+        raise CliError(f"SelectValidCellBarcode: I={o['I']}: no such file")
+    if not os.path.isdir(os.path.dirname(os.path.abspath(o["O"]))):         # IOUtil.assertFileIsWritable (L42)
+        raise CliError(f"SelectValidCellBarcode: O={o['O']}: no such directory")
+    if os.path.isdir(o["O"]):
+        raise CliError(f"SelectValidCellBarcode: O={o['O']}: is a directory")
+    min_umi = o.get("MINUMI", 1)
+    if not -2 ** 31 <= min_umi < 2 ** 31:                                   # a Java int
+        raise CliError(f"sub-command SelectValidCellBarcode: MINUMI {min_umi!r} is not a number")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise CliError("SelectValidCellBarcode runs in one process in this build: start it without torchrun")
+    from . import lib as _lib
+    from .selectvalidcellbarcode import select_valid_cell_barcodes
+    try:
+        info = select_valid_cell_barcodes(o["I"], o["O"], min_umi=min_umi, ed0ed1_ratio=o.get("ED0ED1RATIO", 1.0), log=sys.stderr)
+    except _lib.CellTableError as e:
+        raise CliError(f"SelectValidCellBarcode: I={e}; {o['O']} was not written (the reference stops reading there, leaves a cut-off "
+                       "file and exits 0)")
+    print(f"DONE -- {info['kept']} of {info['total']} barcodes kept", file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
         if not argv or argv[0] in ("-h", "--help", "help"):
             print(__doc__)
+            return 0
+        if argv[0] in ("-version", "--version"):       # `java -version` through bin/java: one line on stderr, as the JVM answers it
+            print("sicelore-2.1_amd: the command lines of NanoporeBC_UMI_finder-2.1.jar and Sicelore-2.1.jar over libsicelore_mi.so (HIP, gfx950)",
+                  file=sys.stderr)
             return 0
         sub, rest = argv[0], argv[1:]
         if sub in ("scanfastq", "assignumis"):
@@ -825,7 +875,9 @@ def main(argv=None):
             return collapsemodel(rest)
         if sub == "FusionDetector":
             return fusiondetector(rest)
-        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, ComputeConsensus, DeduplicateMolecule, AddBamMoleculeTags, AddGeneNameTag, IsoformMatrix, SNPMatrix, CollapseModel and FusionDetector (mergestats, parseillumina: "
+        if sub == "SelectValidCellBarcode":
+            return selectvalidcellbarcode(rest)
+        raise CliError(f"sub-command {sub!r}: this build has scanfastq, assignumis, tagbamwithread, SelectValidCellBarcode, ComputeConsensus, DeduplicateMolecule, AddBamMoleculeTags, AddGeneNameTag, IsoformMatrix, SNPMatrix, CollapseModel and FusionDetector (mergestats, parseillumina: "
                        "SURVEY 2, out of scope)")
     except CliError as e:
         print(f"ERROR: {e}", file=sys.stderr)

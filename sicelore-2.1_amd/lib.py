@@ -81,6 +81,7 @@ EXPORTS = [
     "smi_collapse_validate_begin", "smi_collapse_validate_segment", "smi_collapse_validate_end", "smi_collapse_validate_counts",
     "smi_fusion_default_config", "smi_fusion_create", "smi_fusion_add_segment", "smi_fusion_run", "smi_fusion_output", "smi_fusion_counts",
     "smi_fusion_error_read", "smi_fusion_free", "smi_fusion_host_loop",
+    "smi_select_valid_cells",
 ]
 
 
@@ -154,6 +155,8 @@ def load_library():
     lib.smi_bgzf_inflate.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz), ci]
     lib.smi_bc_counts_device.argtypes = [vp, vp, sz, vp, vp]
     lib.smi_assigned_tsv.argtypes = [vp, vp, sz, ci, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_select_valid_cells.argtypes = [ctypes.c_char_p, sz, ctypes.c_int32, ctypes.c_double, vp, sz, ctypes.POINTER(sz), vp, sz, ctypes.POINTER(sz),
+                                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64)]
     lib.smi_assignumis_default_config.argtypes = [vp]
     lib.smi_assignumis_chunk.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int32)]
     lib.smi_assignumis_last_path.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
@@ -1880,6 +1883,35 @@ def assigned_tsv(keys, counts, max_ed=1):
     if lib.smi_assigned_tsv(k.ctypes.data, c.ctypes.data, k.size, int(max_ed), out, n.value, ctypes.byref(n)):
         raise SmiError(lib.smi_last_error().decode())
     return out.raw[:n.value].decode()
+
+
+class CellTableError(SmiError):
+    """a row of BarcodesAssigned.tsv that SelectValidCellBarcode cannot read; .line: its 1-based line number"""
+
+    def __init__(self, message, line):
+        super().__init__(message)
+        self.line = line
+
+
+def select_valid_cells(tsv, min_umi=1, ed0ed1_ratio=1.0):
+    """smi_select_valid_cells on the bytes of a BarcodesAssigned.tsv -> (kept barcodes' text, removed messages' text, total, kept), both texts
+    as bytes.  Needs no context and no GPU.  A row the reference dies on raises CellTableError with the line number."""
+    lib = load_library()
+    tsv = bytes(tsv)
+    n_out, n_rem, line = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
+    counts = (ctypes.c_int64 * 2)()
+    args = (tsv, len(tsv), int(min_umi), float(ed0ed1_ratio))
+
+    def check(rc):
+        if rc == 2:
+            raise CellTableError(lib.smi_last_error().decode(errors="replace"), int(line.value))
+        if rc:
+            raise SmiError(lib.smi_last_error().decode(errors="replace"))
+
+    check(lib.smi_select_valid_cells(*args, None, 0, ctypes.byref(n_out), None, 0, ctypes.byref(n_rem), counts, ctypes.byref(line)))
+    out, rem = ctypes.create_string_buffer(n_out.value + 1), ctypes.create_string_buffer(n_rem.value + 1)
+    check(lib.smi_select_valid_cells(*args, out, n_out.value, ctypes.byref(n_out), rem, n_rem.value, ctypes.byref(n_rem), counts, ctypes.byref(line)))
+    return out.raw[:n_out.value], rem.raw[:n_rem.value], int(counts[0]), int(counts[1])
 
 
 def gz_inflate(data, alloc=None):

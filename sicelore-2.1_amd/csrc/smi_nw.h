@@ -27,6 +27,7 @@ struct AlnStats {
     int nmis, ins, del;
     int consec, best_two;
     bool term6;
+    uint64_t mask_a, mask_b;  // kLazy only: the step masks the statistics above are read off later (see nw_walk_bits)
 };
 
 // col[c] bit r = read base r of the slice matches pattern base c.
@@ -53,6 +54,10 @@ struct AlnStats {
 // Walk: rows N..1 unrolled; inside a row only consecutive left moves loop.
 // kEnds: end5 / endn / term6 are wanted (the adapter fold); kRuns: consec / best_two are wanted (the TSO rules).  The walk
 // keeps only the bookkeeping of the statistics its caller reads.
+// kLazy: the caller reads end5 / endn or consec / best_two for few of its alignments only (K-SCAN: for the winner of an end, inside a rescue
+// rule or a tie).  The walk then hands over the step masks in their place -- kRuns: mask_a = Mt, the match steps; kEnds: mask_a = X, the error
+// columns, and mask_b = ND, the steps that consume a read base -- and the caller calls nw_runs / nw_end5 / nw_endn_is_zero on them where a rule
+// reads the statistic.  The eager walk calls the same three functions: one statement of the reference's rules for both.
 //
 // Band.  Every caller aligns a candidate that passed the reference's 4-mer gate (> 1 matching 4-mers on the main diagonal of the very
 // slice that is aligned), so at least 5 pattern bases match on the diagonal and the diagonal path scores >= 10 * 5 - 5N.  A path through
@@ -108,7 +113,53 @@ __device__ __forceinline__ float nw_end_errors(int k12, int k10) {
     return e;
 }
 
-template <int N, bool kEnds, bool kRuns, int NM>
+// consec (getNconsecutiveMatchesNeedleman L160-173) and best_two (getSumOfBestTwoMatchStretchesNeedleman L183-196) off the match steps Mt of a
+// walk: runs of matches in walk order; a run counts iff an 'x' was met before it, i.e. unless it starts the walk
+template <class MW>
+__device__ __forceinline__ void nw_runs(MW Mt, int &consec_out, int &best_two_out) {
+    MW m = Mt & (Mt + (MW)1);
+    int consec = 0, s1 = 0, s2 = 0, n_runs = 0;
+    while (m) {
+        const MW lowbit = m & (~m + (MW)1);
+        const MW nxt = m + lowbit;  // the carry runs through the lowest run
+        const int run = nw_ctz(nxt) - nw_ctz(m);
+        m &= nxt;
+        consec = max(consec, run);
+        if (run > 4) {  // getSumOfBestTwoMatchStretchesNeedleman L183-196 as it is written
+            if (n_runs == 0 || run < s1) {
+                s2 = s1;
+                s1 = run;
+            } else if (n_runs == 1 || run < s2) {
+                s2 = run;
+            }
+            n_runs++;
+        }
+    }
+    consec_out = consec;
+    best_two_out = (n_runs >= 1 ? s1 : 0) + (n_runs >= 2 ? s2 : 0);
+}
+// countIndelsMismatchesEndOfRead(n) off the error columns X and the steps ND that consume a read base.  cb of a step = read bases consumed
+// before it = ND steps before it: the steps with cb < n are those up to the n-th ND step, "cb <= 1" those up to the 2nd
+template <class MW>
+__device__ __forceinline__ float nw_end_of_read(MW X, MW ND, MW mn) {
+    const MW m12 = nw_lowmask<MW>(nw_kth_bit(ND, 2) + 1);
+    return nw_end_errors(nw_popc((MW)(X & m12 & mn)), nw_popc((MW)(X & mn & ~m12)));
+}
+template <class MW>
+__device__ __forceinline__ MW nw_end_mask(MW ND, int n_end) {
+    return n_end > 0 ? nw_lowmask<MW>(nw_kth_bit(ND, n_end) + 1) : (MW)0;
+}
+template <class MW>
+__device__ __forceinline__ float nw_end5(MW X, MW ND) {
+    return nw_end_of_read(X, ND, nw_lowmask<MW>(nw_kth_bit(ND, 5) + 1));
+}
+// countIndelsMismatchesEndOfRead(n_end) == 0 without the float sum: nw_end_errors(a, b) == 0 exactly when a == b == 0
+template <class MW>
+__device__ __forceinline__ bool nw_endn_is_zero(MW X, MW ND, int n_end) {
+    return (X & nw_end_mask(ND, n_end)) == (MW)0;
+}
+
+template <int N, bool kEnds, bool kRuns, bool kLazy, int NM>
 __device__ __forceinline__ void nw_walk_bits(const uint32_t (&mlo)[N], const uint32_t (&mhi)[NM], int n_end, AlnStats &out) {
     using MW = typename NwWalkWord<N>::mask_t;  // a row's tags (2 bits per column) and the step masks (<= 2N steps)
     constexpr int B = (int)sizeof(MW) * 8;
@@ -177,42 +228,27 @@ __device__ __forceinline__ void nw_walk_bits(const uint32_t (&mlo)[N], const uin
     out.term6 = false;
     out.end5 = out.endn = 0.0f;
     out.consec = out.best_two = 0;
+    out.mask_a = out.mask_b = 0;
     if (kEnds) {
         out.term6 = (X & (MW)0x3F) == 0 && t_end >= 6;
-        // cb of a step = read bases consumed before it = non-left steps before it: "cb <= 1" are the steps up to the 2nd non-left one
         const MW ND = T0 | T1;
-        const MW m12 = nw_lowmask<MW>(nw_kth_bit(ND, 2) + 1);
-        const MW m5 = nw_lowmask<MW>(nw_kth_bit(ND, 5) + 1);
-        const MW mn = n_end > 0 ? nw_lowmask<MW>(nw_kth_bit(ND, n_end) + 1) : (MW)0;
-        out.end5 = nw_end_errors(nw_popc((MW)(X & m12 & m5)), nw_popc((MW)(X & m5 & ~m12)));
-        out.endn = nw_end_errors(nw_popc((MW)(X & m12 & mn)), nw_popc((MW)(X & mn & ~m12)));
+        if (kLazy) {
+            out.mask_a = X;
+            out.mask_b = ND;
+        } else {
+            out.end5 = nw_end5(X, ND);
+            out.endn = nw_end_of_read(X, ND, nw_end_mask(ND, n_end));
+        }
     }
     if (kRuns) {
-        // runs of matches in walk order; a run counts iff an 'x' was met before it, i.e. unless it starts the walk
-        MW m = Mt & (Mt + (MW)1);
-        int consec = 0, s1 = 0, s2 = 0, n_runs = 0;
-        while (m) {
-            const MW lowbit = m & (~m + (MW)1);
-            const MW nxt = m + lowbit;  // the carry runs through the lowest run
-            const int run = nw_ctz(nxt) - nw_ctz(m);
-            m &= nxt;
-            consec = max(consec, run);
-            if (run > 4) {  // getSumOfBestTwoMatchStretchesNeedleman L183-196 as it is written
-                if (n_runs == 0 || run < s1) {
-                    s2 = s1;
-                    s1 = run;
-                } else if (n_runs == 1 || run < s2) {
-                    s2 = run;
-                }
-                n_runs++;
-            }
-        }
-        out.consec = consec;
-        out.best_two = (n_runs >= 1 ? s1 : 0) + (n_runs >= 2 ? s2 : 0);
+        if (kLazy)
+            out.mask_a = Mt;
+        else
+            nw_runs(Mt, out.consec, out.best_two);
     }
 }
 
-template <int N, bool kEnds = true, bool kRuns = true, int W = N>
+template <int N, bool kEnds = true, bool kRuns = true, int W = N, bool kLazy = false>
 __device__ __forceinline__ void nw_full(const uint32_t (&col)[N], int n_end, AlnStats &out) {
     constexpr int NLO = N < 16 ? N : 16, NHI = N - NLO;
     static_assert(N <= 32, "two 32-bit move words per row");
@@ -278,6 +314,7 @@ __device__ __forceinline__ void nw_full(const uint32_t (&col)[N], int n_end, Aln
         }
     }
 #ifdef SMI_NW_WALK_LOOP
+    static_assert(!kLazy, "the step-by-step walk keeps no masks");
     int c = N, lead = 0;
     int ins = 0, del = 0, sub = 0, trail = 0, cb = 0, t = 0, nx = 0;
     bool trailing = true, term = true;
@@ -378,7 +415,7 @@ __device__ __forceinline__ void nw_full(const uint32_t (&col)[N], int n_end, Aln
     // Match.countErrorsInNeedleman: (float)#x - 0.9f * (float)lead, two roundings
     out.ne = __fsub_rn((float)nx, __fmul_rn(0.9f, (float)lead));
 #else
-    nw_walk_bits<N, kEnds, kRuns>(mlo, mhi, n_end, out);
+    nw_walk_bits<N, kEnds, kRuns, kLazy>(mlo, mhi, n_end, out);
 #endif
 }
 

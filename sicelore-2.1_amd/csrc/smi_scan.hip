@@ -415,11 +415,32 @@ __device__ __forceinline__ int kth_bit(uint64_t m, int k) {
 }
 
 // result of one aligned candidate, as the owner lane needs it (5 words per entry in LDS, odd stride)
+// Words 1, 2 and the low half of word 4 depend on the path (see SMI_SCAN_EAGER_* below).  Lazy: word 1 = Mt of a TSO candidate, words 1 and 2 = X
+// and ND of an adapter candidate (smi_nw.h kLazy), and the low half of b is unused.
 struct Entry {
     float ne, end5, endn;
     uint32_t a;  // nmis | ins << 8 | del(+128) << 16 | term6 << 24
     uint32_t b;  // consec | best_two << 8 | pos << 16
 };
+
+// The statistics few rules read are computed where a rule reads them, from the step masks the alignment leaves in the entry (smi_nw.h kLazy):
+//   TSO      consec and best_two are read by the rescue rules of scanReadForTSOs only, for the winner of an end that is present and did not pass
+//            by nmis: phase C computes them there, behind one ballot
+//   adapter  end5 orders two acceptable candidates of one end that tie on the best ne, endn is tested against zero by the pass-1 filter on the
+//            chosen lane: the fold keeps the incumbent's masks and computes keys on a tie.  Where both masks fit one word each (2 * AD <= 32: the
+//            10-mer); the 22-mer keeps the eager path.
+// Two variant switches compile the eager path of one side, for counter runs (make VARIANT=eagerruns EXTRA=-DSMI_SCAN_EAGER_RUNS=1, VARIANT=eagerends
+// EXTRA=-DSMI_SCAN_EAGER_ENDS=1) -- same results; there is no run-time switch.
+#ifdef SMI_NW_WALK_LOOP  // (the step-by-step walk of smi_nw.h keeps no masks: both sides eager)
+#define SMI_SCAN_EAGER_RUNS 1
+#define SMI_SCAN_EAGER_ENDS 1
+#endif
+#ifndef SMI_SCAN_EAGER_RUNS
+#define SMI_SCAN_EAGER_RUNS 0
+#endif
+#ifndef SMI_SCAN_EAGER_ENDS
+#define SMI_SCAN_EAGER_ENDS 0
+#endif
 
 // Two variant switches for counter runs and cross-checks (make VARIANT=... EXTRA=-D...=1), never set in the shipped library:
 //   SMI_SCAN_SHFL_SCAN     the wave prefix sum through six __shfl_up steps (ds_bpermute) instead of DPP
@@ -584,14 +605,17 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
         // ---- phases B + C(fold): adapter candidates, then TSO candidates -----------------------------------------
         // adapter fold state (AdapterScanRslt best key + getMatchList L275-319)
         // The fold state rides through the alignment loops in few registers: a_pack / t_pack = pos | nmis << 8 | ins << 16 | (del + 128) << 24
-        // (positions are <= 192), t_aux = consec | best_two << 8 | skip << 16
-        float a_best = 3.4028234663852886e+38f, a_key = 0.0f;
+        // (positions are <= 192), t_aux = consec | best_two << 8 | skip << 16 (lazy: the skip position alone; the winner's Mt rides in t_mt)
+        // a_w1, a_w2: the incumbent's words 1 and 2 of its entry -- end5 (not kept: a_key has it) and endn, or X and ND on the lazy path, where a_key
+        // caches the incumbent's end5 once a tie has asked for it (< 0: not computed; the keys are >= 0)
+        constexpr bool kLazyAd = 2 * AD <= 32 && !SMI_SCAN_EAGER_ENDS, kLazyTso = !SMI_SCAN_EAGER_RUNS;
+        float a_best = 3.4028234663852886e+38f, a_key = kLazyAd ? -1.0f : 0.0f;
         bool a_have = false;
         uint32_t a_pack = 0;
-        float a_endn = 0.0f;
+        uint32_t a_w1 = 0, a_w2 = 0;
         // TSO fold state (scanForAdapterOrTSOseq with maxErrors = 5, L96-104; scanForTSO takes the first best position)
         float t_best = 3.4028234663852886e+38f;
-        uint32_t t_pack = 0, t_aux = 0;
+        uint32_t t_pack = 0, t_aux = 0, t_mt = 0;
 #pragma unroll 1
         for (int kind = 0; kind < 2; kind++) {
             // this kind's candidate masks and offsets go to LDS (the previous kind's are dead: wave_sync below).  The TSO gates are
@@ -770,6 +794,7 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
 #endif
                     AlnStats st;
                     st.ne = 9.0f, st.end5 = st.endn = 0.0f, st.nmis = 9, st.ins = st.del = st.consec = st.best_two = 0, st.term6 = false;
+                    st.mask_a = st.mask_b = 0;
                     // the column masks of the alignment are the four base planes of the read slice, selected per pattern
                     // base: four window fetches per candidate, not one per pattern base
                     uint32_t W[4];
@@ -782,17 +807,20 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                         uint32_t col[AD];
 #pragma unroll
                         for (int c = 0; c < AD; c++) col[c] = col_of(SHIP ? shipped_a4<AD>(c) : P.a4(c)) & ((1u << AD) - 1u);
-                        nw_full<AD, true, false, kBandAd>(col, P.min_3p, st);  // the adapter fold reads ne, nmis, ins, del, end5, endn, term6
+                        // the adapter fold reads ne, nmis, ins, del, term6 of every candidate; end5 on a tie and endn in pass 1 (lazy: off X and ND)
+                        nw_full<AD, true, false, kBandAd, kLazyAd>(col, P.min_3p, st);
                     } else if (kind == 1 && !SMI_ABLATED(1)) {
                         uint32_t col[16];
 #pragma unroll
                         for (int c = 0; c < 16; c++) col[c] = col_of(SHIP ? tso4(c) : P.t4(c)) & 0xFFFFu;
-                        nw_full<16, false, true, kBandTso>(col, 0, st);  // the TSO rules read ne, nmis, ins, del, consec, best_two
+                        // the TSO rules read ne, nmis, ins, del of every candidate; consec and best_two in the rescue rules (lazy: off Mt)
+                        nw_full<16, false, true, kBandTso, kLazyTso>(col, 0, st);
                     }
                     uint32_t *o = ent + tid * 5;
                     o[0] = __float_as_uint(st.ne);
-                    o[1] = __float_as_uint(st.end5);
-                    o[2] = __float_as_uint(st.endn);
+                    const bool lazy = kind == 0 ? kLazyAd : kLazyTso;
+                    o[1] = lazy ? (uint32_t)st.mask_a : __float_as_uint(st.end5);
+                    o[2] = lazy ? (uint32_t)st.mask_b : __float_as_uint(st.endn);
                     o[3] = (uint32_t)(st.nmis & 0xFF) | ((uint32_t)(st.ins & 0xFF) << 8) | ((uint32_t)((st.del + 128) & 0xFF) << 16) |
                            ((uint32_t)st.term6 << 24);
                     o[4] = (uint32_t)(st.consec & 0xFF) | ((uint32_t)(st.best_two & 0xFF) << 8) | ((uint32_t)pos << 16);
@@ -814,13 +842,22 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                         if (ne == a_best) {
                             // createNeedlemanMatch L242-247: accepted with <= maxMM errors or 6 terminal matches
                             const bool ok = nmis <= P.max_mm || ((o[3] >> 24) & 1u);
-                            const float key = __uint_as_float(o[1]);
                             // several best positions: smallest countIndelsMismatchesEndOfRead(5), first of its group
-                            if (ok && (!a_have || key < a_key)) {
+                            bool take = ok && !a_have;
+                            float key = kLazyAd ? -1.0f : __uint_as_float(o[1]);
+                            if (ok && a_have) {  // a tie of two acceptable candidates
+                                if (kLazyAd) {
+                                    if (a_key < 0.0f) a_key = nw_end5(a_w1, a_w2);
+                                    key = nw_end5(o[1], o[2]);
+                                }
+                                take = key < a_key;
+                            }
+                            if (take) {
                                 a_have = true;
                                 a_key = key;
                                 a_pack = packed;
-                                a_endn = __uint_as_float(o[2]);
+                                a_w1 = o[1];
+                                a_w2 = o[2];
                             }
                         }
                     } else if (pos >= (int)(t_aux >> 16)) {  // positions jumped over by deltaPos are never aligned (L100-106)
@@ -828,7 +865,10 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                         if (!((float)(int)floorf(__fadd_rn(ne, 0.5f)) > t_max) && ne < t_best) {  // Math.round(ne) <= maxErrors
                             t_best = ne;
                             t_pack = packed;
-                            t_aux = (t_aux & 0xFFFF0000u) | (o[4] & 0xFFFFu);
+                            if (kLazyTso)
+                                t_mt = o[1];
+                            else
+                                t_aux = (t_aux & 0xFFFF0000u) | (o[4] & 0xFFFFu);
                         }
                         if (t_max < ne) {
                             int d = (int)floorf(__fadd_rn(__fsub_rn(ne, t_max), 0.5f)) - 1;
@@ -877,7 +917,7 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
         const int a_pos = (int)(a_pack & 0xFF), a_nmis = (int)((a_pack >> 8) & 0xFF), a_ins = (int)((a_pack >> 16) & 0xFF),
                   a_del = (int)(a_pack >> 24) - 128;
         const int t_pos = (int)(t_pack & 0xFF), t_nmis = (int)((t_pack >> 8) & 0xFF), t_ins = (int)((t_pack >> 16) & 0xFF),
-                  t_del = (int)(t_pack >> 24) - 128, t_consec = (int)(t_aux & 0xFF), t_two = (int)((t_aux >> 8) & 0xFF);
+                  t_del = (int)(t_pack >> 24) - 128;
 
         smi_scan_result res;
         res.flags = flags;
@@ -966,7 +1006,8 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                 }
                 // pass-1 quality filter (short-circuit && chain; the UNSTRANDED quality string is indexed with
                 // stranded coordinates, UsedCellBCListGenerator.java:L201)
-                if (qtail != nullptr && a_endn == 0.0f) {
+                // (countIndelsMismatchesEndOfRead(minAdapter3pMatches) == 0)
+                if (qtail != nullptr && (kLazyAd ? nw_endn_is_zero(a_w1, a_w2, P.min_3p) : __uint_as_float(a_w2) == 0.0f)) {
                     const int ae = res.adapter_end;
                     int sum = 0;
                     bool in_range = ae - 16 >= 1;
@@ -1008,18 +1049,39 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
             mine.nmis = t_nmis;
             mine.passed = mine.present && t_nmis <= (SHIP ? 5 : P.tso_max_mm);  // scanForTSO L350
             mine.end_scan = t_pos + 15 + t_ins - t_del;
-            mine.consec = t_consec;
-            mine.two = t_two;
+            mine.consec = mine.two = 0;
             Tm o;
-            o.present = __shfl_xor(mine.present, 1);
-            o.passed = __shfl_xor(mine.passed, 1);
-            o.nmis = __shfl_xor(mine.nmis, 1);
-            o.end_scan = __shfl_xor(mine.end_scan, 1);
-            o.consec = __shfl_xor(mine.consec, 1);
-            o.two = __shfl_xor(mine.two, 1);
+            if (kLazyTso) {
+                // present, passed, nmis (8 bits) and end_scan (16 bits) in one word: one exchange
+                const uint32_t w = (uint32_t)mine.present | ((uint32_t)mine.passed << 1) | ((uint32_t)mine.nmis << 2) | ((uint32_t)(mine.end_scan & 0xFFFF) << 16);
+                const uint32_t ow = (uint32_t)__shfl_xor((int)w, 1);
+                o.present = (int)(ow & 1u);
+                o.passed = (int)((ow >> 1) & 1u);
+                o.nmis = (int)((ow >> 2) & 0xFFu);
+                o.end_scan = (int)(int16_t)(ow >> 16);
+                o.consec = o.two = 0;
+            } else {
+                mine.consec = (int)(t_aux & 0xFF);
+                mine.two = (int)((t_aux >> 8) & 0xFF);
+                o.present = __shfl_xor(mine.present, 1);
+                o.passed = __shfl_xor(mine.passed, 1);
+                o.nmis = __shfl_xor(mine.nmis, 1);
+                o.end_scan = __shfl_xor(mine.end_scan, 1);
+                o.consec = __shfl_xor(mine.consec, 1);
+                o.two = __shfl_xor(mine.two, 1);
+            }
+            // The rescue rules read consec / two of an end that is present and did not pass by nmis, and of no other (found = present && passed).  Lazy:
+            // the runs of the winner's match mask are counted here, for those ends, when the wave has one (one wave in four on the bench's reads: NOTES R6.26)
+            const bool need = mine.present && !mine.passed;
+            const bool rescue = !kLazyTso || __ballot(need) != 0;  // wave-uniform
+            if (kLazyTso && rescue) {
+                if (need) nw_runs(t_mt, mine.consec, mine.two);
+                o.consec = __shfl_xor(mine.consec, 1);
+                o.two = __shfl_xor(mine.two, 1);
+            }
             Tm f = side == 0 ? mine : o, r = side == 0 ? o : mine;
             auto found = [](const Tm &x) { return x.present && x.passed; };
-            if (!found(f) && !found(r)) {  // L146-153: rescue by >= 8 consecutive matches (config.xml:161)
+            if (rescue && !found(f) && !found(r)) {  // L146-153: rescue by >= 8 consecutive matches (config.xml:161)
                 const int min_consec = SHIP ? 8 : P.tso_min_consec, min_two = SHIP ? 12 : P.tso_min_two;
                 if (f.present) f.passed = f.consec >= min_consec;
                 if (r.present) r.passed = r.consec >= min_consec;

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .bamsegments import BGZF_EOF
 
 _CODE = {"A": 1, "G": 2, "C": 4, "T": 8, "N": 15}
 _DEC = {1: "A", 2: "G", 4: "C", 8: "T", 15: "N"}
@@ -643,7 +644,6 @@ def segment_cuts(ref, cur_n, g0, i0, prev_ref, step):
         i0 = g0 + at
 
 
-_BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
 def bai_ref_extents(bai_path):
@@ -951,7 +951,7 @@ def assignumis_stream(ctx, in_bam, out_prefix, segment_bytes=256 << 20, chunk_si
         g0 += first
     for fh in (f_bc, f_umi):
         if world == 1:
-            fh.write(_BGZF_EOF)
+            fh.write(BGZF_EOF)
         fh.close()
     f_in.close()
     for pb in stage.values():
@@ -1012,7 +1012,7 @@ def _string_shards(out_prefix, world, gc, later_dumps):
                             break
                         dst.write(blk)
                 os.remove(out_prefix + name + f".shard{q}")
-            dst.write(_BGZF_EOF)
+            dst.write(BGZF_EOF)
     return order_dependent
 
 

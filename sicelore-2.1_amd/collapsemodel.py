@@ -4,7 +4,7 @@ unassigned (IT = undef) molecules of the ISOBAM that `IsoformMatrix ISOBAM=true`
     java -jar Sicelore-2.1.jar CollapseModel I=isobam.bam CSV=barcodes.csv REFFLAT=genes.refFlat OUTDIR=out PREFIX=CollapseModel
 
 The BAM is read once in segments of about segment_bytes compressed bytes, inflated one segment ahead by a reader thread
-(isoformmatrix._segments) and loaded by the library's host threads (smi_collapse_add_segment), so no .bai is needed and the input need not be
+(bamsegments.segments) and loaded by the library's host threads (smi_collapse_add_segment), so no .bai is needed and the input need not be
 sorted; K-COLLAPSE, K-COLSTAT and K-FILTER / K-CLASS run on the device and the five texts are rendered from their results
 (smi_collapse_run).  Genes are in byte order of their name.  A record the loader fails on stops the run before any
 file is written.
@@ -18,7 +18,7 @@ import os
 import time
 
 from . import lib as _lib
-from .isoformmatrix import _segments
+from .bamsegments import segments
 
 
 def statistics_lines(c, v=None, cage=None, polya=None):
@@ -66,8 +66,8 @@ def output_names(prefix, delta, rn_min, min_evidence):
 
 
 def _short_segments(short, segment_bytes, n_threads):
-    """_segments over SHORT; a file that is no BGZF stream or no BAM fails by name"""
-    it = _segments(short, segment_bytes, n_threads)
+    """segments over SHORT; a file that is no BGZF stream or no BAM fails by name"""
+    it = segments(short, segment_bytes, n_threads)
     while True:
         try:
             seg = next(it)
@@ -95,7 +95,7 @@ def collapse_model(ctx, in_bam, refflat, csv, outdir, prefix="CollapseModel", se
     h = None
     t0 = time.perf_counter()
     try:
-        for bam, recs, hdr in _segments(in_bam, segment_bytes, n_threads):
+        for bam, recs, hdr in segments(in_bam, segment_bytes, n_threads):
             if hdr is not None:                       # the @SQ dictionary comes with the first segment
                 _text, refs, _start = _lib.bam_header(bam)
                 h = _lib.Collapse(ctx, rf, cs, [r[0] for r in refs], n_threads=n_threads, **cfg)

@@ -36,19 +36,14 @@
 #include <unordered_map>
 #include <vector>
 
+#include "smi_handle.h"
 #include "smi_internal.h"
-#include "smi_longread.h"
-#include "smi_mtx.h"
 
 namespace smi {
 namespace {
 
-using mtx::Events;
 
-template <class T>
-struct DevBuf : mtx::DevBuf<T> {
-    DevBuf() { this->who = "CollapseModel"; }
-};
+constexpr const char *kWho = "CollapseModel";  // the program named when a device allocation fails
 
 constexpr int kColThreads = 256;  // threads of one K-COLLAPSE block: 4 waves
 constexpr int kColWaves = kColThreads / 64;
@@ -354,43 +349,19 @@ int parse_model(const char *text, size_t n, Model &M) {
     std::vector<int32_t> line_gene;
     size_t b = 0;
     int64_t lineno = 0;
+    handle::RefFlatLine R;
+    std::string err;
     while (b < n) {
         size_t e = b;
         while (e < n && text[e] != '\n') e++;
-        std::string_view line(text + b, e - b);
-        if (!line.empty() && line.back() == '\r') line.remove_suffix(1);
+        const int kind = handle::refflat_line("CollapseModel", std::string_view(text + b, e - b), ++lineno, true, R, err);
         b = e + 1;
-        lineno++;
-        auto f = jsplit(line, '\t');
-        auto fail = [&](const std::string &why) {
-            set_error("CollapseModel: REFFLAT line " + std::to_string(lineno) + ": " + why);
+        if (kind == handle::kLineBad) {
+            set_error(err);
             return SMI_ERR_INVALID;
-        };
-        if (f.size() < 11) return fail("has " + std::to_string(f.size()) + " fields, at least 11 are needed");
-        if (f[3] != "+" && f[3] != "-" && f[3] != ".") return fail("field 4 is no strand (+, - or .)");
-        Line L;
-        int32_t v[5];
-        for (int k = 4; k <= 8; k++)
-            if (!jint(f[k], v[k - 4])) return fail("field " + std::to_string(k + 1) + " is not an integer");
-        for (int k = 9; k <= 10; k++) {
-            std::string_view s = f[k];
-            while (!s.empty() && s.back() == ',') s.remove_suffix(1);
-            for (auto t : jsplit(s, ',')) {
-                int32_t x;
-                if (!jint(t, x)) return fail("field " + std::to_string(k + 1) + " is not a list of integers");
-                (k == 9 ? L.xs : L.xe).push_back(x);
-            }
         }
-        if (L.xe.size() < L.xs.size()) return fail("fewer exon ends than exon starts");
-        int64_t bases = 0;
-        for (size_t i = 0; i < L.xs.size(); i++) bases += (int64_t)L.xe[i] - L.xs[i];
-        if ((int32_t)bases == 0) continue;
-        L.gene = std::string(f[0]);
-        L.tx = std::string(f[1]);
-        L.tx_start = v[0];
-        L.tx_end = v[1];
-        L.cds_start = v[2];
-        L.cds_end = v[3];
+        if (kind == handle::kLineDropped) continue;
+        Line L{std::string(R.gene), std::string(R.tx), R.tx_start, R.tx_end, R.cds_start, R.cds_end, R.xs, R.xe};
         L.xe.resize(L.xs.size());
         auto git = M.gene_id.emplace(L.gene, (int32_t)M.genes.size());
         if (git.second) M.genes.push_back(L.gene);
@@ -442,10 +413,10 @@ struct Validator {
     std::vector<int4> keys;                     // the table as uploaded
     std::vector<int32_t> tx_k_off{0}, tx_slot;  // per output transcript: the slots of its novel junctions, -1 = chromosome not in SHORT
     std::vector<uint8_t> ref_keys;
-    DevBuf<int4> d_keys;
-    DevBuf<uint32_t> d_count;
-    DevBuf<uint8_t> d_ref_keys;
-    DevBuf<unsigned long long> d_bound;
+    DevBuf<int4> d_keys{kWho};
+    DevBuf<uint32_t> d_count{kWho};
+    DevBuf<uint8_t> d_ref_keys{kWho};
+    DevBuf<unsigned long long> d_bound{kWho};
     uint32_t mask = 0;
     int32_t n_ref = 0;
     float ms = 0.f;
@@ -743,14 +714,7 @@ extern "C" int smi_collapse_create(smi_ctx *ctx, const smi_collapse_config *cfg,
         delete h;
         return rc;
     }
-    size_t b = 0;  // CellList: every line (readLine: \n, \r\n or \r) with "-1" removed
-    while (b < n_csv) {
-        size_t e = b;
-        while (e < n_csv && csv[e] != '\n' && csv[e] != '\r') e++;
-        h->listed.emplace(drop_minus1(std::string_view(csv + b, e - b)), 0);
-        if (e < n_csv && csv[e] == '\r' && e + 1 < n_csv && csv[e + 1] == '\n') e++;
-        b = e + 1;
-    }
+    for (std::string &cell : handle::cell_list(csv, n_csv)) h->listed.emplace(std::move(cell), 0);
     h->counts[SMI_COL_CELLS] = (int64_t)h->listed.size();
     h->counts[SMI_COL_MODEL_GENES] = (int64_t)h->M.genes.size();
     h->counts[SMI_COL_MODEL_TRANSCRIPTS] = (int64_t)h->M.lines.size();
@@ -778,13 +742,7 @@ extern "C" int smi_collapse_error_read(const smi_collapse *h, char *name, size_t
         set_error("smi_collapse_error_read: null argument");
         return SMI_ERR_INVALID;
     }
-    *record = h->error_record;
-    if (cap) {
-        const size_t k = std::min(cap - 1, h->error_read.size());
-        std::memcpy(name, h->error_read.data(), k);
-        name[k] = 0;
-    }
-    return SMI_OK;
+    return handle::error_read(h->error_read, h->error_record, name, cap, record);
 }
 
 extern "C" int smi_collapse_counts(const smi_collapse *h, int64_t *counts) {
@@ -801,12 +759,7 @@ extern "C" int smi_collapse_output(const smi_collapse *h, int32_t which, uint8_t
         set_error("smi_collapse_output: bad argument");
         return SMI_ERR_INVALID;
     }
-    const std::string &s = h->out[which];
-    *n_out = s.size();
-    if (!out) return SMI_OK;
-    if (cap < s.size()) return 1;
-    std::memcpy(out, s.data(), s.size());
-    return SMI_OK;
+    return handle::get_text(h->out[which], out, cap, n_out);
 }
 
 extern "C" int smi_collapse_add_segment(smi_collapse *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n) {
@@ -968,8 +921,8 @@ extern "C" int smi_collapse_run(smi_collapse *h, float *stage_ms) {
     Events evt;
     // K-COLLAPSE
     std::vector<int32_t> u_founder(nU, -1), cg_nf(nCG, 0), cg_base(nCG + 1, 0);
-    DevBuf<int32_t> d_cgo, d_ujo, d_uf, d_nf, d_base;
-    DevBuf<int2> d_uj;
+    DevBuf<int32_t> d_cgo{kWho}, d_ujo{kWho}, d_uf{kWho}, d_nf{kWho}, d_base{kWho};
+    DevBuf<int2> d_uj{kWho};
     if ((rc = d_cgo.put(cg_off, s)) || (rc = d_ujo.put(u_j_off, s)) || (rc = d_uj.put(uj, s)) || (rc = d_uf.alloc(nU)) || (rc = d_nf.alloc(nCG + 1)) ||
         (rc = d_base.alloc(nCG + 1)))
         return rc;
@@ -983,7 +936,7 @@ extern "C" int smi_collapse_run(smi_collapse *h, float *stage_ms) {
     }
     // K-COLSTAT: the scan of the founder counts (the Novel.<n> numbers), then the statistics per transcript
     {
-        DevBuf<uint8_t> d_tmp;
+        DevBuf<uint8_t> d_tmp{kWho};
         size_t tmp = 0;
         SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_nf.p, d_base.p, nCG + 1, s));
         if ((rc = d_tmp.alloc(tmp))) return rc;
@@ -999,11 +952,11 @@ extern "C" int smi_collapse_run(smi_collapse *h, float *stage_ms) {
     for (int32_t x : cg_nf) c[SMI_COL_MAX_FOUNDERS] = std::max<int64_t>(c[SMI_COL_MAX_FOUNDERS], x);
     std::vector<int32_t> t_count(nT), t_min(nT), t_max(nT), t_last(nT), t_cells(nT);
     if (nk && nT) {
-        DevBuf<int32_t> d_slot, d_ru, d_ucg, d_ts, d_te, d_cell, d_cnt, d_min, d_max, d_last, d_cells;
-        DevBuf<uint64_t> d_code, d_sorted, d_unique;
-        DevBuf<uint32_t> d_rl;
-        DevBuf<int64_t> d_nrun;
-        DevBuf<uint8_t> d_tmp;
+        DevBuf<int32_t> d_slot{kWho}, d_ru{kWho}, d_ucg{kWho}, d_ts{kWho}, d_te{kWho}, d_cell{kWho}, d_cnt{kWho}, d_min{kWho}, d_max{kWho}, d_last{kWho}, d_cells{kWho};
+        DevBuf<uint64_t> d_code{kWho}, d_sorted{kWho}, d_unique{kWho};
+        DevBuf<uint32_t> d_rl{kWho};
+        DevBuf<int64_t> d_nrun{kWho};
+        DevBuf<uint8_t> d_tmp{kWho};
         if ((rc = d_slot.put(rec_slot, s)) || (rc = d_ru.put(rec_u, s)) || (rc = d_ucg.put(u_cg, s)) || (rc = d_ts.put(tx_start, s)) ||
             (rc = d_te.put(tx_end, s)) || (rc = d_cell.put(cell, s)) || (rc = d_cnt.alloc(nT)) || (rc = d_min.alloc(nT)) || (rc = d_max.alloc(nT)) ||
             (rc = d_last.alloc(nT)) || (rc = d_cells.alloc(nT)) || (rc = d_code.alloc(nk)) || (rc = d_sorted.alloc(nk)) || (rc = d_unique.alloc(nk)) ||
@@ -1092,9 +1045,9 @@ extern "C" int smi_collapse_run(smi_collapse *h, float *stage_ms) {
     if (nE) {
         std::vector<int2> pool(M.tj);
         pool.insert(pool.end(), uj.begin(), uj.end());
-        DevBuf<int32_t> d_eo, d_ejo, d_enj, d_eko, d_l0, d_l1, d_ljo, d_keep, d_cat;
-        DevBuf<uint8_t> d_ek, d_kind;
-        DevBuf<int2> d_pool;
+        DevBuf<int32_t> d_eo{kWho}, d_ejo{kWho}, d_enj{kWho}, d_eko{kWho}, d_l0{kWho}, d_l1{kWho}, d_ljo{kWho}, d_keep{kWho}, d_cat{kWho};
+        DevBuf<uint8_t> d_ek{kWho}, d_kind{kWho};
+        DevBuf<int2> d_pool{kWho};
         if ((rc = d_eo.put(e_off, s)) || (rc = d_ejo.put(e_j_off, s)) || (rc = d_enj.put(e_nj, s)) || (rc = d_ek.put(e_known, s)) ||
             (rc = d_eko.put(e_k_off, s)) || (rc = d_l0.put(g_line0, s)) || (rc = d_l1.put(g_line1, s)) || (rc = d_ljo.put(M.l_j_off, s)) ||
             (rc = d_pool.put(pool, s)) || (rc = d_keep.alloc(nE)) || (rc = d_cat.alloc(nE)) || (rc = d_kind.alloc(n_kind)))
@@ -1290,8 +1243,8 @@ extern "C" int smi_collapse_validate_segment(smi_collapse *h, const uint8_t *bam
     if (n == 0 || h->vcounts[SMI_CVAL_JUNCTION_KEYS] == 0) return SMI_OK;
     SMI_HIP(hipSetDevice(h->ctx->device));
     hipStream_t s = h->ctx->stream;
-    DevBuf<uint8_t> d_bam;
-    DevBuf<uint64_t> d_off;
+    DevBuf<uint8_t> d_bam{kWho};
+    DevBuf<uint64_t> d_off{kWho};
     int rc;
     if ((rc = d_bam.alloc(n_bam)) || (rc = d_off.put(off, s))) return rc;
     SMI_HIP(hipMemcpyAsync(d_bam.p, bam, n_bam, hipMemcpyHostToDevice, s));

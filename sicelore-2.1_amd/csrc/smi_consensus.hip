@@ -31,8 +31,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "smi_handle.h"
 #include "smi_internal.h"
-#include "smi_longread.h"
 
 namespace smi {
 namespace {
@@ -451,17 +451,6 @@ int device_cus(int dev) {
     return n;
 }
 
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n) {
-        return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess ? SMI_OK : SMI_ERR_HIP;
-    }
-};
-
 // DP matrix cells of a molecule's slot.  exact: the worst case (the graph holds at most the bases of the reads before read k when read k is
 // aligned); otherwise the first-pass estimate (a graph of at most 3 x the longest read), never above the worst case
 size_t mat_cells(const uint64_t *read_off, int r0, int r1, bool exact) {
@@ -474,14 +463,6 @@ size_t mat_cells(const uint64_t *read_off, int r0, int r1, bool exact) {
     }
     return 5 * (exact ? mat : std::min(mat, std::min(before, 3 * len) * len));
 }
-
-struct Events {  // the two timing events of a launch, destroyed on every way out
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
 
 }  // namespace
 
@@ -513,10 +494,11 @@ int poa_batch(smi_ctx *ctx, const uint8_t *seq, const uint64_t *read_off, const 
     std::vector<int32_t> moff(n_mol + 1);
     for (int m = 0; m <= n_mol; m++) moff[m] = mol_off[m] - r0;
     const uint8_t *seq0 = seq + read_off[r0];
-    DevBuf<uint8_t> d_seq, d_cons, d_arena;
-    DevBuf<uint64_t> d_roff;
-    DevBuf<int32_t> d_moff, d_order, d_len, d_status;
-    DevBuf<uint32_t> d_same, d_counter;
+    constexpr const char *kWho = "smi_poa_batch";  // (the two texts below replace the buffer's own)
+    DevBuf<uint8_t> d_seq{kWho}, d_cons{kWho}, d_arena{kWho};
+    DevBuf<uint64_t> d_roff{kWho};
+    DevBuf<int32_t> d_moff{kWho}, d_order{kWho}, d_len{kWho}, d_status{kWho};
+    DevBuf<uint32_t> d_same{kWho}, d_counter{kWho};
     int rc;
     if ((rc = d_seq.alloc(total)) || (rc = d_cons.alloc(total)) || (rc = d_same.alloc(total)) || (rc = d_roff.alloc(n_reads + 1)) ||
         (rc = d_moff.alloc(n_mol + 1)) || (rc = d_order.alloc(n_mol)) || (rc = d_len.alloc(n_mol)) || (rc = d_status.alloc(n_mol)) ||
@@ -982,11 +964,7 @@ extern "C" int smi_consensus_fastq(const smi_consensus *h, uint8_t *out, size_t 
         set_error("smi_consensus_fastq: null argument");
         return SMI_ERR_INVALID;
     }
-    *n_out = h->fastq.size();
-    if (!out) return SMI_OK;
-    if (cap < h->fastq.size()) return 1;
-    std::memcpy(out, h->fastq.data(), h->fastq.size());
-    return SMI_OK;
+    return handle::get_text(h->fastq, out, cap, n_out);
 }
 
 extern "C" int smi_consensus_counts(const smi_consensus *h, int64_t *counts) {

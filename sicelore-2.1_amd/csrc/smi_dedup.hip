@@ -34,7 +34,6 @@
 #include <vector>
 
 #include "smi_internal.h"
-#include "smi_mtx.h"
 
 namespace smi {
 namespace {
@@ -46,10 +45,7 @@ constexpr uint64_t kNone = ~0ull;
 // transition functions, next state of state s in bits 2s+1 .. 2s: a marker line (0 -> 1) and any other line (0 -> 0); 1 -> 2 -> 3 -> 0 for both
 constexpr uint8_t kFqMarker = 0x39, kFqOther = 0x38, kFaMarker = 0x01, kFaOther = 0x00;
 
-template <class T>
-struct Buf : mtx::DevBuf<T> {
-    Buf() { this->who = "DeduplicateMolecule"; }
-};
+constexpr const char *kWho = "DeduplicateMolecule";  // the program named when a device allocation fails
 
 // a device array that keeps its contents when it grows (the key pool and the record table live across segments)
 template <class T>
@@ -452,7 +448,7 @@ struct smi_dedup {
     smi_dedup_config cfg = {};
     Grow<uint8_t> pool, d_text;
     Grow<DdRec> recs;
-    Buf<uint64_t> d_out_off;
+    DevBuf<uint64_t> d_out_off{kWho};
     uint64_t pool_bytes = 0, n_rec = 0, line_base = 0, err_line = 0;
     std::vector<Segment> segs;
     bool last_seen = false, selected = false;
@@ -521,7 +517,7 @@ extern "C" int smi_dedup_add_segment(smi_dedup *h, const uint8_t *text, size_t n
         int rc;
         if ((rc = h->d_text.reserve(n_bytes, 0, s))) return rc;
         SMI_HIP(hipMemcpyAsync(h->d_text.p, text, n_bytes, hipMemcpyHostToDevice, s));
-        mtx::Events ev;
+        Events ev;
         if ((rc = ev.begin(s))) return rc;
         size_t swept_lines = 0;
         if ((rc = launch_fastq_sweep(h->ctx, h->d_text.p, n_bytes, &swept_lines, s))) return rc;
@@ -532,10 +528,10 @@ extern "C" int smi_dedup_add_segment(smi_dedup *h, const uint8_t *text, size_t n
             return SMI_ERR_INVALID;
         }
         if (n_lines) {
-            Buf<uint64_t> d_line, d_start, d_klen, d_koff;
-            Buf<uint8_t> d_f, d_fs, d_tmp;
-            Buf<uint32_t> d_flag, d_ridx, d_valid, d_vidx;
-            Buf<DdSeg> d_seg;
+            DevBuf<uint64_t> d_line{kWho}, d_start{kWho}, d_klen{kWho}, d_koff{kWho};
+            DevBuf<uint8_t> d_f{kWho}, d_fs{kWho}, d_tmp{kWho};
+            DevBuf<uint32_t> d_flag{kWho}, d_ridx{kWho}, d_valid{kWho}, d_vidx{kWho};
+            DevBuf<DdSeg> d_seg{kWho};
             if ((rc = d_line.alloc(n_lines + 1)) || (rc = d_f.alloc(n_lines)) || (rc = d_fs.alloc(n_lines)) || (rc = d_flag.alloc(n_lines + 1)) ||
                 (rc = d_ridx.alloc(n_lines + 1)) || (rc = d_seg.alloc(1)))
                 return rc;
@@ -665,10 +661,10 @@ extern "C" int smi_dedup_select(smi_dedup *h, float *stage_ms) {
     if (n) {
         SMI_HIP(hipSetDevice(h->ctx->device));
         hipStream_t s = h->ctx->stream;
-        Buf<uint32_t> d_tab, d_group, d_win, d_last;
-        Buf<unsigned long long> d_best, d_cnt;
-        Buf<uint64_t> d_size;
-        Buf<uint8_t> d_tmp;
+        DevBuf<uint32_t> d_tab{kWho}, d_group{kWho}, d_win{kWho}, d_last{kWho};
+        DevBuf<unsigned long long> d_best{kWho}, d_cnt{kWho};
+        DevBuf<uint64_t> d_size{kWho};
+        DevBuf<uint8_t> d_tmp{kWho};
         int rc;
         if ((rc = d_tab.alloc(slots)) || (rc = d_group.alloc(n)) || (rc = d_win.alloc(n)) || (rc = d_last.alloc(n)) || (rc = d_best.alloc(n)) ||
             (rc = d_cnt.alloc(3)) || (rc = d_size.alloc((size_t)n + 1)) || (rc = h->d_out_off.alloc((size_t)n + 1)))
@@ -682,7 +678,7 @@ extern "C" int smi_dedup_select(smi_dedup *h, float *stage_ms) {
         SMI_HIP(hipMemsetAsync(d_best.p, 0, (size_t)n * 8, s));
         SMI_HIP(hipMemsetAsync(d_cnt.p, 0, 3 * 8, s));
         const unsigned grid = (n + kDdBlock - 1) / kDdBlock, grid1 = n / kDdBlock + 1;
-        mtx::Events ev;
+        Events ev;
         if ((rc = ev.begin(s))) return rc;
         TabArgs t = {};
         t.recs = h->recs.p;
@@ -759,10 +755,10 @@ extern "C" int smi_dedup_emit_segment(smi_dedup *h, int32_t segment, const uint8
         return SMI_ERR_INVALID;
     }
     int rc;
-    Buf<uint8_t> d_out;
+    DevBuf<uint8_t> d_out{kWho};
     if ((rc = h->d_text.reserve(sg.consumed, 0, s)) || (rc = d_out.alloc(size))) return rc;
     SMI_HIP(hipMemcpyAsync(h->d_text.p, text, sg.consumed, hipMemcpyHostToDevice, s));
-    mtx::Events ev;
+    Events ev;
     if ((rc = ev.begin(s))) return rc;
     hipLaunchKernelGGL(k_dd_write, dim3((sg.n_rec + kDdWaves - 1) / kDdWaves), dim3(64 * kDdWaves), 0, s, (const uint8_t *)h->d_text.p, (const DdRec *)h->recs.p,
                        (const uint64_t *)h->d_out_off.p, (const uint8_t *)h->pool.p, sg.rec0, sg.n_rec, (int)(h->cfg.fasta != 0), d_out.p);

@@ -36,19 +36,15 @@
 #include <unordered_set>
 #include <vector>
 
+#include "smi_handle.h"
 #include "smi_internal.h"
-#include "smi_longread.h"
 #include "smi_mtx.h"
 
 namespace smi {
 namespace {
 
-using mtx::Events;
 
-template <class T>
-struct DevBuf : mtx::DevBuf<T> {
-    DevBuf() { this->who = "FusionDetector"; }
-};
+constexpr const char *kWho = "FusionDetector";  // the program named when a device allocation fails
 
 constexpr int kFusBlock = 256;
 constexpr uint32_t kEmpty = 0xffffffffu;
@@ -331,7 +327,7 @@ inline unsigned grid(size_t n) { return (unsigned)((n + kFusBlock - 1) / kFusBlo
 
 // hipcub's temporary storage, grown on demand
 struct Tmp {
-    DevBuf<uint8_t> b;
+    DevBuf<uint8_t> b{kWho};
     size_t cap = 0;
     int need(size_t n) {
         if (n <= cap) return SMI_OK;
@@ -436,15 +432,7 @@ extern "C" int smi_fusion_create(smi_ctx *ctx, const smi_fusion_config *cfg, con
     h->ctx = ctx;
     h->cfg = *cfg;
     h->cfg.n_threads = std::max(1, std::min(cfg->n_threads, 256));
-    std::vector<std::string> cells;
-    size_t b = 0;  // CellList: every line (readLine: \n, \r\n or \r) with "-1" removed
-    while (b < n_csv) {
-        size_t e = b;
-        while (e < n_csv && csv[e] != '\n' && csv[e] != '\r') e++;
-        cells.push_back(lr::drop_minus1(std::string_view(csv + b, e - b)));
-        if (e < n_csv && csv[e] == '\r' && e + 1 < n_csv && csv[e + 1] == '\n') e++;
-        b = e + 1;
-    }
+    std::vector<std::string> cells = handle::cell_list(csv, n_csv);
     std::sort(cells.begin(), cells.end());
     cells.erase(std::unique(cells.begin(), cells.end()), cells.end());
     for (auto &c : cells) h->cells.add(c);
@@ -463,13 +451,7 @@ extern "C" int smi_fusion_error_read(const smi_fusion *h, char *name, size_t cap
         set_error("smi_fusion_error_read: null argument");
         return SMI_ERR_INVALID;
     }
-    *record = h->error_record;
-    if (cap) {
-        const size_t k = std::min(cap - 1, h->error_read.size());
-        std::memcpy(name, h->error_read.data(), k);
-        name[k] = 0;
-    }
-    return SMI_OK;
+    return handle::error_read(h->error_read, h->error_record, name, cap, record);
 }
 
 extern "C" int smi_fusion_counts(const smi_fusion *h, int64_t *counts) {
@@ -486,12 +468,7 @@ extern "C" int smi_fusion_output(const smi_fusion *h, int32_t which, uint8_t *ou
         set_error("smi_fusion_output: bad argument");
         return SMI_ERR_INVALID;
     }
-    const std::string &s = h->out[which];
-    *n_out = s.size();
-    if (!out) return SMI_OK;
-    if (cap < s.size()) return 1;
-    std::memcpy(out, s.data(), s.size());
-    return SMI_OK;
+    return handle::get_text(h->out[which], out, cap, n_out);
 }
 
 extern "C" int smi_fusion_add_segment(smi_fusion *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n) {
@@ -613,17 +590,17 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
             (rc = table_size(h, nC, "cells", &mask_c)))
             return rc;
         // the pools
-        DevBuf<uint8_t> d_name, d_bc, d_umi, d_gene, d_cellp, d_has;
-        DevBuf<uint64_t> d_name_off, d_bc_off, d_umi_off, d_gene_off, d_cell_off;
-        DevBuf<int32_t> d_frec;
+        DevBuf<uint8_t> d_name{kWho}, d_bc{kWho}, d_umi{kWho}, d_gene{kWho}, d_cellp{kWho}, d_has{kWho};
+        DevBuf<uint64_t> d_name_off{kWho}, d_bc_off{kWho}, d_umi_off{kWho}, d_gene_off{kWho}, d_cell_off{kWho};
+        DevBuf<int32_t> d_frec{kWho};
         if ((rc = d_name.put(h->names.bytes, s)) || (rc = d_name_off.put(h->names.off, s)) || (rc = d_bc.put(h->bcs.bytes, s)) ||
             (rc = d_bc_off.put(h->bcs.off, s)) || (rc = d_umi.put(h->umis.bytes, s)) || (rc = d_umi_off.put(h->umis.off, s)) ||
             (rc = d_gene.put(h->genes.bytes, s)) || (rc = d_gene_off.put(h->genes.off, s)) || (rc = d_cellp.put(h->cells.bytes, s)) ||
             (rc = d_cell_off.put(h->cells.off, s)) || (rc = d_has.put(h->has_umi, s)) || (rc = d_frec.put(h->f_rec, s)))
             return rc;
         // counters: probe steps, wraps, reads of several records, distinct genes, multiIG molecules; the overflow flag
-        DevBuf<unsigned long long> d_cnt;
-        DevBuf<uint32_t> d_over;
+        DevBuf<unsigned long long> d_cnt{kWho};
+        DevBuf<uint32_t> d_over{kWho};
         if ((rc = d_cnt.alloc(5)) || (rc = d_over.alloc(1))) return rc;
         SMI_HIP(hipMemsetAsync(d_cnt.p, 0, 5 * sizeof(unsigned long long), s));
         SMI_HIP(hipMemsetAsync(d_over.p, 0, sizeof(uint32_t), s));
@@ -645,8 +622,8 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
             return SMI_OK;
         };
         // reads
-        DevBuf<uint32_t> t_read, t_mol, t_gene, t_cell;
-        DevBuf<int32_t> d_rep, d_first, d_last, d_lumi, d_nrec, d_flag, d_rq;
+        DevBuf<uint32_t> t_read{kWho}, t_mol{kWho}, t_gene{kWho}, t_cell{kWho};
+        DevBuf<int32_t> d_rep{kWho}, d_first{kWho}, d_last{kWho}, d_lumi{kWho}, d_nrec{kWho}, d_flag{kWho}, d_rq{kWho};
         if ((rc = d_rep.alloc(n)) || (rc = d_first.alloc(n)) || (rc = d_last.alloc(n)) || (rc = d_lumi.alloc(n)) || (rc = d_nrec.alloc(n)) ||
             (rc = d_flag.alloc((size_t)n + 1)) || (rc = d_rq.alloc((size_t)n + 1)))
             return rc;
@@ -659,9 +636,9 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
         if ((rc = exclusive_sum(s, tmp, d_flag.p, d_rq.p, n + 1))) return rc;
         if ((rc = evt.end(s, &ms[1]))) return rc;
         SMI_HIP(hipMemcpy(&n_reads, d_rq.p + n, 4, hipMemcpyDeviceToHost));
-        DevBuf<int32_t> d_qfirst, d_qlast, d_qumi;
-        DevBuf<uint64_t> d_klen, d_koff;
-        DevBuf<uint8_t> d_key;
+        DevBuf<int32_t> d_qfirst{kWho}, d_qlast{kWho}, d_qumi{kWho};
+        DevBuf<uint64_t> d_klen{kWho}, d_koff{kWho};
+        DevBuf<uint8_t> d_key{kWho};
         if ((rc = d_qfirst.alloc(n_reads)) || (rc = d_qlast.alloc(n_reads)) || (rc = d_qumi.alloc(n_reads)) || (rc = d_klen.alloc((size_t)n_reads + 1)) ||
             (rc = d_koff.alloc((size_t)n_reads + 1)))
             return rc;
@@ -684,7 +661,7 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
         }
         // molecules
         if ((rc = table_size(h, n_reads, "reads", &mask_m))) return rc;
-        DevBuf<int32_t> d_mrep, d_mfirst, d_mlast, d_mn, d_mflag, d_mq, d_read_mol;
+        DevBuf<int32_t> d_mrep{kWho}, d_mfirst{kWho}, d_mlast{kWho}, d_mn{kWho}, d_mflag{kWho}, d_mq{kWho}, d_read_mol{kWho};
         if ((rc = d_mrep.alloc(n_reads)) || (rc = d_mfirst.alloc(n_reads)) || (rc = d_mlast.alloc(n_reads)) || (rc = d_mn.alloc(n_reads)) ||
             (rc = d_mflag.alloc((size_t)n_reads + 1)) || (rc = d_mq.alloc((size_t)n_reads + 1)) || (rc = d_read_mol.alloc(n_reads)))
             return rc;
@@ -697,7 +674,7 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
         if ((rc = exclusive_sum(s, tmp, d_mflag.p, d_mq.p, n_reads + 1))) return rc;
         if ((rc = evt.end(s, &ms[2]))) return rc;
         SMI_HIP(hipMemcpy(&n_mol, d_mq.p + n_reads, 4, hipMemcpyDeviceToHost));
-        DevBuf<int32_t> d_mol_n, d_mol_bc, d_mol_umi, d_mol_de, d_mol_ng, d_mol_gs, d_mol_cell, d_mol_pair;
+        DevBuf<int32_t> d_mol_n{kWho}, d_mol_bc{kWho}, d_mol_umi{kWho}, d_mol_de{kWho}, d_mol_ng{kWho}, d_mol_gs{kWho}, d_mol_cell{kWho}, d_mol_pair{kWho};
         if ((rc = d_mol_n.alloc(n_mol)) || (rc = d_mol_bc.alloc(n_mol)) || (rc = d_mol_umi.alloc(n_mol)) || (rc = d_mol_de.alloc(n_mol)) ||
             (rc = d_mol_ng.alloc(n_mol)) || (rc = d_mol_gs.alloc(n_mol)) || (rc = d_mol_cell.alloc(n_mol)) || (rc = d_mol_pair.alloc(n_mol)))
             return rc;
@@ -710,7 +687,7 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
             if ((rc = evt.end(s, &ms[2]))) return rc;
         }
         // the cell list: its table, then contains(molecule.getBarcode()) per molecule
-        DevBuf<int32_t> d_cgroup;
+        DevBuf<int32_t> d_cgroup{kWho};
         if ((rc = d_cgroup.alloc(nC))) return rc;
         if ((rc = insert(Keys{d_cellp.p, d_cell_off.p}, (uint32_t)nC, mask_c, t_cell, d_cgroup.p))) return rc;
         {
@@ -722,10 +699,10 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
             if ((rc = evt.end(s, &ms[0]))) return rc;
         }
         // genes
-        DevBuf<int32_t> d_grep, d_gfirst;
-        DevBuf<uint64_t> d_code, d_sorted, d_ucode, d_pair, d_psorted, d_upair;
-        DevBuf<uint32_t> d_rl;
-        DevBuf<int64_t> d_nrun;
+        DevBuf<int32_t> d_grep{kWho}, d_gfirst{kWho};
+        DevBuf<uint64_t> d_code{kWho}, d_sorted{kWho}, d_ucode{kWho}, d_pair{kWho}, d_psorted{kWho}, d_upair{kWho};
+        DevBuf<uint32_t> d_rl{kWho};
+        DevBuf<int64_t> d_nrun{kWho};
         if ((rc = d_grep.alloc(nF)) || (rc = d_gfirst.alloc(nF)) || (rc = d_code.alloc(nF)) || (rc = d_sorted.alloc(nF)) || (rc = d_ucode.alloc(nF)) ||
             (rc = d_rl.alloc(std::max(nF, n_mol))) || (rc = d_nrun.alloc(2)) || (rc = d_pair.alloc(n_mol)) || (rc = d_psorted.alloc(n_mol)) ||
             (rc = d_upair.alloc(n_mol)))

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -312,4 +313,53 @@ int ensure_deflate_scratch(smi_ctx *ctx, size_t n_bytes, size_t extra_bytes = 0)
 // two buffers -> two gzip members in the context's deflate scratch (behind the block slots); d_totals: [size a, flags a, size b, flags b]
 int deflate_pair(smi_ctx *ctx, const uint8_t *d_a, size_t na, const uint8_t *d_b, size_t nb, uint8_t **d_za, uint8_t **d_zb, uint64_t **d_totals,
                  hipStream_t s);
+
+// A device array freed on every way out.  who: the program named when an allocation fails.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    const char *who;
+    explicit DevBuf(const char *who_) : who(who_) {}
+    DevBuf(const DevBuf &) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t n) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        if (hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
+            set_error(std::string(who) + ": device allocation of " + std::to_string(n * sizeof(T)) + " bytes failed");
+            return SMI_ERR_HIP;
+        }
+        return SMI_OK;
+    }
+    int put(const std::vector<T> &v, hipStream_t s) {
+        if (int rc = alloc(v.size())) return rc;
+        if (!v.empty()) SMI_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
+        return SMI_OK;
+    }
+};
+
+// The two timing events of a launch, destroyed on every way out; begin / end add the device time between them to *acc.
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    int begin(hipStream_t s) {
+        if (!a) SMI_HIP(hipEventCreate(&a));
+        if (!b) SMI_HIP(hipEventCreate(&b));
+        SMI_HIP(hipEventRecord(a, s));
+        return SMI_OK;
+    }
+    int end(hipStream_t s, float *acc) {
+        SMI_HIP(hipEventRecord(b, s));
+        SMI_HIP(hipEventSynchronize(b));
+        float ms = 0.f;
+        SMI_HIP(hipEventElapsedTime(&ms, a, b));
+        *acc += ms;
+        return SMI_OK;
+    }
+};
 }  // namespace smi

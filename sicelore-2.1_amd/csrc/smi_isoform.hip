@@ -35,15 +35,14 @@
 #include <unordered_map>
 #include <vector>
 
+#include "smi_handle.h"
 #include "smi_internal.h"
-#include "smi_longread.h"
 #include "smi_mtx.h"
 
 namespace smi {
 namespace {
 
-using mtx::DevBuf;
-using mtx::Events;
+constexpr const char *kWho = "IsoformMatrix";  // the program named when a device allocation fails
 
 constexpr int kIsoWaves = 4;     // waves per block of K-ISO
 constexpr int kLdsTx = 2048;     // candidate counts of one wave held in LDS
@@ -218,7 +217,6 @@ __global__ __launch_bounds__(64 * kIsoWaves) void k_iso(IsoArgs a) {
 // ---- host parsing -----------------------------------------------------------------------------------------------------------------------
 using lr::drop_minus1;
 using lr::java_float;
-using lr::jint;
 using lr::jsplit;
 
 struct Model {
@@ -243,37 +241,21 @@ int parse_model(const char *text, size_t n, Model &M) {
     size_t b = 0;
     int64_t lineno = 0;
     std::vector<std::vector<int32_t>> by_gene;
+    handle::RefFlatLine L;
+    std::string err;
     while (b < n) {
         size_t e = b;
         while (e < n && text[e] != '\n') e++;
-        std::string_view line(text + b, e - b);
-        if (!line.empty() && line.back() == '\r') line.remove_suffix(1);  // BufferedReader.readLine
+        const int kind = handle::refflat_line("IsoformMatrix", std::string_view(text + b, e - b), ++lineno, false, L, err);
         b = e + 1;
-        lineno++;
-        auto f = jsplit(line, '\t');
-        auto fail = [&](const std::string &why) {
-            set_error("IsoformMatrix: REFFLAT line " + std::to_string(lineno) + ": " + why);
+        if (kind == handle::kLineBad) {
+            set_error(err);
             return SMI_ERR_INVALID;
-        };
-        if (f.size() < 11) return fail("has " + std::to_string(f.size()) + " fields, at least 11 are needed");
-        int32_t v;
-        for (int k = 4; k <= 8; k++)
-            if (!jint(f[k], v)) return fail("field " + std::to_string(k + 1) + " is not an integer");
-        std::vector<int32_t> xs, xe;
-        for (int k = 9; k <= 10; k++) {
-            std::string_view s = f[k];
-            while (!s.empty() && s.back() == ',') s.remove_suffix(1);  // StringUtils.stripEnd(str, ",")
-            for (auto t : jsplit(s, ',')) {
-                if (!jint(t, v)) return fail("field " + std::to_string(k + 1) + " is not a list of integers");
-                (k == 9 ? xs : xe).push_back(v);
-            }
         }
-        if (xe.size() < xs.size()) return fail("fewer exon ends than exon starts");
-        int64_t bases = 0;
-        for (size_t i = 0; i < xs.size(); i++) bases += (int64_t)xe[i] - xs[i];
-        if ((int32_t)bases == 0) continue;  // parseLine: getExonBases() == 0 -> dropped (int arithmetic)
+        if (kind == handle::kLineDropped) continue;
+        const std::vector<int32_t> &xs = L.xs, &xe = L.xe;
         M.n_lines++;
-        const std::string gname(f[0]);
+        const std::string gname(L.gene);
         auto git = M.gene_id.emplace(gname, (int32_t)M.genes.size());
         if (git.second) {
             M.genes.push_back(gname);
@@ -285,11 +267,11 @@ int parse_model(const char *text, size_t n, Model &M) {
         M.tx_nexon.push_back((int32_t)xs.size());
         for (size_t i = 1; i < xs.size(); i++) M.tj.push_back(make_int2(xe[i - 1], xs[i] + 1));
         M.tx_j_off.push_back((int32_t)M.tj.size());
-        std::string key = std::string(f[1]) + "|" + gname;
+        std::string key = std::string(L.tx) + "|" + gname;
         auto kit = key_of.emplace(key, (int32_t)key_str.size());
         if (kit.second) {
             key_str.push_back(key);
-            line_tx.push_back(std::string(f[1]));
+            line_tx.push_back(std::string(L.tx));
             line_gene.push_back(git.first->second);
         }
         line_key.push_back(kit.first->second);
@@ -433,16 +415,7 @@ extern "C" int smi_isoform_create(smi_ctx *ctx, const smi_isoform_config *cfg, c
         delete h;
         return rc;
     }
-    // CellList: every line (readLine: \n, \r\n or \r) with "-1" removed
-    std::vector<std::string> cells;
-    size_t b = 0;
-    while (b < n_csv) {
-        size_t e = b;
-        while (e < n_csv && csv[e] != '\n' && csv[e] != '\r') e++;
-        cells.push_back(drop_minus1(std::string_view(csv + b, e - b)));
-        if (e < n_csv && csv[e] == '\r' && e + 1 < n_csv && csv[e + 1] == '\n') e++;
-        b = e + 1;
-    }
+    std::vector<std::string> cells = handle::cell_list(csv, n_csv);
     std::sort(cells.begin(), cells.end());
     cells.erase(std::unique(cells.begin(), cells.end()), cells.end());
     h->cells = std::move(cells);
@@ -622,9 +595,9 @@ extern "C" int smi_isoform_run(smi_isoform *h, float *stage_ms) {
     std::vector<int32_t> jset;
     std::vector<int64_t> joff(n_mol + 1, 0);
     if (n_mol) {
-        DevBuf<int32_t> d_mro, d_rjo, d_mgo, d_mg, d_gto, d_gt, d_tjo, d_tk, d_tr, d_guo, d_gu, d_spill, d_key, d_gene, d_st, d_sup, d_nj, d_jout;
-        DevBuf<int2> d_rj, d_tj, d_uj;
-        DevBuf<int64_t> d_so, d_jo;
+        DevBuf<int32_t> d_mro{kWho}, d_rjo{kWho}, d_mgo{kWho}, d_mg{kWho}, d_gto{kWho}, d_gt{kWho}, d_tjo{kWho}, d_tk{kWho}, d_tr{kWho}, d_guo{kWho}, d_gu{kWho}, d_spill{kWho}, d_key{kWho}, d_gene{kWho}, d_st{kWho}, d_sup{kWho}, d_nj{kWho}, d_jout{kWho};
+        DevBuf<int2> d_rj{kWho}, d_tj{kWho}, d_uj{kWho};
+        DevBuf<int64_t> d_so{kWho}, d_jo{kWho};
         int rc = 0;
         if ((rc = d_mro.put(mol_rec_off, s)) || (rc = d_rjo.put(mrec_j_off, s)) || (rc = d_rj.put(mrj, s)) || (rc = d_mgo.put(mol_gene_off, s)) ||
             (rc = d_mg.put(mol_gene, s)) || (rc = d_gto.put(M.gene_tx_off, s)) || (rc = d_gt.put(M.gene_tx, s)) || (rc = d_tjo.put(M.tx_j_off, s)) ||
@@ -868,12 +841,7 @@ extern "C" int smi_isoform_output(const smi_isoform *h, int32_t which, uint8_t *
         set_error("smi_isoform_output: bad argument");
         return SMI_ERR_INVALID;
     }
-    const std::string &s = h->out[which];
-    *n_out = s.size();
-    if (!out) return SMI_OK;
-    if (cap < s.size()) return 1;
-    std::memcpy(out, s.data(), s.size());
-    return SMI_OK;
+    return handle::get_text(h->out[which], out, cap, n_out);
 }
 
 extern "C" int smi_isoform_counts(const smi_isoform *h, int64_t *counts) {
@@ -952,9 +920,9 @@ extern "C" int smi_isoform_isobam(smi_isoform *h, const uint8_t *bam, size_t n_b
         SMI_HIP(hipSetDevice(h->ctx->device));
         hipStream_t s = h->ctx->stream;
         if (!h->d_iso_text) {
-            DevBuf<uint8_t> a;
-            DevBuf<uint64_t> b, c2;
-            DevBuf<uint32_t> d, e;
+            DevBuf<uint8_t> a{kWho};
+            DevBuf<uint64_t> b{kWho}, c2{kWho};
+            DevBuf<uint32_t> d{kWho}, e{kWho};
             int rc;
             if ((rc = a.put(h->iso_text, s)) || (rc = b.put(h->ig_start, s)) || (rc = c2.put(h->it_start, s)) || (rc = d.put(h->ig_len, s)) ||
                 (rc = e.put(h->it_len, s)))
@@ -966,9 +934,9 @@ extern "C" int smi_isoform_isobam(smi_isoform *h, const uint8_t *bam, size_t n_b
             h->d_ig_len = d.p, d.p = nullptr;
             h->d_it_len = e.p, e.p = nullptr;
         }
-        DevBuf<uint8_t> d_bam;
-        DevBuf<smi_bam_record> d_recs;
-        DevBuf<int32_t> d_entry;
+        DevBuf<uint8_t> d_bam{kWho};
+        DevBuf<smi_bam_record> d_recs{kWho};
+        DevBuf<int32_t> d_entry{kWho};
         int rc;
         if ((rc = d_bam.alloc(n_bam + 1)) || (rc = d_recs.alloc(n)) || (rc = d_entry.put(entry, s))) return rc;
         if (n_bam) SMI_HIP(hipMemcpyAsync(d_bam.p, bam, n_bam, hipMemcpyHostToDevice, s));

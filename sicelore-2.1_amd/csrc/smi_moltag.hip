@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "smi_auxedit.h"
+#include "smi_handle.h"
 #include "smi_internal.h"
 
 namespace smi {
@@ -542,13 +543,7 @@ extern "C" int smi_moltag_error_read(const smi_moltag *h, char *name, size_t cap
         set_error("smi_moltag_error_read: null argument");
         return SMI_ERR_INVALID;
     }
-    *record = h->error_record;
-    if (cap) {
-        const size_t k = std::min(cap - 1, h->error_read.size());
-        std::memcpy(name, h->error_read.data(), k);
-        name[k] = 0;
-    }
-    return SMI_OK;
+    return handle::error_read(h->error_read, h->error_record, name, cap, record);
 }
 
 extern "C" int smi_moltag_segment(smi_moltag *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n, uint8_t *out, size_t cap,

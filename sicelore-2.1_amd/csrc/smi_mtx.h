@@ -1,7 +1,7 @@
 // smi_mtx.h -- K-MTX, the dense count matrices of Matrix.writeIsoformMatrix / writeGeneMatrix / writeJunctionMatrix (Matrix.java L158-290),
 // shared by IsoformMatrix (smi_isoform.hip) and SNPMatrix (smi_snp.hip): 64-bit (row << 32 | cell) codes, one per counted UMI; hipcub radix
 // sort + run-length encoding give the counts per (row, cell); the dense rows are rendered in row blocks under a device-memory budget, one
-// wavefront per row: a length pass, a scan, the write.  Also the device buffer and the event pair both programs hold their launches with.
+// wavefront per row: a length pass, a scan, the write.  (DevBuf and Events are in smi_internal.h.)
 #pragma once
 #include <hipcub/hipcub.hpp>
 
@@ -77,53 +77,6 @@ __global__ __launch_bounds__(64 * kRenderWaves) void k_mtx_render(const uint32_t
     if (lane == 0) dst[pos] = '\n';
 }
 
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    const char *who = "IsoformMatrix";  // the program named when an allocation fails
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        if (hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
-            set_error(std::string(who) + ": device allocation of " + std::to_string(n * sizeof(T)) + " bytes failed");
-            return SMI_ERR_HIP;
-        }
-        return SMI_OK;
-    }
-    int put(const std::vector<T> &v, hipStream_t s) {
-        if (int rc = alloc(v.size())) return rc;
-        if (!v.empty()) SMI_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-        return SMI_OK;
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-    int begin(hipStream_t s) {
-        if (!a) SMI_HIP(hipEventCreate(&a));
-        if (!b) SMI_HIP(hipEventCreate(&b));
-        SMI_HIP(hipEventRecord(a, s));
-        return SMI_OK;
-    }
-    int end(hipStream_t s, float *acc) {
-        SMI_HIP(hipEventRecord(b, s));
-        SMI_HIP(hipEventSynchronize(b));
-        float ms = 0.f;
-        SMI_HIP(hipEventElapsedTime(&ms, a, b));
-        *acc += ms;
-        return SMI_OK;
-    }
-};
-
 // K-MTX for one matrix: codes (row << 32 | cell), one per counted UMI -> counts per (row, cell) (sorted codes, device) and the dense rows
 // of `labels` x nc cells appended to dst, rendered in blocks of at most budget_bytes (0: 1 GiB) of device memory; row_total: the sum of
 // each row; *blocks is raised by the row blocks rendered.  who: the program named in an error.
@@ -142,11 +95,10 @@ inline int matrix(hipStream_t s, const char *who, int32_t nc, int64_t budget_byt
     int end_bit = 32;  // cells < 2^31 in the low word; the row in as many bits above as the rows need
     while (end_bit < 64 && ((uint64_t)1 << (end_bit - 32)) < (uint64_t)nrows) end_bit++;
     if (n) {
-        DevBuf<uint64_t> d_in, d_sorted, d_unique;
-        DevBuf<uint32_t> d_cnt;
-        DevBuf<int64_t> d_nrun;
-        DevBuf<uint8_t> d_tmp;
-        d_in.who = d_sorted.who = d_unique.who = d_cnt.who = d_nrun.who = d_tmp.who = who;
+        DevBuf<uint64_t> d_in{who}, d_sorted{who}, d_unique{who};
+        DevBuf<uint32_t> d_cnt{who};
+        DevBuf<int64_t> d_nrun{who};
+        DevBuf<uint8_t> d_tmp{who};
         if (int rc = d_in.put(codes, s)) return rc;
         if (int rc = d_sorted.alloc(n)) return rc;
         if (int rc = d_unique.alloc(n)) return rc;
@@ -182,10 +134,9 @@ inline int matrix(hipStream_t s, const char *who, int32_t nc, int64_t budget_byt
     for (uint32_t x : ucnt) maxc = std::max(maxc, x);
     const int wd = 1 + (int)std::to_string(maxc).size();
     const int64_t budget = budget_bytes > 0 ? budget_bytes : (int64_t)1 << 30;
-    DevBuf<uint8_t> d_lab;
-    DevBuf<uint64_t> d_lab_off, d_ucode;
-    DevBuf<uint32_t> d_ucnt;
-    d_lab.who = d_lab_off.who = d_ucode.who = d_ucnt.who = who;
+    DevBuf<uint8_t> d_lab{who};
+    DevBuf<uint64_t> d_lab_off{who}, d_ucode{who};
+    DevBuf<uint32_t> d_ucnt{who};
     if (int rc = d_lab.put(lab, s)) return rc;
     if (int rc = d_lab_off.put(lab_off, s)) return rc;
     if (int rc = d_ucode.put(ucode, s)) return rc;
@@ -204,10 +155,9 @@ inline int matrix(hipStream_t s, const char *who, int32_t nc, int64_t budget_byt
         const int32_t nb = (int32_t)(r1 - r0);
         size_t k1 = k0;
         while (k1 < ucode.size() && (int64_t)(ucode[k1] >> 32) < r1) k1++;
-        DevBuf<uint32_t> d_dense;
-        DevBuf<uint64_t> d_len, d_off;
-        DevBuf<uint8_t> d_out, d_tmp;
-        d_dense.who = d_len.who = d_off.who = d_out.who = d_tmp.who = who;
+        DevBuf<uint32_t> d_dense{who};
+        DevBuf<uint64_t> d_len{who}, d_off{who};
+        DevBuf<uint8_t> d_out{who}, d_tmp{who};
         if (int rc = d_dense.alloc((size_t)nb * std::max(nc, 1))) return rc;
         if (int rc = d_len.alloc(nb + 1)) return rc;
         if (int rc = d_off.alloc(nb + 1)) return rc;

@@ -29,14 +29,13 @@
 #include <unordered_map>
 #include <vector>
 
+#include "smi_handle.h"
 #include "smi_internal.h"
-#include "smi_longread.h"
 #include "smi_mtx.h"
 
 namespace smi {
 namespace {
 
-using lr::drop_minus1;
 using lr::jint;
 using lr::jsplit;
 
@@ -45,10 +44,7 @@ constexpr int kSnpWaves = 4;  // waves per block of K-SNP
 enum : uint32_t { kHit = 0, kLowRn = 1, kLowQv = 2, kStatusMask = 0xff, kPairNoQual = 1u << 8, kPairNoUmi = 1u << 9 };
 enum : uint8_t { kRecConsidered = 1, kRecBadAux = 2, kRecBadType = 4, kRecNotNull = 8 };
 
-template <class T>
-struct Buf : mtx::DevBuf<T> {
-    Buf() { this->who = "SNPMatrix"; }
-};
+constexpr const char *kWho = "SNPMatrix";  // the program named when a device allocation fails
 
 struct SnpPair {
     int32_t rec, line, cell, rn;  // record of the segment, kept line (file order), cell id or -1 (not in the list)
@@ -374,9 +370,9 @@ struct smi_snp {
     std::vector<std::string> cells;  // byte order
     int32_t n_ref = 0;
     // device tables
-    Buf<int32_t> d_ref_off, d_first, d_last, d_runmax, d_id, d_pos_off, d_pos, d_tab;
-    Buf<uint8_t> d_neg, d_cell_text;
-    Buf<uint32_t> d_cell_off;
+    DevBuf<int32_t> d_ref_off{kWho}, d_first{kWho}, d_last{kWho}, d_runmax{kWho}, d_id{kWho}, d_pos_off{kWho}, d_pos{kWho}, d_tab{kWho};
+    DevBuf<uint8_t> d_neg{kWho}, d_cell_text{kWho};
+    DevBuf<uint32_t> d_cell_off{kWho};
     uint32_t tab_mask = 0;
     // hits of listed cells, in record order
     std::vector<Hit> hits;
@@ -471,15 +467,7 @@ extern "C" int smi_snp_create(smi_ctx *ctx, const smi_snp_config *cfg, const cha
         h->lines.push_back(std::move(L));
     }
     // CellList: every line with "-1" removed
-    std::vector<std::string> cells;
-    b = 0;
-    while (b < n_csv) {
-        size_t e = b;
-        while (e < n_csv && csv[e] != '\n' && csv[e] != '\r') e++;
-        cells.push_back(drop_minus1(std::string_view(csv + b, e - b)));
-        if (e < n_csv && csv[e] == '\r' && e + 1 < n_csv && csv[e + 1] == '\n') e++;
-        b = e + 1;
-    }
+    std::vector<std::string> cells = handle::cell_list(csv, n_csv);
     std::sort(cells.begin(), cells.end());
     cells.erase(std::unique(cells.begin(), cells.end()), cells.end());
     h->cells = std::move(cells);
@@ -564,10 +552,10 @@ extern "C" int smi_snp_add_segment(smi_snp *h, const uint8_t *bam, size_t n_bam,
     if (n == 0 || h->lines.empty()) return SMI_OK;
     SMI_HIP(hipSetDevice(h->ctx->device));
     hipStream_t s = h->ctx->stream;
-    Buf<uint8_t> d_bam, d_flags, d_bq, d_tmp;
-    Buf<smi_bam_record> d_recs;
-    Buf<uint64_t> d_np, d_nb, d_op, d_ob;
-    Buf<SnpPair> d_pairs;
+    DevBuf<uint8_t> d_bam{kWho}, d_flags{kWho}, d_bq{kWho}, d_tmp{kWho};
+    DevBuf<smi_bam_record> d_recs{kWho};
+    DevBuf<uint64_t> d_np{kWho}, d_nb{kWho}, d_op{kWho}, d_ob{kWho};
+    DevBuf<SnpPair> d_pairs{kWho};
     int rc;
     if ((rc = d_bam.alloc(n_bam)) || (rc = d_recs.alloc(n)) || (rc = d_flags.alloc(n)) || (rc = d_np.alloc(n + 1)) || (rc = d_nb.alloc(n + 1)) ||
         (rc = d_op.alloc(n + 1)) || (rc = d_ob.alloc(n + 1)))
@@ -603,7 +591,7 @@ extern "C" int smi_snp_add_segment(smi_snp *h, const uint8_t *bam, size_t n_bam,
     a.n_bytes = d_nb.p;
     a.rec_flags = d_flags.p;
     const unsigned grid = (unsigned)((n + kSnpWaves - 1) / kSnpWaves);
-    mtx::Events ev;
+    Events ev;
     if ((rc = ev.begin(s))) return rc;
     hipLaunchKernelGGL(k_snp<false>, dim3(grid), dim3(64 * kSnpWaves), 0, s, a);
     SMI_HIP(hipGetLastError());
@@ -767,10 +755,10 @@ extern "C" int smi_snp_run(smi_snp *h, float *stage_ms) {
         umi[i] = (uint32_t)h->hits[i].umi;
     }
     {
-        Buf<uint64_t> d_c0, d_c1, d_sel;
-        Buf<uint32_t> d_u0, d_u1;
-        Buf<uint8_t> d_first, d_tmp;
-        Buf<int64_t> d_nsel;
+        DevBuf<uint64_t> d_c0{kWho}, d_c1{kWho}, d_sel{kWho};
+        DevBuf<uint32_t> d_u0{kWho}, d_u1{kWho};
+        DevBuf<uint8_t> d_first{kWho}, d_tmp{kWho};
+        DevBuf<int64_t> d_nsel{kWho};
         int rc;
         if ((rc = d_c0.put(codes, s)) || (rc = d_u0.put(umi, s)) || (rc = d_c1.alloc(nh)) || (rc = d_u1.alloc(nh)) || (rc = d_sel.alloc(nh)) ||
             (rc = d_first.alloc(nh)) || (rc = d_nsel.alloc(1)))
@@ -784,7 +772,7 @@ extern "C" int smi_snp_run(smi_snp *h, float *stage_ms) {
         SMI_HIP(hipcub::DeviceSelect::Flagged(nullptr, t3, d_c0.p, d_first.p, d_sel.p, d_nsel.p, (int)nh, s));
         const size_t cap = std::max(t1, std::max(t2, t3));
         if ((rc = d_tmp.alloc(cap))) return rc;
-        mtx::Events ev;
+        Events ev;
         if ((rc = ev.begin(s))) return rc;
         size_t tmp = cap;
         SMI_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp, d_u0.p, d_u1.p, d_c0.p, d_c1.p, (int)nh, 0, umi_bits, s));
@@ -838,12 +826,7 @@ extern "C" int smi_snp_output(const smi_snp *h, int32_t which, uint8_t *out, siz
         set_error("smi_snp_output: bad argument");
         return SMI_ERR_INVALID;
     }
-    const std::string &s = h->out[which];
-    *n_out = s.size();
-    if (!out) return SMI_OK;
-    if (cap < s.size()) return 1;
-    std::memcpy(out, s.data(), s.size());
-    return SMI_OK;
+    return handle::get_text(h->out[which], out, cap, n_out);
 }
 
 extern "C" int smi_snp_counts(const smi_snp *h, int64_t *counts) {

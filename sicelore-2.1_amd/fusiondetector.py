@@ -4,14 +4,14 @@ cell by cell"): the molecules of a tagged BAM (BC / U8 / GE, optional RN, de / d
     java -jar Sicelore-2.1.jar FusionDetector I=clipped_reads.tags.US.bam O=. PREFIX=fusion CSV=ValidBarcodes.csv
 
 The BAM is read once in segments of about segment_bytes compressed bytes, inflated one segment ahead by a reader thread
-(isoformmatrix._segments) and filtered by the library's host threads (smi_fusion_add_segment); reads, molecules and gene names are grouped
+(bamsegments.segments) and filtered by the library's host threads (smi_fusion_add_segment); reads, molecules and gene names are grouped
 by their bytes on the device and K-MTX renders the matrix (smi_fusion_run).  Cells and rows are in byte order, molinfos in (cell, UMI) byte
 order.  A record the parser fails on stops the run before any file is written."""
 import os
 import time
 
 from . import lib as _lib
-from .isoformmatrix import _segments
+from .bamsegments import segments
 
 
 def fusions_of(metrics):
@@ -69,7 +69,7 @@ def fusion_detector(ctx, in_bam, csv, outdir, prefix="fusion", segment_bytes=256
     h = _lib.Fusion(ctx, cs, n_threads=n_threads, **cfg)
     t0 = time.perf_counter()
     try:
-        for bam, recs, _hdr in _segments(in_bam, segment_bytes, n_threads):
+        for bam, recs, _hdr in segments(in_bam, segment_bytes, n_threads):
             if recs.size:
                 h.add_segment(bam, recs)
         t_parse = time.perf_counter() - t0

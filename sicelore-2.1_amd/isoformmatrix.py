@@ -3,75 +3,19 @@ isoform, cell x gene and cell x junction matrices of a molecule-tagged BAM, STRI
 
     java -jar Sicelore-2.1.jar IsoformMatrix -I in.bam -REFFLAT genes.refFlat -CSV barcodes.csv -OUTDIR out -PREFIX sicelore [-DELTA 2] ...
 
-The BAM is read in segments of about segment_bytes compressed bytes, inflated one segment ahead by a reader thread and parsed by the
+The BAM is read in segments of about segment_bytes compressed bytes (bamsegments.segments) and parsed by the
 library's host threads (smi_isoform_add_segment); K-ISO assigns the molecules and K-MTX counts and renders the matrices on the device
 (smi_isoform_run).  Rows and columns are in byte order and molinfos in (cell, UMI) order.  With ISOBAM a second
 pass over the BAM writes PREFIX_isobam.bam: every record with IG / IT, assembled on the device (smi_isoform_isobam), behind the input's
 header with SO:unsorted.  PREFIX.html and histogram.png (JFreeChart) are not written."""
 import os
-import queue
 import struct
-import threading
 import time
 
 import numpy as np
 
 from . import lib as _lib
-
-
-BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
-
-
-def _segments(in_bam, segment_bytes, n_threads):
-    """(inflated bytes, records, header bytes or None) per segment: the header's bytes come with the first segment"""
-    segments = queue.Queue(maxsize=1)
-
-    def reader():
-        try:
-            with open(in_bam, "rb") as f:
-                tail = np.zeros(0, dtype=np.uint8)
-                while True:
-                    raw = np.fromfile(f, dtype=np.uint8, count=int(segment_bytes))
-                    last = raw.size < int(segment_bytes)
-                    comp = np.concatenate([tail, raw]) if tail.size else raw
-                    buf, used = _lib.bgzf_inflate(comp, n_threads=n_threads) if comp.size else (np.zeros(0, dtype=np.uint8), 0)
-                    tail = comp[used:].copy()
-                    if last and tail.size:
-                        raise _lib.SmiError(f"{in_bam}: truncated BGZF stream")
-                    segments.put((buf, last, None))
-                    if last:
-                        return
-        except BaseException as e:  # noqa: BLE001 -- handed to the consumer
-            segments.put((None, True, e))
-
-    threading.Thread(target=reader, daemon=True).start()
-    pend = np.zeros(0, dtype=np.uint8)
-    header = False
-    eof = False
-    while not eof:
-        buf, eof, e = segments.get()
-        if e is not None:
-            raise e
-        bam = np.concatenate([pend, buf]) if pend.size else buf
-        start = 0
-        if not header:
-            try:
-                _text, _refs, start = _lib.bam_header(bam)
-            except _lib.SmiError:
-                if eof:
-                    raise
-                pend = bam
-                continue
-            header = True
-        hdr = bam[:start].tobytes() if start else None
-        recs, end = _lib.bam_index_records(bam, start, cap=max(1, (bam.size - start) // 36))
-        if eof and end != bam.size:
-            raise _lib.SmiError(f"{in_bam}: truncated BAM record")
-        if recs.size or hdr is not None:
-            yield bam, recs, hdr
-        pend = bam[end:].copy()
-    if not header:
-        raise _lib.SmiError(f"{in_bam}: no BAM header")
+from .bamsegments import BGZF_EOF, segments
 
 
 def unsorted_header(text):
@@ -111,7 +55,7 @@ def isoform_matrix(ctx, in_bam, refflat, csv, outdir, prefix="sicelore", segment
     h = _lib.Isoform(ctx, rf, cs, n_threads=n_threads, **cfg)
     try:
         t0 = time.perf_counter()
-        for bam, recs, _hdr in _segments(in_bam, segment_bytes, n_threads):
+        for bam, recs, _hdr in segments(in_bam, segment_bytes, n_threads):
             if recs.size:
                 h.add_segment(bam, recs)
         t_parse = time.perf_counter() - t0
@@ -128,7 +72,7 @@ def isoform_matrix(ctx, in_bam, refflat, csv, outdir, prefix="sicelore", segment
                     z = ctx.bgzf_deflate_device(np.frombuffer(data, dtype=np.uint8) if isinstance(data, bytes) else data)
                     f.write(memoryview(z[:-28]))
                     return len(z) - 28
-                for bam, recs, hdr in _segments(in_bam, segment_bytes, n_threads):
+                for bam, recs, hdr in segments(in_bam, segment_bytes, n_threads):
                     if hdr is not None:
                         isobam_bytes += emit(isobam_header(hdr))
                     if recs.size:

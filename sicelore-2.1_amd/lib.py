@@ -587,6 +587,131 @@ class NameSet:
     __del__ = close
 
 
+class _Handle:
+    """What the per-program handles (smi_<x>_*) share: the config from keywords, the argument check of a segment, the size protocols of the
+    getters, counters and stage times by name, the read an error names, and close.  A class names its functions (_NAME), its config
+    structure and that structure's tag / int / bool fields, and its counters."""
+    _NAME = _CONFIG = None
+    _TAGS = _INTS = _BOOLS = _COUNTS = ()
+    _TAG_ERROR = "{k}: a tag is two characters"
+    _h = None
+
+    def _fn(self, what):
+        return getattr(self._lib, f"smi_{self._NAME}_{what}")
+
+    def _check(self, rc):
+        if rc:
+            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+
+    def _config(self, kw, *default_args):
+        """smi_<x>_default_config, then the keywords"""
+        self._lib = load_library()
+        cfg = self._CONFIG()
+        self._check(self._fn("default_config")(*default_args, ctypes.byref(cfg)))
+        for k, v in kw.items():
+            if k in self._TAGS:
+                b = str(v).encode()
+                if len(b) != 2:
+                    raise SmiError(self._TAG_ERROR.format(k=k, v=v))
+                setattr(cfg, k, b)
+            elif k in self._INTS:
+                setattr(cfg, k, int(v))
+            elif k in self._BOOLS:
+                setattr(cfg, k, int(bool(v)))
+            else:
+                raise ValueError(f"unknown smi_{self._NAME}_config field {k!r}")
+        return cfg
+
+    def _create(self, ctx, *args):
+        """smi_<x>_create(ctx, ..., &handle); the handle runs on the context's stream, so the context is kept alive"""
+        h = ctypes.c_void_p()
+        self._check(self._fn("create")(ctx._h, *args, ctypes.byref(h)))
+        self._h, self._ctx = h, ctx
+
+    @staticmethod
+    def _text(data):
+        """bytes -> (address or None, size), and the array that owns them"""
+        a = np.frombuffer(bytes(data), dtype=np.uint8)
+        return (_ptr(a) if a.size else None, a.size), a
+
+    @staticmethod
+    def _names(ref_names):
+        names = [str(r).rstrip("\0").encode("latin-1") for r in ref_names]
+        return (ctypes.c_char_p * max(len(names), 1))(*names), len(names)
+
+    @staticmethod
+    def _segment_args(bam, recs):
+        """-> (bam address or None, size, recs address or None, count), and the record array that owns them"""
+        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
+            raise ValueError("bam: a contiguous 1-D uint8 array")
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != BAM_RECORD_DTYPE:
+            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
+        return (_ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)), recs
+
+    def _add_segment(self, bam, recs, what="add_segment"):
+        args, recs = self._segment_args(bam, recs)
+        self._check(self._fn(what)(self._h, *args))
+
+    def _fetch(self, fn, *args):
+        """fn(*args, out, cap, &n) called for the size, then for the bytes -> uint8 array"""
+        n = ctypes.c_size_t(0)
+        self._check(fn(*args, None, 0, ctypes.byref(n)))
+        out = np.empty(max(n.value, 1), dtype=np.uint8)
+        self._check(fn(*args, _ptr(out), out.size, ctypes.byref(n)))
+        return out[:n.value]
+
+    @staticmethod
+    def _grow(call, out, n_out):
+        """call(out) again while it returns 1 (out too small: n_out holds the size; the sized segment stays on the device and the next
+        call writes it) -> (its return code, out)"""
+        while True:
+            rc = call(out)
+            if rc != 1:
+                return rc, out
+            out = np.empty(n_out.value + (n_out.value >> 3), dtype=np.uint8)
+
+    def _named(self, what, names, dtype=np.int64):
+        v = np.zeros(len(names), dtype=dtype)
+        self._fn(what)(self._h, _ptr(v))
+        return dict(zip(names, v.tolist()))
+
+    def _run(self):
+        """smi_<x>_run with its stage times -> {file name suffix: bytes}"""
+        ms = np.zeros(len(self._STAGES), dtype=np.float32)
+        self._check(self._fn("run")(self._h, _ptr(ms)))
+        self.stage_ms = dict(zip(self._STAGES, ms.tolist()))
+        return self._outputs()
+
+    def _outputs(self):
+        return {name: self._fetch(self._fn("output"), self._h, i).tobytes() for i, name in enumerate(self._OUTPUTS)}
+
+    def _error_read(self):
+        """(name bytes, record index) of smi_<x>_error_read"""
+        name, rec = ctypes.create_string_buffer(256), ctypes.c_int64(-1)
+        self._fn("error_read")(self._h, name, 256, ctypes.byref(rec))
+        return name.value, rec.value
+
+    def _add_segment_naming_read(self, bam, recs):
+        try:
+            self._add_segment(bam, recs)
+        except SmiError:
+            name, rec = self._error_read()
+            if rec >= 0:
+                self.error_read = (name.decode(errors="replace"), rec)
+            raise
+
+    def counts(self):
+        return self._named("counts", self._COUNTS)
+
+    def close(self):
+        h, self._h = self._h, None           # (a second call, a failed constructor and interpreter shutdown find nothing to free)
+        if h:
+            self._fn("free")(h)
+
+    __del__ = close
+
+
 class TagBamConfig(ctypes.Structure):
     """smi_tagbam_config"""
     _fields_ = [("read_tag", ctypes.c_char * 4), ("qv_tag", ctypes.c_char * 4), ("with_qv", ctypes.c_int32), ("hash_bits", ctypes.c_int32)]
@@ -595,30 +720,29 @@ class TagBamConfig(ctypes.Structure):
 TAGBAM_STAGES = ("key", "build", "probe", "size", "assemble")
 
 
-class TagBam:
+class TagBam(_Handle):
     """K-TAG (smi_tagbam_*): the FASTQ text resident on the device as a table of read names, BAM segments tagged against it"""
+    _NAME = "tagbam"
 
     def __init__(self, ctx, fastq_text, read_tag="US", qv_tag=None, hash_bits=0):
-        self._lib = load_library()
         text = np.frombuffer(fastq_text, dtype=np.uint8) if not isinstance(fastq_text, np.ndarray) else fastq_text
         if text.dtype != np.uint8 or text.ndim != 1 or not text.flags.c_contiguous:
             raise ValueError("fastq_text: a contiguous 1-D uint8 array (or bytes)")
+        self._lib = load_library()
         cfg = TagBamConfig()
         self._lib.smi_tagbam_default_config(ctypes.byref(cfg))
-        cfg.read_tag = str(read_tag).encode()[:3]
+        for what, field, v in (("read", "read_tag", read_tag), ("QV", "qv_tag", qv_tag)):
+            if v is not None:
+                if len(str(v).encode()) != 2:
+                    raise SmiError(f"{what} tag must be two characters")
+                setattr(cfg, field, str(v).encode())
         cfg.with_qv = qv_tag is not None
-        if qv_tag is not None:
-            cfg.qv_tag = str(qv_tag).encode()[:3]
-        if len(str(read_tag).encode()) != 2:
-            raise SmiError("read tag must be two characters")
-        if qv_tag is not None and len(str(qv_tag).encode()) != 2:
-            raise SmiError("QV tag must be two characters")
         cfg.hash_bits = int(hash_bits)
-        self._h, self.errors = ctypes.c_void_p(), ctypes.c_uint32(0)
-        if self._lib.smi_tagbam_create(ctx._h, text.ctypes.data if text.size else None, text.size, ctypes.byref(cfg), ctypes.byref(self._h),
-                                       ctypes.byref(self.errors)):
-            raise SmiError(self._lib.smi_last_error().decode())
-        self._ctx = ctx                       # (the handle runs on the context's stream: keep the context alive)
+        self.errors = ctypes.c_uint32(0)
+        h = ctypes.c_void_p()
+        self._check(self._lib.smi_tagbam_create(ctx._h, text.ctypes.data if text.size else None, text.size, ctypes.byref(cfg), ctypes.byref(h),
+                                                ctypes.byref(self.errors)))
+        self._h, self._ctx = h, ctx           # (the handle runs on the context's stream: keep the context alive)
         n = ctypes.c_size_t(0)
         self._lib.smi_tagbam_records(self._h, ctypes.byref(n))
         self.n_records = n.value
@@ -627,38 +751,19 @@ class TagBam:
         """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it -> (output records as uint8 array, indices of
         the records whose name is not in the FASTQ, number of unmapped records dropped).  out: a uint8 array to write into when it is large
         enough (e.g. page-locked memory reused from call to call; a view of it is returned)"""
-        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
-            raise ValueError("bam: a contiguous 1-D uint8 array")
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != BAM_RECORD_DTYPE:
-            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
-        n = int(recs.size)
-        missing = np.zeros(max(n, 1), dtype=np.int32)
+        args, recs = self._segment_args(bam, recs)
+        missing = np.zeros(max(args[3], 1), dtype=np.int32)
         n_out, n_miss, n_unm = ctypes.c_size_t(0), ctypes.c_int32(0), ctypes.c_int32(0)
         if out is None:
             out = np.empty(max(64, 2 * bam.size), dtype=np.uint8)
-        while True:
-            rc = self._lib.smi_tagbam_segment(self._h, bam.ctypes.data if bam.size else None, bam.size, recs.ctypes.data if n else None, n,
-                                              out.ctypes.data, out.size, ctypes.byref(n_out), missing.ctypes.data, ctypes.byref(n_miss),
-                                              ctypes.byref(n_unm))
-            if rc == 0:
-                return out[:n_out.value], missing[:n_miss.value], n_unm.value
-            if rc != 1:
-                raise SmiError(self._lib.smi_last_error().decode())
-            out = np.empty(n_out.value + (n_out.value >> 3), dtype=np.uint8)     # the sized segment stays on the device: written by the next call
+        rc, out = self._grow(lambda o: self._lib.smi_tagbam_segment(self._h, *args, o.ctypes.data, o.size, ctypes.byref(n_out), missing.ctypes.data,
+                                                                     ctypes.byref(n_miss), ctypes.byref(n_unm)), out, n_out)
+        self._check(rc)
+        return out[:n_out.value], missing[:n_miss.value], n_unm.value
 
     def stage_ms(self):
         """{stage: device ms} of the last create (key, build) and the last segment (probe, size, assemble)"""
-        ms = np.zeros(len(TAGBAM_STAGES), dtype=np.float32)
-        self._lib.smi_tagbam_stage_ms(self._h, ms.ctypes.data)
-        return dict(zip(TAGBAM_STAGES, (float(x) for x in ms)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.smi_tagbam_free(self._h)
-            self._h = None
-
-    __del__ = close
+        return self._named("stage_ms", TAGBAM_STAGES, np.float32)
 
 
 class ConsensusConfig(ctypes.Structure):
@@ -675,65 +780,27 @@ CONSENSUS_COUNTS = ("records", "valid", "unvalid", "mapqv0", "no_gene", "no_umi"
 CONSENSUS_TAGS = ("cell_tag", "umi_tag", "gene_tag", "tso_end_tag", "polya_start_tag", "cdna_tag", "us_tag", "rn_tag")
 
 
-class Consensus:
+class Consensus(_Handle):
     """ComputeConsensus (smi_consensus_*): BAM segments in, the molecules' consensus FASTQ out.  Keywords: the fields of
     smi_consensus_config (tags as two-character strings, mapqv0 as a bool)."""
+    _NAME, _CONFIG, _TAGS, _COUNTS = "consensus", ConsensusConfig, CONSENSUS_TAGS, CONSENSUS_COUNTS
+    _INTS = ("max_clip", "mapqv0", "max_reads", "min_ps", "max_ps", "n_threads", "scratch_bytes")
 
     def __init__(self, ctx, **kw):
-        self._lib = load_library()
-        cfg = ConsensusConfig()
-        self._lib.smi_consensus_default_config(ctypes.byref(cfg))
-        for k, v in kw.items():
-            if k in CONSENSUS_TAGS:
-                b = str(v).encode()
-                if len(b) != 2:
-                    raise SmiError(f"{k}: a tag is two characters")
-                setattr(cfg, k, b)
-            elif k in ("max_clip", "mapqv0", "max_reads", "min_ps", "max_ps", "n_threads", "scratch_bytes"):
-                setattr(cfg, k, int(v))
-            else:
-                raise ValueError(f"unknown smi_consensus_config field {k!r}")
-        self._h = ctypes.c_void_p()
-        if self._lib.smi_consensus_create(ctx._h, ctypes.byref(cfg), ctypes.byref(self._h)):
-            self._h = None
-            raise SmiError(self._lib.smi_last_error().decode())
-        self._ctx = ctx
+        cfg = self._config(kw)
+        self._create(ctx, ctypes.byref(cfg))
         self.kernel_ms = 0.0
 
     def add_segment(self, bam, recs):
         """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
-        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
-            raise ValueError("bam: a contiguous 1-D uint8 array")
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != BAM_RECORD_DTYPE:
-            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
-        if self._lib.smi_consensus_add_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)):
-            raise SmiError(self._lib.smi_last_error().decode())
+        self._add_segment(bam, recs)
 
     def run(self):
         """molecules, read selection, K-POA -> the FASTQ as bytes"""
         ms = ctypes.c_float(0.0)
-        if self._lib.smi_consensus_run(self._h, ctypes.byref(ms)):
-            raise SmiError(self._lib.smi_last_error().decode())
+        self._check(self._lib.smi_consensus_run(self._h, ctypes.byref(ms)))
         self.kernel_ms = float(ms.value)
-        n = ctypes.c_size_t(0)
-        self._lib.smi_consensus_fastq(self._h, None, 0, ctypes.byref(n))
-        out = np.zeros(max(n.value, 1), dtype=np.uint8)
-        if self._lib.smi_consensus_fastq(self._h, _ptr(out), out.size, ctypes.byref(n)):
-            raise SmiError(self._lib.smi_last_error().decode())
-        return out[:n.value].tobytes()
-
-    def counts(self):
-        c = np.zeros(len(CONSENSUS_COUNTS), dtype=np.int64)
-        self._lib.smi_consensus_counts(self._h, _ptr(c))
-        return dict(zip(CONSENSUS_COUNTS, (int(x) for x in c)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.smi_consensus_free(self._h)
-            self._h = None
-
-    __del__ = close
+        return self._fetch(self._lib.smi_consensus_fastq, self._h).tobytes()
 
 
 class IsoformConfig(ctypes.Structure):
@@ -753,85 +820,34 @@ ISOFORM_OUTPUTS = ("isomatrix.txt", "isometrics.txt", "molinfos.txt", "genematri
 ISOFORM_TAGS = ("cell_tag", "umi_tag", "gene_tag", "rn_tag")
 
 
-class Isoform:
+class Isoform(_Handle):
     """IsoformMatrix (smi_isoform_*): the refFlat and cell-list texts, then BAM segments in; the output texts out.  Keywords: the fields
     of smi_isoform_config (tags as two-character strings, mapqv0 / to_bulk as bools)."""
+    _NAME, _CONFIG, _TAGS, _COUNTS, _OUTPUTS = "isoform", IsoformConfig, ISOFORM_TAGS, ISOFORM_COUNTS, ISOFORM_OUTPUTS
+    _INTS = ("max_clip", "mapqv0", "delta", "to_bulk", "n_threads", "lds_tx", "budget_bytes")
+    _STAGES = ("iso", "sort", "render")
 
     def __init__(self, ctx, refflat, csv, **kw):
-        self._lib = load_library()
-        cfg = IsoformConfig()
-        self._lib.smi_isoform_default_config(ctypes.byref(cfg))
-        for k, v in kw.items():
-            if k in ISOFORM_TAGS:
-                b = str(v).encode()
-                if len(b) != 2:
-                    raise SmiError(f"{k}: a tag is two characters")
-                setattr(cfg, k, b)
-            elif k in ("max_clip", "mapqv0", "delta", "to_bulk", "n_threads", "lds_tx", "budget_bytes"):
-                setattr(cfg, k, int(v))
-            else:
-                raise ValueError(f"unknown smi_isoform_config field {k!r}")
-        rf = np.frombuffer(bytes(refflat), dtype=np.uint8)
-        cs = np.frombuffer(bytes(csv), dtype=np.uint8)
-        self._h = ctypes.c_void_p()
-        if self._lib.smi_isoform_create(ctx._h, ctypes.byref(cfg), _ptr(rf) if rf.size else None, rf.size, _ptr(cs) if cs.size else None, cs.size,
-                                        ctypes.byref(self._h)):
-            self._h = None
-            raise SmiError(self._lib.smi_last_error().decode())
-        self._ctx = ctx
-        self.stage_ms = dict(iso=0.0, sort=0.0, render=0.0)
+        cfg = self._config(kw)
+        (rf, _a), (cs, _b) = self._text(refflat), self._text(csv)
+        self._create(ctx, ctypes.byref(cfg), *rf, *cs)
+        self.stage_ms = dict.fromkeys(self._STAGES, 0.0)
 
     def add_segment(self, bam, recs):
         """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
-        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
-            raise ValueError("bam: a contiguous 1-D uint8 array")
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != BAM_RECORD_DTYPE:
-            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
-        if self._lib.smi_isoform_add_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)):
-            raise SmiError(self._lib.smi_last_error().decode())
+        self._add_segment(bam, recs)
 
     def run(self):
         """reads, molecules, K-ISO, K-MTX -> {file name suffix: bytes} (the bulk files only with to_bulk)"""
-        ms = np.zeros(3, dtype=np.float32)
-        if self._lib.smi_isoform_run(self._h, _ptr(ms)):
-            raise SmiError(self._lib.smi_last_error().decode())
-        self.stage_ms = dict(iso=float(ms[0]), sort=float(ms[1]), render=float(ms[2]))
-        outs = {}
-        for i, name in enumerate(ISOFORM_OUTPUTS):
-            n = ctypes.c_size_t(0)
-            self._lib.smi_isoform_output(self._h, i, None, 0, ctypes.byref(n))
-            out = np.zeros(max(n.value, 1), dtype=np.uint8)
-            if self._lib.smi_isoform_output(self._h, i, _ptr(out), out.size, ctypes.byref(n)):
-                raise SmiError(self._lib.smi_last_error().decode())
-            outs[name] = out[:n.value].tobytes()
-        return outs
+        return self._run()
 
     def isobam(self, bam, recs):
         """ISOBAM after run(): the segment's records with IG / IT (inflated BAM record bytes, input order)"""
         recs = np.ascontiguousarray(recs)
         if recs.dtype != BAM_RECORD_DTYPE:
             raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
-        n = ctypes.c_size_t(0)
-        args = (self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size))
-        if self._lib.smi_isoform_isobam(*args, None, 0, ctypes.byref(n)):
-            raise SmiError(self._lib.smi_last_error().decode())
-        out = np.zeros(max(n.value, 1), dtype=np.uint8)
-        if self._lib.smi_isoform_isobam(*args, _ptr(out), out.size, ctypes.byref(n)):
-            raise SmiError(self._lib.smi_last_error().decode())
-        return out[:n.value]
-
-    def counts(self):
-        c = np.zeros(len(ISOFORM_COUNTS), dtype=np.int64)
-        self._lib.smi_isoform_counts(self._h, _ptr(c))
-        return dict(zip(ISOFORM_COUNTS, (int(x) for x in c)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.smi_isoform_free(self._h)
-            self._h = None
-
-    __del__ = close
+        return self._fetch(self._lib.smi_isoform_isobam, self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None,
+                           int(recs.size))
 
 
 class SnpConfig(ctypes.Structure):
@@ -847,82 +863,34 @@ SNP_COUNTS = ("records", "lines", "cells", "hits", "lowRN", "lowQV", "pairs", "k
 SNP_OUTPUTS = ("snpmatrix.txt", "snpmetrics.txt", "snpmolinfos.txt")
 
 
-class Snp:
+class Snp(_Handle):
     """SNPMatrix (smi_snp_*): the SNP and cell-list texts and the BAM's reference names, then BAM segments in; the output texts out.
     Keywords: the fields of smi_snp_config (tags as two-character strings)."""
+    _NAME, _CONFIG, _TAGS, _COUNTS, _OUTPUTS = "snp", SnpConfig, ISOFORM_TAGS, SNP_COUNTS, SNP_OUTPUTS
+    _INTS = ("max_clip", "min_rn", "min_qv", "n_threads", "budget_bytes")
+    _STAGES = ("snp", "sort", "render")
 
     def __init__(self, ctx, snp, csv, ref_names, **kw):
-        self._lib = load_library()
-        cfg = SnpConfig()
-        self._lib.smi_snp_default_config(ctypes.byref(cfg))
-        for k, v in kw.items():
-            if k in ISOFORM_TAGS:
-                b = str(v).encode()
-                if len(b) != 2:
-                    raise SmiError(f"{k}: a tag is two characters")
-                setattr(cfg, k, b)
-            elif k in ("max_clip", "min_rn", "min_qv", "n_threads", "budget_bytes"):
-                setattr(cfg, k, int(v))
-            else:
-                raise ValueError(f"unknown smi_snp_config field {k!r}")
-        sn = np.frombuffer(bytes(snp), dtype=np.uint8)
-        cs = np.frombuffer(bytes(csv), dtype=np.uint8)
-        names = [str(r).rstrip("\0").encode("latin-1") for r in ref_names]
-        arr = (ctypes.c_char_p * max(len(names), 1))(*names)
-        self._h = ctypes.c_void_p()
-        if self._lib.smi_snp_create(ctx._h, ctypes.byref(cfg), _ptr(sn) if sn.size else None, sn.size, _ptr(cs) if cs.size else None, cs.size,
-                                    arr, len(names), ctypes.byref(self._h)):
-            self._h = None
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-        self._ctx = ctx
-        self.stage_ms = dict(snp=0.0, sort=0.0, render=0.0)
+        cfg = self._config(kw)
+        (sn, _a), (cs, _b) = self._text(snp), self._text(csv)
+        self._create(ctx, ctypes.byref(cfg), *sn, *cs, *self._names(ref_names))
+        self.stage_ms = dict.fromkeys(self._STAGES, 0.0)
 
     def add_segment(self, bam, recs):
         """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
-        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
-            raise ValueError("bam: a contiguous 1-D uint8 array")
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != BAM_RECORD_DTYPE:
-            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
-        if self._lib.smi_snp_add_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._add_segment(bam, recs)
 
     def run(self):
         """rows, distinct UMIs, K-MTX -> {file name suffix: bytes}, all empty when there is no row"""
-        ms = np.zeros(3, dtype=np.float32)
-        if self._lib.smi_snp_run(self._h, _ptr(ms)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-        self.stage_ms = dict(snp=float(ms[0]), sort=float(ms[1]), render=float(ms[2]))
-        outs = {}
-        for i, name in enumerate(SNP_OUTPUTS):
-            n = ctypes.c_size_t(0)
-            self._lib.smi_snp_output(self._h, i, None, 0, ctypes.byref(n))
-            out = np.zeros(max(n.value, 1), dtype=np.uint8)
-            if self._lib.smi_snp_output(self._h, i, _ptr(out), out.size, ctypes.byref(n)):
-                raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-            outs[name] = out[:n.value].tobytes()
-        return outs
-
-    def counts(self):
-        c = np.zeros(len(SNP_COUNTS), dtype=np.int64)
-        self._lib.smi_snp_counts(self._h, _ptr(c))
-        return dict(zip(SNP_COUNTS, (int(x) for x in c)))
+        return self._run()
 
     def line_counts(self):
         """per line read from the SNP text: (hits, lowRN, lowQV), or (-1, -1, -1) for a line on a chromosome outside the BAM"""
         n = ctypes.c_size_t(0)
         self._lib.smi_snp_line_counts(self._h, None, 0, ctypes.byref(n))
         c = np.zeros((max(n.value, 1), 3), dtype=np.int64)
-        if self._lib.smi_snp_line_counts(self._h, _ptr(c), n.value, ctypes.byref(n)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._check(self._lib.smi_snp_line_counts(self._h, _ptr(c), n.value, ctypes.byref(n)))
         return c[:n.value]
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.smi_snp_free(self._h)
-            self._h = None
-
-    __del__ = close
 
 
 class CollapseConfig(ctypes.Structure):
@@ -944,130 +912,58 @@ COLLAPSE_VALIDATE_COUNTS = ("valid_isoforms", "valid_evidences", "gencode_valid"
                             "table_slots", "cage_references", "cage_entries", "polya_references", "polya_entries")
 
 
-class Collapse:
+class Collapse(_Handle):
     """CollapseModel (smi_collapse_*): the refFlat and cell-list texts and the BAM's reference names, then BAM segments in; the five output
     texts out.  Keywords: the fields of smi_collapse_config (tags as two-character strings).  A record the loader fails on raises SmiError;
     error_read then holds (read name, record index).  After run(), validate_begin / validate_segment / validate_end run the validator over
     CAGE, POLYA and the segments of SHORT, and validate_end returns the five texts with its results."""
+    _NAME, _CONFIG, _TAGS, _COUNTS, _OUTPUTS = "collapse", CollapseConfig, ISOFORM_TAGS + ("iso_tag",), COLLAPSE_COUNTS, COLLAPSE_OUTPUTS
+    _INTS = ("max_clip", "delta", "min_evidence", "rn_min", "n_threads", "lds_junc")
+    _STAGES = ("collapse", "colstat", "filter_class")
 
     def __init__(self, ctx, refflat, csv, ref_names, **kw):
-        self._lib = load_library()
-        cfg = CollapseConfig()
-        self._lib.smi_collapse_default_config(ctypes.byref(cfg))
-        for k, v in kw.items():
-            if k in ISOFORM_TAGS + ("iso_tag",):
-                b = str(v).encode()
-                if len(b) != 2:
-                    raise SmiError(f"{k}: a tag is two characters")
-                setattr(cfg, k, b)
-            elif k in ("max_clip", "delta", "min_evidence", "rn_min", "n_threads", "lds_junc"):
-                setattr(cfg, k, int(v))
-            else:
-                raise ValueError(f"unknown smi_collapse_config field {k!r}")
-        rf = np.frombuffer(bytes(refflat), dtype=np.uint8)
-        cs = np.frombuffer(bytes(csv), dtype=np.uint8)
-        self._h = ctypes.c_void_p()
-        if self._lib.smi_collapse_create(ctx._h, ctypes.byref(cfg), _ptr(rf) if rf.size else None, rf.size, _ptr(cs) if cs.size else None, cs.size,
-                                         ctypes.byref(self._h)):
-            self._h = None
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-        names = [str(r).rstrip("\0").encode("latin-1") for r in ref_names]
-        arr = (ctypes.c_char_p * max(len(names), 1))(*names)
-        if self._lib.smi_collapse_set_references(self._h, arr, len(names)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-        self._ctx = ctx
+        cfg = self._config(kw)
+        (rf, _a), (cs, _b) = self._text(refflat), self._text(csv)
+        self._create(ctx, ctypes.byref(cfg), *rf, *cs)
+        self._check(self._lib.smi_collapse_set_references(self._h, *self._names(ref_names)))
         self.error_read = None
-        self.stage_ms = dict(collapse=0.0, colstat=0.0, filter_class=0.0)
+        self.stage_ms = dict.fromkeys(self._STAGES, 0.0)
 
     def add_segment(self, bam, recs):
         """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
-        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
-            raise ValueError("bam: a contiguous 1-D uint8 array")
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != BAM_RECORD_DTYPE:
-            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
-        if self._lib.smi_collapse_add_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)):
-            msg = self._lib.smi_last_error().decode(errors="replace")
-            name = ctypes.create_string_buffer(256)
-            rec = ctypes.c_int64(-1)
-            self._lib.smi_collapse_error_read(self._h, name, 256, ctypes.byref(rec))
-            if rec.value >= 0:
-                self.error_read = (name.value.decode(errors="replace"), rec.value)
-            raise SmiError(msg)
+        self._add_segment_naming_read(bam, recs)
 
     def run(self):
         """K-COLLAPSE, K-COLSTAT, K-FILTER / K-CLASS -> {file name suffix: bytes}"""
-        ms = np.zeros(3, dtype=np.float32)
-        if self._lib.smi_collapse_run(self._h, _ptr(ms)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-        self.stage_ms = dict(collapse=float(ms[0]), colstat=float(ms[1]), filter_class=float(ms[2]))
-        return self._outputs()
-
-    def _outputs(self):
-        outs = {}
-        for i, name in enumerate(COLLAPSE_OUTPUTS):
-            n = ctypes.c_size_t(0)
-            self._lib.smi_collapse_output(self._h, i, None, 0, ctypes.byref(n))
-            out = np.zeros(max(n.value, 1), dtype=np.uint8)
-            if self._lib.smi_collapse_output(self._h, i, _ptr(out), out.size, ctypes.byref(n)):
-                raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-            outs[name] = out[:n.value].tobytes()
-        return outs
-
-    def counts(self):
-        c = np.zeros(len(COLLAPSE_COUNTS), dtype=np.int64)
-        self._lib.smi_collapse_counts(self._h, _ptr(c))
-        return dict(zip(COLLAPSE_COUNTS, (int(x) for x in c)))
+        return self._run()
 
     def validate_begin(self, cage, polya, short_ref_names, cage_co=50, polya_co=50, junc_co=1, table_log2=0):
         """after run(): the CAGE and POLYA texts, the @SQ names of SHORT and the three cut-offs of UCSCRefFlatParser.validator; the distances
         of every transcript and the device table of the novel junctions (table_log2: its size, for tests).  A BED line the reference's
         parser stops at raises SmiError naming it."""
-        cg = np.frombuffer(bytes(cage), dtype=np.uint8)
-        pa = np.frombuffer(bytes(polya), dtype=np.uint8)
-        names = [str(r).rstrip("\0").encode("latin-1") for r in short_ref_names]
-        arr = (ctypes.c_char_p * max(len(names), 1))(*names)
-        if self._lib.smi_collapse_validate_begin(self._h, _ptr(cg) if cg.size else None, cg.size, _ptr(pa) if pa.size else None, pa.size, arr,
-                                                 len(names), int(cage_co), int(polya_co), int(junc_co), int(table_log2)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        (cg, _a), (pa, _b) = self._text(cage), self._text(polya)
+        self._check(self._lib.smi_collapse_validate_begin(self._h, *cg, *pa, *self._names(short_ref_names), int(cage_co), int(polya_co), int(junc_co),
+                                                          int(table_log2)))
 
     def validate_segment(self, bam, recs):
         """one inflated segment of SHORT and the BAM_RECORD_DTYPE entries of the records in it: K-JSUP"""
-        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
-            raise ValueError("bam: a contiguous 1-D uint8 array")
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != BAM_RECORD_DTYPE:
-            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
-        if self._lib.smi_collapse_validate_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None,
-                                                   int(recs.size)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._add_segment(bam, recs, "validate_segment")
 
     def validate_end(self):
         """the supports back, the validator's fields per transcript -> {file name suffix: bytes}, validated"""
         ms = np.zeros(1, dtype=np.float32)
-        if self._lib.smi_collapse_validate_end(self._h, _ptr(ms)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._check(self._lib.smi_collapse_validate_end(self._h, _ptr(ms)))
         self.stage_ms["jsup"] = float(ms[0])
         return self._outputs()
 
     def validate_counts(self):
-        c = np.zeros(len(COLLAPSE_VALIDATE_COUNTS), dtype=np.int64)
-        self._lib.smi_collapse_validate_counts(self._h, _ptr(c))
-        return dict(zip(COLLAPSE_VALIDATE_COUNTS, (int(x) for x in c)))
+        return self._named("validate_counts", COLLAPSE_VALIDATE_COUNTS)
 
     def host_loop(self):
         """after run(): the reference's single-thread collapse() on the same arrays -> (seconds, records whose founder differs from K-COLLAPSE's)"""
         sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
-        if self._lib.smi_collapse_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._check(self._lib.smi_collapse_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)))
         return sec.value, bad.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.smi_collapse_free(self._h)
-            self._h = None
-
-    __del__ = close
 
 
 class FusionConfig(ctypes.Structure):
@@ -1083,77 +979,32 @@ FUSION_OUTPUTS = ("_fusmatrix.txt", "_fusmetrics.txt", "_fusmolinfos.txt")
 FUSION_STAGES = ("insert", "read", "mol", "genes", "mtx_sort", "mtx_render")
 
 
-class Fusion:
+class Fusion(_Handle):
     """FusionDetector (smi_fusion_*): the cell-list text, then BAM segments in; the three output texts out.  Keywords: the fields of
     smi_fusion_config.  A record the parser fails on raises SmiError; error_read then holds (read name, record index)."""
+    _NAME, _CONFIG, _COUNTS, _OUTPUTS, _STAGES = "fusion", FusionConfig, FUSION_COUNTS, FUSION_OUTPUTS, FUSION_STAGES
+    _INTS = ("table_log2", "n_threads", "budget_bytes")
 
     def __init__(self, ctx, csv, **kw):
-        self._lib = load_library()
-        cfg = FusionConfig()
-        self._lib.smi_fusion_default_config(ctypes.byref(cfg))
-        for k, v in kw.items():
-            if k not in ("table_log2", "n_threads", "budget_bytes"):
-                raise ValueError(f"unknown smi_fusion_config field {k!r}")
-            setattr(cfg, k, int(v))
-        cs = np.frombuffer(bytes(csv), dtype=np.uint8)
-        self._h = ctypes.c_void_p()
-        if self._lib.smi_fusion_create(ctx._h, ctypes.byref(cfg), _ptr(cs) if cs.size else None, cs.size, ctypes.byref(self._h)):
-            self._h = None
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-        self._ctx = ctx
+        cfg = self._config(kw)
+        cs, _a = self._text(csv)
+        self._create(ctx, ctypes.byref(cfg), *cs)
         self.error_read = None
         self.stage_ms = dict.fromkeys(FUSION_STAGES, 0.0)
 
     def add_segment(self, bam, recs):
         """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
-        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
-            raise ValueError("bam: a contiguous 1-D uint8 array")
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != BAM_RECORD_DTYPE:
-            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
-        if self._lib.smi_fusion_add_segment(self._h, _ptr(bam) if bam.size else None, bam.size, _ptr(recs) if recs.size else None, int(recs.size)):
-            msg = self._lib.smi_last_error().decode(errors="replace")
-            name = ctypes.create_string_buffer(256)
-            rec = ctypes.c_int64(-1)
-            self._lib.smi_fusion_error_read(self._h, name, 256, ctypes.byref(rec))
-            if rec.value >= 0:
-                self.error_read = (name.value.decode(errors="replace"), rec.value)
-            raise SmiError(msg)
+        self._add_segment_naming_read(bam, recs)
 
     def run(self):
         """K-FUS-INSERT, K-FUS-READ, K-FUS-MOL, K-FUS-GENES, K-MTX -> {file name suffix: bytes}"""
-        ms = np.zeros(len(FUSION_STAGES), dtype=np.float32)
-        if self._lib.smi_fusion_run(self._h, _ptr(ms)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-        self.stage_ms = dict(zip(FUSION_STAGES, (float(x) for x in ms)))
-        outs = {}
-        for i, name in enumerate(FUSION_OUTPUTS):
-            n = ctypes.c_size_t(0)
-            self._lib.smi_fusion_output(self._h, i, None, 0, ctypes.byref(n))
-            out = np.zeros(max(n.value, 1), dtype=np.uint8)
-            if self._lib.smi_fusion_output(self._h, i, _ptr(out), out.size, ctypes.byref(n)):
-                raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-            outs[name] = out[:n.value].tobytes()
-        return outs
-
-    def counts(self):
-        c = np.zeros(len(FUSION_COUNTS), dtype=np.int64)
-        self._lib.smi_fusion_counts(self._h, _ptr(c))
-        return dict(zip(FUSION_COUNTS, (int(x) for x in c)))
+        return self._run()
 
     def host_loop(self):
         """after run(): the reference's single-thread loops over the same pools -> (seconds, molecules that differ from the device's)"""
         sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
-        if self._lib.smi_fusion_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._check(self._lib.smi_fusion_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)))
         return sec.value, bad.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.smi_fusion_free(self._h)
-            self._h = None
-
-    __del__ = close
 
 
 class DedupConfig(ctypes.Structure):
@@ -1176,23 +1027,14 @@ class DedupError(SmiError):
         self.line = line
 
 
-class Dedup:
+class Dedup(_Handle):
     """DeduplicateMolecule (smi_dedup_*): the text in segments (pass 1), select, the same segments again (pass 2).
     Keywords: the fields of smi_dedup_config."""
+    _NAME, _CONFIG, _COUNTS, _INTS = "dedup", DedupConfig, DEDUP_COUNTS, ("fasta", "select", "hash_bits", "min_table_slots")
 
     def __init__(self, ctx, **kw):
-        self._lib = load_library()
-        cfg = DedupConfig()
-        self._lib.smi_dedup_default_config(ctypes.byref(cfg))
-        for k, v in kw.items():
-            if k not in ("fasta", "select", "hash_bits", "min_table_slots"):
-                raise ValueError(f"unknown smi_dedup_config field {k!r}")
-            setattr(cfg, k, int(v))
-        self._h = ctypes.c_void_p()
-        if self._lib.smi_dedup_create(ctx._h, ctypes.byref(cfg), ctypes.byref(self._h)):
-            self._h = None
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
-        self._ctx = ctx
+        cfg = self._config(kw)
+        self._create(ctx, ctypes.byref(cfg))
 
     @staticmethod
     def _bytes(text):
@@ -1204,46 +1046,33 @@ class Dedup:
         """-> bytes consumed; 0 without is_last: nothing was taken, come again with more bytes"""
         text = self._bytes(text)
         used = ctypes.c_size_t(0)
-        if self._lib.smi_dedup_add_segment(self._h, _ptr(text) if text.size else None, text.size, int(bool(is_last)), ctypes.byref(used)):
-            msg = self._lib.smi_last_error().decode(errors="replace")
+        try:
+            self._check(self._lib.smi_dedup_add_segment(self._h, _ptr(text) if text.size else None, text.size, int(bool(is_last)), ctypes.byref(used)))
+        except SmiError as e:
             line = ctypes.c_int64(0)
             self._lib.smi_dedup_error_line(self._h, ctypes.byref(line))
-            raise DedupError(msg, line.value) if line.value else SmiError(msg)
+            if line.value:
+                raise DedupError(str(e), line.value) from None
+            raise
         return used.value
 
     def select(self):
-        if self._lib.smi_dedup_select(self._h, None):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._check(self._lib.smi_dedup_select(self._h, None))
 
     def emit_segment(self, segment, text):
         """-> the segment's part of the output (bytes)"""
         text = self._bytes(text)
         n = ctypes.c_size_t(0)
-        if self._lib.smi_dedup_emit_segment(self._h, segment, None, 0, None, 0, ctypes.byref(n)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._check(self._lib.smi_dedup_emit_segment(self._h, segment, None, 0, None, 0, ctypes.byref(n)))   # (the size query takes no text)
         if n.value == 0:
             return b""
         out = np.empty(n.value, dtype=np.uint8)
-        if self._lib.smi_dedup_emit_segment(self._h, segment, _ptr(text) if text.size else None, text.size, _ptr(out), out.size, ctypes.byref(n)):
-            raise SmiError(self._lib.smi_last_error().decode(errors="replace"))
+        self._check(self._lib.smi_dedup_emit_segment(self._h, segment, _ptr(text) if text.size else None, text.size, _ptr(out), out.size,
+                                                     ctypes.byref(n)))
         return out[:n.value].tobytes()
 
-    def counts(self):
-        c = np.zeros(len(DEDUP_COUNTS), dtype=np.int64)
-        self._lib.smi_dedup_counts(self._h, _ptr(c))
-        return dict(zip(DEDUP_COUNTS, (int(x) for x in c)))
-
     def stage_ms(self):
-        ms = np.zeros(len(DEDUP_STAGES), dtype=np.float32)
-        self._lib.smi_dedup_stage_ms(self._h, _ptr(ms))
-        return dict(zip(DEDUP_STAGES, (float(x) for x in ms)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.smi_dedup_free(self._h)
-            self._h = None
-
-    __del__ = close
+        return self._named("stage_ms", DEDUP_STAGES, np.float32)
 
 
 class MolTagConfig(ctypes.Structure):
@@ -1268,72 +1097,35 @@ class MolTagError(SmiError):
         self.read, self.record = read, record
 
 
-class MolTag:
+class MolTag(_Handle):
     """AddBamMoleculeTags / AddGeneNameTag (smi_moltag_*): BAM segments rewritten with their attributes edited.  program: MOLTAG_MOLECULE or
     MOLTAG_GENE (then genes: a GeneTagger, kept alive by this object).  Keywords: the other fields of smi_moltag_config."""
+    _NAME, _CONFIG, _COUNTS = "moltag", MolTagConfig, MOLTAG_COUNTS
+    _TAGS = ("cell_tag", "umi_tag", "rn_tag", "gene_tag", "strand_tag", "function_tag")
+    _BOOLS = ("use_strand_info", "allow_multi_gene_reads")
+    _TAG_ERROR = "{k} {v!r} is not a two-character tag"
 
     def __init__(self, ctx, program, genes=None, **kw):
-        self._lib = load_library()
-        cfg = MolTagConfig()
-        if self._lib.smi_moltag_default_config(int(program), ctypes.byref(cfg)):
-            raise SmiError(self._lib.smi_last_error().decode())
-        for k, v in kw.items():
-            if k in ("use_strand_info", "allow_multi_gene_reads"):
-                setattr(cfg, k, int(bool(v)))
-            elif k in ("cell_tag", "umi_tag", "rn_tag", "gene_tag", "strand_tag", "function_tag"):
-                b = str(v).encode("latin-1")
-                if len(b) != 2:
-                    raise SmiError(f"{k} {v!r} is not a two-character tag")
-                setattr(cfg, k, b)
-            else:
-                raise ValueError(f"unknown smi_moltag_config field {k!r}")
-        self._h = ctypes.c_void_p()
-        self._genes, self._ctx = genes, ctx       # (the handle reads the model and runs on the context's stream: keep both alive)
-        if self._lib.smi_moltag_create(ctx._h, ctypes.byref(cfg), genes._h if genes is not None else None, ctypes.byref(self._h)):
-            self._h = None
-            raise SmiError(self._lib.smi_last_error().decode())
+        cfg = self._config(kw, int(program))
+        self._genes = genes                       # (the handle reads the model: keep it alive)
+        self._create(ctx, ctypes.byref(cfg), genes._h if genes is not None else None)
 
     def segment(self, bam, recs, out=None):
         """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it -> every record as written (uint8 array)"""
-        if not isinstance(bam, np.ndarray) or bam.dtype != np.uint8 or bam.ndim != 1 or not bam.flags.c_contiguous:
-            raise ValueError("bam: a contiguous 1-D uint8 array")
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != BAM_RECORD_DTYPE:
-            raise ValueError("recs: BAM_RECORD_DTYPE entries (bam_index_records)")
-        n = int(recs.size)
+        args, recs = self._segment_args(bam, recs)
         n_out = ctypes.c_size_t(0)
         if out is None:
-            out = np.empty(max(64, bam.size + 64 * n), dtype=np.uint8)
-        while True:
-            rc = self._lib.smi_moltag_segment(self._h, bam.ctypes.data if bam.size else None, bam.size, recs.ctypes.data if n else None, n,
-                                              out.ctypes.data, out.size, ctypes.byref(n_out))
-            if rc == 0:
-                return out[:n_out.value]
+            out = np.empty(max(64, bam.size + 64 * args[3]), dtype=np.uint8)
+        rc, out = self._grow(lambda o: self._lib.smi_moltag_segment(self._h, *args, o.ctypes.data, o.size, ctypes.byref(n_out)), out, n_out)
+        if rc == 2:
             msg = self._lib.smi_last_error().decode(errors="replace")
-            if rc == 2:
-                name, rec = ctypes.create_string_buffer(256), ctypes.c_int64(-1)
-                self._lib.smi_moltag_error_read(self._h, name, 256, ctypes.byref(rec))
-                raise MolTagError(msg, name.value.decode("latin-1"), rec.value)
-            if rc != 1:
-                raise SmiError(msg)
-            out = np.empty(n_out.value + (n_out.value >> 3), dtype=np.uint8)     # the sized segment stays on the device: written by the next call
-
-    def counts(self):
-        c = np.zeros(len(MOLTAG_COUNTS), dtype=np.int64)
-        self._lib.smi_moltag_counts(self._h, _ptr(c))
-        return dict(zip(MOLTAG_COUNTS, (int(x) for x in c)))
+            name, rec = self._error_read()
+            raise MolTagError(msg, name.decode("latin-1"), rec)
+        self._check(rc)
+        return out[:n_out.value]
 
     def stage_ms(self):
-        ms = np.zeros(len(MOLTAG_STAGES), dtype=np.float32)
-        self._lib.smi_moltag_stage_ms(self._h, _ptr(ms))
-        return dict(zip(MOLTAG_STAGES, (float(x) for x in ms)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.smi_moltag_free(self._h)
-            self._h = None
-
-    __del__ = close
+        return self._named("stage_ms", MOLTAG_STAGES, np.float32)
 
 
 # smi_poa_batch_ex's statistics, in SMI_POA_STAT_* order

@@ -5,7 +5,7 @@ GE / GS / XF from a refFlat gene model.
     java -jar Sicelore-2.1.jar AddBamMoleculeTags -I molecules.bam -O molecules.tags.bam [-CELLTAG BC] [-UMITAG U8] [-RNTAG RN]
     java -jar Sicelore-2.1.jar AddGeneNameTag -I molecules.tags.bam -O molecules.tags.GE.bam -REFFLAT genes.refFlat [-GENETAG GE] ...
 
-The BAM is read in segments (isoformmatrix._segments); K-NAME / K-GENE decide the edits of a segment and K-EDIT writes its records
+The BAM is read in segments (bamsegments.segments); K-NAME / K-GENE decide the edits of a segment and K-EDIT writes its records
 (smi_moltag_segment), which are deflated on the device into BGZF blocks and followed by the EOF block, as ISOBAM is written.  The output
 goes to a temporary file beside OUTPUT that takes OUTPUT's name once the last segment is written: a record on which the reference's loop
 dies raises lib.MolTagError and leaves no file."""
@@ -15,7 +15,8 @@ import time
 import numpy as np
 
 from . import lib as _lib
-from .isoformmatrix import BGZF_EOF, _segments, isobam_header
+from .bamsegments import BGZF_EOF, segments
+from .isoformmatrix import isobam_header
 
 
 def _rewrite(ctx, h, in_bam, out_bam, header, segment_bytes, n_threads):
@@ -34,7 +35,7 @@ def _rewrite(ctx, h, in_bam, out_bam, header, segment_bytes, n_threads):
                 secs["deflate"] += t1 - t0
                 secs["write"] += time.perf_counter() - t1
                 return len(z) - 28
-            for bam, recs, hdr in _segments(in_bam, segment_bytes, n_threads):
+            for bam, recs, hdr in segments(in_bam, segment_bytes, n_threads):
                 if hdr is not None:
                     written += emit(header(hdr))
                 if recs.size:

@@ -4,7 +4,7 @@ by cell"): the cell x SNP / editing-site matrix of a molecule BAM.
     java -jar Sicelore-2.1.jar SNPMatrix I=molecules.GE.tags.bam MINRN=0 MINQV=0 CSV=barcodes.csv SNP=snps.csv O=. PREFIX=snp
 
 The BAM is read once in segments of about segment_bytes compressed bytes, inflated one segment ahead by a reader thread
-(isoformmatrix._segments); K-SNP evaluates every site line against every record of a segment on the device (smi_snp_add_segment), so no
+(bamsegments.segments); K-SNP evaluates every site line against every record of a segment on the device (smi_snp_add_segment), so no
 .bai is needed and the input need not be sorted; the distinct UMIs per (row, cell) are counted and the dense matrix is rendered on the
 device (smi_snp_run).  Rows and cells are in byte order, molinfos in SNP-file line order, then BAM record order.
 PREFIX_snpmatrix.txt, PREFIX_snpmetrics.txt and PREFIX_snpmolinfos.txt are written only when at least one row exists."""
@@ -13,7 +13,7 @@ import re
 import time
 
 from . import lib as _lib
-from .isoformmatrix import _segments
+from .bamsegments import segments
 
 NOTHING = ("end of processing...\tnothing has been detected, check your input parameters (if Illumina set CELLBC=CB UMITAG=UB), "
            "no output files generated\t")
@@ -43,7 +43,7 @@ def snp_matrix(ctx, in_bam, csv, snp, outdir, prefix="snp", min_rn=0, min_qv=0, 
     h = None
     t0 = time.perf_counter()
     try:
-        for bam, recs, hdr in _segments(in_bam, segment_bytes, n_threads):
+        for bam, recs, hdr in segments(in_bam, segment_bytes, n_threads):
             if hdr is not None:                       # the @SQ dictionary comes with the first segment
                 _text, refs, _start = _lib.bam_header(bam)
                 h = _lib.Snp(ctx, snp_text, cs, [r[0] for r in refs], min_rn=min_rn, min_qv=min_qv, n_threads=n_threads, **cfg)

@@ -4,20 +4,17 @@ a reference gets its read's bases (and qualities) from the FASTQ as Z attributes
     java -jar NanoporeBC_UMI_finder-2.1.jar tagbamwithread --inFastq <fastq[.gz]> --inBam <bam> --outBam <bam> --readTag US [--qvTag QS]
 
 The FASTQ is inflated on the host (plain or multi-member gzip, as pigz writes it) and stays on the device as K-TAG's table of read names
-(smi_tagbam_create); the BAM is read in segments of about segment_bytes compressed bytes, inflated one segment ahead by a reader thread,
+(smi_tagbam_create); the BAM is read in segments of about segment_bytes compressed bytes (bamsegments.segments),
 each segment's records tagged on the device (smi_tagbam_segment) and BGZF-deflated (on the device, or with zlib-level host threads) into
 the output behind the input's header.  Records without a reference are dropped; a record whose read is not in the FASTQ is reported on
 stderr and dropped, and the run goes on (L96-101).  No .bai is written (main.nf:117 runs `samtools index` right after)."""
-import queue
 import sys
-import threading
 import time
 
 import numpy as np
 
 from . import lib as _lib
-
-BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+from .bamsegments import BGZF_EOF, segments
 
 
 def miss_message(name):
@@ -54,30 +51,7 @@ def tag_bam_with_reads(ctx, in_fastq, in_bam, out_bam, read_tag, qv_tag=None, se
     first = table.stage_ms()
     stage_ms["key"], stage_ms["build"] = first["key"], first["build"]
 
-    segments = queue.Queue(maxsize=1)
-
-    def reader():
-        try:
-            with open(in_bam, "rb") as f:
-                tail = np.zeros(0, dtype=np.uint8)
-                while True:
-                    t1 = time.perf_counter()
-                    raw = np.fromfile(f, dtype=np.uint8, count=int(segment_bytes))
-                    last = raw.size < int(segment_bytes)
-                    comp = np.concatenate([tail, raw]) if tail.size else raw
-                    buf, used = _lib.bgzf_inflate(comp, n_threads=n_threads) if comp.size else (np.zeros(0, dtype=np.uint8), 0)
-                    tail = comp[used:].copy()
-                    if last and tail.size:
-                        raise _lib.SmiError(f"{in_bam}: truncated BGZF stream")
-                    segments.put((buf, last, None, time.perf_counter() - t1))
-                    if last:
-                        return
-        except BaseException as e:  # noqa: BLE001 -- handed to the consumer
-            segments.put((None, True, e, 0.0))
-
     n_in = n_written = n_unmapped = n_missing = 0
-    pend = np.zeros(0, dtype=np.uint8)
-    header = None
     stage = None
     fh = open(out_bam, "wb")
     try:
@@ -91,30 +65,9 @@ def tag_bam_with_reads(ctx, in_fastq, in_bam, out_bam, read_tag, qv_tag=None, se
                 fh.write(memoryview(z[:-28]))       # without the end-of-file block: more follows
             secs["bgzf_write"] += time.perf_counter() - t1
 
-        threading.Thread(target=reader, daemon=True).start()
-        eof = False
-        while not eof:
-            buf, eof, e, dt = segments.get()
-            if e is not None:
-                raise e
-            secs["bam_read_inflate"] += dt
-            bam = np.concatenate([pend, buf]) if pend.size else buf
-            start = 0
-            if header is None:
-                try:
-                    _text, _refs, start = _lib.bam_header(bam)
-                except _lib.SmiError:
-                    if eof:
-                        raise
-                    pend = bam                    # the header is not complete yet: read on
-                    continue
-                header = bam[:start].copy()
-                emit(header)                      # the input's header bytes, as assignumis copies them (BamWriter L32-48)
-            t1 = time.perf_counter()
-            recs, end = _lib.bam_index_records(bam, start, cap=max(1, (bam.size - start) // 36))
-            if eof and end != bam.size:
-                raise _lib.SmiError(f"{in_bam}: truncated BAM record")
-            secs["index"] += time.perf_counter() - t1
+        for bam, recs, hdr in segments(in_bam, segment_bytes, n_threads, secs):
+            if hdr is not None:
+                emit(np.frombuffer(hdr, dtype=np.uint8))  # the input's header bytes, as assignumis copies them (BamWriter L32-48)
             if recs.size:
                 t1 = time.perf_counter()
                 if stage is None or stage.array.size < 2 * bam.size:
@@ -134,9 +87,6 @@ def tag_bam_with_reads(ctx, in_fastq, in_bam, out_bam, read_tag, qv_tag=None, se
                 n_written += int(recs.size) - int(missing.size) - int(unmapped)
                 secs["tag"] += time.perf_counter() - t1
                 emit(out)
-            pend = bam[end:].copy()
-        if header is None:
-            raise _lib.SmiError(f"{in_bam}: no BAM header")
         fh.write(BGZF_EOF)
     finally:
         fh.close()

@@ -158,7 +158,9 @@ def select(by_gene, gene, tx):
 
 
 def cell_list(text):
-    """CellList: every line with "-1" removed, as a sorted list of distinct cells"""
+    """CellList: every line with "-1" removed, as a sorted list of distinct cells (an empty text has no line)"""
+    if text == "":
+        return []
     return sorted(set(line.replace("-1", "") for line in re.split("\r\n|\r|\n", text)[:-1 if re.search("(\r\n|\r|\n)$", text) else None]))
 
 

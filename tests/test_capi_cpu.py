@@ -154,3 +154,91 @@ def test_size_t_return_is_not_truncated(built):
     big = lib.smi_read_planes_words(1 << 36, 1)
     assert big >= (1 << 36) // 8 and big > 2 ** 31
     assert libmod.EXPORTS.count("smi_read_planes_words") == 1
+
+
+# the eight per-program handles: (class, C struct, counters / outputs / stages macro -> the tuple lib.py hands the library a buffer for)
+def _handles(libmod):
+    m = libmod
+    return [
+        (m.TagBam, "smi_tagbam_config", m.TagBamConfig, dict(SMI_TAGBAM_STAGES=m.TAGBAM_STAGES)),
+        (m.Consensus, "smi_consensus_config", m.ConsensusConfig, dict(SMI_CONSENSUS_COUNTS=m.CONSENSUS_COUNTS)),
+        (m.Isoform, "smi_isoform_config", m.IsoformConfig,
+         dict(SMI_ISOFORM_COUNTS=m.ISOFORM_COUNTS, SMI_ISOFORM_OUTPUTS=m.ISOFORM_OUTPUTS, SMI_ISOFORM_STAGES=m.Isoform._STAGES)),
+        (m.Snp, "smi_snp_config", m.SnpConfig, dict(SMI_SNP_COUNTS=m.SNP_COUNTS, SMI_SNP_OUTPUTS=m.SNP_OUTPUTS, SMI_SNP_STAGES=m.Snp._STAGES)),
+        (m.Dedup, "smi_dedup_config", m.DedupConfig, dict(SMI_DEDUP_COUNTS=m.DEDUP_COUNTS, SMI_DEDUP_STAGES=m.DEDUP_STAGES)),
+        (m.MolTag, "smi_moltag_config", m.MolTagConfig, dict(SMI_MOLTAG_COUNTS=m.MOLTAG_COUNTS, SMI_MOLTAG_STAGES=m.MOLTAG_STAGES)),
+        (m.Collapse, "smi_collapse_config", m.CollapseConfig,
+         dict(SMI_COLLAPSE_COUNTS=m.COLLAPSE_COUNTS, SMI_COLLAPSE_OUTPUTS=m.COLLAPSE_OUTPUTS, SMI_COLLAPSE_STAGES=m.Collapse._STAGES,
+              SMI_COLLAPSE_VALIDATE_COUNTS=m.COLLAPSE_VALIDATE_COUNTS)),
+        (m.Fusion, "smi_fusion_config", m.FusionConfig,
+         dict(SMI_FUSION_COUNTS=m.FUSION_COUNTS, SMI_FUSION_OUTPUTS=m.FUSION_OUTPUTS, SMI_FUSION_STAGES=m.FUSION_STAGES)),
+    ]
+
+
+def test_handle_configs_and_name_tuples_match_the_header(pkg, tmp_path):
+    """counts() and stage_ms() hand the library a buffer of len(tuple) values and the library writes SMI_X_COUNTS / _STAGES of them; the
+    eight ctypes config structures mirror the header's by hand: sizeof, every offsetof and every macro, compiled from the header"""
+    from sicelore_amd import lib as libmod
+
+    exprs, want = [], []
+    for _cls, cname, cfg, macros in _handles(libmod):
+        exprs.append(f"sizeof({cname})")
+        want.append(ctypes.sizeof(cfg))
+        for field, _type in cfg._fields_:
+            exprs.append(f"offsetof({cname},{field})")
+            want.append(getattr(cfg, field).offset)
+            exprs.append(f"sizeof((({cname}*)0)->{field})")
+            want.append(getattr(cfg, field).size)
+        for macro, names in macros.items():
+            exprs.append(macro)
+            want.append(len(names))
+            assert len(set(names)) == len(names)
+    # every such macro of the header is compared (a new one must be added to _handles)
+    declared = set(re.findall(r"#define (SMI_\w*(?:COUNTS|OUTPUTS|STAGES))\b", open(HEADER).read()))
+    assert declared == {k for h in _handles(libmod) for k in h[3]}
+    src = tmp_path / "cfg.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sicelore_mi.h"\nint main(){\n' +
+                   "".join(f'printf("%zu\\n",(size_t)({e}));\n' for e in exprs) + "return 0;}\n")
+    exe = tmp_path / "cfg"
+    subprocess.check_call(["gcc", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert len(got) == len(want)
+    assert [(e, g) for e, g, w in zip(exprs, got, want) if g != w] == []
+
+
+def test_handle_config_from_keywords(built):
+    """smi_*_default_config needs no GPU: the defaults come through, each keyword lands in its field and in no other, an unknown keyword
+    is a ValueError, a tag of one or of three characters (and one that is not ASCII) an SmiError"""
+    from sicelore_amd import lib as libmod
+
+    lib = built.load_library()
+
+    def values(cfg):
+        return {f: getattr(cfg, f) for f, _t in cfg._fields_}
+
+    for cls, cname, cfg_type, _macros in _handles(libmod):
+        if cls is libmod.TagBam:                      # (positional arguments and with_qv: its constructor sets the two tags itself)
+            continue
+        args = (libmod.MOLTAG_GENE,) if cls is libmod.MolTag else ()
+        default = cfg_type()
+        assert getattr(lib, f"smi_{cls._NAME}_default_config")(*args, ctypes.byref(default)) == 0
+        assert values(cls.__new__(cls)._config({}, *args)) == values(default) and any(values(default).values())
+        fields = [f for f, _t in cfg_type._fields_ if f not in ("reserved", "program")]
+        assert sorted(fields) == sorted(cls._TAGS + cls._INTS + cls._BOOLS), cname
+        for i, f in enumerate(fields):
+            v, want = ("Zq", b"Zq") if f in cls._TAGS else (True, 1) if f in cls._BOOLS else (1000 + i, 1000 + i)
+            got = values(cls.__new__(cls)._config({f: v}, *args))
+            assert got == dict(values(default), **{f: want}), (cname, f)
+        with pytest.raises(ValueError, match=f"unknown smi_{cls._NAME}_config field 'no_such_field'"):
+            cls.__new__(cls)._config(dict(no_such_field=1), *args)
+        for f in cls._TAGS:
+            for bad in ("Z", "Zqx", "", "éq"):
+                with pytest.raises(libmod.SmiError):
+                    cls.__new__(cls)._config({f: bad}, *args)
+    for kw in (dict(read_tag="U"), dict(read_tag="USX"), dict(read_tag="US", qv_tag="Q"), dict(read_tag="US", qv_tag="QSX")):
+        with pytest.raises(libmod.SmiError, match="(read|QV) tag must be two characters"):
+            libmod.TagBam(None, b"", **kw)                  # (refused before the context is looked at)
+    with pytest.raises(libmod.SmiError, match="cell_tag: a tag is two characters"):
+        libmod.Consensus.__new__(libmod.Consensus)._config(dict(cell_tag="B"))
+    with pytest.raises(libmod.SmiError, match="gene_tag 'GEN' is not a two-character tag"):
+        libmod.MolTag.__new__(libmod.MolTag)._config(dict(gene_tag="GEN"), libmod.MOLTAG_GENE)

@@ -806,6 +806,7 @@ def leg_validator(pkg, synth, ctx, dev, wl, used, res):
     import tempfile
 
     iso = importlib.import_module(graft.PKG_NAME + ".isoformmatrix")
+    segments = importlib.import_module(graft.PKG_NAME + ".bamsegments").segments
     lib = importlib.import_module(graft.PKG_NAME + ".lib")
     n_genes = int(os.environ.get("SMI_MB_VAL_GENES", "20000"))
     n_recs = int(os.environ.get("SMI_MB_VAL_RECS", "2000000"))
@@ -826,7 +827,7 @@ def leg_validator(pkg, synth, ctx, dev, wl, used, res):
         iso.isoform_matrix(ctx, os.path.join(d, "in.bam"), os.path.join(d, "r.refFlat"), os.path.join(d, "c.csv"), d, n_threads=16, isobam=True)
         print("validator: ISOBAM written", file=sys.stderr, flush=True)
         t0 = time.perf_counter()
-        for bam, recs, hdr in iso._segments(os.path.join(d, "sicelore_isobam.bam"), 256 << 20, 16):
+        for bam, recs, hdr in segments(os.path.join(d, "sicelore_isobam.bam"), 256 << 20, 16):
             if hdr is not None:
                 h = lib.Collapse(ctx, ref.encode(), csv.encode(), [r[0] for r in lib.bam_header(bam)[1]], n_threads=16)
             if recs.size:
@@ -847,7 +848,7 @@ def leg_validator(pkg, synth, ctx, dev, wl, used, res):
         sec = dict(inflate_index_wait=0.0, upload_kernel=0.0, begin=0.0, end_render=0.0)
         inflated = 0
         t_all = t0 = time.perf_counter()
-        for bam, recs, hdr in iso._segments(os.path.join(d, "short.bam"), seg_bytes, 16):
+        for bam, recs, hdr in segments(os.path.join(d, "short.bam"), seg_bytes, 16):
             sec["inflate_index_wait"] += time.perf_counter() - t0
             if hdr is not None:
                 t0 = time.perf_counter()

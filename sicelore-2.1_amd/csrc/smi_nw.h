@@ -106,6 +106,9 @@ __device__ __forceinline__ int nw_kth_bit(W x, int k) {
 }
 // float sum of the reference's end-of-read error weights: k12 times (float)((double)e + 1.2), then k10 times e + 1.0f (the x-columns that
 // lie over the first two read bases come first on the way back, countIndelsMismatchesEndOfRead L109-123)
+// (A table of these sums, indexed by the two counts, was measured in place of the loop -- NOTES R6.28: SQ_INSTS_VALU per wave of the step's kernel
+// 3,838.6 with the loop, 3,839.2 with the table: its index, bounds test and load are as many instructions as the turns the loop takes in a tie.
+// Not kept.)
 __device__ __forceinline__ float nw_end_errors(int k12, int k10) {
     float e = 0.0f;
     for (int i = 0; i < k12; i++) e = (float)((double)e + 1.2);

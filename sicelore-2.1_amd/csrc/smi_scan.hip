@@ -43,6 +43,9 @@ constexpr int kBlock = 256;
 #ifndef SMI_SCAN_GENERIC_FULL
 #define SMI_SCAN_GENERIC_FULL 0
 #endif
+#ifndef SMI_SCAN_FINDER_TAIL_LOOPS
+#define SMI_SCAN_FINDER_TAIL_LOOPS 0  // 1: find_polyt_bits extends, walks back and steps forward in loops again (see "the tail as mask operations"), for counter runs
+#endif
 #ifndef SMI_SCAN_GENERIC_WAVES
 #define SMI_SCAN_GENERIC_WAVES 3  // (four: 128 registers with 17 spilled values -- not in this kernel, see above; 4.78 instead of 5.47 ms per 10 M reads)
 #endif
@@ -219,7 +222,8 @@ __device__ __forceinline__ uint64_t mask64(const uint64_t *m, int tid, int p) {
 //   >= 12 / >= 10 masks  read one position further on (pos + 1)   the same words, and position kFinderMaxWindow alone: bit 0 of the next word,
 //                                                                  which is one popcount of the exact-T bits [window, window + 15)
 //   five-counts c5       at q, q + 5, q + 10 for q < window       one more word, of which bits 0 .. 9 are read: they need T bits 0 .. 13 of that word only
-//   walk back            endpos = start + 14 <= window + 13        words 0 .. kFinderBackWords - 1
+//   walk back            endpos = start + 14 <= window + 13        words 0 .. kFinderBackWords - 1 (the tail as loops, SMI_SCAN_FINDER_TAIL_LOOPS; the
+//                                                                  tail as mask operations reads the exact-T bits it needs from the planes)
 // (the forward steps behind the walk back go on to n - 1 = window + 24 through get64 on the planes, which reads all seven words)
 // smi_scan_device accepts window + polya_len + 10 <= 175 only, i.e. windows up to 150 for the 15-base polyT this finder is built for: the part of
 // these words that serves windows 151 .. 160 (the top ten bits of the fifth position word and the popcount for position 160) is reached by no
@@ -292,6 +296,96 @@ __device__ __forceinline__ bool find_polyt_bits(const uint32_t *planes, uint64_t
 #pragma unroll
     for (int q = 0; q < 3; q++) go_lds[q * kBlock + tid] = ((uint64_t)gom[2 * q + 1] << 32) | gom[2 * q];
     if (first < 0) return false;
+#ifdef SMI_MEASURE
+    if (SMI_ABLATED(32)) {  // timing only: the front alone
+        begin1 = first + 1;
+        end1 = first + ML;
+        return true;
+    }
+#endif
+#if !SMI_SCAN_FINDER_TAIL_LOOPS
+    // ---- the tail as mask operations ---------------------------------------------------------------------------------------------------------
+    // Until here nothing loops; the tail used to (the variant below): eight `while (go(start + s)) start += s`, a walk back over six word masks
+    // built for every end, three forward loops -- loops over the lane's own data whose trip count is the wave's worst lane's (17 evaluations
+    // of go per wave on the bench generator's reads, tools/scan_finder_model.py).
+    //   Extension.  Stride s advances `start` by s times the number of consecutive set probes G[start + s], G[start + 2 s], ...: with nw = ~G
+    // from `start` on in a 64-bit register and M_s = the bits s, 2 s, 3 s, ... < 64 (a constant), the first failing probe is the lowest bit of
+    // z = nw & M_s and the advance is ctz(z) - s.  nw is shifted down by the advance, which shifts zeros = "passes" in at the top, so z == 0
+    // says "every probe the register still holds passed": then, and only then, the lane refills the register at `start` (a register that was
+    // taken at `start` and is exhausted moves on by the probes it covered first) and asks the same stride again -- correct for any mask, and it
+    // terminates because G ends at `window`.  The greedy order of the strides and a stride's jump over holes of G (PolyATSearcher.java:L223-230)
+    // are kept as they are: each stride tests exactly the probes the loop tested.  Stride 20 is where the long advances happen (a register taken
+    // at `first` alone is exhausted by 23 % of the ends with a polyT on the generator's reads, and every wave has such an end), so it has a
+    // register of its own and the other seven share one taken at the `start` it leaves: on the generator's reads no wave takes a slow path then
+    // (profiles/scan_finder/finder_model.json).
+    int start = first;
+    {
+        // stride 20: the register is taken at first + 20, so that it holds four probes (bits 0, 20, 40, 60) where one taken at `first` holds three
+        uint64_t nw = ~mask64(go_lds, tid, first + 20);
+        constexpr uint64_t kFour20 = 1ull | (1ull << 20) | (1ull << 40) | (1ull << 60);
+        uint64_t z20 = nw & kFour20;
+        while (z20 == 0) {  // slow: an advance of 80 and more
+            start += 80;
+            nw = ~mask64(go_lds, tid, start + 20);
+            z20 = nw & kFour20;
+        }
+        start += __builtin_ctzll(z20);
+        int gbase = start;
+        nw = ~mask64(go_lds, tid, start);
+        const int INC[8] = {20, 15, 10, 5, 4, 3, 2, 1};  // L223-230
+#pragma unroll
+        for (int k = 1; k < 8; k++) {
+            const int s = INC[k];
+            uint64_t ms = 0;
+#pragma unroll
+            for (int b = s; b < 64; b += s) ms |= 1ull << b;
+            uint64_t z = nw & ms;
+            while (z == 0) {  // slow: every probe in the register passed
+                if (gbase == start) start += s * (63 / s);
+                gbase = start;
+                nw = ~mask64(go_lds, tid, start);
+                z = nw & ms;
+            }
+            const int adv = __builtin_ctzll(z) - s;
+            start += adv;
+            nw >>= adv;
+        }
+    }
+    // Walk back and forward steps: the exact-T bits through ONE 64-bit window round endpos = start + 14, kFinderBackBelow positions below it for
+    // the walk back (5 on average, 11 at most on the generator's reads) and 23 above it for the forward steps.  back(e) needs T[e - 4 .. e], so the
+    // window decides the positions from its fifth on (from position 5 on when it begins at 0: positions 0 .. 4 never pass); no back position
+    // among those sends the lane to the loop of find_polyt from the first undecided position down.
+    constexpr int kFinderBackBelow = 40;
+    const uint32_t *t_plane = planes + 3 * kLdsWords * kBlock;
+    int endpos = start + ML - 1;  // L231
+    int wbase = max(endpos - kFinderBackBelow, 0);
+    uint64_t wbits = get64(t_plane, tid, wbase) & ~get64(planes, tid, wbase);
+    {
+        // lambda$findpolyAT$3 L122-142: the last position <= endpos (and > 4) that passes; 4 when there is none
+        const uint64_t l1 = wbits << 1, l2 = wbits << 2, l3 = wbits << 3, l4 = wbits << 4;
+        uint64_t back = wbits & l1 & ((l2 & l3) | (l4 & (l2 ^ l3)));
+        back &= ((2ull << (endpos - wbase)) - 1ull) & (wbase ? ~15ull : ~31ull);
+        if (back) {
+            endpos = wbase + 63 - __builtin_clzll(back);
+        } else {
+            int e = wbase ? wbase + 3 : 4;
+            while (e > 4) {  // slow: not decided by the window
+                const uint32_t x = get32_t(planes, tid, e - 4);  // bit i = base e - 4 + i
+                if (((x >> 4) & 1u) && __popc((x >> 3) & 3u) >= 2 && __popc((x >> 1) & 15u) >= 3 && __popc(x & 31u) >= 4) break;
+                e--;
+            }
+            endpos = e;
+        }
+    }
+    auto look = [&](int p) -> uint32_t {  // exact-T bits from position p on, five of them at least (a forward step reads no more)
+        if (p < wbase || p + 5 > wbase + 64) {  // slow: the steps left the window
+            wbase = p;
+            wbits = get64(t_plane, tid, p) & ~get64(planes, tid, p);
+        }
+        return (uint32_t)(wbits >> (p - wbase));
+    };
+#else
+    // -DSMI_SCAN_FINDER_TAIL_LOOPS=1 (make VARIANT=finderloops EXTRA=-DSMI_SCAN_FINDER_TAIL_LOOPS=1): the tail as loops, for counter runs -- same results
     int start = first;
     {
         int wbase = first;
@@ -342,6 +436,7 @@ __device__ __forceinline__ bool find_polyt_bits(const uint32_t *planes, uint64_t
     };
     wbase = endpos + 1;
     wbits = get64(planes + 3 * kLdsWords * kBlock, tid, wbase) & ~get64(planes, tid, wbase);
+#endif
     while (n > endpos + 6 && __popc(look(endpos + 1) & 31u) > 3) endpos += 5;  // L145-147
     while (n > endpos + 4 && __popc(look(endpos + 1) & 7u) > 1) endpos += 3;   // L156-158
     while (endpos < n - 1 && (look(endpos + 1) & 1u)) endpos++;                // L171-172

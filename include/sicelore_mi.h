@@ -1063,6 +1063,9 @@ int smi_tagbam_stage_ms(const smi_tagbam *h, float *ms);
  *   with use_strand_info -- both REMOVED when no gene is kept.  allow_multi_gene_reads = 0 keeps no gene at all, as the reference's
  *   retainAll on an empty set does (L208).  A value of two or more genes lists them in the reference's HashSet order: those records are
  *   counted (SMI_MOLTAG_MULTI_GENE) and ordered by the host code behind smi_gene_tag_chunk.
+ * SMI_MOLTAG_READ (AddBamReadTags.doWork, org/ipmc/sicelore/programs/AddBamReadTags.java:L38-72): the read name split at '_' under the same
+ *   String.split rules; exactly three pieces -> gene_tag = piece 0, cell_tag = piece 1, umi_tag = piece 2, exactly four -> pieces 1, 2, 3
+ *   (L51-62), all Z, set in that order (a later one wins when tags coincide); any other count leaves the record as it is.  No record stops it.
  * DEVIATION: where the reference's loop dies in an exception its catch swallows (L62-64 / L111), leaving a cut-off file -- a third name piece
  *   that is no int (L56); a mapped record without an M / = / X operation whose interval [start, start + reference length - 1] overlaps a gene
  *   (L362) -- smi_moltag_segment returns 2, smi_last_error and smi_moltag_error_read name the first such read in input order, and the
@@ -1072,8 +1075,9 @@ int smi_tagbam_stage_ms(const smi_tagbam *h, float *ms);
  * use_strand_info).  smi_moltag_stage_ms: device ms of K-NAME, K-GENE, K-EDIT SIZE + scan, K-EDIT WRITE of the last segment. */
 #define SMI_MOLTAG_MOLECULE 0
 #define SMI_MOLTAG_GENE 1
+#define SMI_MOLTAG_READ 2
 #define SMI_MOLTAG_RECORDS 0            /* records seen */
-#define SMI_MOLTAG_TAGGED 1             /* MOLECULE: records with three name pieces; GENE: mapped records */
+#define SMI_MOLTAG_TAGGED 1             /* MOLECULE: records with three name pieces; GENE: mapped records; READ: records with 3 or 4 pieces */
 #define SMI_MOLTAG_TOTAL_READS 2        /* TOTAL_READS */
 #define SMI_MOLTAG_WRONG_STRAND 3       /* READS_WRONG_STRAND */
 #define SMI_MOLTAG_RIGHT_STRAND 4       /* READS_RIGHT_STRAND */
@@ -1085,7 +1089,7 @@ int smi_tagbam_stage_ms(const smi_tagbam *h, float *ms);
 #define SMI_MOLTAG_COUNTS 10
 #define SMI_MOLTAG_STAGES 4
 typedef struct {
-    int32_t program;                                  /* SMI_MOLTAG_MOLECULE / SMI_MOLTAG_GENE */
+    int32_t program;                                  /* SMI_MOLTAG_MOLECULE / SMI_MOLTAG_GENE / SMI_MOLTAG_READ */
     char cell_tag[4], umi_tag[4], rn_tag[4];          /* CELLTAG, UMITAG, RNTAG (AddBamMoleculeTags.java:L26-31): two characters + NUL */
     char gene_tag[4], strand_tag[4], function_tag[4]; /* GENETAG, STRANDTAG, FUNCTIONTAG (AddGeneNameTag.java:L38-43) */
     int32_t use_strand_info;                          /* USE_STRAND_INFO (L44-45) */
@@ -1547,6 +1551,52 @@ int smi_fusion_free(smi_fusion *h);
  * host thread with ordinary hash maps over the same pools: its wall time (the baseline tools/microbench.py reports beside the device's
  * grouping) and the number of molecules whose gene count, pair of names or selection differs from the device's (0) */
 int smi_fusion_host_loop(const smi_fusion *h, double *seconds, int64_t *mismatches);
+
+/* ---- ExportClippedReads (K-CLIP-FLAG, K-CLIP-KEY, K-CLIP-INSERT, K-CLIP-WRITE, smi_clipexport.hip) ----------------------------------------
+ * Replaces ExportClippedReads.doWork (org/ipmc/sicelore/programs/ExportClippedReads.java:L50-104).  Per record in file order: the key is the
+ * read name up to its first '_' (String.split, L68), '_', GENETAG, '_', CELLTAG, '_', UMITAG (L72-76; a missing attribute is the text
+ * "null"); the record is clipped when its first or its last CIGAR operation is S or H with a length > min_clip (L78-85); the first clipped
+ * record of a key writes "@" key "\n" US "\n+\n" QS "\n" (L87-95; a missing US / QS is "null", their lengths are not compared).
+ * DEVIATION: where the reference's loop dies in an exception its catch swallows (L100), leaving a cut-off FASTQ -- a name of '_' only (L76), a
+ *   gene / cell / UMI attribute that is no string on any record (L72-74), a US / QS that is no string on a record that is written (L91-92),
+ *   a record without CIGAR (L82), a last clip directly behind an '=' operation (L84) -- smi_clipexport_segment returns 2, smi_last_error and
+ *   smi_clipexport_error_read name the first such read in input order, the handle takes no further segment and the caller writes no file.
+ * smi_clipexport_default_config: MINCLIP 150, BC / U8 / GE / US / QS (L29-40), table_log2 0, keep_records 0.
+ * smi_clipexport_segment: bam / recs / out / cap / *n_out and the two-call protocol are those of smi_tagbam_segment; out receives the FASTQ
+ *   text of the segment's written records in file order.  The table of the keys written so far stays on the device from segment to segment.
+ * smi_clipexport_counts: SMI_CLIP_N_COUNT entries summed over the segments.  smi_clipexport_stage_ms: SMI_CLIP_N_STAGE device times of the last
+ *   segment: K-CLIP-FLAG, the key scan + K-CLIP-KEY, table growth + K-CLIP-INSERT + K-CLIP-PICK + scans + K-CLIP-COMMIT, K-CLIP-WRITE. */
+#define SMI_CLIP_RECORDS 0      /* records seen (`records`, L66) */
+#define SMI_CLIP_CLIPPED 1      /* records clipped (isClipped, L82-85) */
+#define SMI_CLIP_WRITTEN 2      /* records written (`clippedRecords`, L88) = distinct keys among the clipped records */
+#define SMI_CLIP_SEGMENTS 3     /* segments taken */
+#define SMI_CLIP_TABLE_SLOTS 4  /* K-CLIP-INSERT: slots of the table now */
+#define SMI_CLIP_TABLE_GROWS 5  /* ... times it was rebuilt at a larger size */
+#define SMI_CLIP_PROBE_STEPS 6  /* ... slots passed over (depends on the race for the slots) */
+#define SMI_CLIP_WRAPS 7        /* ... probe chains that went past the end of the table (the same) */
+#define SMI_CLIP_N_COUNT 8
+#define SMI_CLIP_N_STAGE 4
+typedef struct {
+    int32_t min_clip;                                              /* MINCLIP (L29-30), a Java int */
+    char cell_tag[4], umi_tag[4], gene_tag[4], us_tag[4], qs_tag[4]; /* CELLTAG, UMITAG, GENETAG, USTAG, QSTAG (L31-40): two characters + NUL */
+    int32_t table_log2;   /* TEST ONLY: the table starts at 2^table_log2 slots (1 .. 31) so that growth, long probe chains and wrap-around
+                             happen at test sizes; 0 (default): 1024.  It grows to the power of two >= 2 x (keys written + clipped records
+                             of the segment) either way */
+    int32_t keep_records; /* keep on the host what smi_clipexport_host_loop reads of every record (measurement and tests) */
+} smi_clipexport_config;
+typedef struct smi_clipexport smi_clipexport;
+int smi_clipexport_default_config(smi_clipexport_config *cfg);
+int smi_clipexport_create(smi_ctx *ctx, const smi_clipexport_config *cfg, smi_clipexport **out);
+int smi_clipexport_segment(smi_clipexport *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n, uint8_t *out, size_t cap,
+                           size_t *n_out);
+int smi_clipexport_counts(const smi_clipexport *h, int64_t *counts);
+/* the read that ended the run (smi_clipexport_segment returned 2): its name (cut to cap - 1 bytes) and its index over all segments; -1 = none */
+int smi_clipexport_error_read(const smi_clipexport *h, char *name, size_t cap, int64_t *record);
+int smi_clipexport_stage_ms(const smi_clipexport *h, float *ms);
+int smi_clipexport_free(smi_clipexport *h);
+/* with keep_records, after the last segment: the reference's loop as it runs it (L64-96), one host thread with a hash set of the keys over
+ * the same records: its wall time and the number of records whose decision (clipped, written) differs from the device's (0) */
+int smi_clipexport_host_loop(const smi_clipexport *h, double *seconds, int64_t *mismatches);
 
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */

@@ -86,6 +86,36 @@ __device__ __forceinline__ void remove_field(Field *f, int &n, uint16_t key) {
         }
 }
 
+// One step of the walk below for a kernel that looks attributes up and rewrites none (K-CLIP-FLAG, smi_clipexport.hip): the attribute at p
+// (tag at p, type at p + 2, value at p + 3) -> the offset behind it under the same type rules; 0: malformed, unknown type or past `end`
+__device__ __forceinline__ uint64_t aux_next(const uint8_t *__restrict__ bam, uint64_t p, uint64_t end) {
+    if (p + 3 > end) return 0;
+    const uint8_t ty = bam[p + 2];
+    const uint64_t v = p + 3;
+    uint64_t q;
+    switch (ty) {
+        case 'A': case 'c': case 'C': q = v + 1; break;
+        case 's': case 'S': q = v + 2; break;
+        case 'i': case 'I': case 'f': q = v + 4; break;
+        case 'Z': case 'H':
+            q = v;
+            while (q < end && bam[q]) q++;
+            if (q >= end) return 0;
+            q++;
+            break;
+        case 'B': {
+            if (v + 5 > end) return 0;
+            const uint8_t sub = bam[v];
+            const uint32_t w = sub == 'c' || sub == 'C' ? 1 : sub == 's' || sub == 'S' ? 2 : sub == 'i' || sub == 'I' || sub == 'f' ? 4 : 0;
+            if (!w) return 0;
+            q = v + 5 + (uint64_t)w * ld_u32(bam + v + 1);
+            break;
+        }
+        default: return 0;
+    }
+    return q > end ? 0 : q;
+}
+
 // lane 0: the attribute list of record rec as written (its own attributes, then what `tail` puts), in f[0 .. n), sorted by binary tag;
 // returns SMI_TAG_* error bits (0 = fine)
 template <class Tail>

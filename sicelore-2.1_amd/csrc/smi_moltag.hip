@@ -1,8 +1,9 @@
-// smi_moltag.hip -- `AddBamMoleculeTags` (org/ipmc/sicelore/programs/AddBamMoleculeTags.java:L38-67) and `AddGeneNameTag`
-// (AddGeneNameTag.java:L76-160) on the device: both read a BAM, decide up to three attributes per record and write every record back in
+// smi_moltag.hip -- `AddBamMoleculeTags` (org/ipmc/sicelore/programs/AddBamMoleculeTags.java:L38-67), `AddGeneNameTag`
+// (AddGeneNameTag.java:L76-160) and `AddBamReadTags` (AddBamReadTags.java:L38-72) on the device: all three read a BAM, decide up to three attributes per record and write every record back in
 // input order with those attributes set, replaced or removed.
 //   K-NAME  one thread per record: the read name split as Java's String.split does it (L48-57) -> three edits or none; a third piece that
-//           is no int is reported through atomicMin of the record index (the first such read of the segment)
+//           is no int is reported through atomicMin of the record index (the first such read of the segment); AddBamReadTags' form of it
+//           (k_name_read) splits at '_' into up to four pieces and sets three strings
 //   K-GENE  one wavefront per mapped record: alignment blocks from the CIGAR 64 operations per round (wave prefix sum, as K-SNP walks it),
 //           the candidate genes of the record's contig by two binary searches over (start, running maximum of end), lanes testing 64 genes
 //           at a time, and per candidate the read's locus function and exon hit WITHOUT per-base arrays: lanes hold the blocks of a round,
@@ -87,8 +88,9 @@ struct EditSource {
 
 // ---- K-NAME ----------------------------------------------------------------------------------------------------------------------------
 // String.split(one literal character) of s[0 .. len): the number of pieces (trailing empty pieces dropped, leading and inner ones kept, a
-// string without the character one piece, a string of separators only none) and [start, end) of the first three in b
-__device__ int java_split3(const uint8_t *s, int len, uint8_t sep, int *b) {
+// string without the character one piece, a string of separators only none) and [start, end) of the first MAX in b
+template <int MAX>
+__device__ int java_split(const uint8_t *s, int len, uint8_t sep, int *b) {
     int last = -1;
     for (int k = 0; k < len; k++)
         if (s[k] != sep) last = k;
@@ -99,14 +101,14 @@ __device__ int java_split3(const uint8_t *s, int len, uint8_t sep, int *b) {
     int pieces = 1, start = 0;
     for (int k = 0; k < last; k++)
         if (s[k] == sep) {
-            if (pieces <= 3) {
+            if (pieces <= MAX) {
                 b[2 * (pieces - 1)] = start;
                 b[2 * (pieces - 1) + 1] = k;
             }
             pieces++;
             start = k + 1;
         }
-    if (pieces <= 3) {
+    if (pieces <= MAX) {
         b[2 * (pieces - 1)] = start;
         b[2 * (pieces - 1) + 1] = last + 1;
     }
@@ -122,8 +124,8 @@ __global__ void k_name(const uint8_t *__restrict__ bam, const smi_bam_record *__
         const uint8_t *s = bam + rec.name_off;
         const int len = rec.l_read_name ? rec.l_read_name - 1 : 0;
         int b[6] = {0, 0, 0, 0, 0, 0};
-        int pieces = java_split3(s, len, '-', b);            // L49
-        if (pieces == 1) pieces = java_split3(s, len, '|', b);  // L50-51
+        int pieces = java_split<3>(s, len, '-', b);            // L49
+        if (pieces == 1) pieces = java_split<3>(s, len, '|', b);  // L50-51
         Edit e[kEdits] = {};
         if (pieces == 3) {  // L53-57
             // new Integer(info[2]): an optional sign, decimal digits, the int range, nothing else
@@ -150,6 +152,32 @@ __global__ void k_name(const uint8_t *__restrict__ bam, const smi_bam_record *__
                 e[1] = {(uint16_t)umi_key, EDIT_SET_Z, 0, (uint32_t)(b[3] - b[2]), rec.name_off + (uint64_t)b[2], 0};
                 e[2] = {(uint16_t)rn_key, EDIT_SET_INT, 0, 0, 0, x};
             }
+        }
+        for (int k = 0; k < kEdits; k++) edits[(size_t)kEdits * i + k] = e[k];
+    }
+    const unsigned long long m = __ballot(tagged);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_tagged, (unsigned long long)__popcll(m));
+}
+
+// K-NAME of AddBamReadTags (AddBamReadTags.java:L48-62): the name split at '_'; three pieces are gene, cell, UMI, four pieces carry them
+// behind a first piece that is not used; no record stops the program
+__global__ void k_name_read(const uint8_t *__restrict__ bam, const smi_bam_record *__restrict__ recs, size_t n, uint32_t gene_key, uint32_t cell_key,
+                            uint32_t umi_key, Edit *__restrict__ edits, unsigned long long *__restrict__ n_tagged) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    bool tagged = false;
+    if (i < n) {
+        const smi_bam_record rec = recs[i];
+        const uint8_t *s = bam + rec.name_off;
+        const int len = rec.l_read_name ? rec.l_read_name - 1 : 0;
+        int b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const int pieces = java_split<4>(s, len, '_', b);  // L49
+        Edit e[kEdits] = {};
+        if (pieces == 3 || pieces == 4) {  // L51-62
+            tagged = true;
+            const int *p = b + (pieces == 4 ? 2 : 0);
+            e[0] = {(uint16_t)gene_key, EDIT_SET_Z, 0, (uint32_t)(p[1] - p[0]), rec.name_off + (uint64_t)p[0], 0};
+            e[1] = {(uint16_t)cell_key, EDIT_SET_Z, 0, (uint32_t)(p[3] - p[2]), rec.name_off + (uint64_t)p[2], 0};
+            e[2] = {(uint16_t)umi_key, EDIT_SET_Z, 0, (uint32_t)(p[5] - p[4]), rec.name_off + (uint64_t)p[4], 0};
         }
         for (int k = 0; k < kEdits; k++) edits[(size_t)kEdits * i + k] = e[k];
     }
@@ -416,7 +444,7 @@ EditSource edit_source(const smi_moltag *h) { return {h->d_edits, h->cfg.program
 }  // namespace
 
 extern "C" int smi_moltag_default_config(int32_t program, smi_moltag_config *cfg) {
-    if (!cfg || (program != SMI_MOLTAG_MOLECULE && program != SMI_MOLTAG_GENE)) {
+    if (!cfg || (program != SMI_MOLTAG_MOLECULE && program != SMI_MOLTAG_GENE && program != SMI_MOLTAG_READ)) {
         set_error("smi_moltag_default_config: bad argument");
         return SMI_ERR_INVALID;
     }
@@ -440,7 +468,8 @@ extern "C" int smi_moltag_create(smi_ctx *ctx, const smi_moltag_config *cfg, con
     }
     *out = nullptr;
     const bool gene = cfg->program == SMI_MOLTAG_GENE;
-    if (!gene && cfg->program != SMI_MOLTAG_MOLECULE) {
+    const bool read = cfg->program == SMI_MOLTAG_READ;
+    if (!gene && !read && cfg->program != SMI_MOLTAG_MOLECULE) {
         set_error("smi_moltag_create: unknown program");
         return SMI_ERR_INVALID;
     }
@@ -448,8 +477,10 @@ extern "C" int smi_moltag_create(smi_ctx *ctx, const smi_moltag_config *cfg, con
         set_error("smi_moltag_create: AddGeneNameTag needs a gene model");
         return SMI_ERR_INVALID;
     }
-    const char *tags[3] = {gene ? cfg->gene_tag : cfg->cell_tag, gene ? cfg->strand_tag : cfg->umi_tag, gene ? cfg->function_tag : cfg->rn_tag};
-    const char *names[3] = {gene ? "GENETAG" : "CELLTAG", gene ? "STRANDTAG" : "UMITAG", gene ? "FUNCTIONTAG" : "RNTAG"};
+    const char *tags[3] = {gene || read ? cfg->gene_tag : cfg->cell_tag, gene ? cfg->strand_tag : read ? cfg->cell_tag : cfg->umi_tag,
+                           gene ? cfg->function_tag : read ? cfg->umi_tag : cfg->rn_tag};
+    const char *names[3] = {gene || read ? "GENETAG" : "CELLTAG", gene ? "STRANDTAG" : read ? "CELLTAG" : "UMITAG",
+                            gene ? "FUNCTIONTAG" : read ? "UMITAG" : "RNTAG"};
     for (int k = 0; k < 3; k++)
         if (!valid_tag(tags[k])) {
             set_error(std::string(names[k]) + " must be two characters");
@@ -555,7 +586,7 @@ extern "C" int smi_moltag_segment(smi_moltag *h, const uint8_t *bam, size_t n_ba
     *n_out = 0;
     SMI_HIP(hipSetDevice(h->ctx->device));
     hipStream_t s = h->ctx->stream;
-    const bool gene = h->cfg.program == SMI_MOLTAG_GENE;
+    const bool gene = h->cfg.program == SMI_MOLTAG_GENE, read = h->cfg.program == SMI_MOLTAG_READ;
     const bool cached = h->last_n == n && h->last_bam == bam && h->last_recs == recs && h->last_n_bam == n_bam;
     h->last_n = -1;
     uint64_t total = 0;
@@ -581,7 +612,10 @@ extern "C" int smi_moltag_segment(smi_moltag *h, const uint8_t *bam, size_t n_ba
         SMI_HIP(hipMemsetAsync(h->d_words, 0xFF, 8, s));
         SMI_HIP(hipMemsetAsync(h->d_words + 1, 0, 8, s));
         SMI_HIP(hipEventRecord(h->ev[0], s));
-        if (n && !gene)
+        if (n && read)
+            hipLaunchKernelGGL(k_name_read, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const uint8_t *)h->d_bam, (const smi_bam_record *)h->d_recs, (size_t)n,
+                               tag_key(h->cfg.gene_tag), tag_key(h->cfg.cell_tag), tag_key(h->cfg.umi_tag), h->d_edits, h->d_words + 1);
+        if (n && !gene && !read)
             hipLaunchKernelGGL(k_name, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const uint8_t *)h->d_bam, (const smi_bam_record *)h->d_recs, (size_t)n,
                                tag_key(h->cfg.cell_tag), tag_key(h->cfg.umi_tag), tag_key(h->cfg.rn_tag), h->d_edits, h->d_words, h->d_words + 1);
         if (n && gene) {

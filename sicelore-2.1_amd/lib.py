@@ -81,6 +81,8 @@ EXPORTS = [
     "smi_collapse_validate_begin", "smi_collapse_validate_segment", "smi_collapse_validate_end", "smi_collapse_validate_counts",
     "smi_fusion_default_config", "smi_fusion_create", "smi_fusion_add_segment", "smi_fusion_run", "smi_fusion_output", "smi_fusion_counts",
     "smi_fusion_error_read", "smi_fusion_free", "smi_fusion_host_loop",
+    "smi_clipexport_default_config", "smi_clipexport_create", "smi_clipexport_segment", "smi_clipexport_counts", "smi_clipexport_error_read",
+    "smi_clipexport_stage_ms", "smi_clipexport_free", "smi_clipexport_host_loop",
     "smi_select_valid_cells",
 ]
 
@@ -319,6 +321,14 @@ def load_library():
     lib.smi_fusion_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
     lib.smi_fusion_free.argtypes = [vp]
     lib.smi_fusion_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_clipexport_default_config.argtypes = [vp]
+    lib.smi_clipexport_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
+    lib.smi_clipexport_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_clipexport_counts.argtypes = [vp, vp]
+    lib.smi_clipexport_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_clipexport_stage_ms.argtypes = [vp, vp]
+    lib.smi_clipexport_free.argtypes = [vp]
+    lib.smi_clipexport_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     lib.smi_poa_batch_ex.argtypes = lib.smi_poa_batch.argtypes + [vp]
@@ -1082,7 +1092,7 @@ class MolTagConfig(ctypes.Structure):
                 ("use_strand_info", ctypes.c_int32), ("allow_multi_gene_reads", ctypes.c_int32)]
 
 
-MOLTAG_MOLECULE, MOLTAG_GENE = 0, 1
+MOLTAG_MOLECULE, MOLTAG_GENE, MOLTAG_READ = 0, 1, 2
 # smi_moltag_counts, in SMI_MOLTAG_* order
 MOLTAG_COUNTS = ("records", "tagged", "total_reads", "wrong_strand", "right_strand", "ambiguous_fixed", "ambiguous_rejected", "multi_gene_records",
                  "with_gene", "genes")
@@ -1098,8 +1108,9 @@ class MolTagError(SmiError):
 
 
 class MolTag(_Handle):
-    """AddBamMoleculeTags / AddGeneNameTag (smi_moltag_*): BAM segments rewritten with their attributes edited.  program: MOLTAG_MOLECULE or
-    MOLTAG_GENE (then genes: a GeneTagger, kept alive by this object).  Keywords: the other fields of smi_moltag_config."""
+    """AddBamMoleculeTags / AddGeneNameTag / AddBamReadTags (smi_moltag_*): BAM segments rewritten with their attributes edited.  program:
+    MOLTAG_MOLECULE, MOLTAG_READ or MOLTAG_GENE (then genes: a GeneTagger, kept alive by this object).  Keywords: the other fields of
+    smi_moltag_config."""
     _NAME, _CONFIG, _COUNTS = "moltag", MolTagConfig, MOLTAG_COUNTS
     _TAGS = ("cell_tag", "umi_tag", "rn_tag", "gene_tag", "strand_tag", "function_tag")
     _BOOLS = ("use_strand_info", "allow_multi_gene_reads")
@@ -1126,6 +1137,63 @@ class MolTag(_Handle):
 
     def stage_ms(self):
         return self._named("stage_ms", MOLTAG_STAGES, np.float32)
+
+
+class ClipExportConfig(ctypes.Structure):
+    """smi_clipexport_config"""
+    _fields_ = [("min_clip", ctypes.c_int32), ("cell_tag", ctypes.c_char * 4), ("umi_tag", ctypes.c_char * 4), ("gene_tag", ctypes.c_char * 4),
+                ("us_tag", ctypes.c_char * 4), ("qs_tag", ctypes.c_char * 4), ("table_log2", ctypes.c_int32), ("keep_records", ctypes.c_int32)]
+
+
+# smi_clipexport_counts, in SMI_CLIP_* order (SMI_CLIP_N_COUNT entries); smi_clipexport_stage_ms (SMI_CLIP_N_STAGE entries)
+CLIPEXPORT_COUNTS = ("records", "clipped", "written", "segments", "table_slots", "table_grows", "probe_steps", "wraps")
+CLIPEXPORT_STAGES = ("flag", "key", "insert", "write")
+
+
+class ClipExportError(SmiError):
+    """a record on which the reference's loop dies (smi_clipexport_segment returned 2); .read: its name, .record: its index in the input"""
+
+    def __init__(self, msg, read, record):
+        super().__init__(msg)
+        self.read, self.record = read, record
+
+
+class ClipExport(_Handle):
+    """ExportClippedReads (smi_clipexport_*): BAM segments in, the FASTQ text of the clipped records that are first of their key out; the
+    table of the keys written stays on the device between segments.  Keywords: the fields of smi_clipexport_config."""
+    _NAME, _CONFIG, _COUNTS = "clipexport", ClipExportConfig, CLIPEXPORT_COUNTS
+    _TAGS = ("cell_tag", "umi_tag", "gene_tag", "us_tag", "qs_tag")
+    _INTS = ("min_clip", "table_log2")
+    _BOOLS = ("keep_records",)
+    _TAG_ERROR = "{k} {v!r} is not a two-character tag"
+
+    def __init__(self, ctx, **kw):
+        cfg = self._config(kw)
+        self._create(ctx, ctypes.byref(cfg))
+
+    def segment(self, bam, recs, out=None):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it -> the FASTQ text of the segment (uint8 array)"""
+        args, recs = self._segment_args(bam, recs)
+        n_out = ctypes.c_size_t(0)
+        if out is None:
+            out = np.empty(max(64, bam.size // 4), dtype=np.uint8)
+        rc, out = self._grow(lambda o: self._lib.smi_clipexport_segment(self._h, *args, o.ctypes.data, o.size, ctypes.byref(n_out)), out, n_out)
+        if rc == 2:
+            msg = self._lib.smi_last_error().decode(errors="replace")
+            name, rec = self._error_read()
+            raise ClipExportError(msg, name.decode("latin-1"), rec)
+        self._check(rc)
+        return out[:n_out.value]
+
+    def stage_ms(self):
+        return self._named("stage_ms", CLIPEXPORT_STAGES, np.float32)
+
+    def host_loop(self):
+        """with keep_records, after the last segment: the reference's single-thread loop over the same records -> (seconds, records whose
+        decision differs from the device's)"""
+        sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
+        self._check(self._lib.smi_clipexport_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)))
+        return sec.value, bad.value
 
 
 # smi_poa_batch_ex's statistics, in SMI_POA_STAT_* order

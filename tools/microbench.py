@@ -37,9 +37,10 @@ def main():
     used = synth.pick_used(wl, 5000, seed=2)
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
-            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse, "fusion": leg_fusion, "validator": leg_validator}
+            "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse, "fusion": leg_fusion, "validator": leg_validator,
+            "fusionprep": leg_fusionprep}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -941,6 +942,78 @@ def leg_fusion(pkg, synth, ctx, dev, wl, used, res):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     res["fusion"] = out
+
+
+def _fusionprep_fixture(n_recs, seed=81, clipped_share=4):
+    """a seeded BAM of n_recs long reads as tagbamwithread leaves them: GE / BC / U8, US and QS of 400 .. 800 bytes cut from one random
+    text, names <read>_<n>; one record in `clipped_share` carries a soft clip above MINCLIP; the reads come in groups of 1 .. 3 records of
+    one name and tags (supplementary alignments), so the keys have duplicates -> (BGZF bytes, records, clipped records)"""
+    import struct
+
+    from sicelore_amd import lib
+
+    rng = np.random.default_rng(seed)
+    seq = bytes(b"ACGT"[int(x)] for x in rng.integers(0, 4, 1 << 16))
+    qual = bytes(33 + int(x) for x in rng.integers(0, 40, 1 << 16))
+    recs, k, r, n_clip = [], 0, 0, 0
+    while k < n_recs:
+        name = b"read%08d_%d\0" % (r, r % 7)
+        tags = b"GEZGENE%d\0BCZCELL%05dACGTAC\0U8ZUMI%09d\0" % (r % 20000, r % 5000, r)
+        for j in range(int(rng.integers(1, 4))):
+            L, at = int(rng.integers(400, 801)), int(rng.integers(0, (1 << 16) - 800))
+            clip = int(rng.integers(clipped_share)) == 0
+            n_clip += clip
+            cig = struct.pack("<3I", (int(rng.integers(151, 400)) if clip else int(rng.integers(1, 151))) << 4 | 4, 300 << 4 | 0, 20 << 4 | 4)
+            aux = tags + b"USZ" + seq[at:at + L] + b"\0QSZ" + qual[at:at + L] + b"\0"
+            body = struct.pack("<iiBBHHHiiii", 0, int(rng.integers(10_000, 100_000_000)), len(name), 60, 4680, 3, 0x800 if j else 0, 0, -1, -1, 0) + name + cig + aux
+            recs.append(struct.pack("<I", len(body)) + body)
+            k += 1
+        r += 1
+    head = b"BAM\1" + struct.pack("<I", 0) + struct.pack("<I", 1) + struct.pack("<I", 5) + b"chr1\0" + struct.pack("<I", 2 ** 31 - 1)
+    return lib.bgzf_deflate(np.frombuffer(head + b"".join(recs), dtype=np.uint8), level=1, n_threads=16), k, n_clip, head
+
+
+def leg_fusionprep(pkg, synth, ctx, dev, wl, used, res):
+    """K-CLIP-FLAG / K-CLIP-KEY / K-CLIP-INSERT / K-CLIP-WRITE (`ExportClippedReads`) and K-NAME's '_' form + K-EDIT (`AddBamReadTags`), file
+    to file: a seeded BAM of SMI_MB_FP_RECS records (100,000) with US / QS, a quarter of them clipped, the keys with duplicates, in
+    segments of SMI_MB_FP_SEGMENT compressed bytes (8 MiB, so that the key table is carried over segments); then one record per written
+    FASTQ name, standing in for the mapper, through AddBamReadTags.  Device ms per stage (HIP events), seconds in parse, in the device calls,
+    in deflate and in file writes, wall seconds, and beside the device's decisions the wall time of the reference's single-thread loop over
+    the same records (smi_clipexport_host_loop), with the records on which the two differ (0)."""
+    import shutil
+    import struct
+    import tempfile
+
+    fp = importlib.import_module(graft.PKG_NAME + ".fusionprep")
+    lib = importlib.import_module(graft.PKG_NAME + ".lib")
+    n_recs = int(os.environ.get("SMI_MB_FP_RECS", "100000"))
+    seg = int(os.environ.get("SMI_MB_FP_SEGMENT", str(8 << 20)))
+    t0 = time.perf_counter()
+    z, n_rec, n_clip, head = _fusionprep_fixture(n_recs)
+    out = {"records": n_rec, "clipped_generated": n_clip, "bam_bytes": int(z.size), "segment_bytes": seg, "fixture_s": time.perf_counter() - t0}
+    d = tempfile.mkdtemp(prefix="fusionprep_")
+    try:
+        src, fq = os.path.join(d, "in.bam"), os.path.join(d, "clipped.fastq")
+        z.tofile(src)
+        fp.export_clipped_reads(ctx, src, fq, segment_bytes=seg, n_threads=16)          # the first run loads the code objects
+        info = fp.export_clipped_reads(ctx, src, fq, segment_bytes=seg, n_threads=16, host_loop=True)
+        out["export_clipped_reads"] = dict({k: info[k] for k in lib.CLIPEXPORT_COUNTS}, stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"],
+                                           bytes_written=info["bytes_written"], records_per_s=info["records"] / info["wall_s"])
+        out["host_loop_wall_s"] = info["host_loop_s"]
+        out["host_loop_mismatches"] = info["host_loop_mismatches"]
+        names = open(fq, "rb").read().split(b"\n")[0::4]
+        recs = []
+        for k, nm in enumerate(n[1:] + b"\0" for n in names if n):
+            body = struct.pack("<iiBBHHHiiii", 0, 1000 + k, len(nm), 60, 4680, 1, 0, 0, -1, -1, 0) + nm + struct.pack("<I", 500 << 4) + b"NMC\1"
+            recs.append(struct.pack("<I", len(body)) + body)
+        lib.bgzf_deflate(np.frombuffer(head + b"".join(recs), dtype=np.uint8), level=1, n_threads=16).tofile(os.path.join(d, "mapped.bam"))
+        fp.add_bam_read_tags(ctx, os.path.join(d, "mapped.bam"), os.path.join(d, "tags.bam"), segment_bytes=seg, n_threads=16)
+        info = fp.add_bam_read_tags(ctx, os.path.join(d, "mapped.bam"), os.path.join(d, "tags.bam"), segment_bytes=seg, n_threads=16)
+        out["add_bam_read_tags"] = dict(records=info["records"], tagged=info["tagged"], stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"],
+                                        bytes_written=info["bytes_written"], records_per_s=info["records"] / info["wall_s"])
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    res["fusionprep"] = out
 
 
 def _snp_fixture(n_recs, n_lines, n_cells, seed=51):

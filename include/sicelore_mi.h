@@ -1598,6 +1598,47 @@ int smi_clipexport_free(smi_clipexport *h);
  * the same records: its wall time and the number of records whose decision (clipped, written) differs from the device's (0) */
 int smi_clipexport_host_loop(const smi_clipexport *h, double *seconds, int64_t *mismatches);
 
+/* ---- BamIndex (K-BAI-REC, K-BAI-ORDER, K-BAI-CHUNK, K-BAI-LIN, K-BAI-BINS, K-BAI-FILL, smi_bamindex.hip) ----------------------------------
+ * The .bai (SAM specification 5.2) of a coordinate-sorted BAM, in the place of `samtools index`: this build's own canonical form (DESIGN.md
+ * section 8l), which every reader of the format reads; it is not byte-equal to samtools' or htsjdk's file.
+ * smi_bgzf_block_table (host): coffset (base + offset in `in`) and inflated length of the complete BGZF blocks in in[0 .. n_in), from BSIZE
+ *   and ISIZE alone (nothing is inflated); *n_blocks = their number always, *consumed = the bytes they take; coffset / isize may be NULL
+ *   (the number alone), else cap entries are filled and 1 is returned when there are more.
+ * smi_bamindex_create: n_ref references of the header and their lengths (they size the linear index: a reference holds the 16 kb windows
+ *   its length covers, at most 2^15).
+ * smi_bamindex_add_blocks: the next blocks of the file, in file order (empty ones included or not); end_coffset: the file offset behind
+ *   the last of them.  The blocks under a segment come before the segment.
+ * smi_bamindex_add_segment: bam / n_bam / recs / n as smi_tagbam_segment takes them; stream_off: the offset of bam[0] in the inflated
+ *   stream the blocks make up.  Returns 2 at a record out of coordinate order (records on a reference by (ref_id, pos), the others last),
+ *   a record on a reference with pos < 0, one that ends behind 2^29 or behind its reference's length, or a ref_id outside the header:
+ *   smi_last_error and smi_bamindex_error_read name the first such read, and the handle takes nothing further.
+ * smi_bamindex_finish: the file's bytes (out == NULL: their size in *n_out; 1 = cap is too small).
+ * smi_bamindex_counts: SMI_BAI_N_COUNT entries.  smi_bamindex_stage_ms: SMI_BAI_N_STAGE device times of the last add_segment (the first
+ *   four) or of finish (the fifth). */
+#define SMI_BAI_RECORDS 0           /* records taken */
+#define SMI_BAI_REFS_WITH_RECORDS 1 /* references with at least one record (after finish) */
+#define SMI_BAI_CHUNKS 2            /* chunks: runs of records with one (ref_id, bin) */
+#define SMI_BAI_NO_COOR 3           /* records with ref_id < 0 */
+#define SMI_BAI_SEGMENTS 4          /* segments taken */
+#define SMI_BAI_BLOCKS 5            /* non-empty BGZF blocks taken */
+#define SMI_BAI_BINS 6              /* distinct (ref_id, bin) (after finish) */
+#define SMI_BAI_WINDOWS 7           /* linear index entries written (after finish) */
+#define SMI_BAI_WINDOWS_HELD 8      /* linear index entries held on the device */
+#define SMI_BAI_N_COUNT 9
+#define SMI_BAI_N_STAGE 5
+typedef struct smi_bamindex smi_bamindex;
+int smi_bgzf_block_table(const uint8_t *in, size_t n_in, uint64_t base, uint64_t *coffset, uint32_t *isize, size_t cap, size_t *n_blocks,
+                         size_t *consumed);
+int smi_bamindex_create(smi_ctx *ctx, int32_t n_ref, const int32_t *ref_len, smi_bamindex **out);
+int smi_bamindex_add_blocks(smi_bamindex *h, const uint64_t *coffset, const uint32_t *isize, size_t n, uint64_t end_coffset);
+int smi_bamindex_add_segment(smi_bamindex *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n, uint64_t stream_off);
+int smi_bamindex_finish(smi_bamindex *h, uint8_t *out, size_t cap, size_t *n_out);
+int smi_bamindex_counts(const smi_bamindex *h, int64_t *counts);
+/* the read that ended the run (smi_bamindex_add_segment returned 2): its name (cut to cap - 1 bytes) and its 0-based number in the file; -1 = none */
+int smi_bamindex_error_read(const smi_bamindex *h, char *name, size_t cap, int64_t *record);
+int smi_bamindex_stage_ms(const smi_bamindex *h, float *ms);
+int smi_bamindex_free(smi_bamindex *h);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

@@ -751,7 +751,7 @@ def assignumis_stream(ctx, in_bam, out_prefix, segment_bytes=256 << 20, chunk_si
     if world > 1:
         bai = next((p_ for p_ in (in_bam + ".bai", in_bam[:-4] + ".bai") if os.path.isfile(p_)), None)
         if bai is None:
-            raise _lib.SmiError(f"assignumis over {world} ranks needs the BAM index ({in_bam}.bai: samtools index) to deal whole chromosomes to the ranks")
+            raise _lib.SmiError(f"assignumis over {world} ranks needs the BAM index ({in_bam}.bai: sicelore-2.1_amd/bamindex.py or samtools index) to deal whole chromosomes to the ranks")
         extents = bai_ref_extents(bai)
         size = os.path.getsize(in_bam)
         far = max((e[1] >> 16 for e in extents if e is not None), default=0)

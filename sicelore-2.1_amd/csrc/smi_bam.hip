@@ -84,6 +84,25 @@ extern "C" int smi_bgzf_uncompressed_size(const uint8_t *in, size_t n_in, size_t
     return SMI_OK;
 }
 
+extern "C" int smi_bgzf_block_table(const uint8_t *in, size_t n_in, uint64_t base, uint64_t *coffset, uint32_t *isize, size_t cap, size_t *n_blocks,
+                                    size_t *consumed) {
+    if ((!in && n_in) || !n_blocks || (!coffset != !isize)) {
+        set_error("smi_bgzf_block_table: null argument");
+        return SMI_ERR_INVALID;
+    }
+    std::vector<Block> blocks;
+    size_t total = 0, used = 0;
+    if (int rc = scan_blocks(in, n_in, blocks, &total, &used)) return rc;
+    *n_blocks = blocks.size();
+    if (consumed) *consumed = used;
+    if (!coffset) return SMI_OK;
+    for (size_t k = 0; k < std::min(cap, blocks.size()); k++) {
+        coffset[k] = base + blocks[k].off;
+        isize[k] = blocks[k].isize;
+    }
+    return cap < blocks.size() ? 1 : SMI_OK;
+}
+
 extern "C" int smi_bgzf_inflate(const uint8_t *in, size_t n_in, uint8_t *out, size_t cap_out, size_t *n_out, size_t *consumed,
                                 int n_threads) {
     if ((!in && n_in) || (!out && cap_out) || !n_out) {

@@ -70,13 +70,13 @@ def export_clipped_reads(ctx, in_bam, out_fastq, min_clip=150, cell_tag="BC", um
     return dict(counts, stage_ms=stage_ms, seconds=secs, bytes_written=written, wall_s=wall)
 
 
-def add_bam_read_tags(ctx, in_bam, out_bam, gene_tag="GE", cell_tag="BC", umi_tag="U8", segment_bytes=256 << 20, n_threads=4):
+def add_bam_read_tags(ctx, in_bam, out_bam, gene_tag="GE", cell_tag="BC", umi_tag="U8", segment_bytes=256 << 20, n_threads=4, index=False):
     """-> dict of counts (records, tagged), device ms per stage, seconds and bytes written.  The header is copied as it is (presorted =
-    true, L44)."""
+    true, L44).  index: also leave <out_bam>.bai (moltags._rewrite)."""
     from .moltags import _rewrite
     h = _lib.MolTag(ctx, _lib.MOLTAG_READ, gene_tag=gene_tag, cell_tag=cell_tag, umi_tag=umi_tag)
     try:
-        info = _rewrite(ctx, h, in_bam, out_bam, lambda hdr: hdr, segment_bytes, n_threads)
+        info = _rewrite(ctx, h, in_bam, out_bam, lambda hdr: hdr, segment_bytes, n_threads, index=index)
     finally:
         h.close()
     info["seconds"]["parse"] = max(0.0, info["wall_s"] - sum(info["seconds"].values()))      # reading, inflating and indexing the segments

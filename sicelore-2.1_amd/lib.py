@@ -83,6 +83,8 @@ EXPORTS = [
     "smi_fusion_error_read", "smi_fusion_free", "smi_fusion_host_loop",
     "smi_clipexport_default_config", "smi_clipexport_create", "smi_clipexport_segment", "smi_clipexport_counts", "smi_clipexport_error_read",
     "smi_clipexport_stage_ms", "smi_clipexport_free", "smi_clipexport_host_loop",
+    "smi_bgzf_block_table", "smi_bamindex_create", "smi_bamindex_add_blocks", "smi_bamindex_add_segment", "smi_bamindex_finish",
+    "smi_bamindex_counts", "smi_bamindex_error_read", "smi_bamindex_stage_ms", "smi_bamindex_free",
     "smi_select_valid_cells",
 ]
 
@@ -329,6 +331,15 @@ def load_library():
     lib.smi_clipexport_stage_ms.argtypes = [vp, vp]
     lib.smi_clipexport_free.argtypes = [vp]
     lib.smi_clipexport_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_bgzf_block_table.argtypes = [vp, sz, ctypes.c_uint64, vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    lib.smi_bamindex_create.argtypes = [vp, ctypes.c_int32, vp, ctypes.POINTER(vp)]
+    lib.smi_bamindex_add_blocks.argtypes = [vp, vp, vp, sz, ctypes.c_uint64]
+    lib.smi_bamindex_add_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32, ctypes.c_uint64]
+    lib.smi_bamindex_finish.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_bamindex_counts.argtypes = [vp, vp]
+    lib.smi_bamindex_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_bamindex_stage_ms.argtypes = [vp, vp]
+    lib.smi_bamindex_free.argtypes = [vp]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     lib.smi_poa_batch_ex.argtypes = lib.smi_poa_batch.argtypes + [vp]
@@ -1194,6 +1205,71 @@ class ClipExport(_Handle):
         sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
         self._check(self._lib.smi_clipexport_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)))
         return sec.value, bad.value
+
+
+# smi_bamindex_counts, in SMI_BAI_* order (SMI_BAI_N_COUNT entries); smi_bamindex_stage_ms (SMI_BAI_N_STAGE entries)
+BAMINDEX_COUNTS = ("records", "refs_with_records", "chunks", "no_coor", "segments", "blocks", "bins", "windows", "windows_held")
+BAMINDEX_STAGES = ("record", "order", "chunk", "linear", "finish")
+
+
+class BamIndexError(SmiError):
+    """a record a .bai cannot be built over (smi_bamindex_add_segment returned 2); .read: its name, .record: its 0-based number in the file"""
+
+    def __init__(self, msg, read, record):
+        super().__init__(msg)
+        self.read, self.record = read, record
+
+
+def bgzf_block_table(data, base=0):
+    """(coffset uint64 array, inflated length uint32 array, bytes consumed) of the complete BGZF blocks of `data` (numpy uint8), the
+    coffsets counted from `base`; BSIZE and ISIZE are read, nothing is inflated"""
+    lib = load_library()
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    n, used = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    if lib.smi_bgzf_block_table(data.ctypes.data, data.size, int(base), None, None, 0, ctypes.byref(n), ctypes.byref(used)):
+        raise SmiError(lib.smi_last_error().decode())
+    coff, isize = np.zeros(max(n.value, 1), dtype=np.uint64), np.zeros(max(n.value, 1), dtype=np.uint32)
+    if lib.smi_bgzf_block_table(data.ctypes.data, data.size, int(base), coff.ctypes.data, isize.ctypes.data, coff.size, ctypes.byref(n),
+                                ctypes.byref(used)):
+        raise SmiError(lib.smi_last_error().decode())
+    return coff[:n.value], isize[:n.value], used.value
+
+
+class BamIndex(_Handle):
+    """The .bai of a coordinate-sorted BAM (smi_bamindex_*): the file's BGZF blocks and the inflated stream in segments in, the index's
+    bytes out.  ref_lengths: the lengths of the header's references, in order."""
+    _NAME, _COUNTS = "bamindex", BAMINDEX_COUNTS
+
+    def __init__(self, ctx, ref_lengths):
+        self._lib = load_library()
+        lens = np.ascontiguousarray(ref_lengths, dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32)
+        self._create(ctx, int(lens.size), _ptr(lens) if lens.size else None)
+
+    def add_blocks(self, coffset, isize, end_coffset):
+        """the next BGZF blocks of the file in file order (bgzf_block_table) and the file offset behind the last of them"""
+        coffset, isize = np.ascontiguousarray(coffset, dtype=np.uint64), np.ascontiguousarray(isize, dtype=np.uint32)
+        if coffset.size != isize.size:
+            raise ValueError("coffset and isize: one entry per block")
+        self._check(self._lib.smi_bamindex_add_blocks(self._h, _ptr(coffset) if coffset.size else None, _ptr(isize) if isize.size else None,
+                                                      int(coffset.size), int(end_coffset)))
+
+    def add_segment(self, bam, recs, stream_off):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it, stream_off: the offset of bam[0] in the
+        inflated stream"""
+        args, recs = self._segment_args(bam, recs)
+        rc = self._lib.smi_bamindex_add_segment(self._h, *args, int(stream_off))
+        if rc == 2:
+            msg = self._lib.smi_last_error().decode(errors="replace")
+            name, rec = self._error_read()
+            raise BamIndexError(msg, name.decode("latin-1"), rec)
+        self._check(rc)
+
+    def finish(self):
+        """-> the .bai's bytes"""
+        return self._fetch(self._lib.smi_bamindex_finish, self._h).tobytes()
+
+    def stage_ms(self):
+        return self._named("stage_ms", BAMINDEX_STAGES, np.float32)
 
 
 # smi_poa_batch_ex's statistics, in SMI_POA_STAT_* order

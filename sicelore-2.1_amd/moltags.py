@@ -19,25 +19,33 @@ from .bamsegments import BGZF_EOF, segments
 from .isoformmatrix import isobam_header
 
 
-def _rewrite(ctx, h, in_bam, out_bam, header, segment_bytes, n_threads):
+def _rewrite(ctx, h, in_bam, out_bam, header, segment_bytes, n_threads, index=False):
+    """index: also leave <out_bam>.bai, built from the records and the BGZF blocks as they are written (bamindex.WriterIndex); the info
+    then has `index` (its counts and times; None when the output is not in coordinate order: the BAM is kept and `index_error` says why)"""
     t_all = time.perf_counter()
     tmp = f"{out_bam}.tmp{os.getpid()}"
     written = 0
     secs = dict(device=0.0, deflate=0.0, write=0.0)
     stage_ms = dict.fromkeys(_lib.MOLTAG_STAGES, 0.0)
+    wix = None
+    if index:
+        from .bamindex import WriterIndex
+        wix = WriterIndex(ctx)
     try:
         with open(tmp, "wb") as f:
-            def emit(data):
+            def emit(data, records=True):
                 t0 = time.perf_counter()
                 z = ctx.bgzf_deflate_device(np.frombuffer(data, dtype=np.uint8) if isinstance(data, bytes) else data)
                 t1 = time.perf_counter()
                 f.write(memoryview(z[:-28]))
                 secs["deflate"] += t1 - t0
                 secs["write"] += time.perf_counter() - t1
+                if wix is not None:
+                    wix.emitted(data, z[:-28], written, records)
                 return len(z) - 28
             for bam, recs, hdr in segments(in_bam, segment_bytes, n_threads):
                 if hdr is not None:
-                    written += emit(header(hdr))
+                    written += emit(header(hdr), records=False)
                 if recs.size:
                     t0 = time.perf_counter()
                     out = h.segment(bam, recs)
@@ -48,17 +56,24 @@ def _rewrite(ctx, h, in_bam, out_bam, header, segment_bytes, n_threads):
             f.write(BGZF_EOF)
             written += len(BGZF_EOF)
         os.replace(tmp, out_bam)
+        info = dict(h.counts(), stage_ms=stage_ms, seconds=secs, bytes_written=written)
+        if wix is not None:
+            info["index"], info["index_error"] = wix.finish(f"{out_bam}.bai", written - len(BGZF_EOF))
     finally:
+        if wix is not None:
+            wix.close()
         if os.path.exists(tmp):
             os.remove(tmp)
-    return dict(h.counts(), stage_ms=stage_ms, seconds=secs, bytes_written=written, wall_s=time.perf_counter() - t_all)
+    info["wall_s"] = time.perf_counter() - t_all
+    return info
 
 
-def add_bam_molecule_tags(ctx, in_bam, out_bam, cell_tag="BC", umi_tag="U8", rn_tag="RN", segment_bytes=256 << 20, n_threads=4):
-    """-> dict of counts, device ms per stage, seconds and bytes written.  The header is copied as it is (presorted = true, L44)."""
+def add_bam_molecule_tags(ctx, in_bam, out_bam, cell_tag="BC", umi_tag="U8", rn_tag="RN", segment_bytes=256 << 20, n_threads=4, index=False):
+    """-> dict of counts, device ms per stage, seconds and bytes written.  The header is copied as it is (presorted = true, L44).
+    index: also leave <out_bam>.bai, in the place of the `samtools index` the scripts run next (_rewrite)."""
     h = _lib.MolTag(ctx, _lib.MOLTAG_MOLECULE, cell_tag=cell_tag, umi_tag=umi_tag, rn_tag=rn_tag)
     try:
-        return _rewrite(ctx, h, in_bam, out_bam, lambda hdr: hdr, segment_bytes, n_threads)
+        return _rewrite(ctx, h, in_bam, out_bam, lambda hdr: hdr, segment_bytes, n_threads, index=index)
     finally:
         h.close()
 
@@ -68,9 +83,10 @@ METRICS = "TOTAL READS [{total_reads}] CORRECT_STRAND [{right_strand}]  WRONG_ST
 
 
 def add_gene_name_tag(ctx, in_bam, out_bam, refflat, gene_tag="GE", strand_tag="GS", function_tag="XF", use_strand_info=True,
-                      allow_multi_gene_reads=True, segment_bytes=256 << 20, n_threads=4, log=None):
+                      allow_multi_gene_reads=True, segment_bytes=256 << 20, n_threads=4, log=None, index=False):
     """-> dict of counts (the five metrics among them), device ms per stage, seconds and bytes written.  The header gets SO:unsorted (L80)
-    as ISOBAM's does.  log: a text stream for `Loaded <n> transcripts.` (L84) and the metrics line (L113)."""
+    as ISOBAM's does.  log: a text stream for `Loaded <n> transcripts.` (L84) and the metrics line (L113).  index: also leave
+    <out_bam>.bai (_rewrite); the records keep the input's order, and the index follows the records, not the header's SO."""
     with open(refflat, "rb") as f:
         rf = f.read()
     with open(in_bam, "rb") as f:                      # the reference dictionary comes first: the model keeps the genes on its sequences
@@ -84,7 +100,7 @@ def add_gene_name_tag(ctx, in_bam, out_bam, refflat, gene_tag="GE", strand_tag="
                         use_strand_info=use_strand_info, allow_multi_gene_reads=allow_multi_gene_reads)
         if log is not None:
             print(f"Loaded {genes.n_genes} transcripts.", file=log)
-        info = _rewrite(ctx, h, in_bam, out_bam, isobam_header, segment_bytes, n_threads)
+        info = _rewrite(ctx, h, in_bam, out_bam, isobam_header, segment_bytes, n_threads, index=index)
         if log is not None:
             print(METRICS.format(**info), file=log)
         return info

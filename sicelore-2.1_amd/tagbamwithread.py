@@ -7,7 +7,8 @@ The FASTQ is inflated on the host (plain or multi-member gzip, as pigz writes it
 (smi_tagbam_create); the BAM is read in segments of about segment_bytes compressed bytes (bamsegments.segments),
 each segment's records tagged on the device (smi_tagbam_segment) and BGZF-deflated (on the device, or with zlib-level host threads) into
 the output behind the input's header.  Records without a reference are dropped; a record whose read is not in the FASTQ is reported on
-stderr and dropped, and the run goes on (L96-101).  No .bai is written (main.nf:117 runs `samtools index` right after)."""
+stderr and dropped, and the run goes on (L96-101).  No .bai is written (main.nf:117 runs `samtools index` right after) unless index=True
+asks for the one htsjdk leaves beside the output (<outBam without .bam>.bai), built as the records are written (bamindex.WriterIndex)."""
 import sys
 import time
 
@@ -31,10 +32,11 @@ def read_fastq_text(path, n_threads=4):
 
 
 def tag_bam_with_reads(ctx, in_fastq, in_bam, out_bam, read_tag, qv_tag=None, segment_bytes=256 << 20, n_threads=4, bgzf="device", hash_bits=0,
-                       err=None):
+                       err=None, index=False):
     """`tagbamwithread -f in_fastq -b in_bam -o out_bam -r read_tag [-q qv_tag]` -> dict of counts (records in, written, unmapped dropped,
     missing) and seconds per phase.  The miss messages go to err (default sys.stderr) in record order.  bgzf: "device" (K-DEFLATE) or
-    "zlib" (host threads, level 5).  hash_bits: test only (smi_tagbam_config)."""
+    "zlib" (host threads, level 5).  hash_bits: test only (smi_tagbam_config).  index: also leave the .bai; the dict then has `index`
+    (its counts and times; None when the records written are not in coordinate order: the BAM is kept and `index_error` says why)."""
     if bgzf not in ("device", "zlib"):
         raise ValueError("bgzf: 'device' or 'zlib'")
     err = sys.stderr if err is None else err
@@ -53,9 +55,14 @@ def tag_bam_with_reads(ctx, in_fastq, in_bam, out_bam, read_tag, qv_tag=None, se
 
     n_in = n_written = n_unmapped = n_missing = 0
     stage = None
+    wix, at = None, 0
+    if index:
+        from .bamindex import WriterIndex
+        wix = WriterIndex(ctx)
     fh = open(out_bam, "wb")
     try:
-        def emit(data):
+        def emit(data, records=True):
+            nonlocal at
             t1 = time.perf_counter()
             if data.size:
                 if bgzf == "device":
@@ -63,11 +70,14 @@ def tag_bam_with_reads(ctx, in_fastq, in_bam, out_bam, read_tag, qv_tag=None, se
                 else:
                     z = _lib.bgzf_deflate(data, level=5, n_threads=n_threads)
                 fh.write(memoryview(z[:-28]))       # without the end-of-file block: more follows
+                if wix is not None:
+                    wix.emitted(data, z[:-28], at, records)
+                at += len(z) - 28
             secs["bgzf_write"] += time.perf_counter() - t1
 
         for bam, recs, hdr in segments(in_bam, segment_bytes, n_threads, secs):
             if hdr is not None:
-                emit(np.frombuffer(hdr, dtype=np.uint8))  # the input's header bytes, as assignumis copies them (BamWriter L32-48)
+                emit(np.frombuffer(hdr, dtype=np.uint8), records=False)  # the input's header bytes, as assignumis copies them (BamWriter L32-48)
             if recs.size:
                 t1 = time.perf_counter()
                 if stage is None or stage.array.size < 2 * bam.size:
@@ -88,13 +98,20 @@ def tag_bam_with_reads(ctx, in_fastq, in_bam, out_bam, read_tag, qv_tag=None, se
                 secs["tag"] += time.perf_counter() - t1
                 emit(out)
         fh.write(BGZF_EOF)
+        fh.close()
+        extra = {}
+        if wix is not None:
+            bai = (out_bam[:-4] if out_bam.endswith(".bam") else out_bam) + ".bai"      # htsjdk's name for it
+            extra["index"], extra["index_error"] = wix.finish(bai, at, log=err)
     finally:
         fh.close()
         table.close()
+        if wix is not None:
+            wix.close()
         if stage is not None:
             stage.close()
     return dict(records=n_in, written=n_written, unmapped=n_unmapped, missing=n_missing, fastq_records=table.n_records, seconds=secs,
-                stage_ms=stage_ms, wall_s=time.perf_counter() - t_all)
+                stage_ms=stage_ms, wall_s=time.perf_counter() - t_all, **extra)
 
 
 def _lib_read_name(bam, rec):

@@ -38,9 +38,9 @@ def main():
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
             "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse, "fusion": leg_fusion, "validator": leg_validator,
-            "fusionprep": leg_fusionprep}
+            "fusionprep": leg_fusionprep, "bamindex": leg_bamindex}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep", "bamindex")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -1014,6 +1014,85 @@ def leg_fusionprep(pkg, synth, ctx, dev, wl, used, res):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     res["fusionprep"] = out
+
+
+def _bamindex_fixture(n_recs, seed=91, n_ref=25, n_ops=32):
+    """a seeded, coordinate-sorted BAM of n_recs records over n_ref references: names of the molecule form (<16 bases>-<12 bases>-<n>), a
+    spliced CIGAR of n_ops operations (M of 20 .. 200 alternating with I, D or an N of 100 .. 5000), no sequence, one record in 500 without
+    a reference at the end -> (BGZF bytes, records)"""
+    from sicelore_amd import lib
+
+    rng = np.random.default_rng(seed)
+    n_un = n_recs // 500
+    n = n_recs - n_un
+    key = np.sort(rng.integers(0, n_ref << 27, n, dtype=np.int64))
+    rec = np.zeros(n_recs, dtype=[("bs", "<u4"), ("ref", "<i4"), ("pos", "<i4"), ("l_name", "u1"), ("mapq", "u1"), ("bin", "<u2"), ("n_cig", "<u2"),
+                                  ("flag", "<u2"), ("l_seq", "<i4"), ("nref", "<i4"), ("npos", "<i4"), ("tlen", "<i4"), ("name", "u1", (38,)),
+                                  ("cigar", "<u4", (n_ops,))])
+    rec["bs"] = rec.dtype.itemsize - 4
+    rec["ref"][:n], rec["pos"][:n] = key >> 27, key & ((1 << 27) - 1)
+    rec["ref"][n:], rec["pos"][n:] = -1, -1
+    rec["flag"][n:] = 4
+    rec["l_name"], rec["mapq"], rec["bin"], rec["n_cig"], rec["nref"], rec["npos"] = 38, 60, 4680, n_ops, -1, -1
+    rec["n_cig"][n:] = 0
+    rec["name"][:, :30] = np.frombuffer(b"ACGTACGTACGTACGT-TTTTGGGGCCCC-", dtype=np.uint8)
+    k = np.arange(n_recs, dtype=np.int64)
+    for j in range(7):
+        rec["name"][:, 36 - j] = 48 + (k // 10 ** j) % 10
+    ops = np.where(np.arange(n_ops) % 2 == 0, 0, rng.integers(1, 4, (n_recs, n_ops)))            # M, then I / D / N
+    length = np.where(ops == 0, rng.integers(20, 201, (n_recs, n_ops)), np.where(ops == 3, rng.integers(100, 5001, (n_recs, n_ops)), rng.integers(1, 6, (n_recs, n_ops))))
+    rec["cigar"] = (length << 4 | ops).astype(np.uint32)
+    rec["cigar"][n:] = 0                                       # (the bytes stay: records of one size; n_cigar says 0 -> they are attribute bytes no one reads)
+    body = rec.view(np.uint8).reshape(n_recs, -1)
+    # records without a reference carry no CIGAR: cut their rows to the 74 bytes of the fixed part and the name
+    placed = body[:n].reshape(-1)
+    tail = body[n:, :74].copy()
+    tail[:, :4] = np.frombuffer(struct.pack("<I", 70), dtype=np.uint8)
+    refs = b"".join(struct.pack("<I", len(nm) + 1) + nm + b"\0" + struct.pack("<I", 1 << 28) for nm in (b"chr%d" % (r + 1) for r in range(n_ref)))
+    head = b"BAM\1" + struct.pack("<I", 0) + struct.pack("<I", n_ref) + refs
+    data = np.concatenate([np.frombuffer(head, dtype=np.uint8), placed, tail.reshape(-1)])
+    return lib.bgzf_deflate(data, level=1, n_threads=16), n_recs
+
+
+def leg_bamindex(pkg, synth, ctx, dev, wl, used, res):
+    """K-BAI (`bamindex.py`, in the place of `samtools index`), file to file: a seeded, sorted BAM of SMI_MB_BAI_RECS records (2,000,000) in
+    segments of SMI_MB_BAI_SEGMENT compressed bytes (64 MiB); index_bam once (after a run that loads the code objects): device ms per
+    stage (HIP events), the seconds in read and inflate, in the record index, in the device calls and in the write, wall seconds.  Then
+    AddBamMoleculeTags on the same file with index=False and with index=True: the difference is what the index costs as a by-product of
+    the write."""
+    import shutil
+    import tempfile
+
+    bi = importlib.import_module(graft.PKG_NAME + ".bamindex")
+    mt = importlib.import_module(graft.PKG_NAME + ".moltags")
+    n_recs = int(os.environ.get("SMI_MB_BAI_RECS", "2000000"))
+    seg = int(os.environ.get("SMI_MB_BAI_SEGMENT", str(64 << 20)))
+    t0 = time.perf_counter()
+    z, n_rec = _bamindex_fixture(n_recs)
+    out = {"records": n_rec, "bam_bytes": int(z.size), "segment_bytes": seg, "fixture_s": time.perf_counter() - t0}
+    d = tempfile.mkdtemp(prefix="bamindex_")
+    try:
+        src = os.path.join(d, "in.bam")
+        z.tofile(src)
+        bi.index_bam(ctx, src, segment_bytes=seg, n_threads=16)                         # the first run loads the code objects
+        info = bi.index_bam(ctx, src, segment_bytes=seg, n_threads=16)
+        out["index_bam"] = dict({k: info[k] for k in ("records", "refs_with_records", "chunks", "no_coor", "segments", "blocks", "bins", "windows")},
+                                stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"], bytes_written=info["bytes_written"],
+                                records_per_s=info["records"] / info["wall_s"])
+        dst = os.path.join(d, "tags.bam")
+        mt.add_bam_molecule_tags(ctx, src, dst, segment_bytes=seg, n_threads=16)
+        for name, flag in (("add_bam_molecule_tags", False), ("add_bam_molecule_tags_index", True)):
+            info = mt.add_bam_molecule_tags(ctx, src, dst, segment_bytes=seg, n_threads=16, index=flag)
+            out[name] = dict(records=info["records"], seconds=info["seconds"], wall_s=info["wall_s"], bytes_written=info["bytes_written"])
+            if flag:
+                ix = info["index"]
+                out[name]["index"] = None if ix is None else dict(stage_ms=ix["stage_ms"], seconds=ix["seconds"], bytes_written=ix["bytes_written"],
+                                                                  chunks=ix["chunks"], segments=ix["segments"])
+                out[name]["index_error"] = info["index_error"]
+        out["index_by_product_wall_s"] = out["add_bam_molecule_tags_index"]["wall_s"] - out["add_bam_molecule_tags"]["wall_s"]
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    res["bamindex"] = out
 
 
 def _snp_fixture(n_recs, n_lines, n_cells, seed=51):

@@ -1639,6 +1639,54 @@ int smi_bamindex_error_read(const smi_bamindex *h, char *name, size_t cap, int64
 int smi_bamindex_stage_ms(const smi_bamindex *h, float *ms);
 int smi_bamindex_free(smi_bamindex *h);
 
+/* ---- BamSort (K-SORT-KEY, K-SORT-PERM, K-SORT-WINDOWS, K-SORT-GATHER, smi_bamsort.hip) -----------------------------------------------------
+ * The coordinate sort of a BAM, in the place of `samtools sort`: this build's own canonical order: reference rank
+ * (ref_id for 0 <= ref_id < n_ref, n_ref for a negative one), then pos + 1 as an unsigned 32-bit number, then the reverse-strand bit
+ * (flag 0x10); records with equal keys keep their input order.  The record bytes of the whole file stay resident in device memory.
+ * smi_bamsort_create: n_ref references of the header; resident_bytes bounds the record bytes plus SMI_BAMSORT_PER_RECORD bytes per record
+ *   (0: two fifths of the free device memory); window_bytes: the output leaves in windows of at most that many bytes of whole records,
+ *   at least one record each.  SMI_BAMSORT_STORE_BYTES=4 in the environment at creation: K-SORT-GATHER in 4-byte words (measurement; the same
+ *   bytes come out).
+ * smi_bamsort_add_segment: bam / n_bam / recs / n as smi_tagbam_segment takes them.  Returns 2 at a ref_id >= n_ref: smi_last_error and
+ *   smi_bamsort_error_read name the first such read, and the handle takes nothing further.  A file beyond resident_bytes and more than
+ *   2^31 - 1 records are refused by name (SMI_ERR_INVALID).
+ * smi_bamsort_finish: sorts; *n_windows output windows, *n_records records.
+ * smi_bamsort_window: window k (any order, any number of times) gathered in rank order and deflated into BGZF blocks on the device
+ *   (smi_bgzf_deflate_device; no end-of-file block).  out_bgzf == NULL: *n_out = the room out_bgzf needs, *n_inflated = the window's
+ *   inflated bytes, nothing runs; 1 = cap or cap_inflated is too small.  out_inflated (may be NULL): the window's records as they stand
+ *   in the blocks.
+ * smi_bamsort_counts: SMI_BAMSORT_N_COUNT entries.  smi_bamsort_stage_ms: SMI_BAMSORT_N_STAGE device times of the last add_segment
+ *   (key), finish (sort) or window (gather, deflate: the latter with its copy to the host).
+ * smi_bamsort_host_loop (measurement and tests, after finish): the same sort on one host thread over the bytes the device holds (the
+ *   keys rebuilt from the records, std::stable_sort, one memcpy per record): its seconds, the copies from the device not counted, and
+ *   the number of records whose bytes in the device's windows differ from it (0). */
+#define SMI_BAMSORT_RECORDS 0        /* records taken */
+#define SMI_BAMSORT_SEGMENTS 1       /* segments taken */
+#define SMI_BAMSORT_WINDOWS 2        /* output windows (after finish) */
+#define SMI_BAMSORT_ARENA_BYTES 3    /* record bytes resident */
+#define SMI_BAMSORT_ARENA_HELD 4     /* bytes the arena holds room for */
+#define SMI_BAMSORT_LARGEST_WINDOW 5 /* bytes of the largest window (after finish) */
+#define SMI_BAMSORT_BYTES_OUT 6      /* inflated bytes that left through smi_bamsort_window */
+#define SMI_BAMSORT_N_COUNT 7
+#define SMI_BAMSORT_MS_KEY 0
+#define SMI_BAMSORT_MS_SORT 1
+#define SMI_BAMSORT_MS_GATHER 2
+#define SMI_BAMSORT_MS_DEFLATE 3
+#define SMI_BAMSORT_N_STAGE 4
+#define SMI_BAMSORT_PER_RECORD 48
+typedef struct smi_bamsort smi_bamsort;
+int smi_bamsort_create(smi_ctx *ctx, int32_t n_ref, uint64_t resident_bytes, uint64_t window_bytes, smi_bamsort **out);
+int smi_bamsort_add_segment(smi_bamsort *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n);
+int smi_bamsort_finish(smi_bamsort *h, int64_t *n_windows, int64_t *n_records);
+int smi_bamsort_window(smi_bamsort *h, int64_t k, uint8_t *out_bgzf, size_t cap, size_t *n_out, uint8_t *out_inflated, size_t cap_inflated,
+                       size_t *n_inflated);
+int smi_bamsort_counts(const smi_bamsort *h, int64_t *counts);
+int smi_bamsort_stage_ms(const smi_bamsort *h, float *ms);
+/* the read that ended the run (smi_bamsort_add_segment returned 2): its name (cut to cap - 1 bytes) and its 0-based number in the file; -1 = none */
+int smi_bamsort_error_read(const smi_bamsort *h, char *name, size_t cap, int64_t *record);
+int smi_bamsort_free(smi_bamsort *h);
+int smi_bamsort_host_loop(smi_bamsort *h, double *seconds, int64_t *mismatches);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

@@ -85,6 +85,8 @@ EXPORTS = [
     "smi_clipexport_stage_ms", "smi_clipexport_free", "smi_clipexport_host_loop",
     "smi_bgzf_block_table", "smi_bamindex_create", "smi_bamindex_add_blocks", "smi_bamindex_add_segment", "smi_bamindex_finish",
     "smi_bamindex_counts", "smi_bamindex_error_read", "smi_bamindex_stage_ms", "smi_bamindex_free",
+    "smi_bamsort_create", "smi_bamsort_add_segment", "smi_bamsort_finish", "smi_bamsort_window", "smi_bamsort_counts", "smi_bamsort_stage_ms",
+    "smi_bamsort_error_read", "smi_bamsort_free", "smi_bamsort_host_loop",
     "smi_select_valid_cells",
 ]
 
@@ -340,6 +342,15 @@ def load_library():
     lib.smi_bamindex_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
     lib.smi_bamindex_stage_ms.argtypes = [vp, vp]
     lib.smi_bamindex_free.argtypes = [vp]
+    lib.smi_bamsort_create.argtypes = [vp, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(vp)]
+    lib.smi_bamsort_add_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32]
+    lib.smi_bamsort_finish.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_bamsort_window.argtypes = [vp, ctypes.c_int64, vp, sz, ctypes.POINTER(sz), vp, sz, ctypes.POINTER(sz)]
+    lib.smi_bamsort_counts.argtypes = [vp, vp]
+    lib.smi_bamsort_stage_ms.argtypes = [vp, vp]
+    lib.smi_bamsort_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_bamsort_free.argtypes = [vp]
+    lib.smi_bamsort_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     lib.smi_poa_batch_ex.argtypes = lib.smi_poa_batch.argtypes + [vp]
@@ -1270,6 +1281,70 @@ class BamIndex(_Handle):
 
     def stage_ms(self):
         return self._named("stage_ms", BAMINDEX_STAGES, np.float32)
+
+
+# smi_bamsort_counts, in SMI_BAMSORT_* order (SMI_BAMSORT_N_COUNT entries); smi_bamsort_stage_ms (SMI_BAMSORT_N_STAGE entries)
+BAMSORT_COUNTS = ("records", "segments", "windows", "arena_bytes", "arena_held", "largest_window", "bytes_out")
+BAMSORT_STAGES = ("key", "sort", "gather", "deflate")
+
+
+class BamSortError(SmiError):
+    """a record the sort stops at (smi_bamsort_add_segment returned 2: a ref_id outside the header); .read: its name, .record: its 0-based
+    number in the file"""
+
+    def __init__(self, msg, read, record):
+        super().__init__(msg)
+        self.read, self.record = read, record
+
+
+class BamSort(_Handle):
+    """The coordinate sort of a BAM that is resident in device memory (smi_bamsort_*): the inflated stream in segments in, after finish()
+    the sorted records out in windows of BGZF blocks.  n_ref: the number of the header's references; resident_bytes: the bound on the
+    record bytes and the per-record arrays on the device (None: two fifths of the free device memory)."""
+    _NAME, _COUNTS = "bamsort", BAMSORT_COUNTS
+
+    def __init__(self, ctx, n_ref, resident_bytes=None, window_bytes=64 << 20):
+        self._lib = load_library()
+        self._z = self._data = None
+        self._create(ctx, int(n_ref), int(resident_bytes or 0), int(window_bytes))
+
+    def add_segment(self, bam, recs):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
+        args, recs = self._segment_args(bam, recs)
+        rc = self._lib.smi_bamsort_add_segment(self._h, *args)
+        if rc == 2:
+            msg = self._lib.smi_last_error().decode(errors="replace")
+            name, rec = self._error_read()
+            raise BamSortError(msg, name.decode("latin-1"), rec)
+        self._check(rc)
+
+    def finish(self):
+        """sorts -> (number of output windows, number of records)"""
+        nw, nr = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.smi_bamsort_finish(self._h, ctypes.byref(nw), ctypes.byref(nr)))
+        return nw.value, nr.value
+
+    def window(self, k, inflated=False):
+        """window k -> (its BGZF blocks without an end-of-file block, its inflated records or None), uint8 views of buffers that the next
+        call writes again"""
+        nz, nd = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self._check(self._lib.smi_bamsort_window(self._h, int(k), None, 0, ctypes.byref(nz), None, 0, ctypes.byref(nd)))
+        if self._z is None or self._z.size < nz.value:
+            self._z = np.empty(nz.value, dtype=np.uint8)
+        if inflated and (self._data is None or self._data.size < nd.value):
+            self._data = np.empty(max(nd.value, 1), dtype=np.uint8)
+        self._check(self._lib.smi_bamsort_window(self._h, int(k), _ptr(self._z), self._z.size, ctypes.byref(nz), _ptr(self._data) if inflated else None,
+                                                 self._data.size if inflated else 0, ctypes.byref(nd)))
+        return self._z[:nz.value], self._data[:nd.value] if inflated else None
+
+    def stage_ms(self):
+        return self._named("stage_ms", BAMSORT_STAGES, np.float32)
+
+    def host_loop(self):
+        """-> (seconds of the same sort on one host thread, records whose bytes differ from the device's windows)"""
+        sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
+        self._check(self._lib.smi_bamsort_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)))
+        return sec.value, bad.value
 
 
 # smi_poa_batch_ex's statistics, in SMI_POA_STAT_* order

@@ -38,9 +38,9 @@ def main():
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
             "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse, "fusion": leg_fusion, "validator": leg_validator,
-            "fusionprep": leg_fusionprep, "bamindex": leg_bamindex}
+            "fusionprep": leg_fusionprep, "bamindex": leg_bamindex, "bamsort": leg_bamsort}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep", "bamindex")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep", "bamindex", "bamsort")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -1093,6 +1093,103 @@ def leg_bamindex(pkg, synth, ctx, dev, wl, used, res):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     res["bamindex"] = out
+
+
+def _bamsort_fixture(n_recs, with_seq, seed=101, n_ref=25, n_ops=8, chunk=1000):
+    """a seeded BAM of n_recs records in shuffled order over n_ref references: names of the molecule form, a CIGAR of n_ops operations, no
+    sequence, random strand, one record in 500 without a reference; with_seq: the attributes US:Z and QS:Z of L bytes each, L seeded in
+    400 .. 800 and one L per run of `chunk` records (the rows of a run are built as one array) -> (BGZF bytes, records, inflated bytes)"""
+    from sicelore_amd import lib
+
+    rng = np.random.default_rng(seed)
+    refs = b"".join(struct.pack("<I", len(nm) + 1) + nm + b"\0" + struct.pack("<I", 1 << 28) for nm in (b"chr%d" % (r + 1) for r in range(n_ref)))
+    parts = [np.frombuffer(b"BAM\1" + struct.pack("<I", 0) + struct.pack("<I", n_ref) + refs, dtype=np.uint8)]
+    for at in range(0, n_recs, chunk):
+        m = min(chunk, n_recs - at)
+        L = int(rng.integers(400, 801)) if with_seq else 0
+        fields = [("bs", "<u4"), ("ref", "<i4"), ("pos", "<i4"), ("l_name", "u1"), ("mapq", "u1"), ("bin", "<u2"), ("n_cig", "<u2"), ("flag", "<u2"),
+                  ("l_seq", "<i4"), ("nref", "<i4"), ("npos", "<i4"), ("tlen", "<i4"), ("name", "u1", (38,)), ("cigar", "<u4", (n_ops,))]
+        if with_seq:
+            fields += [("us_tag", "u1", (3,)), ("us", "u1", (L + 1,)), ("qs_tag", "u1", (3,)), ("qs", "u1", (L + 1,))]
+        rec = np.zeros(m, dtype=fields)
+        rec["bs"] = rec.dtype.itemsize - 4
+        rec["ref"], rec["pos"] = rng.integers(0, n_ref, m), rng.integers(0, 1 << 27, m)
+        rec["flag"] = 16 * rng.integers(0, 2, m)
+        un = rng.integers(0, 500, m) == 0
+        rec["ref"][un], rec["pos"][un], rec["flag"][un] = -1, -1, 4
+        rec["l_name"], rec["mapq"], rec["bin"], rec["n_cig"], rec["nref"], rec["npos"] = 38, 60, 4680, n_ops, -1, -1
+        rec["name"][:, :30] = np.frombuffer(b"ACGTACGTACGTACGT-TTTTGGGGCCCC-", dtype=np.uint8)
+        k = np.arange(at, at + m, dtype=np.int64)
+        for j in range(7):
+            rec["name"][:, 36 - j] = 48 + (k // 10 ** j) % 10
+        rec["cigar"] = (rng.integers(20, 201, (m, n_ops)) << 4 | (np.arange(n_ops) % 2) * 3).astype(np.uint32)      # M and N in turn
+        if with_seq:
+            rec["us_tag"], rec["qs_tag"] = np.frombuffer(b"USZ", dtype=np.uint8), np.frombuffer(b"QSZ", dtype=np.uint8)
+            rec["us"][:, :L] = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, (m, L))]
+            rec["qs"][:, :L] = rng.integers(35, 75, (m, L), dtype=np.uint8)
+        parts.append(rec.view(np.uint8).reshape(-1))
+    data = np.concatenate(parts)
+    return lib.bgzf_deflate(data, level=1, n_threads=16), n_recs, int(data.size)
+
+
+def leg_bamsort(pkg, synth, ctx, dev, wl, used, res):
+    """K-SORT (`bamsort.py`, in the place of `samtools sort` and `samtools index`), file to file: a seeded BAM of SMI_MB_SORT_RECS records
+    (2,000,000) in shuffled order, once without sequence and once with US / QS of 400 .. 800 bytes, in segments of SMI_MB_SORT_SEGMENT
+    compressed bytes (64 MiB) and windows of 64 MiB; sort_bam after a run that loads the code objects, without and with index=True: device
+    ms per stage (HIP events), the seconds in read and inflate, in the device calls and in the write, wall seconds; the gather's bytes per
+    second from its stage time, and the same run with the gather's 4-byte stores (SMI_BAMSORT_STORE_BYTES=4); then
+    smi_bamsort_host_loop: the seconds of the same sort on one host thread and its mismatch count."""
+    import shutil
+    import tempfile
+
+    bs = importlib.import_module(graft.PKG_NAME + ".bamsort")
+    segs = importlib.import_module(graft.PKG_NAME + ".bamsegments")
+    lib = importlib.import_module(graft.PKG_NAME + ".lib")
+    n_recs = int(os.environ.get("SMI_MB_SORT_RECS", "2000000"))
+    seg = int(os.environ.get("SMI_MB_SORT_SEGMENT", str(64 << 20)))
+    res["bamsort"] = {}
+    for case, with_seq in (("no_sequence", False), ("us_qs_400_800", True)):
+        t0 = time.perf_counter()
+        z, n_rec, inflated = _bamsort_fixture(n_recs, with_seq)
+        out = {"records": n_rec, "bam_bytes": int(z.size), "inflated_bytes": inflated, "segment_bytes": seg, "fixture_s": time.perf_counter() - t0}
+        d = tempfile.mkdtemp(prefix="bamsort_")
+        try:
+            src, dst = os.path.join(d, "in.bam"), os.path.join(d, "out.bam")
+            z.tofile(src)
+            del z
+            bs.sort_bam(ctx, src, dst, segment_bytes=seg, n_threads=16)                         # the first run loads the code objects
+            for name, flag in (("sort_bam", False), ("sort_bam_index", True)):
+                info = bs.sort_bam(ctx, src, dst, segment_bytes=seg, n_threads=16, index=flag)
+                out[name] = dict({k: info[k] for k in ("records", "segments", "windows", "arena_bytes", "arena_held", "largest_window")},
+                                 stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"], bytes_written=info["bytes_written"],
+                                 gather_bytes_per_s=info["arena_bytes"] / max(info["stage_ms"]["gather"], 1e-6) * 1e3)
+                if flag:
+                    ix = info["index"]
+                    out[name]["index"] = None if ix is None else dict(stage_ms=ix["stage_ms"], seconds=ix["seconds"], bytes_written=ix["bytes_written"])
+                    out[name]["index_error"] = info["index_error"]
+            os.environ["SMI_BAMSORT_STORE_BYTES"] = "4"
+            try:
+                info = bs.sort_bam(ctx, src, dst, segment_bytes=seg, n_threads=16)
+            finally:
+                del os.environ["SMI_BAMSORT_STORE_BYTES"]
+            out["gather_4_byte_stores"] = dict(gather_ms=info["stage_ms"]["gather"],
+                                               gather_bytes_per_s=info["arena_bytes"] / max(info["stage_ms"]["gather"], 1e-6) * 1e3)
+            h = None
+            try:
+                for bam, recs, hdr in segs.segments(src, seg, 16):
+                    if hdr is not None:
+                        h = lib.BamSort(ctx, len(lib.bam_header(np.frombuffer(hdr, dtype=np.uint8))[1]))
+                    if recs.size:
+                        h.add_segment(bam, recs)
+                h.finish()
+                sec, bad = h.host_loop()
+                out["host_loop"] = dict(seconds=sec, mismatches=bad)
+            finally:
+                if h is not None:
+                    h.close()
+        finally:
+            shutil.rmtree(d, ignore_errors=True)
+        res["bamsort"][case] = out
 
 
 def _snp_fixture(n_recs, n_lines, n_cells, seed=51):

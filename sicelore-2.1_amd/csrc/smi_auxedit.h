@@ -13,13 +13,13 @@
 //   uint32_t Tail::put(Field *f, int &n)    ... applied after it as put_field / remove_field calls in order -> SMI_TAG_* error bits
 //   const uint8_t *payload() const          the byte array the kind-3 (Z) payloads are copied from
 // AuxRewriter is the host side of the sequence: SIZE launch, hipcub exclusive scan, WRITE launch, with the buffers they need.
+// (ld_u32, st_u32 and the hipcub scratch are smi_device.h's.)
 #pragma once
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <functional>
 #include <string>
 
+#include "smi_device.h"
 #include "smi_internal.h"
 
 namespace smi {
@@ -60,10 +60,6 @@ __device__ __forceinline__ int hex_val(uint8_t c) {
     if (c >= 'a' && c <= 'f') return c - 'a' + 10;
     return -1;
 }
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
-__device__ __forceinline__ void st_u32(uint8_t *p, uint32_t v) {
-    for (int k = 0; k < 4; k++) p[k] = (uint8_t)(v >> (8 * k));
-}
 
 // insert or replace (a repeated tag keeps its last value); false: more than kMaxFields attributes
 static __device__ bool put_field(Field *f, int &n, const Field &x) {
@@ -86,38 +82,10 @@ __device__ __forceinline__ void remove_field(Field *f, int &n, uint16_t key) {
         }
 }
 
-// One step of the walk below for a kernel that looks attributes up and rewrites none (K-CLIP-FLAG, smi_clipexport.hip): the attribute at p
-// (tag at p, type at p + 2, value at p + 3) -> the offset behind it under the same type rules; 0: malformed, unknown type or past `end`
-__device__ __forceinline__ uint64_t aux_next(const uint8_t *__restrict__ bam, uint64_t p, uint64_t end) {
-    if (p + 3 > end) return 0;
-    const uint8_t ty = bam[p + 2];
-    const uint64_t v = p + 3;
-    uint64_t q;
-    switch (ty) {
-        case 'A': case 'c': case 'C': q = v + 1; break;
-        case 's': case 'S': q = v + 2; break;
-        case 'i': case 'I': case 'f': q = v + 4; break;
-        case 'Z': case 'H':
-            q = v;
-            while (q < end && bam[q]) q++;
-            if (q >= end) return 0;
-            q++;
-            break;
-        case 'B': {
-            if (v + 5 > end) return 0;
-            const uint8_t sub = bam[v];
-            const uint32_t w = sub == 'c' || sub == 'C' ? 1 : sub == 's' || sub == 'S' ? 2 : sub == 'i' || sub == 'I' || sub == 'f' ? 4 : 0;
-            if (!w) return 0;
-            q = v + 5 + (uint64_t)w * ld_u32(bam + v + 1);
-            break;
-        }
-        default: return 0;
-    }
-    return q > end ? 0 : q;
-}
-
 // lane 0: the attribute list of record rec as written (its own attributes, then what `tail` puts), in f[0 .. n), sorted by binary tag;
-// returns SMI_TAG_* error bits (0 = fine)
+// returns SMI_TAG_* error bits (0 = fine).  The walk decodes each value where it steps over it, so it carries the size rule of lr::aux_size
+// (smi_longread.h) itself: stepping with that function and decoding after it cost K-TAG-ASM's WRITE pass 2.4 % (profiles/device_layer_compare.md);
+// the damaged lists of tests/auxcases.py go through both.
 template <class Tail>
 static __device__ uint32_t parse_fields(const uint8_t *__restrict__ bam, const smi_bam_record &rec, const Tail &tail, Field *f, int &n) {
     n = 0;
@@ -311,8 +279,7 @@ inline std::string aux_error_text(uint32_t err) {
 struct AuxRewriter {
     uint64_t *d_size = nullptr, *d_off = nullptr;
     size_t size_cap = 0, off_cap = 0;
-    void *d_cub = nullptr;
-    size_t cub_cap = 0;
+    Scratch cub{"the attribute rewrite"};
     uint8_t *d_out = nullptr;
     size_t out_cap = 0;
     uint32_t *d_err = nullptr, err = 0;  // err: the bits of the last size() / write()
@@ -321,7 +288,7 @@ struct AuxRewriter {
     AuxRewriter() = default;
     AuxRewriter(const AuxRewriter &) = delete;
     ~AuxRewriter() {  // (on the device of the buffers: the owners set it before they release)
-        for (void *p : {(void *)d_size, (void *)d_off, d_cub, (void *)d_out, (void *)d_err})
+        for (void *p : {(void *)d_size, (void *)d_off, (void *)d_out, (void *)d_err})
             if (p) (void)hipFree(p);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -334,11 +301,10 @@ struct AuxRewriter {
              float *ms, const std::function<hipError_t()> &before_wait = nullptr) {
         *total = 0;
         err = 0;
-        size_t cub = 0;
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub, (uint64_t *)nullptr, (uint64_t *)nullptr, n + 1, s));
         if (int rc = grow(&d_size, size_cap, n + 1)) return rc;
         if (int rc = grow(&d_off, off_cap, n + 1)) return rc;
-        if (int rc = grow((uint8_t **)&d_cub, cub_cap, cub)) return rc;
+        const auto scan = [&](void *p, size_t &t) { return hipcub::DeviceScan::ExclusiveSum(p, t, d_size, d_off, n + 1, s); };
+        if (int rc = reserve(cub, scan)) return rc;
         if (!d_err) SMI_HIP(hipMalloc((void **)&d_err, 4));
         for (hipEvent_t &e : ev)
             if (!e) SMI_HIP(hipEventCreate(&e));
@@ -349,7 +315,7 @@ struct AuxRewriter {
             hipLaunchKernelGGL((k_aux_rewrite<false, Source>), dim3(blocks_for(n, kAuxWaves)), dim3(64 * kAuxWaves), 0, s, d_bam, d_recs, n, src, d_size,
                                (const uint64_t *)nullptr, (uint8_t *)nullptr, (uint64_t)0, d_err);
         SMI_HIP(hipGetLastError());
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_cub, cub, d_size, d_off, n + 1, s));
+        if (int rc = run_reserved(cub, scan)) return rc;
         SMI_HIP(hipEventRecord(ev[1], s));
         SMI_HIP(hipMemcpyAsync(total, d_off + n, 8, hipMemcpyDeviceToHost, s));
         SMI_HIP(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s));

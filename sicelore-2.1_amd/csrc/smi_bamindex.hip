@@ -17,10 +17,10 @@
 // the window values of a sorted file being non-decreasing).  The host serialises the sorted arrays.
 #include <climits>
 #include <cstring>
-#include <hipcub/hipcub.hpp>
 #include <string>
 #include <vector>
 
+#include "smi_device.h"
 #include "smi_handle.h"
 #include "smi_internal.h"
 
@@ -56,12 +56,6 @@ struct Meta {  // per reference
     unsigned long long *min_off, *max_off, *n_mapped, *n_flag4;
     uint32_t *max_end, *n_bin;
 };
-
-__device__ __forceinline__ uint32_t ld32(const uint8_t *p) {
-    uint32_t w;
-    __builtin_memcpy(&w, p, 4);
-    return w;
-}
 
 // start[0] <= p: the last block j with start[j] <= p (the slice ends with the entry of the position behind its last byte)
 __device__ __forceinline__ uint64_t virtual_offset(const uint64_t *__restrict__ start, const uint64_t *__restrict__ coff, uint32_t nb, uint64_t p) {
@@ -114,7 +108,7 @@ __global__ __launch_bounds__(kBaiBlock) void k_bai_rec(RecArgs a) {
         ref = r->ref_id;
         pos = r->pos;
         for (uint32_t k = sub; k < n_cigar; k += kBaiLanes) {
-            const uint32_t w = ld32(a.bam + cigar + 4ull * k);
+            const uint32_t w = ld_u32(a.bam + cigar + 4ull * k);
             if ((0x18Du >> (w & 15)) & 1) sum += w >> 4;  // M D N = X
         }
     }
@@ -367,8 +361,8 @@ struct smi_bamindex {
     BaiRec *d_rec = nullptr;
     uint32_t *d_head = nullptr, *d_incl = nullptr;
     uint64_t *d_blk = nullptr;  // start[nb], coff[nb]
-    void *d_cub = nullptr;
-    size_t bam_cap = 0, recs_cap = 0, rec_cap = 0, head_cap = 0, incl_cap = 0, blk_cap = 0, cub_cap = 0;
+    Scratch cub{"BamIndex"};    // hipcub's
+    size_t bam_cap = 0, recs_cap = 0, rec_cap = 0, head_cap = 0, incl_cap = 0, blk_cap = 0;
     Events ev;
     int64_t counts[SMI_BAI_N_COUNT] = {};
     float ms[SMI_BAI_N_STAGE] = {};
@@ -386,13 +380,11 @@ namespace {
 
 void bai_release(smi_bamindex *h) {
     void *bufs[] = {h->d_win_off, h->d_win_cap, h->d_lin, h->d_meta64, h->d_meta32, h->d_ckey, h->d_cval, h->d_carry, h->d_words,
-                    h->d_bam,     h->d_recs,    h->d_rec, h->d_head,   h->d_incl,   h->d_blk,  h->d_cub};
+                    h->d_bam,     h->d_recs,    h->d_rec, h->d_head,   h->d_incl,   h->d_blk};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     delete h;
 }
-
-int bai_cub(smi_bamindex *h, size_t bytes) { return grow((uint8_t **)&h->d_cub, h->cub_cap, bytes); }
 
 }  // namespace
 
@@ -572,9 +564,8 @@ extern "C" int smi_bamindex_add_segment(smi_bamindex *h, const uint8_t *bam, siz
     if (int rc = grow(&h->d_blk, h->blk_cap, 2 * nb)) return rc;
     if (int rc = grow_keep(&h->d_ckey, h->ckey_cap, (size_t)h->n_chunks, (size_t)h->n_chunks + N, s)) return rc;
     if (int rc = grow_keep(&h->d_cval, h->cval_cap, (size_t)h->n_chunks, (size_t)h->n_chunks + N, s)) return rc;
-    size_t cub = 0;
-    SMI_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, cub, h->d_head, h->d_incl, n, s));
-    if (int rc = bai_cub(h, cub)) return rc;
+    const auto scan = [&](void *p, size_t &t) { return hipcub::DeviceScan::InclusiveSum(p, t, h->d_head, h->d_incl, n, s); };
+    if (int rc = reserve(h->cub, scan)) return rc;
     h->failed = true;  // until the segment is through: a call that fails half-way leaves the resident arrays in no known state
     SMI_HIP(hipMemcpyAsync(h->d_bam, bam, n_bam, hipMemcpyHostToDevice, s));
     SMI_HIP(hipMemcpyAsync(h->d_recs, recs, N * sizeof(smi_bam_record), hipMemcpyHostToDevice, s));
@@ -593,8 +584,7 @@ extern "C" int smi_bamindex_add_segment(smi_bamindex *h, const uint8_t *bam, siz
     if (int rc = h->ev.begin(s)) return rc;
     hipLaunchKernelGGL(k_bai_order, dim3(grid(N)), dim3(kBaiBlock), 0, s, h->d_rec, (uint32_t)n, (const Carry *)h->d_carry, h->d_head, h->meta(), h->d_words);
     SMI_HIP(hipGetLastError());
-    cub = h->cub_cap;
-    SMI_HIP(hipcub::DeviceScan::InclusiveSum(h->d_cub, cub, h->d_head, h->d_incl, n, s));
+    if (int rc = run_reserved(h->cub, scan)) return rc;
     if (int rc = h->ev.end(s, &h->ms[1])) return rc;
     unsigned long long words[W_COUNT] = {};
     uint32_t heads = 0;
@@ -657,13 +647,11 @@ int bai_finish(smi_bamindex *h) {
     if (nc) {
         int ref_bits = 1;
         while (ref_bits < 31 && (1ll << ref_bits) < h->n_ref) ref_bits++;
-        size_t t1 = 0, t2 = 0;
-        SMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, h->d_ckey, skey.p, h->d_cval, sval.p, (int)nc, 0, 32 + ref_bits, s));
-        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, skey.p, ukey.p, ucount.p, n_runs.p, (int)nc, s));
-        if (int rc = bai_cub(h, std::max(t1, t2))) return rc;
-        t1 = t2 = h->cub_cap;
-        SMI_HIP(hipcub::DeviceRadixSort::SortPairs(h->d_cub, t1, h->d_ckey, skey.p, h->d_cval, sval.p, (int)nc, 0, 32 + ref_bits, s));
-        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(h->d_cub, t2, skey.p, ukey.p, ucount.p, n_runs.p, (int)nc, s));
+        const auto sort = [&](void *p, size_t &t) { return hipcub::DeviceRadixSort::SortPairs(p, t, h->d_ckey, skey.p, h->d_cval, sval.p, (int)nc, 0, 32 + ref_bits, s); };
+        const auto bins = [&](void *p, size_t &t) { return hipcub::DeviceRunLengthEncode::Encode(p, t, skey.p, ukey.p, ucount.p, n_runs.p, (int)nc, s); };
+        if (int rc = reserve(h->cub, sort, bins)) return rc;
+        if (int rc = run_reserved(h->cub, sort)) return rc;
+        if (int rc = run_reserved(h->cub, bins)) return rc;
         hipLaunchKernelGGL(k_bai_bins, dim3(grid(nc)), dim3(kBaiBlock), 0, s, (const unsigned long long *)ukey.p, (const uint32_t *)n_runs.p, m.n_bin);
         SMI_HIP(hipGetLastError());
     }

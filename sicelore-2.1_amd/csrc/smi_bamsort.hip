@@ -16,11 +16,11 @@
 #include <climits>
 #include <cstdlib>
 #include <cstring>
-#include <hipcub/hipcub.hpp>
 #include <numeric>
 #include <string>
 #include <vector>
 
+#include "smi_device.h"
 #include "smi_handle.h"
 #include "smi_internal.h"
 
@@ -381,7 +381,7 @@ int sort_finish(smi_bamsort *h) {
     DevBuf<unsigned long long> skey("BamSort");
     DevBuf<uint32_t> iota("BamSort"), wrank("BamSort"), nwin("BamSort");
     DevBuf<uint64_t> wbyte("BamSort");
-    DevBuf<uint8_t> cub("BamSort");
+    Scratch cub("BamSort");
     if (int rc = skey.alloc(n)) return rc;
     if (int rc = iota.alloc(n)) return rc;
     if (int rc = wrank.alloc(cap_w + 1)) return rc;
@@ -391,17 +391,16 @@ int sort_finish(smi_bamsort *h) {
     SMI_HIP(hipMalloc((void **)&h->d_ooff, (n + 1) * sizeof(uint64_t)));
     int ref_bits = 1;  // the ranks 0 .. n_ref
     while (ref_bits < 31 && (1ll << ref_bits) <= h->n_ref) ref_bits++;
-    size_t t1 = 0, t2 = 0;
-    SMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, h->d_key, skey.p, iota.p, h->d_ord, (int)n, 0, 33 + ref_bits, s));
-    SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, h->d_ooff, h->d_ooff, (int)(n + 1), s));
-    if (int rc = cub.alloc(std::max(t1, t2))) return rc;
+    const auto sort = [&](void *p, size_t &t) { return hipcub::DeviceRadixSort::SortPairs(p, t, h->d_key, skey.p, iota.p, h->d_ord, (int)n, 0, 33 + ref_bits, s); };
+    const auto offsets = [&](void *p, size_t &t) { return hipcub::DeviceScan::ExclusiveSum(p, t, h->d_ooff, h->d_ooff, (int)(n + 1), s); };
+    if (int rc = reserve(cub, sort, offsets)) return rc;
     if (int rc = h->ev.begin(s)) return rc;
     hipLaunchKernelGGL(k_sort_iota, dim3(sort_grid(n)), dim3(kSortBlock), 0, s, iota.p, (uint32_t)n);
     SMI_HIP(hipGetLastError());
-    SMI_HIP(hipcub::DeviceRadixSort::SortPairs(cub.p, t1, h->d_key, skey.p, iota.p, h->d_ord, (int)n, 0, 33 + ref_bits, s));
+    if (int rc = run_reserved(cub, sort)) return rc;
     hipLaunchKernelGGL(k_sort_perm, dim3(sort_grid(n + 1)), dim3(kSortBlock), 0, s, (const uint32_t *)h->d_ord, (const uint32_t *)h->d_len, (uint32_t)n, h->d_ooff);
     SMI_HIP(hipGetLastError());
-    SMI_HIP(hipcub::DeviceScan::ExclusiveSum(cub.p, t2, h->d_ooff, h->d_ooff, (int)(n + 1), s));
+    if (int rc = run_reserved(cub, offsets)) return rc;
     hipLaunchKernelGGL(k_sort_windows, dim3(1), dim3(1), 0, s, (const uint64_t *)h->d_ooff, (uint32_t)n, h->window_bytes, (uint32_t)cap_w, wrank.p, wbyte.p, nwin.p);
     SMI_HIP(hipGetLastError());
     if (int rc = h->ev.end(s, &h->ms[SMI_BAMSORT_MS_SORT])) return rc;

@@ -26,6 +26,7 @@
 #include <cctype>
 
 #include "smi_internal.h"
+#include "smi_longread.h"
 
 using namespace smi;
 
@@ -187,49 +188,17 @@ struct Attributes {
 bool read_aux(const uint8_t *aux, size_t n, Attributes &a, std::string &err) {
     size_t p = 0;
     while (p < n) {
-        if (p + 3 > n) {
-            err = "truncated attribute in a BAM record";
+        size_t size;
+        if (const int bad = lr::aux_size(aux + p, aux + n, &size)) {
+            err = bad == lr::kAuxShortArray ? "truncated array attribute in a BAM record"
+                  : bad == lr::kAuxBadElement ? "unknown BAM array element type"
+                  : bad == lr::kAuxBadType  ? "unknown BAM aux type"
+                                            : "truncated attribute in a BAM record";
             return false;
         }
         const char tag[2] = {(char)aux[p], (char)aux[p + 1]};
         const uint8_t ty = aux[p + 2];
-        size_t q;
-        auto fixed = [&](size_t bytes) { return p + 3 + bytes; };
-        switch (ty) {
-        case 'A': q = fixed(1); break;
-        case 'c': case 'C': q = fixed(1); break;
-        case 's': case 'S': q = fixed(2); break;
-        case 'i': case 'I': case 'f': q = fixed(4); break;
-        case 'Z': case 'H': {
-            q = p + 3;
-            while (q < n && aux[q]) q++;
-            q++;
-            break;
-        }
-        case 'B': {
-            if (p + 8 > n) {
-                err = "truncated array attribute in a BAM record";
-                return false;
-            }
-            const uint8_t sub = aux[p + 3];
-            const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
-            if (!es) {
-                err = "unknown BAM array element type";
-                return false;
-            }
-            uint32_t cnt;
-            std::memcpy(&cnt, aux + p + 4, 4);
-            q = p + 8 + es * (size_t)cnt;
-            break;
-        }
-        default:
-            err = "unknown BAM aux type";
-            return false;
-        }
-        if (q > n) {
-            err = "truncated attribute in a BAM record";
-            return false;
-        }
+        const size_t q = p + size;
         long long v = 0;
         bool is_int = true;
         switch (ty) {

@@ -5,12 +5,12 @@
 //
 // The BAM comes in segments (smi_clipexport_segment); per segment:
 //   K-CLIP-FLAG    one lane per record: the first and the last CIGAR word (L78-85), the five attributes by one walk over the record's
-//                  attributes (aux_next of smi_auxedit.h; a repeated tag keeps its last value), the name up to its first '_' (L68, L76);
+//                  attributes (lr::aux_size; a repeated tag keeps its last value), the name up to its first '_' (L68, L76);
 //                  -> clipped or not, the length of the key, and the records the reference's loop dies on (atomicMin of the record index)
 //   K-CLIP-KEY     hipcub exclusive scan of the key lengths, then the keys of the clipped records into the segment's byte pool
-//   K-CLIP-INSERT  the HashSet of L58 / L87 / L94 as an open-addressing table over the key bytes, with the rules of K-FUS-INSERT and
-//                  K-DD-INSERT: 64-bit FNV-1a, a key claims an empty slot by CAS or joins the slot's key when length and bytes are equal,
-//                  else probes on, wrapping at the end.  The table and the pool of the keys written so far stay on the device across
+//   K-CLIP-INSERT  the HashSet of L58 / L87 / L94 as an open-addressing table over the key bytes, walked by probe() of smi_device.h as
+//                  K-FUS-INSERT and K-DD-INSERT walk theirs: 64-bit FNV-1a, a key claims an empty slot by CAS or joins the slot's key when
+//                  length and bytes are equal, else probes on, wrapping at the end.  The table and the pool of the keys written so far stay on the device across
 //                  segments: an entry below `resident` is a key of an earlier segment (the record loses), any other entry is a record of
 //                  this segment, and among the records of one key the smallest record index wins (atomicMin).  Which record of a group
 //                  holds the slot is a race; what is written is not.
@@ -38,7 +38,6 @@ namespace {
 
 constexpr int kClipBlock = 256;
 constexpr int kClipWaves = 4;  // waves per block of K-CLIP-WRITE
-constexpr uint32_t kEmpty = 0xffffffffu;
 constexpr unsigned long long kNoRecord = ~0ull;
 constexpr int kTags = 5;  // GENETAG, CELLTAG, UMITAG, USTAG, QSTAG
 
@@ -88,11 +87,12 @@ __global__ __launch_bounds__(kClipBlock) void k_clip_flag(FlagArgs a) {
         const uint64_t end = r.aux_off + r.aux_len;
         bool bad_aux = false;
         for (uint64_t p = r.aux_off; p < end;) {
-            const uint64_t q = aux_next(a.bam, p, end);
-            if (!q) {
+            size_t size;
+            if (lr::aux_size(a.bam + p, a.bam + end, &size)) {
                 bad_aux = true;
                 break;
             }
+            const uint64_t q = p + size;
             const uint32_t key = (uint32_t)a.bam[p + 1] << 8 | a.bam[p];
             const bool z = a.bam[p + 2] == 'Z';
 #pragma unroll
@@ -159,12 +159,6 @@ __global__ __launch_bounds__(kClipBlock) void k_clip_key(const uint8_t *__restri
     }
 }
 
-__device__ __forceinline__ bool same_bytes(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint32_t n) {
-    for (uint32_t k = 0; k < n; k++)
-        if (a[k] != b[k]) return false;
-    return true;
-}
-
 // K-CLIP-INSERT.  Table entries: e < resident: key e of the resident pool; else candidate e - resident of this call.  Candidate i is
 // spool[soff[i] .. soff[i + 1]); an empty one takes no part.  group[i] = the entry that holds the candidate's key (kEmpty: no candidate,
 // or the table ran full: *overflow set).  first[c] (may be null) = the smallest candidate whose key candidate c's entry holds.
@@ -185,34 +179,21 @@ __global__ __launch_bounds__(kClipBlock) void k_clip_insert(InsArgs a) {
     const uint32_t len = (uint32_t)(a.soff[i + 1] - o);
     uint32_t res = kEmpty;
     if (len) {
-        const uint8_t *mine = a.spool + o;
-        uint64_t h = 14695981039346656037ull;
-        for (uint32_t k = 0; k < len; k++) h = (h ^ mine[k]) * 1099511628211ull;
-        uint32_t slot = (uint32_t)(h ^ (h >> 32)) & a.mask, steps = 0, wraps = 0;
-        while (steps <= a.mask) {  // at most one turn round the table
-            uint32_t cur = __hip_atomic_load(&a.tab[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == kEmpty) {
-                cur = atomicCAS(&a.tab[slot], kEmpty, a.resident + i);
-                if (cur == kEmpty) {
-                    res = a.resident + i;
-                    break;
-                }
-            }
-            const bool old = cur < a.resident;
-            const uint64_t *off = old ? a.roff + cur : a.soff + (cur - a.resident);
-            const uint8_t *theirs = (old ? a.rpool : a.spool) + off[0];
-            if ((uint32_t)(off[1] - off[0]) == len && same_bytes(mine, theirs, len)) {
-                res = cur;
-                break;
-            }
-            slot = (slot + 1) & a.mask;
-            steps++;
-            wraps += slot == 0;
-        }
+        const Bytes mine = {a.spool + o, len};
+        const uint64_t h = fnv1a(mine.p, len);
+        const uint8_t *rpool = a.rpool, *spool = a.spool;
+        const uint64_t *roff = a.roff, *soff = a.soff;
+        const uint32_t resident = a.resident;
+        const Probed p = probe<true>(a.tab, a.mask, (uint32_t)(h ^ (h >> 32)) & a.mask, resident + i, mine, [=](uint32_t e) {
+            const bool old = e < resident;
+            const uint64_t *off = old ? roff + e : soff + (e - resident);
+            return Bytes{(old ? rpool : spool) + off[0], (uint32_t)(off[1] - off[0])};
+        });
+        res = p.entry;
         if (res == kEmpty) atomicOr(a.words + W_BAD, 2ull);
         else if (a.first && res >= a.resident) atomicMin(&a.first[res - a.resident], i);
-        if (steps) atomicAdd(a.words + W_STEPS, (unsigned long long)steps);
-        if (wraps) atomicAdd(a.words + W_WRAPS, (unsigned long long)wraps);
+        if (p.steps) atomicAdd(a.words + W_STEPS, (unsigned long long)p.steps);
+        if (p.wraps) atomicAdd(a.words + W_WRAPS, (unsigned long long)p.wraps);
     }
     if (a.group) a.group[i] = res;
 }
@@ -280,20 +261,6 @@ __global__ __launch_bounds__(kClipBlock) void k_clip_remap(uint32_t *__restrict_
     if (s >= slots) return;
     const uint32_t v = tab[s];
     if (v != kEmpty && v >= resident) tab[s] = resident + (uint32_t)rnew[v - resident];
-}
-
-// all lanes: dst[0 .. n) = src[0 .. n); the destination's dwords are stored whole
-__device__ __forceinline__ void wave_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint64_t n, int lane) {
-    const uint64_t to_dword = (4 - ((uintptr_t)dst & 3)) & 3, head = n < to_dword ? n : to_dword;
-    if ((uint64_t)lane < head) dst[lane] = src[lane];
-    const uint64_t words = (n - head) >> 2;
-    for (uint64_t k = lane; k < words; k += 64) {
-        uint32_t w;
-        __builtin_memcpy(&w, src + head + 4 * k, 4);
-        *reinterpret_cast<uint32_t *>(dst + head + 4 * k) = w;
-    }
-    const uint64_t done = head + 4 * words;
-    if (done + lane < n) dst[done + lane] = src[done + lane];
 }
 
 // K-CLIP-WRITE: "@" + readName + "\n" + US + "\n+\n" + QS + "\n" (L93)
@@ -376,8 +343,7 @@ struct smi_clipexport {
     uint64_t *d_scan = nullptr;  // 8 arrays of n + 1: klen, koff, osize, ooff, rflag, rnew, rsize, rkoff
     uint32_t *d_group = nullptr, *d_first = nullptr, *d_wlist = nullptr;
     size_t bam_cap = 0, spool_cap = 0, decision_cap = 0, out_cap = 0, recs_cap = 0, cr_cap = 0, scan_cap = 0, group_cap = 0, first_cap = 0, wlist_cap = 0;
-    void *d_cub = nullptr;
-    size_t cub_cap = 0;
+    Scratch cub{"ExportClippedReads"};  // hipcub's, kept across segments
     unsigned long long *d_words = nullptr;
     hipEvent_t ev[2] = {};
     // the segment the last call sized and did not write
@@ -407,7 +373,7 @@ namespace {
 
 void clip_release(smi_clipexport *h) {
     void *bufs[] = {h->d_rpool, h->d_roff, h->d_tab, h->d_bam, h->d_spool, h->d_decision, h->d_out, h->d_recs, h->d_cr, h->d_scan, h->d_group, h->d_first,
-                    h->d_wlist, h->d_cub, h->d_words};
+                    h->d_wlist, h->d_words};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev)
@@ -416,12 +382,7 @@ void clip_release(smi_clipexport *h) {
 }
 
 int clip_scan(smi_clipexport *h, hipStream_t s, const uint64_t *in, uint64_t *out, size_t n) {
-    size_t t = 0;
-    SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t, in, out, n, s));
-    if (int rc = grow((uint8_t **)&h->d_cub, h->cub_cap, t)) return rc;
-    t = h->cub_cap;
-    SMI_HIP(hipcub::DeviceScan::ExclusiveSum(h->d_cub, t, in, out, n, s));
-    return SMI_OK;
+    return run(h->cub, [=](void *p, size_t &t) { return hipcub::DeviceScan::ExclusiveSum(p, t, in, out, n, s); });
 }
 
 // a table of at least 2 x keys slots, a power of two; when the present one is smaller, a new one is filled from the resident pool

@@ -24,8 +24,6 @@
 // The validator (validator L279-366 over BEDParser.java, smi_collapse_validate_*): the BED texts and both distances per transcript on the
 //   host; K-JSUP: one lane per record of the short-read BAM, every alignment-block boundary looked up in a device table of the novel
 //   junctions; then the validator's fields per transcript and the five texts again.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -36,6 +34,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "smi_device.h"
 #include "smi_handle.h"
 #include "smi_internal.h"
 
@@ -49,15 +48,6 @@ constexpr int kColThreads = 256;  // threads of one K-COLLAPSE block: 4 waves
 constexpr int kColWaves = kColThreads / 64;
 constexpr int kLdsJunc = 1024;    // junctions of a founder staged in LDS (8 KiB); a longer list is read from global memory
 constexpr int kFcWaves = 4;       // waves per block of K-FILTER / K-CLASS
-
-__device__ __forceinline__ bool near(int2 a, int2 b, int d) { return abs(a.x - b.x) <= d && abs(a.y - b.y) <= d; }
-
-// isIn(j, lst, DELTA) (UCSCRefFlatParser L368-377)
-__device__ __forceinline__ bool is_in(int2 j, const int2 *lst, int n, int d) {
-    for (int i = 0; i < n; i++)
-        if (near(lst[i], j, d)) return true;
-    return false;
-}
 
 // isAllInclude(j1, j2) (L694-703): every junction of j1 isIn j2
 __device__ __forceinline__ bool all_include(const int2 *__restrict__ j1, int n1, const int2 *__restrict__ j2, int n2, int d) {
@@ -936,12 +926,11 @@ extern "C" int smi_collapse_run(smi_collapse *h, float *stage_ms) {
     }
     // K-COLSTAT: the scan of the founder counts (the Novel.<n> numbers), then the statistics per transcript
     {
-        DevBuf<uint8_t> d_tmp{kWho};
-        size_t tmp = 0;
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_nf.p, d_base.p, nCG + 1, s));
-        if ((rc = d_tmp.alloc(tmp))) return rc;
+        Scratch tmp{kWho};
+        const auto scan = [&](void *p, size_t &t) { return hipcub::DeviceScan::ExclusiveSum(p, t, d_nf.p, d_base.p, nCG + 1, s); };
+        if ((rc = reserve(tmp, scan))) return rc;
         if ((rc = evt.begin(s))) return rc;
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp, d_nf.p, d_base.p, nCG + 1, s));
+        if ((rc = run_reserved(tmp, scan))) return rc;
         if ((rc = evt.end(s, &ms[1]))) return rc;
         SMI_HIP(hipMemcpy(cg_base.data(), d_base.p, (size_t)(nCG + 1) * 4, hipMemcpyDeviceToHost));
         if (nCG) SMI_HIP(hipMemcpy(cg_nf.data(), d_nf.p, (size_t)nCG * 4, hipMemcpyDeviceToHost));
@@ -956,26 +945,21 @@ extern "C" int smi_collapse_run(smi_collapse *h, float *stage_ms) {
         DevBuf<uint64_t> d_code{kWho}, d_sorted{kWho}, d_unique{kWho};
         DevBuf<uint32_t> d_rl{kWho};
         DevBuf<int64_t> d_nrun{kWho};
-        DevBuf<uint8_t> d_tmp{kWho};
+        Scratch tmp{kWho};
         if ((rc = d_slot.put(rec_slot, s)) || (rc = d_ru.put(rec_u, s)) || (rc = d_ucg.put(u_cg, s)) || (rc = d_ts.put(tx_start, s)) ||
             (rc = d_te.put(tx_end, s)) || (rc = d_cell.put(cell, s)) || (rc = d_cnt.alloc(nT)) || (rc = d_min.alloc(nT)) || (rc = d_max.alloc(nT)) ||
             (rc = d_last.alloc(nT)) || (rc = d_cells.alloc(nT)) || (rc = d_code.alloc(nk)) || (rc = d_sorted.alloc(nk)) || (rc = d_unique.alloc(nk)) ||
             (rc = d_rl.alloc(nk)) || (rc = d_nrun.alloc(1)))
             return rc;
-        size_t t1 = 0, t2 = 0;
-        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, d_code.p, d_sorted.p, (int)nk, 0, 64, s));
-        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, d_sorted.p, d_unique.p, d_rl.p, d_nrun.p, (int)nk, s));
-        if ((rc = d_tmp.alloc(std::max(t1, t2)))) return rc;
+        const auto cells = sort_rle(s, d_code.p, d_sorted.p, d_unique.p, d_rl.p, d_nrun.p, (int)nk, 64);
+        if ((rc = cells.reserve(tmp))) return rc;
         StatArgs a = {d_slot.p, d_ru.p, d_ucg.p, d_uf.p, d_base.p, d_ts.p, d_te.p, d_cell.p, (int32_t)nk, n_slots,
                       d_cnt.p, d_min.p, d_max.p, d_last.p, d_code.p};
         if ((rc = evt.begin(s))) return rc;
         hipLaunchKernelGGL(k_colstat_init, dim3((unsigned)((nT + 255) / 256)), dim3(256), 0, s, d_cnt.p, d_min.p, d_max.p, d_last.p, d_cells.p, nT);
         hipLaunchKernelGGL(k_colstat, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, a);
         SMI_HIP(hipGetLastError());
-        size_t tmp = std::max(t1, t2);
-        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(d_tmp.p, tmp, d_code.p, d_sorted.p, (int)nk, 0, 64, s));
-        tmp = std::max(t1, t2);
-        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(d_tmp.p, tmp, d_sorted.p, d_unique.p, d_rl.p, d_nrun.p, (int)nk, s));
+        if ((rc = cells.run_reserved(tmp))) return rc;
         hipLaunchKernelGGL(k_colstat_cells, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, d_unique.p, d_nrun.p, d_cells.p);
         SMI_HIP(hipGetLastError());
         if ((rc = evt.end(s, &ms[1]))) return rc;

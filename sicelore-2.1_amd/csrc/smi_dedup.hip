@@ -13,8 +13,9 @@
 //     ids[0] + ids[1]; the key bytes are appended to a device pool and the record's fields to a device table, both kept across segments.
 //     The smallest offending line number is kept by an atomic minimum.
 // smi_dedup_select, once the record count is known:
-//   K-DD-INSERT: open addressing over a table of a power of two >= 2 x records; a record claims an empty slot by CAS of its index, or
-//     joins the slot's representative when length and bytes of the two keys are equal (compared in the pool), or probes on.  Which
+//   K-DD-INSERT: open addressing over a table of a power of two >= 2 x records, walked by probe() of smi_device.h; a record claims an
+//     empty slot by CAS of its index, or joins the slot's representative when length and bytes of the two keys are equal (compared in
+//     the pool), or probes on.  Which
 //     record of a group becomes its representative is a race; the group's accumulators are indexed by it and nothing else depends on it.
 //   K-DD-PICK: FASTQ with SELECT (L208-217): 64-bit atomicMax of rn << 32 | sequence length per group, then atomicMin of the index among
 //     the records that equal it.  FASTA (L128-136; the four-argument Molecule constructor leaves consensusLength 0, so an equal rn
@@ -25,14 +26,13 @@
 //   K-DD-WRITE: one wavefront per record of the segment, the ones that lost leave at once.  Lane 0 writes the marker, the separators and
 //     the decimal rn; all lanes copy ids[0], ids[1] (from the pool), the sequence and the quality line: bytes up to the destination's
 //     next 4-byte boundary, then dwords, then the tail.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "smi_device.h"
 #include "smi_internal.h"
 
 namespace smi {
@@ -40,7 +40,6 @@ namespace {
 
 constexpr int kDdBlock = 256;
 constexpr int kDdWaves = 4;  // waves per block of K-DD-WRITE
-constexpr uint32_t kEmpty = 0xffffffffu;
 constexpr uint64_t kNone = ~0ull;
 // transition functions, next state of state s in bits 2s+1 .. 2s: a marker line (0 -> 1) and any other line (0 -> 0); 1 -> 2 -> 3 -> 0 for both
 constexpr uint8_t kFqMarker = 0x39, kFqOther = 0x38, kFaMarker = 0x01, kFaOther = 0x00;
@@ -154,7 +153,7 @@ struct Name {
 // field or no number: an error both ways.  rn = Integer(ids[2]): an optional '+', decimal digits, at most 2147483647.
 template <bool WRITE>
 __device__ Name parse_name(const uint8_t *__restrict__ p, uint32_t n, uint8_t marker, uint8_t *__restrict__ key) {
-    Name o = {0, 0, 0, 14695981039346656037ull, false};
+    Name o = {0, 0, 0, kFnvBasis, false};
     uint32_t i = 0, field = 0, nd = 0, k = 0, at = 0;
     uint64_t v = 0;
     bool bad = false;
@@ -175,7 +174,7 @@ __device__ Name parse_name(const uint8_t *__restrict__ p, uint32_t n, uint8_t ma
             continue;
         }
         if (field < 2) {
-            o.hash = (o.hash ^ c) * 1099511628211ull;
+            o.hash = fnv1a_add(o.hash, c);
             if (WRITE) key[k] = c;
             k++;
             if (field == 0) o.len0++;
@@ -286,33 +285,14 @@ __global__ __launch_bounds__(kDdBlock) void k_dd_insert(TabArgs a) {
     const uint32_t i = blockIdx.x * kDdBlock + threadIdx.x;
     if (i >= a.n) return;
     const DdRec r = a.recs[i];
-    const uint8_t *mine = a.pool + r.pool_off;
-    uint32_t slot = (uint32_t)(r.hash & a.hash_mask) & a.mask, steps = 0, wraps = 0;
-    for (;;) {
-        uint32_t cur = __hip_atomic_load(&a.tab[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == kEmpty) {
-            cur = atomicCAS(&a.tab[slot], kEmpty, i);
-            if (cur == kEmpty) {
-                a.group[i] = i;
-                break;
-            }
-        }
-        const DdRec &c = a.recs[cur];
-        bool same = c.key_len == r.key_len;
-        if (same) {
-            const uint8_t *theirs = a.pool + c.pool_off;
-            for (uint32_t k = 0; k < r.key_len && same; k++) same = mine[k] == theirs[k];
-        }
-        if (same) {
-            a.group[i] = cur;
-            break;
-        }
-        slot = (slot + 1) & a.mask;
-        steps++;
-        wraps += slot == 0;
-    }
-    if (steps) atomicAdd(a.probe_steps, (unsigned long long)steps);
-    if (wraps) atomicAdd(a.wraps, (unsigned long long)wraps);
+    const DdRec *recs = a.recs;
+    const uint8_t *pool = a.pool;
+    // (the table has two slots per record: the walk always ends at an entry)
+    const Probed p = probe<true>(a.tab, a.mask, (uint32_t)(r.hash & a.hash_mask) & a.mask, i, Bytes{pool + r.pool_off, r.key_len},
+                                 [recs, pool](uint32_t e) { return Bytes{pool + recs[e].pool_off, recs[e].key_len}; });
+    a.group[i] = p.entry;
+    if (p.steps) atomicAdd(a.probe_steps, (unsigned long long)p.steps);
+    if (p.wraps) atomicAdd(a.wraps, (unsigned long long)p.wraps);
 }
 
 enum : int { kModeSelect = 0, kModeFasta = 1, kModeFirst = 2 };
@@ -350,15 +330,6 @@ __global__ __launch_bounds__(kDdBlock) void k_dd_pick_index(PickArgs a) {
     if (a.mode == kModeFasta && r.seq_len > 0) atomicMax(&a.last_ne[g], i + 1);
 }
 
-__device__ __forceinline__ int dd_digits(uint32_t v) {
-    int n = 1;
-    while (v >= 10) {
-        v /= 10;
-        n++;
-    }
-    return n;
-}
-
 // size[i]: bytes of record i in the output, 0 when it is not its molecule's winner
 __global__ __launch_bounds__(kDdBlock) void k_dd_size(PickArgs a) {
     const uint32_t i = blockIdx.x * kDdBlock + threadIdx.x;
@@ -371,7 +342,7 @@ __global__ __launch_bounds__(kDdBlock) void k_dd_size(PickArgs a) {
         uint64_t sz = 0;
         if (won) {
             const DdRec &r = a.recs[i];
-            sz = 1 + (uint64_t)r.key_len + 2 + dd_digits((uint32_t)r.rn) + 1 + r.seq_len + 1;  // marker ids0 - ids1 - rn \n seq \n
+            sz = 1 + (uint64_t)r.key_len + 2 + digits((uint32_t)r.rn) + 1 + r.seq_len + 1;  // marker ids0 - ids1 - rn \n seq \n
             if (a.mode != kModeFasta) sz += 2 + (uint64_t)r.qual_len + 1;                       // + \n qual \n
         }
         a.size[i] = sz;
@@ -380,20 +351,6 @@ __global__ __launch_bounds__(kDdBlock) void k_dd_size(PickArgs a) {
     }
     const unsigned long long bal = __ballot(won);
     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(a.n_mol, (unsigned long long)__popcll(bal));
-}
-
-// all lanes: dst[0 .. n) = src[0 .. n); the destination's dwords are stored whole
-__device__ __forceinline__ void wave_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint64_t n, int lane) {
-    const uint64_t to_dword = (4 - ((uintptr_t)dst & 3)) & 3, head = n < to_dword ? n : to_dword;
-    if ((uint64_t)lane < head) dst[lane] = src[lane];
-    const uint64_t words = (n - head) >> 2;
-    for (uint64_t k = lane; k < words; k += 64) {
-        uint32_t w;
-        __builtin_memcpy(&w, src + head + 4 * k, 4);
-        *reinterpret_cast<uint32_t *>(dst + head + 4 * k) = w;
-    }
-    const uint64_t done = head + 4 * words;
-    if (done + lane < n) dst[done + lane] = src[done + lane];
 }
 
 __global__ __launch_bounds__(64 * kDdWaves) void k_dd_write(const uint8_t *__restrict__ text, const DdRec *__restrict__ recs,
@@ -408,7 +365,7 @@ __global__ __launch_bounds__(64 * kDdWaves) void k_dd_write(const uint8_t *__res
     const DdRec r = recs[i];
     uint8_t *dst = out + (o - out_off[rec0]);
     const uint32_t len1 = r.key_len - r.len0;
-    const int nd = dd_digits((uint32_t)r.rn);
+    const int nd = digits((uint32_t)r.rn);
     uint8_t *num = dst + 1 + r.len0 + 1 + len1 + 1, *seq = num + nd + 1, *qual = seq + r.seq_len + 3;
     if (lane == 0) {
         dst[0] = fasta ? '>' : '@';
@@ -529,7 +486,8 @@ extern "C" int smi_dedup_add_segment(smi_dedup *h, const uint8_t *text, size_t n
         }
         if (n_lines) {
             DevBuf<uint64_t> d_line{kWho}, d_start{kWho}, d_klen{kWho}, d_koff{kWho};
-            DevBuf<uint8_t> d_f{kWho}, d_fs{kWho}, d_tmp{kWho};
+            DevBuf<uint8_t> d_f{kWho}, d_fs{kWho};
+            Scratch tmp{kWho};
             DevBuf<uint32_t> d_flag{kWho}, d_ridx{kWho}, d_valid{kWho}, d_vidx{kWho};
             DevBuf<DdSeg> d_seg{kWho};
             if ((rc = d_line.alloc(n_lines + 1)) || (rc = d_f.alloc(n_lines)) || (rc = d_fs.alloc(n_lines)) || (rc = d_flag.alloc(n_lines + 1)) ||
@@ -543,18 +501,16 @@ extern "C" int smi_dedup_add_segment(smi_dedup *h, const uint8_t *text, size_t n
             hipLaunchKernelGGL(k_dd_func, dim3(grid_l), dim3(kDdBlock), 0, s, (const uint8_t *)h->d_text.p, (const uint64_t *)d_line.p, n_lines, h->line_base,
                                (int)fasta, d_f.p, d_seg.p);
             SMI_HIP(hipGetLastError());
-            size_t t1 = 0, t2 = 0, t3 = 0;
-            SMI_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, t1, d_f.p, d_fs.p, Compose(), (int)n_lines, s));
-            SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, d_flag.p, d_ridx.p, (int)n_lines + 1, s));
-            SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, (uint64_t *)nullptr, (uint64_t *)nullptr, (int)n_lines + 1, s));
-            const size_t tmp_bytes = std::max(t1, std::max(t2, t3));
-            if ((rc = d_tmp.alloc(tmp_bytes))) return rc;
-            size_t tb = tmp_bytes;
-            SMI_HIP(hipcub::DeviceScan::InclusiveScan(d_tmp.p, tb, d_f.p, d_fs.p, Compose(), (int)n_lines, s));
+            const auto compose = [&](void *p, size_t &t) { return hipcub::DeviceScan::InclusiveScan(p, t, d_f.p, d_fs.p, Compose(), (int)n_lines, s); };
+            const auto sum = [s](auto *in, auto *out, size_t m) {
+                return [=](void *p, size_t &t) { return hipcub::DeviceScan::ExclusiveSum(p, t, in, out, (int)m, s); };
+            };
+            const auto flags = sum(d_flag.p, d_ridx.p, n_lines + 1);
+            if ((rc = reserve(tmp, compose, flags))) return rc;
+            if ((rc = run_reserved(tmp, compose))) return rc;
             hipLaunchKernelGGL(k_dd_flag, dim3(grid_l), dim3(kDdBlock), 0, s, (const uint8_t *)d_f.p, (const uint8_t *)d_fs.p, n_lines, d_flag.p, d_seg.p);
             SMI_HIP(hipGetLastError());
-            tb = tmp_bytes;
-            SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, d_flag.p, d_ridx.p, (int)n_lines + 1, s));
+            if ((rc = run_reserved(tmp, flags))) return rc;
             uint32_t n_starts = 0;
             SMI_HIP(hipMemcpyAsync(&n_starts, d_ridx.p + n_lines, 4, hipMemcpyDeviceToHost, s));
             if ((rc = ev.end(s, &h->ms[SMI_DEDUP_MS_INDEX]))) return rc;
@@ -562,6 +518,9 @@ extern "C" int smi_dedup_add_segment(smi_dedup *h, const uint8_t *text, size_t n
                 if ((rc = d_start.alloc(n_starts)) || (rc = d_valid.alloc((size_t)n_starts + 1)) || (rc = d_vidx.alloc((size_t)n_starts + 1)) ||
                     (rc = d_klen.alloc((size_t)n_starts + 1)) || (rc = d_koff.alloc((size_t)n_starts + 1)))
                     return rc;
+                const auto valid = sum(d_valid.p, d_vidx.p, (size_t)n_starts + 1);
+                const auto keys = sum(d_klen.p, d_koff.p, (size_t)n_starts + 1);
+                if ((rc = reserve(tmp, valid, keys))) return rc;
                 if ((rc = ev.begin(s))) return rc;
                 hipLaunchKernelGGL(k_dd_starts, dim3(grid_l), dim3(kDdBlock), 0, s, (const uint32_t *)d_flag.p, (const uint32_t *)d_ridx.p, n_lines, d_start.p);
                 SMI_HIP(hipMemsetAsync(d_valid.p + n_starts, 0, 4, s));
@@ -581,10 +540,7 @@ extern "C" int smi_dedup_add_segment(smi_dedup *h, const uint8_t *text, size_t n
                 const unsigned grid_r = (n_starts + kDdBlock - 1) / kDdBlock;
                 hipLaunchKernelGGL(k_dd_parse<false>, dim3(grid_r), dim3(kDdBlock), 0, s, a);
                 SMI_HIP(hipGetLastError());
-                tb = tmp_bytes;
-                SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, d_valid.p, d_vidx.p, (int)n_starts + 1, s));
-                tb = tmp_bytes;
-                SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, d_klen.p, d_koff.p, (int)n_starts + 1, s));
+                if ((rc = run_reserved(tmp, valid)) || (rc = run_reserved(tmp, keys))) return rc;
                 uint32_t n_valid = 0;
                 uint64_t key_bytes = 0;
                 SMI_HIP(hipMemcpyAsync(&n_valid, d_vidx.p + n_starts, 4, hipMemcpyDeviceToHost, s));
@@ -664,14 +620,13 @@ extern "C" int smi_dedup_select(smi_dedup *h, float *stage_ms) {
         DevBuf<uint32_t> d_tab{kWho}, d_group{kWho}, d_win{kWho}, d_last{kWho};
         DevBuf<unsigned long long> d_best{kWho}, d_cnt{kWho};
         DevBuf<uint64_t> d_size{kWho};
-        DevBuf<uint8_t> d_tmp{kWho};
+        Scratch tmp{kWho};
         int rc;
         if ((rc = d_tab.alloc(slots)) || (rc = d_group.alloc(n)) || (rc = d_win.alloc(n)) || (rc = d_last.alloc(n)) || (rc = d_best.alloc(n)) ||
             (rc = d_cnt.alloc(3)) || (rc = d_size.alloc((size_t)n + 1)) || (rc = h->d_out_off.alloc((size_t)n + 1)))
             return rc;
-        size_t tmp_bytes = 0;
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_size.p, h->d_out_off.p, (int)n + 1, s));
-        if ((rc = d_tmp.alloc(tmp_bytes))) return rc;
+        const auto offsets = [&](void *p, size_t &t) { return hipcub::DeviceScan::ExclusiveSum(p, t, d_size.p, h->d_out_off.p, (int)n + 1, s); };
+        if ((rc = reserve(tmp, offsets))) return rc;
         SMI_HIP(hipMemsetAsync(d_tab.p, 0xff, slots * 4, s));
         SMI_HIP(hipMemsetAsync(d_win.p, 0xff, (size_t)n * 4, s));
         SMI_HIP(hipMemsetAsync(d_last.p, 0, (size_t)n * 4, s));
@@ -708,7 +663,7 @@ extern "C" int smi_dedup_select(smi_dedup *h, float *stage_ms) {
         if (p.mode != kModeFirst) hipLaunchKernelGGL(k_dd_pick_index, dim3(grid), dim3(kDdBlock), 0, s, p);
         hipLaunchKernelGGL(k_dd_size, dim3(grid1), dim3(kDdBlock), 0, s, p);
         SMI_HIP(hipGetLastError());
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_size.p, h->d_out_off.p, (int)n + 1, s));
+        if ((rc = run_reserved(tmp, offsets))) return rc;
         if ((rc = ev.end(s, &h->ms[SMI_DEDUP_MS_PICK]))) return rc;
         unsigned long long cnt[3] = {0, 0, 0};
         uint64_t total = 0;

@@ -8,9 +8,9 @@
 //   de and the fields of GE.split(",") (Longread.addRecord L40-54) go to pools that live across segments.
 // Device (smi_fusion_run): every group is a group of equal byte strings; no host map takes part.
 //   K-FUS-INSERT: one kernel over a byte pool and an offset table, used for the read names, the molecule keys, the gene names and the cell
-//     list.  Open addressing over a table of a power of two >= 2 x keys (or 2^table_log2), 64-bit FNV-1a of the bytes; a key claims an
-//     empty slot by CAS of its index, or joins the slot's representative when length and bytes of the two keys are equal, or probes on,
-//     wrapping at the end.  Which key of a group becomes its representative is a race: the group's accumulators are indexed by it, every
+//     list.  Open addressing over a table of a power of two >= 2 x keys (or 2^table_log2), 64-bit FNV-1a of the bytes, walked by probe()
+//     of smi_device.h: a key claims an empty slot by CAS of its index, or joins the slot's representative when length and bytes of the
+//     two keys are equal, or probes on, wrapping at the end.  Which key of a group becomes its representative is a race: the group's accumulators are indexed by it, every
 //     one of them is an atomicMin / atomicMax / integer atomicAdd over record numbers, and groups are renumbered by their smallest member,
 //     so nothing that leaves the device depends on it.  The look-up form of the same kernel answers the cell list's contains().
 //   K-FUS-READ: LongreadParser L61-79 and Longread.addRecord per read group: its first kept record (atomicMin), its last record
@@ -24,8 +24,6 @@
 //     from the bytes; a shared bucket: byte order); the ordered pairs sorted and run-length encoded once more, which numbers them.
 // Host again: the label of every pair (L82-85), the labels sorted; K-MTX (smi_mtx.h) renders the matrix from one (row << 32 | cell) code
 //   per counted molecule and gives the row totals of the metrics; the molinfos text (Matrix.writeIsoformMatrix L209-214).
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -36,6 +34,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "smi_device.h"
 #include "smi_handle.h"
 #include "smi_internal.h"
 #include "smi_mtx.h"
@@ -47,7 +46,6 @@ namespace {
 constexpr const char *kWho = "FusionDetector";  // the program named when a device allocation fails
 
 constexpr int kFusBlock = 256;
-constexpr uint32_t kEmpty = 0xffffffffu;
 constexpr uint64_t kNoPair = ~0ull;
 constexpr int32_t kMaxClip = 10000;  // FusionDetector.java L64
 
@@ -57,10 +55,9 @@ struct Keys {
     const uint64_t *off;
 };
 
-__device__ __forceinline__ bool same_bytes(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint32_t n) {
-    for (uint32_t k = 0; k < n; k++)
-        if (a[k] != b[k]) return false;
-    return true;
+__device__ __forceinline__ Bytes key_bytes(const Keys &k, uint32_t i) {
+    const uint64_t o = k.off[i];
+    return {k.pool + o, (uint32_t)(k.off[i + 1] - o)};
 }
 
 // K-FUS-INSERT.  INSERT: key i of `keys` -> group[i] = the representative of its group (a key index), -1 if the table is full (*overflow
@@ -82,35 +79,14 @@ __global__ __launch_bounds__(kFusBlock) void k_fus_insert(InsArgs a) {
     if (i >= a.n) return;
     const Keys &mk = LOOKUP ? a.query : a.keys;
     const uint32_t me = LOOKUP ? (uint32_t)a.idx[i] : i;
-    const uint8_t *mine = mk.pool + mk.off[me];
-    const uint32_t len = (uint32_t)(mk.off[me + 1] - mk.off[me]);
-    uint64_t h = 14695981039346656037ull;
-    for (uint32_t k = 0; k < len; k++) h = (h ^ mine[k]) * 1099511628211ull;
-    uint32_t slot = (uint32_t)(h ^ (h >> 32)) & a.mask, steps = 0, wraps = 0;
-    int32_t res = -1;
-    while (steps <= a.mask) {  // at most one turn round the table
-        uint32_t cur = __hip_atomic_load(&a.tab[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == kEmpty) {
-            if (LOOKUP) break;
-            cur = atomicCAS(&a.tab[slot], kEmpty, i);
-            if (cur == kEmpty) {
-                res = (int32_t)i;
-                break;
-            }
-        }
-        const uint64_t o = a.keys.off[cur];
-        if ((uint32_t)(a.keys.off[cur + 1] - o) == len && same_bytes(mine, a.keys.pool + o, len)) {
-            res = (int32_t)cur;
-            break;
-        }
-        slot = (slot + 1) & a.mask;
-        steps++;
-        wraps += slot == 0;
-    }
-    a.group[i] = res;
-    if (!LOOKUP && res < 0) atomicOr(a.overflow, 1u);
-    if (steps) atomicAdd(a.probe_steps, (unsigned long long)steps);
-    if (wraps) atomicAdd(a.wraps, (unsigned long long)wraps);
+    const Bytes mine = key_bytes(mk, me);
+    const uint64_t h = fnv1a(mine.p, mine.n);
+    const Keys keys = a.keys;
+    const Probed r = probe<!LOOKUP>(a.tab, a.mask, (uint32_t)(h ^ (h >> 32)) & a.mask, i, mine, [keys](uint32_t e) { return key_bytes(keys, e); });
+    a.group[i] = (int32_t)r.entry;  // kEmpty is -1
+    if (!LOOKUP && r.entry == kEmpty) atomicOr(a.overflow, 1u);
+    if (r.steps) atomicAdd(a.probe_steps, (unsigned long long)r.steps);
+    if (r.wraps) atomicAdd(a.wraps, (unsigned long long)r.wraps);
 }
 
 // lo[i] = INT_MAX, hi[i] = hi2[i] = -1, cnt[i] = 0 (a null array is left out)
@@ -324,39 +300,6 @@ __global__ __launch_bounds__(kFusBlock) void k_fus_pair_id(const uint64_t *__res
 }
 
 inline unsigned grid(size_t n) { return (unsigned)((n + kFusBlock - 1) / kFusBlock); }
-
-// hipcub's temporary storage, grown on demand
-struct Tmp {
-    DevBuf<uint8_t> b{kWho};
-    size_t cap = 0;
-    int need(size_t n) {
-        if (n <= cap) return SMI_OK;
-        cap = n;
-        return b.alloc(n);
-    }
-};
-
-template <class T>
-int exclusive_sum(hipStream_t s, Tmp &tmp, const T *in, T *out, int n) {
-    size_t t = 0;
-    SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t, in, out, n, s));
-    if (int rc = tmp.need(t)) return rc;
-    SMI_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.b.p, t, in, out, n, s));
-    return SMI_OK;
-}
-
-// sorted distinct values of `in` (n > 0) and their number
-int sort_unique(hipStream_t s, Tmp &tmp, const uint64_t *in, uint64_t *sorted, uint64_t *unique, uint32_t *cnt, int64_t *n_run, int n) {
-    size_t t1 = 0, t2 = 0;
-    SMI_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, in, sorted, n, 0, 64, s));
-    SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, sorted, unique, cnt, n_run, n, s));
-    if (int rc = tmp.need(std::max(t1, t2))) return rc;
-    size_t t = std::max(t1, t2);
-    SMI_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.b.p, t, in, sorted, n, 0, 64, s));
-    t = std::max(t1, t2);
-    SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(tmp.b.p, t, sorted, unique, cnt, n_run, n, s));
-    return SMI_OK;
-}
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
 // strings back to back: string i is pool[off[i] .. off[i + 1])
@@ -579,7 +522,10 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
     c[SMI_FUS_GENE_FIELDS] = nF;
     int rc = 0;
     Events evt;
-    Tmp tmp;
+    Scratch tmp{kWho};
+    auto exclusive_sum = [&](auto *in, auto *out, int m) {
+        return run(tmp, [=](void *p, size_t &t) { return hipcub::DeviceScan::ExclusiveSum(p, t, in, out, m, s); });
+    };
     int32_t n_reads = 0, n_mol = 0;
     int64_t n_pairs = 0;
     std::vector<int32_t> mol_n, mol_bc, mol_umi, mol_de, mol_cell, mol_pair, mol_ng;
@@ -633,7 +579,7 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
         hipLaunchKernelGGL(k_fus_read, dim3(grid(n)), dim3(kFusBlock), 0, s, d_rep.p, d_has.p, n, d_first.p, d_last.p, d_lumi.p, d_nrec.p);
         hipLaunchKernelGGL(k_fus_flag, dim3(grid((size_t)n + 1)), dim3(kFusBlock), 0, s, d_rep.p, d_first.p, n, d_flag.p);
         SMI_HIP(hipGetLastError());
-        if ((rc = exclusive_sum(s, tmp, d_flag.p, d_rq.p, n + 1))) return rc;
+        if ((rc = exclusive_sum(d_flag.p, d_rq.p, n + 1))) return rc;
         if ((rc = evt.end(s, &ms[1]))) return rc;
         SMI_HIP(hipMemcpy(&n_reads, d_rq.p + n, 4, hipMemcpyDeviceToHost));
         DevBuf<int32_t> d_qfirst{kWho}, d_qlast{kWho}, d_qumi{kWho};
@@ -649,7 +595,7 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
             if ((rc = evt.begin(s))) return rc;
             hipLaunchKernelGGL(k_fus_read_list, dim3(grid(n)), dim3(kFusBlock), 0, s, a);
             SMI_HIP(hipGetLastError());
-            if ((rc = exclusive_sum(s, tmp, d_klen.p, d_koff.p, n_reads + 1))) return rc;
+            if ((rc = exclusive_sum(d_klen.p, d_koff.p, n_reads + 1))) return rc;
             uint64_t key_bytes = 0;
             SMI_HIP(hipMemcpyAsync(&key_bytes, d_koff.p + n_reads, 8, hipMemcpyDeviceToHost, s));
             SMI_HIP(hipStreamSynchronize(s));
@@ -671,7 +617,7 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
         hipLaunchKernelGGL(k_fus_mol, dim3(grid(n_reads)), dim3(kFusBlock), 0, s, d_mrep.p, n_reads, d_mfirst.p, d_mlast.p, d_mn.p);
         hipLaunchKernelGGL(k_fus_flag, dim3(grid((size_t)n_reads + 1)), dim3(kFusBlock), 0, s, d_mrep.p, d_mfirst.p, n_reads, d_mflag.p);
         SMI_HIP(hipGetLastError());
-        if ((rc = exclusive_sum(s, tmp, d_mflag.p, d_mq.p, n_reads + 1))) return rc;
+        if ((rc = exclusive_sum(d_mflag.p, d_mq.p, n_reads + 1))) return rc;
         if ((rc = evt.end(s, &ms[2]))) return rc;
         SMI_HIP(hipMemcpy(&n_mol, d_mq.p + n_reads, 4, hipMemcpyDeviceToHost));
         DevBuf<int32_t> d_mol_n{kWho}, d_mol_bc{kWho}, d_mol_umi{kWho}, d_mol_de{kWho}, d_mol_ng{kWho}, d_mol_gs{kWho}, d_mol_cell{kWho}, d_mol_pair{kWho};
@@ -717,14 +663,14 @@ extern "C" int smi_fusion_run(smi_fusion *h, float *stage_ms) {
             CodeArgs a = {d_grep.p, d_gfirst.p, d_frec.p, d_rep.p, d_first.p, d_rq.p, d_read_mol.p, nF, d_code.p, d_cnt.p + 3};
             hipLaunchKernelGGL(k_fus_codes, dim3(grid(nF)), dim3(kFusBlock), 0, s, a);
             SMI_HIP(hipGetLastError());
-            if ((rc = sort_unique(s, tmp, d_code.p, d_sorted.p, d_ucode.p, d_rl.p, d_nrun.p, nF))) return rc;
+            if ((rc = sort_rle(s, d_code.p, d_sorted.p, d_ucode.p, d_rl.p, d_nrun.p, nF, 64).run(tmp))) return rc;
             hipLaunchKernelGGL(k_fus_gene_count, dim3(grid(nF)), dim3(kFusBlock), 0, s, d_ucode.p, d_nrun.p, d_mol_ng.p, d_mol_gs.p);
         }
         {
             SelArgs a = {d_mol_ng.p, d_mol_gs.p, d_mol_umi.p, d_mol_cell.p, d_ucode.p, Keys{d_gene.p, d_gene_off.p}, n_mol, d_pair.p, d_cnt.p + 4};
             hipLaunchKernelGGL(k_fus_select, dim3(grid(n_mol)), dim3(kFusBlock), 0, s, a);
             SMI_HIP(hipGetLastError());
-            if ((rc = sort_unique(s, tmp, d_pair.p, d_psorted.p, d_upair.p, d_rl.p, d_nrun.p + 1, n_mol))) return rc;
+            if ((rc = sort_rle(s, d_pair.p, d_psorted.p, d_upair.p, d_rl.p, d_nrun.p + 1, n_mol, 64).run(tmp))) return rc;
             hipLaunchKernelGGL(k_fus_pair_id, dim3(grid(n_mol)), dim3(kFusBlock), 0, s, d_pair.p, n_mol, d_upair.p, d_nrun.p + 1, d_mol_pair.p);
             SMI_HIP(hipGetLastError());
         }

@@ -299,9 +299,6 @@ void *pin_words(smi_ctx *ctx);
 int region_group_from_sorted(void **work, const uint64_t *keys, size_t n_pos, int32_t n, const uint64_t *has_bits, int32_t max_dist, int keep_data_end,
                              int32_t *region, int32_t *n_done);  // *work: scratch kept between calls (ctx->region_work)
 void region_work_free(void *work);
-int region_group_from_sorted(void **work, const uint64_t *keys, size_t n_pos, int32_t n, const uint64_t *has_bits, int32_t max_dist, int keep_data_end,
-                             int32_t *region, int32_t *n_done);  // *work: scratch kept between calls (ctx->region_work)
-void region_work_free(void *work);
 int region_group_strided(const void *recs, size_t stride, size_t pos_off, size_t flags_off, uint32_t has_pos_bit, uint32_t rev_bit, int32_t n,
                          int32_t max_dist, int keep_data_end, int32_t *region, int32_t *n_done);
 // K-DEFLATE (smi_deflate.hip): d_in -> one gzip member / raw deflate stream in d_out; d_total[0] = its size, d_total[1] = error flags (device)

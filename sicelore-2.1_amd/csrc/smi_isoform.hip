@@ -23,8 +23,6 @@
 // K-MTX: 64-bit (row << 32 | cell) codes per counted molecule; hipcub radix sort + run-length encoding give the UMI counts (a molecule is
 //   one UMI of its cell); the dense rows are rendered in row blocks under a device-memory budget, one wavefront per row: a length pass, a
 //   scan, the write (smi_mtx.h, shared with SNPMatrix).
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <charconv>
 #include <cmath>
@@ -71,15 +69,6 @@ struct IsoArgs {
     const int64_t *junc_off;      // WRITE: molecule m's junction ids go to junc_out[junc_off[m] ..)
     int32_t *junc_out;
 };
-
-__device__ __forceinline__ bool near(int2 a, int2 b, int d) { return abs(a.x - b.x) <= d && abs(a.y - b.y) <= d; }
-
-// isIn(j, lst, DELTA) (L309-318)
-__device__ __forceinline__ bool is_in(int2 j, const int2 *__restrict__ lst, int n, int d) {
-    for (int i = 0; i < n; i++)
-        if (near(lst[i], j, d)) return true;
-    return false;
-}
 
 // the j-th candidate transcript of a molecule (genes in order, their lines in file order); *base: the index of its gene's first line
 __device__ __forceinline__ int tx_of(const IsoArgs &a, int g0, int g1, int j, int *base = nullptr) {

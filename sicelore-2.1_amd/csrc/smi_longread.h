@@ -1,8 +1,9 @@
 // smi_longread.h -- LongreadRecord.fromSAMRecord and the LongreadParser filter, once, for the programs that read molecule records:
 // the attribute helpers, the CIGAR walk and the Java text rules (SNPMatrix in smi_snp.hip reads these too), the record reader (Reader),
 // the filters of IsoformMatrix, ComputeConsensus, CollapseModel and FusionDetector on top of it (read_isoform, read_consensus,
-// read_collapse, read_fusion) and the per-segment fan-out over host threads (read_segment).  Host only: no HIP call and no set_error,
-// so that a plain C++ compiler builds it (tools/asan/longread_host.cpp runs it on a CPU).
+// read_collapse, read_fusion) and the per-segment fan-out over host threads (read_segment).  Host code but for aux_size, which the
+// kernels that walk attributes call too; no HIP call and no set_error, so that a plain C++ compiler builds it
+// (tools/asan/longread_host.cpp runs it on a CPU).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,37 +28,46 @@ struct Aux {
     size_t n = 0;
 };
 
-// bytes of the attribute at p (tag, type, value) -> 0, or -1 when it is malformed or runs past end
-inline int aux_size(const uint8_t *p, const uint8_t *end, size_t *n) {
-    if (end - p < 3) return -1;
-    const uint8_t t = p[2];
-    switch (t) {
+// Why aux_size refuses an attribute; kAuxOk = 0
+enum AuxBad : int { kAuxOk = 0, kAuxTruncated, kAuxShortArray, kAuxBadElement, kAuxBadType };
+
+// The one rule for the bytes of the attribute at p (tag, type, value), host and device: *n = its size and kAuxOk, or why it is refused:
+// it runs past end (a Z / H without NUL in front of end included), a B with fewer than the 8 bytes of its header, a B of an unknown
+// element type, an unknown type.  Nothing at or behind end is read.
+__host__ __device__ inline int aux_size(const uint8_t *p, const uint8_t *end, size_t *n) {
+    const size_t left = (size_t)(end - p);
+    if (left < 3) return kAuxTruncated;
+    switch (p[2]) {
         case 'A': case 'c': case 'C': *n = 4; break;
         case 's': case 'S': *n = 5; break;
         case 'i': case 'I': case 'f': *n = 7; break;
         case 'Z': case 'H': {
-            const uint8_t *z = (const uint8_t *)std::memchr(p + 3, 0, end - p - 3);
-            if (!z) return -1;
+#ifdef __HIP_DEVICE_COMPILE__
+            const uint8_t *z = p + 3;
+            while (z < end && *z) z++;
+            if (z == end) return kAuxTruncated;
+#else
+            const uint8_t *z = (const uint8_t *)std::memchr(p + 3, 0, left - 3);
+            if (!z) return kAuxTruncated;
+#endif
             *n = (size_t)(z - p) + 1;
             break;
         }
         case 'B': {
-            if (end - p < 8) return -1;
+            if (left < 8) return kAuxShortArray;
             size_t w;
             switch (p[3]) {
                 case 'c': case 'C': w = 1; break;
                 case 's': case 'S': w = 2; break;
                 case 'i': case 'I': case 'f': w = 4; break;
-                default: return -1;
+                default: return kAuxBadElement;
             }
-            uint32_t cnt;
-            std::memcpy(&cnt, p + 4, 4);
-            *n = 8 + w * cnt;
+            *n = 8 + w * ((uint32_t)p[4] | (uint32_t)p[5] << 8 | (uint32_t)p[6] << 16 | (uint32_t)p[7] << 24);
             break;
         }
-        default: return -1;
+        default: return kAuxBadType;
     }
-    return p + *n <= end ? 0 : -1;
+    return *n <= left ? kAuxOk : kAuxTruncated;
 }
 
 // (Integer) getAttribute: htsjdk boxes c C s S i, and I up to 2^31 - 1, as Integer -> false for any other type

@@ -203,14 +203,6 @@ struct GeneArgs {
     unsigned long long *err_rec;
 };
 
-__device__ __forceinline__ int64_t wave_incl_sum(int64_t v, int lane) {
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long y = __shfl_up((long long)v, o);
-        if (lane >= o) v += y;
-    }
-    return v;
-}
-
 // one round of the CIGAR: lane k0 + lane's operation as a block [bs, be] (is_m) and the reference position behind the round
 __device__ __forceinline__ void cigar_round(const GeneArgs &a, const smi_bam_record &r, int k0, int lane, int64_t ref_base, bool &is_m, int64_t &bs,
                                             int64_t &be, int64_t &round_end) {

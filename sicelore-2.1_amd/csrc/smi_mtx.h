@@ -1,29 +1,19 @@
 // smi_mtx.h -- K-MTX, the dense count matrices of Matrix.writeIsoformMatrix / writeGeneMatrix / writeJunctionMatrix (Matrix.java L158-290),
 // shared by IsoformMatrix (smi_isoform.hip) and SNPMatrix (smi_snp.hip): 64-bit (row << 32 | cell) codes, one per counted UMI; hipcub radix
 // sort + run-length encoding give the counts per (row, cell); the dense rows are rendered in row blocks under a device-memory budget, one
-// wavefront per row: a length pass, a scan, the write.  (DevBuf and Events are in smi_internal.h.)
+// wavefront per row: a length pass, a scan, the write.  (DevBuf and Events are in smi_internal.h, the hipcub scratch, sort_rle and the wave
+// helpers in smi_device.h.)
 #pragma once
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <string>
 #include <vector>
 
-#include "smi_internal.h"
+#include "smi_device.h"
 
 namespace smi {
 namespace mtx {
 
 constexpr int kRenderWaves = 4;  // waves per block of the renderer
-
-__device__ __forceinline__ int digits(uint32_t v) {
-    int n = 1;
-    while (v >= 10) {
-        v /= 10;
-        n++;
-    }
-    return n;
-}
 
 // dense[(row - r0) * nc + cell] = count, for the runs of rows r0 ..
 static __global__ void k_mtx_scatter(const uint64_t *__restrict__ code, const uint32_t *__restrict__ cnt, int64_t k0, int64_t k1, int32_t r0, int32_t nc,
@@ -58,11 +48,7 @@ __global__ __launch_bounds__(64 * kRenderWaves) void k_mtx_render(const uint32_t
         const int c = c0 + lane;
         const uint32_t v = c < nc ? row[c] : 0;
         const int w = c < nc ? 1 + digits(v) : 0;
-        int incl = w;  // inclusive prefix sum across the wave
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(incl, o);
-            if (lane >= o) incl += y;
-        }
+        const int incl = wave_incl_sum(w, lane);
         if (c < nc) {
             uint8_t *p = dst + pos + (incl - w);
             p[0] = '\t';
@@ -98,21 +84,16 @@ inline int matrix(hipStream_t s, const char *who, int32_t nc, int64_t budget_byt
         DevBuf<uint64_t> d_in{who}, d_sorted{who}, d_unique{who};
         DevBuf<uint32_t> d_cnt{who};
         DevBuf<int64_t> d_nrun{who};
-        DevBuf<uint8_t> d_tmp{who};
+        Scratch tmp{who};
         if (int rc = d_in.put(codes, s)) return rc;
         if (int rc = d_sorted.alloc(n)) return rc;
         if (int rc = d_unique.alloc(n)) return rc;
         if (int rc = d_cnt.alloc(n)) return rc;
         if (int rc = d_nrun.alloc(1)) return rc;
-        size_t t1 = 0, t2 = 0;
-        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, d_in.p, d_sorted.p, (int)n, 0, end_bit, s));
-        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, d_sorted.p, d_unique.p, d_cnt.p, d_nrun.p, (int)n, s));
-        if (int rc = d_tmp.alloc(std::max(t1, t2))) return rc;
-        size_t tmp = std::max(t1, t2);
+        const auto count = sort_rle(s, d_in.p, d_sorted.p, d_unique.p, d_cnt.p, d_nrun.p, (int)n, end_bit);
+        if (int rc = count.reserve(tmp)) return rc;
         if (int rc = ev.begin(s)) return rc;
-        SMI_HIP(hipcub::DeviceRadixSort::SortKeys(d_tmp.p, tmp, d_in.p, d_sorted.p, (int)n, 0, end_bit, s));
-        tmp = std::max(t1, t2);
-        SMI_HIP(hipcub::DeviceRunLengthEncode::Encode(d_tmp.p, tmp, d_sorted.p, d_unique.p, d_cnt.p, d_nrun.p, (int)n, s));
+        if (int rc = count.run_reserved(tmp)) return rc;
         if (int rc = ev.end(s, ms_sort)) return rc;
         int64_t nrun = 0;
         SMI_HIP(hipMemcpy(&nrun, d_nrun.p, sizeof(nrun), hipMemcpyDeviceToHost));
@@ -141,6 +122,7 @@ inline int matrix(hipStream_t s, const char *who, int32_t nc, int64_t budget_byt
     if (int rc = d_lab_off.put(lab_off, s)) return rc;
     if (int rc = d_ucode.put(ucode, s)) return rc;
     if (int rc = d_ucnt.put(ucnt, s)) return rc;
+    Scratch tmp{who};  // the blocks' scans
     int64_t r0 = 0;
     size_t k0 = 0;
     while (r0 < nrows) {
@@ -157,10 +139,12 @@ inline int matrix(hipStream_t s, const char *who, int32_t nc, int64_t budget_byt
         while (k1 < ucode.size() && (int64_t)(ucode[k1] >> 32) < r1) k1++;
         DevBuf<uint32_t> d_dense{who};
         DevBuf<uint64_t> d_len{who}, d_off{who};
-        DevBuf<uint8_t> d_out{who}, d_tmp{who};
+        DevBuf<uint8_t> d_out{who};
         if (int rc = d_dense.alloc((size_t)nb * std::max(nc, 1))) return rc;
         if (int rc = d_len.alloc(nb + 1)) return rc;
         if (int rc = d_off.alloc(nb + 1)) return rc;
+        const auto scan = [&](void *p, size_t &t) { return hipcub::DeviceScan::ExclusiveSum(p, t, d_len.p, d_off.p, nb + 1, s); };
+        if (int rc = reserve(tmp, scan)) return rc;
         if (int rc = ev.begin(s)) return rc;
         SMI_HIP(hipMemsetAsync(d_dense.p, 0, (size_t)nb * std::max(nc, 1) * 4, s));
         SMI_HIP(hipMemsetAsync(d_len.p, 0, (nb + 1) * sizeof(uint64_t), s));
@@ -171,10 +155,7 @@ inline int matrix(hipStream_t s, const char *who, int32_t nc, int64_t budget_byt
         hipLaunchKernelGGL(k_mtx_render<false>, dim3(gb), dim3(64 * kRenderWaves), 0, s, d_dense.p, nb, nc, (int32_t)r0, d_lab.p, d_lab_off.p,
                            d_len.p, (uint8_t *)nullptr);
         SMI_HIP(hipGetLastError());
-        size_t tmp = 0;
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_len.p, d_off.p, nb + 1, s));
-        if (int rc = d_tmp.alloc(tmp)) return rc;
-        SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp, d_len.p, d_off.p, nb + 1, s));
+        if (int rc = run_reserved(tmp, scan)) return rc;
         uint64_t total = 0;
         SMI_HIP(hipMemcpyAsync(&total, d_off.p + nb, sizeof(total), hipMemcpyDeviceToHost, s));
         SMI_HIP(hipStreamSynchronize(s));

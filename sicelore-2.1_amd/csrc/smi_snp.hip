@@ -18,8 +18,6 @@
 //   compared).  Output per pair: record, line, cell or -1, rn, status (hit / lowRN / lowQV, L165-180), and per position base and quality.
 // K-MTX: (row, cell, UMI id) triples of the hits of listed cells: two stable hipcub radix sorts (by UMI, then by row and cell), a flag
 //   kernel and a select drop the repeats; the run lengths of what is left are the distinct UMIs (Matrix.addMolecule L88-105).
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -40,6 +38,7 @@ using lr::jint;
 using lr::jsplit;
 
 constexpr int kSnpWaves = 4;  // waves per block of K-SNP
+constexpr uint64_t kCellBasis = 1469598103934665603ull;  // where the FNV-1a walk over a barcode starts: the host's cell table and find_cell
 
 enum : uint32_t { kHit = 0, kLowRn = 1, kLowQv = 2, kStatusMask = 0xff, kPairNoQual = 1u << 8, kPairNoUmi = 1u << 9 };
 enum : uint8_t { kRecConsidered = 1, kRecBadAux = 2, kRecBadType = 4, kRecNotNull = 8 };
@@ -80,13 +79,13 @@ struct AuxInfo {
 
 // the barcode with every "-1" removed (String.replace, left to right) against the cell list
 __device__ int32_t find_cell(const SnpArgs &a, const uint8_t *s, uint32_t n) {
-    uint64_t h = 1469598103934665603ull;
+    uint64_t h = kCellBasis;
     for (uint32_t i = 0; i < n; i++) {
         if (s[i] == '-' && i + 1 < n && s[i + 1] == '1') {
             i++;
             continue;
         }
-        h = (h ^ s[i]) * 1099511628211ull;
+        h = fnv1a_add(h, s[i]);
     }
     for (uint32_t slot = (uint32_t)h & a.tab_mask;; slot = (slot + 1) & a.tab_mask) {
         const int32_t id = a.cell_tab[slot];
@@ -116,37 +115,13 @@ __device__ AuxInfo scan_aux(const SnpArgs &a, const smi_bam_record &r) {
     uint32_t cell_n = 0;
     uint8_t t_cell = 0, t_umi = 0, t_gene = 0, t_rn = 0, t_de = 0, t_df = 0;
     while (p < end) {
-        if (end - p < 3) {
+        size_t n;
+        if (lr::aux_size(p, end, &n)) {
             o.flags |= kRecBadAux;
             break;
         }
         const uint16_t tag = (uint16_t)(p[0] | p[1] << 8);
         const uint8_t t = p[2];
-        uint64_t n = 0;
-        switch (t) {
-            case 'A': case 'c': case 'C': n = 4; break;
-            case 's': case 'S': n = 5; break;
-            case 'i': case 'I': case 'f': n = 7; break;
-            case 'Z': case 'H': {
-                const uint8_t *q = p + 3;
-                while (q < end && *q) q++;
-                n = q < end ? (uint64_t)(q - p) + 1 : 0;
-                break;
-            }
-            case 'B': {
-                if (end - p >= 8) {
-                    const uint8_t e = p[3];
-                    const uint64_t w = (e == 'c' || e == 'C') ? 1 : (e == 's' || e == 'S') ? 2 : (e == 'i' || e == 'I' || e == 'f') ? 4 : 0;
-                    const uint64_t cnt = (uint64_t)p[4] | (uint64_t)p[5] << 8 | (uint64_t)p[6] << 16 | (uint64_t)p[7] << 24;
-                    n = w ? 8 + w * cnt : 0;
-                }
-                break;
-            }
-        }
-        if (n == 0 || n > (uint64_t)(end - p)) {
-            o.flags |= kRecBadAux;
-            break;
-        }
         if (tag == a.tag_cell) {
             t_cell = t;
             cell = p + 3;
@@ -172,7 +147,7 @@ __device__ AuxInfo scan_aux(const SnpArgs &a, const smi_bam_record &r) {
             case 's': o.rn = (int16_t)(rn[0] | rn[1] << 8); break;
             case 'S': o.rn = rn[0] | rn[1] << 8; break;
             case 'i': case 'I': {
-                const uint32_t v = (uint32_t)rn[0] | (uint32_t)rn[1] << 8 | (uint32_t)rn[2] << 16 | (uint32_t)rn[3] << 24;
+                const uint32_t v = ld_u32(rn);
                 if (t_rn == 'I' && v > 0x7fffffffu) o.flags |= kRecBadType;
                 o.rn = (int32_t)v;
                 break;
@@ -187,14 +162,6 @@ __device__ AuxInfo scan_aux(const SnpArgs &a, const smi_bam_record &r) {
     return o;
 }
 
-__device__ __forceinline__ int64_t wave_incl_sum(int64_t v, int lane) {
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long y = __shfl_up((long long)v, o);
-        if (lane >= o) v += y;
-    }
-    return v;
-}
-
 // the positions pp[0 .. P) (ascending) of one line against the record's CIGAR: true when every position lies in an M / = / X operation
 // at a read offset below the read length (L138-146: min > 0 and readLength > max).  *min_q: the smallest quality (at most 100, L149).
 // EMIT: base (complemented on the reverse strand, 0 = the empty string of complementBase) and quality per position at bq / bq + P.
@@ -207,10 +174,7 @@ __device__ bool resolve(const SnpArgs &a, const smi_bam_record &r, int lane, con
     for (int k0 = 0; k0 < (int)r.n_cigar && !fail && pi < P; k0 += 64) {
         const int k = k0 + lane;
         uint32_t c = 0;
-        if (k < (int)r.n_cigar) {
-            const uint8_t *q = a.bam + r.cigar_off + 4ull * k;
-            c = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
-        }
+        if (k < (int)r.n_cigar) c = ld_u32(a.bam + r.cigar_off + 4ull * k);
         const uint32_t op = c & 15;
         const int64_t len = c >> 4;
         const bool is_m = op == 0 || op == 7 || op == 8;
@@ -505,8 +469,8 @@ extern "C" int smi_snp_create(smi_ctx *ctx, const smi_snp_config *cfg, const cha
         const std::string &c = h->cells[i];
         cell_text.insert(cell_text.end(), c.begin(), c.end());
         cell_off.push_back((uint32_t)cell_text.size());
-        uint64_t x = 1469598103934665603ull;
-        for (unsigned char ch : c) x = (x ^ ch) * 1099511628211ull;
+        uint64_t x = kCellBasis;
+        for (unsigned char ch : c) x = fnv1a_add(x, ch);
         uint32_t slot = (uint32_t)x & h->tab_mask;
         while (tab[slot] >= 0) slot = (slot + 1) & h->tab_mask;
         tab[slot] = (int32_t)i;
@@ -552,7 +516,8 @@ extern "C" int smi_snp_add_segment(smi_snp *h, const uint8_t *bam, size_t n_bam,
     if (n == 0 || h->lines.empty()) return SMI_OK;
     SMI_HIP(hipSetDevice(h->ctx->device));
     hipStream_t s = h->ctx->stream;
-    DevBuf<uint8_t> d_bam{kWho}, d_flags{kWho}, d_bq{kWho}, d_tmp{kWho};
+    DevBuf<uint8_t> d_bam{kWho}, d_flags{kWho}, d_bq{kWho};
+    Scratch tmp{kWho};
     DevBuf<smi_bam_record> d_recs{kWho};
     DevBuf<uint64_t> d_np{kWho}, d_nb{kWho}, d_op{kWho}, d_ob{kWho};
     DevBuf<SnpPair> d_pairs{kWho};
@@ -595,11 +560,10 @@ extern "C" int smi_snp_add_segment(smi_snp *h, const uint8_t *bam, size_t n_bam,
     if ((rc = ev.begin(s))) return rc;
     hipLaunchKernelGGL(k_snp<false>, dim3(grid), dim3(64 * kSnpWaves), 0, s, a);
     SMI_HIP(hipGetLastError());
-    size_t tmp = 0;
-    SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_np.p, d_op.p, n + 1, s));
-    if ((rc = d_tmp.alloc(tmp))) return rc;
-    SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp, d_np.p, d_op.p, n + 1, s));
-    SMI_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp, d_nb.p, d_ob.p, n + 1, s));
+    const auto sum = [&](uint64_t *in, uint64_t *out) {  // (the iterator types of the renderer's scan: one set of scan kernels in this file)
+        return run(tmp, [=](void *p, size_t &t) { return hipcub::DeviceScan::ExclusiveSum(p, t, in, out, n + 1, s); });
+    };
+    if ((rc = sum(d_np.p, d_op.p)) || (rc = sum(d_nb.p, d_ob.p))) return rc;
     if ((rc = ev.end(s, &h->ms[0]))) return rc;
     uint64_t n_pairs = 0, n_bytes = 0;
     SMI_HIP(hipMemcpy(&n_pairs, d_op.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -757,7 +721,8 @@ extern "C" int smi_snp_run(smi_snp *h, float *stage_ms) {
     {
         DevBuf<uint64_t> d_c0{kWho}, d_c1{kWho}, d_sel{kWho};
         DevBuf<uint32_t> d_u0{kWho}, d_u1{kWho};
-        DevBuf<uint8_t> d_first{kWho}, d_tmp{kWho};
+        DevBuf<uint8_t> d_first{kWho};
+        Scratch tmp{kWho};
         DevBuf<int64_t> d_nsel{kWho};
         int rc;
         if ((rc = d_c0.put(codes, s)) || (rc = d_u0.put(umi, s)) || (rc = d_c1.alloc(nh)) || (rc = d_u1.alloc(nh)) || (rc = d_sel.alloc(nh)) ||
@@ -766,22 +731,16 @@ extern "C" int smi_snp_run(smi_snp *h, float *stage_ms) {
         int umi_bits = 1, end_bit = 32;
         while (umi_bits < 32 && ((uint64_t)1 << umi_bits) < h->umis.size()) umi_bits++;
         while (end_bit < 64 && ((uint64_t)1 << (end_bit - 32)) < (uint64_t)nrows) end_bit++;
-        size_t t1 = 0, t2 = 0, t3 = 0;
-        SMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, d_u0.p, d_u1.p, d_c0.p, d_c1.p, (int)nh, 0, umi_bits, s));
-        SMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, d_c1.p, d_c0.p, d_u1.p, d_u0.p, (int)nh, 0, end_bit, s));
-        SMI_HIP(hipcub::DeviceSelect::Flagged(nullptr, t3, d_c0.p, d_first.p, d_sel.p, d_nsel.p, (int)nh, s));
-        const size_t cap = std::max(t1, std::max(t2, t3));
-        if ((rc = d_tmp.alloc(cap))) return rc;
+        const auto by_umi = [&](void *p, size_t &t) { return hipcub::DeviceRadixSort::SortPairs(p, t, d_u0.p, d_u1.p, d_c0.p, d_c1.p, (int)nh, 0, umi_bits, s); };
+        const auto by_code = [&](void *p, size_t &t) { return hipcub::DeviceRadixSort::SortPairs(p, t, d_c1.p, d_c0.p, d_u1.p, d_u0.p, (int)nh, 0, end_bit, s); };
+        const auto select = [&](void *p, size_t &t) { return hipcub::DeviceSelect::Flagged(p, t, d_c0.p, d_first.p, d_sel.p, d_nsel.p, (int)nh, s); };
+        if ((rc = reserve(tmp, by_umi, by_code, select))) return rc;
         Events ev;
         if ((rc = ev.begin(s))) return rc;
-        size_t tmp = cap;
-        SMI_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp, d_u0.p, d_u1.p, d_c0.p, d_c1.p, (int)nh, 0, umi_bits, s));
-        tmp = cap;
-        SMI_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp, d_c1.p, d_c0.p, d_u1.p, d_u0.p, (int)nh, 0, end_bit, s));
+        if ((rc = run_reserved(tmp, by_umi)) || (rc = run_reserved(tmp, by_code))) return rc;
         hipLaunchKernelGGL(k_snp_first, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, d_c0.p, d_u0.p, (int64_t)nh, d_first.p);
         SMI_HIP(hipGetLastError());
-        tmp = cap;
-        SMI_HIP(hipcub::DeviceSelect::Flagged(d_tmp.p, tmp, d_c0.p, d_first.p, d_sel.p, d_nsel.p, (int)nh, s));
+        if ((rc = run_reserved(tmp, select))) return rc;
         if ((rc = ev.end(s, &h->ms[1]))) return rc;
         int64_t nsel = 0;
         SMI_HIP(hipMemcpy(&nsel, d_nsel.p, sizeof(nsel), hipMemcpyDeviceToHost));

@@ -38,14 +38,9 @@ __device__ __forceinline__ uint64_t mix64(uint64_t h) {  // splitmix64's finalis
     return h ^ (h >> 31);
 }
 __device__ __forceinline__ uint64_t hash_bytes(const uint8_t *p, uint32_t n, uint64_t hash_mask) {
-    uint64_t h = 0xcbf29ce484222325ull ^ n;  // FNV-1a over the bytes, then mixed
-    for (uint32_t i = 0; i < n; i++) h = (h ^ p[i]) * 0x100000001b3ull;
+    uint64_t h = kFnvBasis ^ n;  // FNV-1a over the bytes, then mixed
+    for (uint32_t i = 0; i < n; i++) h = fnv1a_add(h, p[i]);
     return mix64(h) & hash_mask;
-}
-__device__ __forceinline__ bool same_bytes(const uint8_t *a, const uint8_t *b, uint32_t n) {
-    for (uint32_t i = 0; i < n; i++)
-        if (a[i] != b[i]) return false;
-    return true;
 }
 
 __global__ void k_tag_key(const uint8_t *__restrict__ text, const uint64_t *__restrict__ name_start, const uint32_t *__restrict__ name_len,

@@ -202,3 +202,10 @@ def remapped_bam(fastq):
     names = [ln[1:].decode() for ln in fastq.split(b"\n")[0::4] if ln]
     recs = [bammodel.bam_record(nm, 0, 0, 1000 + 10 * k, 60, [("M", 100)], "ACGT", aux=tm.aux_int("NM", "C", 1) + tm.aux_f("de", 0.01)) for k, nm in enumerate(names)]
     return bam(recs)
+
+
+def damaged_cases():
+    """name -> a BAM with one clipped record whose attributes no walker accepts (tests/auxcases.py DAMAGED) between good ones, for
+    K-CLIP-FLAG's clean refusal"""
+    import auxcases
+    return {k: bam(hand_records()[:4] + [rec("damaged", S200, extra=v)] + hand_records()[4:8]) for k, v in auxcases.DAMAGED.items()}

@@ -114,6 +114,12 @@ CASES = {
     "b_of_type_x": (_one(rec("x", extra=b"XBBx" + struct.pack("<I", 1) + b"\0")), dict(malformed="x")),
     "b_past_the_end": (bam(_good(0) + [rec("x", extra=b"XBBi" + struct.pack("<I", 9) + b"\0" * 8)]), dict(malformed="x")),
     "two_bytes": (bam(_good(0) + [rec("x", extra=b"XY")]), dict(malformed="x")),
+    "one_byte": (_one(rec("x", extra=b"X")), dict(malformed="x")),
+    "i_cut_short": (bam(_good(0) + [rec("x", extra=b"XIi\1\0\0")]), dict(malformed="x")),
+    "h_without_nul": (bam(_good(0) + [rec("x", extra=b"XHH1a")]), dict(malformed="x")),
+    "b_seven_bytes": (_one(rec("x", extra=b"XBBc\0\0\0")), dict(malformed="x")),
+    "b_count_max": (_one(rec("x", extra=b"XBBc" + struct.pack("<I", 0xffffffff) + b"\1\2\3")), dict(malformed="x")),
+    "type_q": (_one(rec("x", extra=b"XYq\0\0\0\0")), dict(malformed="x")),
     # CIGAR and filter order
     "clip_no_block": (_one(rec("x", cigar=[("S", 10001)])), {}),
     "clip_no_block_151": (_one(rec("x", cigar=[("S", 151)])), {}),

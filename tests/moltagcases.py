@@ -185,3 +185,9 @@ def error_case(under_gene):
 
 
 GENE_CASES = {"search": search_case, "locus": locus_case, "cigar": cigar_case, "strand": strand_case, "collision": lambda: collision_case()[:3]}
+
+
+def damaged_records():
+    """name -> a record whose attributes no walker accepts (tests/auxcases.py DAMAGED), for K-EDIT's clean refusal"""
+    import auxcases
+    return {k: rec("plain", [("M", 4)], aux=tm.aux_z("XA", "a") + v) for k, v in auxcases.DAMAGED.items()}

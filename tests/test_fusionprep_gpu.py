@@ -124,6 +124,15 @@ def test_stop_cases_exit_1_name_the_read_and_leave_no_file(fp, lib, gpu_ctx, tmp
     assert os.listdir(tmp_path) == ["in.bam"]                     # no output file, no temporary file
 
 
+def test_damaged_attributes_are_refused_and_leave_no_file(fp, lib, gpu_ctx, tmp_path):
+    """every way an attribute list goes wrong (tests/auxcases.py DAMAGED) under K-CLIP-FLAG's walk"""
+    for name, bam in pc.damaged_cases().items():
+        (tmp_path / "in.bam").write_bytes(bammodel.bgzf_compress(bam))
+        with pytest.raises(lib.SmiError, match="a record's attributes cannot be read: malformed or unknown attribute type"):
+            fp.export_clipped_reads(gpu_ctx, str(tmp_path / "in.bam"), str(tmp_path / "out.fastq"))
+        assert os.listdir(tmp_path) == ["in.bam"], name
+
+
 def test_a_stop_behind_a_written_record_of_its_key_is_none(fp, gpu_ctx, tmp_path):
     R = pc.hand_records()
     _export(fp, gpu_ctx, tmp_path, pc.bam(R + [pc.rec("hus_first", pc.S200, ge="GH"), pc.STOPS["h_typed_us"]()]), block=600, segment_bytes=700)

@@ -1,11 +1,13 @@
 """The record reader of csrc/smi_longread.h on a CPU: tools/asan/longread_host.cpp, built here with g++, runs the filters of
 IsoformMatrix, ComputeConsensus, CollapseModel and FusionDetector through lr::read_segment over the BAMs of tests/longreadcases.py; the
-counters, the kept records and the read an error names must be those of the Python models, for every case and every program."""
+counters, the kept records and the read an error names must be those of the Python models, for every case and every program.  Its --aux
+mode walks the attribute lists of tests/auxcases.py with lr::aux_size alone, the rule the kernels call too."""
 import os
 import subprocess
 
 import pytest
 
+import auxcases as ac
 import longreadcases as lc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,3 +111,31 @@ def test_the_cases_hold_what_they_are_named_for():
     assert all(v["null"] > 0 and v["records"] == 8200 for v in kind("threaded").values())
     e = lc.expected("threaded_errors")
     assert all(e[p][:2] == ("error", "t4100") for p in lc.PROGRAMS)
+
+
+def test_the_attribute_size_rule_walks_every_list_as_the_model_does(tool, tmp_path):
+    names = sorted(ac.CASES)
+    (tmp_path / "blobs.txt").write_text("".join(ac.CASES[n].hex() + "\n" for n in names))
+    text = subprocess.run([tool, "--aux", str(tmp_path / "blobs.txt")], check=True, capture_output=True).stdout.decode()
+    lines = text.split("\n")[:-1]
+    assert len(lines) == len(names)
+    for name, line in zip(names, lines):
+        got = [tuple(int(x) for x in step.split(":")) for step in line.split()]
+        assert got == ac.walk(ac.CASES[name]), name
+
+
+def test_the_attribute_lists_hold_what_they_are_named_for():
+    w = {n: ac.walk(b) for n, b in ac.CASES.items()}
+    assert w["empty"] == [] and w["one_byte"] == w["two_bytes"] == w["tag_and_type"] == [(0, ac.TRUNCATED)]
+    assert w["good_then_one"] == w["good_then_two"] == [(4, ac.FINE), (0, ac.TRUNCATED)]
+    for t, width in ac.WIDTH.items():
+        assert w[f"scalar_{t}"] == [(4, ac.FINE), (3 + width, ac.FINE)] and w[f"scalar_{t}_short"] == [(4, ac.FINE), (0, ac.TRUNCATED)], t
+    assert w["z"] == [(4, ac.FINE), (7, ac.FINE)] and w["z_empty"] == [(4, ac.FINE)] and w["z_then_good"] == [(6, ac.FINE), (4, ac.FINE)]
+    assert w["z_no_nul"] == w["h_no_nul"] == [(4, ac.FINE), (0, ac.TRUNCATED)] and w["z_no_value"] == [(0, ac.TRUNCATED)]
+    assert w["h"] == [(4, ac.FINE), (8, ac.FINE)] and w["h_odd"] == [(7, ac.FINE), (4, ac.FINE)] and w["h_not_hex"] == [(6, ac.FINE)]
+    for e, width in ac.ELEMENT.items():
+        assert w[f"b_{e}_0"] == [(4, ac.FINE), (8, ac.FINE), (4, ac.FINE)] and w[f"b_{e}_1"] == [(8 + width, ac.FINE), (4, ac.FINE)], e
+    assert w["b_seven_left"] == [(4, ac.FINE), (0, ac.SHORT_ARRAY)] and w["b_header_only_type"] == [(0, ac.SHORT_ARRAY)]
+    assert w["b_bad_element"] == [(4, ac.FINE), (0, ac.BAD_ELEMENT)] and w["b_bad_element_short"] == [(0, ac.SHORT_ARRAY)]
+    assert w["b_one_past"] == w["b_huge"] == [(4, ac.FINE), (0, ac.TRUNCATED)] and w["b_one_past_i"] == w["b_huge_f"] == [(0, ac.TRUNCATED)]
+    assert w["bad_type"] == w["bad_type_last"] == [(4, ac.FINE), (0, ac.BAD_TYPE)] and w["bad_type_nul"] == [(0, ac.BAD_TYPE)]

@@ -94,6 +94,10 @@ def test_attribute_limit(mt, lib, gpu_ctx, tmp_path):
         src, dst = _write(tmp_path, mc.bam_of([("chr1", 10 ** 6)], [mc.rec("plain", [("M", 4)], aux=bad)]))
         with pytest.raises(lib.SmiError, match=msg):
             mt.add_bam_molecule_tags(gpu_ctx, src, dst)
+    for record in mc.damaged_records().values():                    # every way an attribute list goes wrong: SMI_TAG_BAD_AUX
+        src, dst = _write(tmp_path, mc.bam_of([("chr1", 10 ** 6)], mc.name_records() + [record]))
+        with pytest.raises(lib.SmiError, match="malformed or unknown attribute type"):
+            mt.add_bam_molecule_tags(gpu_ctx, src, dst)
 
 
 @pytest.mark.parametrize("stop", mc.STOP_NAMES)

@@ -177,3 +177,17 @@ def test_errors_name_the_line_or_the_read(pkg, snp, gpu_ctx, tmp_path, what, msg
     cli = importlib.import_module("sicelore_amd.cli")
     assert cli.main(["SNPMatrix", f"I={args[0]}", f"CSV={args[1]}", f"SNP={args[2]}", f"O={args[3]}"]) == 1
     assert not [f for f in os.listdir(tmp_path) if f.startswith("snp_")]
+
+
+def test_damaged_attributes_are_malformed_attributes(pkg, snp, gpu_ctx, tmp_path):
+    """every way an attribute list goes wrong (tests/auxcases.py DAMAGED) under K-SNP's walk: kRecBadAux, the read named"""
+    import auxcases
+    (tmp_path / "s.csv").write_text("chr1,1010,+,s\n")
+    (tmp_path / "c.csv").write_text(sm.CSV)
+    for name, extra in auxcases.DAMAGED.items():
+        recs = [sm.rec("good", [("M", 100)], 1000, "CELL1", "U0"), sm.rec("bad", [("M", 100)], 1000, "CELL1", "U", extra=extra),
+                sm.rec("good2", [("M", 100)], 1000, "CELL1", "U1")]
+        (tmp_path / "in.bam").write_bytes(bammodel.bgzf_compress(bammodel.bam_bytes(sm.HEAD, sm.REFS, recs)))
+        with pytest.raises(pkg.SmiError) as e:
+            snp.snp_matrix(gpu_ctx, str(tmp_path / "in.bam"), str(tmp_path / "c.csv"), str(tmp_path / "s.csv"), str(tmp_path))
+        assert str(e.value).endswith("read bad: malformed attributes"), (name, str(e.value))

@@ -8,6 +8,10 @@
 // Output, per program: `<program> refused <text>`, or `<program> error <index> <read> <text>`, or `<program> counts k=v ...` followed
 // by one `<program> kept <read> <barcode, "-1" removed> <umi or *> <cdna or *> <junctions end-start,...>` per kept record.  Fields are
 // separated by tabs.
+//   longread_host --aux blobs.txt            the attribute-size rule alone (lr::aux_size, which the kernels that walk attributes call too):
+// blobs.txt holds one attribute list per line as hex digits (an empty line: the empty list); per list one line of `size:reason` steps, as
+// the rule walks it from the first byte: the size of each attribute it accepts with reason 0, then, where it refuses, `0:reason`
+// (lr::AuxBad) and nothing more.  Every list is walked in a heap block of exactly its size.
 // tests/test_longread_cpu.py builds and runs it and compares with the Python models.
 #include <cstdio>
 #include <fstream>
@@ -98,9 +102,39 @@ static void report(const char *program, const uint8_t *bam, const smi_bam_record
         }
 }
 
+// --aux: see the head of the file
+static int walk_aux(const char *path) {
+    std::ifstream f(path);
+    if (!f) {
+        std::fprintf(stderr, "longread_host: cannot open the input\n");
+        return 2;
+    }
+    for (std::string line; std::getline(f, line);) {
+        if (line.size() & 1) {
+            std::fprintf(stderr, "longread_host: odd number of hex digits\n");
+            return 2;
+        }
+        std::vector<uint8_t> blob(line.size() / 2);
+        for (size_t i = 0; i < blob.size(); i++) blob[i] = (uint8_t)std::stoi(line.substr(2 * i, 2), nullptr, 16);
+        const uint8_t *p = blob.data(), *end = p + blob.size();
+        const char *sep = "";
+        while (p < end) {
+            size_t n = 0;
+            const int bad = lr::aux_size(p, end, &n);
+            std::printf("%s%zu:%d", sep, bad ? (size_t)0 : n, bad);
+            sep = " ";
+            if (bad) break;
+            p += n;
+        }
+        std::printf("\n");
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc == 3 && !std::strcmp(argv[1], "--aux")) return walk_aux(argv[2]);
     if (argc != 3) {
-        std::fprintf(stderr, "usage: longread_host in.bam settings.txt\n");
+        std::fprintf(stderr, "usage: longread_host in.bam settings.txt | longread_host --aux blobs.txt\n");
         return 2;
     }
     std::ifstream fb(argv[1], std::ios::binary), fs(argv[2]);

@@ -189,8 +189,10 @@ int smi_set_barcode_set_device(smi_ctx *ctx, const uint32_t *d_keys, size_t n, i
  * set_hbm_bytes and for cross-checks of the build kernels): out[0] distinct keys, out[1] bytes of device memory the structures of the loaded set
  * occupy (pyramid + nb + nb5 + nt + n1 / n2 / nb2 as far as they are valid for this set), out[2] wall time of the build in microseconds (launch to
  * drained stream), out[3] bits set in nb, out[4] bits set in nb5, out[5] an order-sensitive digest of nb5 (sum of popcount(word) * (index mod 2^20 + 1)),
- * out[6] slots of nt, out[7] entries in nt.  With digests != 0 the counting kernels run (a few ms for the whole whitelist); 0 leaves out[3..7] zero. */
-int smi_set_stats(smi_ctx *ctx, uint64_t out[8], int digests);
+ * out[6] slots of nt, out[7] entries in nt.  With digests != 0 the counting kernels run (a few ms for the whole whitelist); 0 leaves out[3..7] zero.
+ * `out` has eight entries; a caller that sets bit 1 of `digests` (2 or 3) passes TEN and also gets out[8] bits set in nbl (nb5 with its two outer offsets
+ * folded so that a read's five filter bits share one 128-byte line, 2 GiB, counted in out[1]) and out[9] its digest, both zero where nbl was not built. */
+int smi_set_stats(smi_ctx *ctx, uint64_t *out, int digests);
 
 /* Replaces BarcodeMatchTester.call for the 5 offsets + the best/second rule of Parser.assignBarcode
  * (BarcodeMatchTester.java:L198-374, Parser.java:L203-311).  max_ed in {0,1,2}; five_prime = 1 for -h/--fivePbc. */

@@ -13,6 +13,7 @@
 // Integer/bitwise work only: no MFMA, no LDS (the pyramid's top level lives in L2, the window batch in
 // registers).
 #include <chrono>
+#include <mutex>
 
 #include <hipcub/hipcub.hpp>
 
@@ -122,6 +123,43 @@ __device__ __forceinline__ uint32_t nb5_bit_index(uint32_t key, int d, uint32_t 
     const uint32_t flank = ((key >> 24) & ~low & 0xFFu) | (key & low);      // the 2 + d leading bases above the 2 - d trailing ones
     word = core * 40u + (uint32_t)(d + 2) * 8u + (flank >> 5);
     return flank & 31u;
+}
+
+// nbl: nb5 in ONE 128-byte line per core.  The L2 and the fabric fetch 128 bytes at a time, and a row of 160 bytes at a multiple of 160 always lies in two
+// such lines: two filter misses per read.  A row of 1,280 bits needs only 256 fewer to fit one line: offsets 0 and +-1 keep their eight words, offsets
+// +-2 get four (word j ORed onto word j & 3).  32 words = one aligned line per core, 2 GiB.  OR only adds bits: nbl is a SUPERSET filter.  A window that
+// passes it by the fold finds no entry of its sequence in the neighbourhood table (whose compare is exact) and gets code 0, as if the filter had stopped it;
+// only the two outer offsets are denser (two rows of ~ 10 % ORed), so that happens for a fifth of them.  Words per d = -2 .. 2: 4 / 8 / 8 / 8 / 4 at bases
+// 0 / 4 / 12 / 20 / 28.
+constexpr size_t kNblWords = ((size_t)1 << 24) * 32;
+__device__ __forceinline__ uint32_t nbl_bit_index(uint32_t key, int d, uint32_t &word) {
+    const int sh = 2 * (2 - d);
+    const uint32_t core = (key >> sh) & 0xFFFFFFu;
+    const uint32_t low = (1u << sh) - 1u;
+    const uint32_t flank = ((key >> 24) & ~low & 0xFFu) | (key & low);
+    const uint32_t base = d == -2 ? 0u : (uint32_t)(8 * d + 12);            // 0, 4, 12, 20, 28
+    const uint32_t mask = (d == -2 || d == 2) ? 3u : 7u;
+    word = (core << 5) + base + ((flank >> 5) & mask);                      // (+: the bases 4, 12 and 20 are no multiples of eight)
+    return flank & 31u;
+}
+// The fold: row r of nbl = row r of nb5 with words 4 .. 7 of its first and last block ORed onto words 0 .. 3.  One 16-byte piece of output per lane and
+// turn: piece 0 = input pieces 0 | 1, pieces 1 .. 6 = input pieces 2 .. 7, piece 7 = input pieces 8 | 9 (a row of nb5 is ten pieces).  Streams 2.5 GiB in,
+// 2 GiB out; every word of nbl is written.
+__global__ __launch_bounds__(256) void k_nbl_from_nb5(const uint4 *__restrict__ nb5, uint4 *__restrict__ nbl) {
+    const size_t n16 = kNblWords / 4;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t v = (uint32_t)i & 7u;
+        const uint4 *row = nb5 + (i >> 3) * 10;
+        uint4 a;
+        if (v == 0u || v == 7u) {
+            const uint32_t p = v == 0u ? 0u : 8u;
+            const uint4 b = row[p + 1];
+            a = row[p];
+            a.x |= b.x, a.y |= b.y, a.z |= b.z, a.w |= b.w;
+        } else
+            a = row[v + 1];
+        nbl[i] = a;
+    }
 }
 
 __global__ void k_set_nb(const uint32_t *__restrict__ keys, size_t n, uint32_t *__restrict__ nb, uint32_t *__restrict__ nb5) {
@@ -328,23 +366,47 @@ __global__ void k_nt_entries(const uint64_t *__restrict__ nt, size_t cap, unsign
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
     if ((threadIdx.x & 63) == 0) atomicAdd(out, cnt);
 }
-int launch_set_digests(smi_ctx *ctx, uint64_t *out5, hipStream_t s) {
+// nbl is folded when the loaded set is first looked up at ed <= 1 (or its digest asked for), not when the set is loaded: the ed <= 2 matcher and pass 1
+// never read it, and the two-pass mode loads a set per batch -- the fold streams 4.5 GiB (0.93 ms) whatever the list holds.  The fold runs on the caller's
+// stream and is waited for, so that a lane that finds the flag up may read the table from any stream; lanes of one owner that arrive together take turns.
+int ensure_nbl(smi_ctx *ctx, hipStream_t s) {
+    if (ctx->nbl_valid) return SMI_OK;
+    smi_ctx *o = ctx->set_owner ? const_cast<smi_ctx *>(ctx->set_owner) : ctx;
+    if (!o->nbl_wanted || !o->nb5_valid) return SMI_OK;
+    static std::mutex mu;
+    std::lock_guard<std::mutex> guard(mu);
+    if (!o->nbl_valid) {
+        hipLaunchKernelGGL(k_nbl_from_nb5, dim3(256 * 32), dim3(256), 0, s, reinterpret_cast<const uint4 *>(o->nb5), reinterpret_cast<uint4 *>(o->nbl));  // (every word of nbl is written: no memset)
+        SMI_HIP(hipGetLastError());
+        SMI_HIP(hipStreamSynchronize(s));
+        o->nbl_valid = true;
+    }
+    ctx->nbl = o->nbl;
+    ctx->nbl_valid = true;
+    return SMI_OK;
+}
+
+int launch_set_digests(smi_ctx *ctx, uint64_t *out7, hipStream_t s) {
+    if (int rc = ensure_nbl(ctx, s)) return rc;
     unsigned long long *d = nullptr;
-    SMI_HIP(hipMalloc((void **)&d, 5 * 8));
-    SMI_HIP(hipMemsetAsync(d, 0, 5 * 8, s));
+    SMI_HIP(hipMalloc((void **)&d, 7 * 8));
+    SMI_HIP(hipMemsetAsync(d, 0, 7 * 8, s));
     if (ctx->nb_valid) hipLaunchKernelGGL(k_bits_digest, dim3(4096), dim3(256), 0, s, ctx->nb, kFineWords, d);
     if (ctx->nb5_valid) hipLaunchKernelGGL(k_bits_digest, dim3(4096), dim3(256), 0, s, ctx->nb5, kNb5Words, d + 2);
     if (ctx->nt_cap) hipLaunchKernelGGL(k_nt_entries, dim3(4096), dim3(256), 0, s, ctx->nt, (size_t)ctx->nt_cap, d + 4);
-    unsigned long long h[5];
+    if (ctx->nb5_valid && ctx->nbl_valid) hipLaunchKernelGGL(k_bits_digest, dim3(4096), dim3(256), 0, s, ctx->nbl, kNblWords, d + 5);
+    unsigned long long h[7];
     hipError_t e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(d);
     SMI_HIP(e);
-    out5[0] = h[0];  // bits of nb
-    out5[1] = h[2];  // bits of nb5
-    out5[2] = h[3];  // digest of nb5
-    out5[3] = ctx->nt_cap;
-    out5[4] = h[4];
+    out7[0] = h[0];  // bits of nb
+    out7[1] = h[2];  // bits of nb5
+    out7[2] = h[3];  // digest of nb5
+    out7[3] = ctx->nt_cap;
+    out7[4] = h[4];
+    out7[5] = h[5];  // bits of nbl
+    out7[6] = h[6];  // digest of nbl
     return SMI_OK;
 }
 
@@ -400,6 +462,8 @@ int launch_build_pyramid(smi_ctx *ctx, const uint32_t *d_keys, size_t n, hipStre
     SMI_HIP(hipMemcpyAsync(&last[1], ctx->block_counts + (kRankEntries - 1), 4, hipMemcpyDeviceToHost, s));
     ctx->nb_valid = false;
     ctx->nb5_valid = false;
+    ctx->nbl_wanted = false;
+    ctx->nbl_valid = false;
     ctx->nt_cap = 0;
     mark("rank scan");
     if (n > 0 && !membership_only && !std::getenv("SMI_BC1_NO_FILTER")) {  // (the switch: tests run K-BC1 with and without the filter)
@@ -410,6 +474,13 @@ int launch_build_pyramid(smi_ctx *ctx, const uint32_t *d_keys, size_t n, hipStre
         const bool want_nb5 = !std::getenv("SMI_BC1_NO_TABLE") && !std::getenv("SMI_BC1_NO_NB5");  // (the second switch: cross-checks of the two layouts)
         if (want_nb5 && !ctx->nb5 && hipMalloc((void **)&ctx->nb5, kNb5Words * 4) != hipSuccess) {
             ctx->nb5 = nullptr;
+            (void)hipGetLastError();
+        }
+        // nbl is folded from nb5; a device that cannot spare its 2 GiB keeps nb5, as it keeps nb where nb5 cannot be had.  (SMI_BC1_NO_NBL: the third
+        // switch, today's nb5 probe as the cross-check of the fold.)
+        const bool want_nbl = want_nb5 && ctx->nb5 && !std::getenv("SMI_BC1_NO_NBL");
+        if (want_nbl && !ctx->nbl && hipMalloc((void **)&ctx->nbl, kNblWords * 4) != hipSuccess) {
+            ctx->nbl = nullptr;
             (void)hipGetLastError();
         }
         // Round 6: the bitmap chain (nb, then nb5 from it) and the table are independent and bound by different things (atomics on 512 MiB against
@@ -463,6 +534,7 @@ int launch_build_pyramid(smi_ctx *ctx, const uint32_t *d_keys, size_t n, hipStre
         }
         ctx->nb_valid = true;
         ctx->nb5_valid = want_nb5 && ctx->nb5 != nullptr;
+        ctx->nbl_wanted = want_nbl && ctx->nbl != nullptr;  // (folded from either build of nb5 by the first look-up that reads it: ensure_nbl)
         ctx->nt_cap = 0;
         if (!std::getenv("SMI_BC1_NO_TABLE")) {  // (the switch: the filtered kernel that enumerates the mutants of the flagged offsets)
             const size_t pairs = n * (size_t)kN1Slots;
@@ -1194,67 +1266,108 @@ __global__ __launch_bounds__(256) void k_bc_match_ed1f(const smi_bc_window *__re
 // the insertion behind position 14 of a window that does not end in A (the Java shift wrap, see `mutate`).  The smallest valid index is
 // the match the reference's HashSet keeps.  -> one byte per pair: exact << 7 | (index + 1).  No mutant is generated, no membership probed.
 // k_bc_pick_ed1t: one lane = one read: the HashSet-order / best-second rule over its five bytes.
+// The look-up of one (read, offset) pair -> its byte.  A slot is compared in 32-bit halves (entry = 1 << 40 | sequence << 8 | step: the low word XOR
+// sequence << 8 is below 256 -- and then IS the step -- where the low 24 bits agree, the high word equals 0x100 | sequence >> 24 where the rest does; an
+// empty slot has a high word of 0), and slots fill from the front in both builds of the table (the counters hand them out in order, the compare-and-swap
+// build takes the first free one), so a bucket has a free slot exactly when its LAST slot is free.  -DSMI_BC1_BUCKET_COMPARE64=1: the 64-bit compares and
+// the free-slot test over all eight slots, as they were (the counter runs' "before").
+// The offset of pair q (0, -1, 1, -2, 2: the reference's order, Parser.java:L203) by arithmetic: as a chain of selects on a lane-varying q the compiler
+// built it from divergent branches.  -DSMI_BC1_OFFSET_SELECTS=1: the chain of selects, as it was.
+__device__ __forceinline__ uint32_t bc1_code(const smi_bc_window *__restrict__ w, int q, bool fp, const Pyramid &P) {
+#if SMI_BC1_OFFSET_SELECTS
+    const int off = q == 0 ? 0 : (q == 1 ? -1 : (q == 2 ? 1 : (q == 3 ? -2 : 2)));
+#else
+    const int mag = (q + 1) >> 1, off = (q & 1) ? -mag : mag;
+#endif
+    // the window as ONE 16-byte load (as `win[i]` the flags word was fetched and tested first, the bases behind that wait: a fourth
+    // dependent round trip in front of the filter bit, the bucket and the store)
+    smi_bc_window my;
+    {
+        const uint4 raw = *reinterpret_cast<const uint4 *>(w);
+        my.bases = ((uint64_t)raw.y << 32) | raw.x;
+        my.nmask = raw.z;
+        my.flags = raw.w;
+    }
+    uint32_t code = 0;
+    // key and filter word for every lane, valid window or not (any 32-bit key lies inside the 512 MiB bitmap): nothing but the window's
+    // own load stands in front of the probe
+    const OffsetKey k = make_key(my.bases, my.nmask, off, fp);
+    const uint32_t K = k.key;
+    uint32_t word, wbit = K & 31u;
+    if (P.nbl) {  // (wave-uniform) the five lanes of a read ask for words of ONE 128-byte line; a superset of nb5's bits, and the bucket compare decides
+        uint32_t wi;
+        wbit = nbl_bit_index(K, fp ? -off : off, wi);
+        word = P.nbl[wi];
+    } else if (P.nb5) {  // (wave-uniform) the five lanes of a read ask for neighbouring words: 160 consecutive bytes, two 128-byte lines
+        uint32_t wi;
+        wbit = nb5_bit_index(K, fp ? -off : off, wi);
+        word = P.nb5[wi];
+    } else
+        word = P.nb[K >> 5];
+    if ((my.flags & SMI_WIN_VALID) && k.usable && ((word >> wbit) & 1u)) {
+        uint32_t best = 255u;
+        uint32_t idx = nt_slot(K, P.nt_cap);
+#if !SMI_BC1_BUCKET_COMPARE64
+        const uint32_t k_lo = K << 8, k_hi = (K >> 24) | 0x100u;
+#endif
+        for (;;) {
+            uint64_t e[8];
+            __builtin_memcpy(e, P.nt + idx, 64);  // one bucket = one line
+#if SMI_BC1_BUCKET_COMPARE64
+            bool open = false;
+#else
+            const bool open = (uint32_t)(e[7] >> 32) == 0u;
+#endif
+#pragma unroll
+            for (int t = 0; t < 8; t++) {
+#if SMI_BC1_BUCKET_COMPARE64
+                open = open || e[t] == 0ull;
+                const uint32_t step = (uint32_t)e[t];
+                if ((uint32_t)(e[t] >> 8) == K && (e[t] >> 40)) {
+#else
+                const uint32_t step = (uint32_t)e[t] ^ k_lo;
+                if (step < 256u && (uint32_t)(e[t] >> 32) == k_hi) {
+#endif
+                    const uint32_t kind = step & 3u, pos = (step >> 2) & 15u, base = (step >> 6) & 3u;
+                    if (kind == 0u) {
+                        code |= 0x80u;  // exact match (BarcodeMatchTester.java:L204-206)
+                    } else if (kind == 1u) {
+                        const uint32_t cur = (K >> (30 - 2 * pos)) & 3u;
+                        best = min(best, 8u * pos + base - (base > cur ? 1u : 0u));  // substitutions by ascending base, the current one skipped
+                    } else if (kind == 2u) {
+                        if (!(pos == 14u && (K & 3u) != 0u)) best = min(best, 8u * pos + 3u + base);
+                    } else {
+                        if (base == k.del_base) best = min(best, 8u * pos + 7u);
+                    }
+                }
+            }
+            if (open) break;  // a bucket with a free slot has never overflowed into the next one
+            idx = idx + 8 == P.nt_cap ? 0u : idx + 8;
+        }
+        if (best != 255u) code |= best + 1u;
+    }
+    return code;
+}
+
+// (read, offset) = (j / 5, j mod 5) in 32 bits where every index of the grid-stride loop fits them -- as size_t the quotient and the remainder are 64-bit
+// multiply-high sequences in every lane.  -DSMI_BC1_INDEX64=1: 64 bits for every batch (the counter runs' "before").
 __global__ __launch_bounds__(256) void k_bc_codes_ed1t(const smi_bc_window *__restrict__ win, size_t n, int five_prime, Pyramid P,
                                                        uint8_t *__restrict__ codes) {
     const bool fp = five_prime != 0;
     const size_t total = n * 5;
+#if !SMI_BC1_INDEX64
+    if (total + (size_t)gridDim.x * blockDim.x <= 0xFFFFFFFFull) {  // (no index of the loop, the one that ends it included, wraps)
+        const uint32_t total32 = (uint32_t)total, stride = gridDim.x * blockDim.x;
+        for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < total32; j += stride) {
+            const uint32_t i = j / 5u;
+            codes[j] = (uint8_t)bc1_code(win + i, (int)(j - 5u * i), fp, P);
+        }
+        return;
+    }
+#endif
     for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < total; j += (size_t)gridDim.x * blockDim.x) {
         const size_t i = j / 5;
-        const int q = (int)(j - 5 * i);
-        const int off = q == 0 ? 0 : (q == 1 ? -1 : (q == 2 ? 1 : (q == 3 ? -2 : 2)));  // the reference's order (Parser.java:L203)
-        // the window as ONE 16-byte load (as `win[i]` the flags word was fetched and tested first, the bases behind that wait: a fourth
-        // dependent round trip in front of the filter bit, the bucket and the store)
-        smi_bc_window my;
-        {
-            const uint4 raw = *reinterpret_cast<const uint4 *>(win + i);
-            my.bases = ((uint64_t)raw.y << 32) | raw.x;
-            my.nmask = raw.z;
-            my.flags = raw.w;
-        }
-        uint32_t code = 0;
-        {
-            // key and filter word for every lane, valid window or not (any 32-bit key lies inside the 512 MiB bitmap): nothing but the window's
-            // own load stands in front of the probe
-            const OffsetKey k = make_key(my.bases, my.nmask, off, fp);
-            const uint32_t K = k.key;
-            uint32_t word, wbit = K & 31u;
-            if (P.nb5) {  // (wave-uniform) the five lanes of a read ask for neighbouring words: three sectors per read instead of five
-                uint32_t wi;
-                wbit = nb5_bit_index(K, fp ? -off : off, wi);
-                word = P.nb5[wi];
-            } else
-                word = P.nb[K >> 5];
-            if ((my.flags & SMI_WIN_VALID) && k.usable && ((word >> wbit) & 1u)) {
-                uint32_t best = 255u;
-                uint32_t idx = nt_slot(K, P.nt_cap);
-                for (;;) {
-                    uint64_t e[8];
-                    __builtin_memcpy(e, P.nt + idx, 64);  // one bucket = one line
-                    bool open = false;
-#pragma unroll
-                    for (int t = 0; t < 8; t++) {
-                        open = open || e[t] == 0ull;
-                        if ((uint32_t)(e[t] >> 8) == K && (e[t] >> 40)) {
-                            const uint32_t kind = (uint32_t)e[t] & 3u, pos = ((uint32_t)e[t] >> 2) & 15u, base = ((uint32_t)e[t] >> 6) & 3u;
-                            if (kind == 0u) {
-                                code |= 0x80u;  // exact match (BarcodeMatchTester.java:L204-206)
-                            } else if (kind == 1u) {
-                                const uint32_t cur = (K >> (30 - 2 * pos)) & 3u;
-                                best = min(best, 8u * pos + base - (base > cur ? 1u : 0u));  // substitutions by ascending base, the current one skipped
-                            } else if (kind == 2u) {
-                                if (!(pos == 14u && (K & 3u) != 0u)) best = min(best, 8u * pos + 3u + base);
-                            } else {
-                                if (base == k.del_base) best = min(best, 8u * pos + 7u);
-                            }
-                        }
-                    }
-                    if (open) break;  // a bucket with a free slot has never overflowed into the next one
-                    idx = idx + 8 == P.nt_cap ? 0u : idx + 8;
-                }
-                if (best != 255u) code |= best + 1u;
-            }
-        }
-        codes[j] = (uint8_t)code;
+        codes[j] = (uint8_t)bc1_code(win + i, (int)(j - 5 * i), fp, P);
     }
 }
 
@@ -1296,6 +1409,8 @@ int launch_bc_match(smi_ctx *ctx, const smi_bc_window *d_win, size_t n, int max_
                     smi_bc_result *d_out, hipStream_t s) {
     if (!n) return SMI_OK;
     if (max_ed == 2) return launch_bc_match2(ctx, d_win, n, five_prime, d_out, s);
+    if (max_ed == 1 && ctx->nt_cap)  // (the table path's look-up kernel is the one reader of nbl)
+        if (int rc = ensure_nbl(ctx, s)) return rc;
     Pyramid P = pyramid_of(ctx);
     const size_t n_waves = (n + 63) / 64;
     const unsigned grid = (unsigned)((n_waves + 3) / 4);  // one batch of 64 reads per wave: measured 3 % faster than a capped grid

@@ -49,6 +49,7 @@ Pyramid pyramid_of(const smi_ctx *ctx) {
     p.nb2 = ctx->n1_valid && ctx->nb2_valid ? ctx->n1_owner : nullptr;
     p.nb = ctx->nb_valid ? ctx->nb : nullptr;
     p.nb5 = ctx->nb_valid && ctx->nb5_valid ? ctx->nb5 : nullptr;
+    p.nbl = p.nb5 && ctx->nbl_valid ? ctx->nbl : nullptr;
     p.nt = ctx->nb_valid && ctx->nt_cap ? ctx->nt : nullptr;
     p.nt_cap = ctx->nt_cap;
     return p;
@@ -208,6 +209,9 @@ int smi_ctx_lane_refresh(smi_ctx *lane) {
     lane->nb_valid = o->nb_valid;
     lane->nb5 = o->nb5;
     lane->nb5_valid = o->nb5_valid;
+    lane->nbl = o->nbl;
+    lane->nbl_wanted = o->nbl_wanted;
+    lane->nbl_valid = o->nbl_valid;
     lane->nt = o->nt;
     lane->nt_cap = o->nt_cap;
     lane->fine = o->fine;
@@ -235,6 +239,7 @@ int smi_ctx_destroy(smi_ctx *ctx) {
         (void)hipFree(ctx->n1);
         (void)hipFree(ctx->nb);
         (void)hipFree(ctx->nb5);
+        (void)hipFree(ctx->nbl);
         (void)hipFree(ctx->nt);
         (void)hipFree(ctx->n1_owner);
         (void)hipFree(ctx->fine);
@@ -342,7 +347,7 @@ int smi_set_barcode_set_device(smi_ctx *ctx, const uint32_t *d_keys, size_t n, i
     return SMI_OK;
 }
 
-int smi_set_stats(smi_ctx *ctx, uint64_t out[8], int digests) {
+int smi_set_stats(smi_ctx *ctx, uint64_t *out, int digests) {
     if (int rc = bind(ctx)) return rc;
     if (!out) {
         set_error("smi_set_stats: null argument");
@@ -359,15 +364,17 @@ int smi_set_stats(smi_ctx *ctx, uint64_t out[8], int digests) {
     uint64_t bytes = (2 * kL0Words + kL1Words + 4 * kL0Words + kFineWords) * 4ull + 2ull * kRankEntries * 4;
     if (o->nb_valid) bytes += kFineWords * 4ull;
     if (o->nb5_valid) bytes += ((uint64_t)1 << 24) * 40 * 4;
+    if (o->nbl_wanted) bytes += ((uint64_t)1 << 24) * 32 * 4;  // (allocated for this set, folded at its first ed <= 1 look-up)
     if (o->nt_cap) bytes += (uint64_t)o->nt_alloc * 8 + (o->nt_alloc >> 3) * 4;  // (the table as allocated, with the build's bucket counters behind it)
     if (o->n1_valid) bytes += 4ull * kL1Words * 4;
     if (o->nb2_valid) bytes += kFineWords * 4ull;
     out[1] = bytes;
     out[2] = o->set_build_us;
     if (digests) {
-        uint64_t d5[5];
-        if (int rc = launch_set_digests(const_cast<smi_ctx *>(o), d5, ctx->stream)) return rc;
-        for (int i = 0; i < 5; i++) out[3 + i] = d5[i];
+        uint64_t d7[7];
+        if (int rc = launch_set_digests(const_cast<smi_ctx *>(o), d7, ctx->stream)) return rc;
+        for (int i = 0; i < 5; i++) out[3 + i] = d7[i];
+        if (digests & 2) out[8] = d7[5], out[9] = d7[6];  // (the caller says that its array has ten entries)
     }
     return SMI_OK;
 }

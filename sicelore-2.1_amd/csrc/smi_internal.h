@@ -132,6 +132,7 @@ struct Pyramid {
     const uint32_t *nb2; // K-BC2's offset filter for short used lists (else null): 1 bit per key, set for every sequence TWO steps away from a barcode
     const uint32_t *nb;  // K-BC1's offset filter (else null): 1 bit per key, set for every sequence one mutation step away from a barcode (512 MiB)
     const uint32_t *nb5; // the same filter laid out by the 12 bases the five offsets' windows share (else null; smi_bc.hip "nb5"): the five bits of a read in 160 consecutive bytes
+    const uint32_t *nbl; // nb5 with the two outer offsets folded to half their words (else null; smi_bc.hip "nbl"): the five bits of a read in ONE aligned 128-byte line; a superset filter
     const uint64_t *nt;  // K-BC1's neighbourhood table (else null): open addressing, entry = 1 << 40 | sequence << 8 | the step that leads from it to a barcode
     uint32_t nt_cap;     // its slots
 };
@@ -156,6 +157,9 @@ struct smi_ctx {
     uint32_t *nb = nullptr;   // allocated with the first barcode set (512 MiB)
     uint32_t *nb5 = nullptr;  // allocated with the first neighbourhood table (2.5 GiB); nb5_valid: describes the set that is loaded now
     bool nb5_valid = false;
+    uint32_t *nbl = nullptr;  // allocated with the first nb5 (2 GiB), folded from it by the first ed <= 1 look-up of a set (ensure_nbl: K-BC2 and pass 1 never read it)
+    bool nbl_wanted = false;  // the set that is loaded now is to be probed through nbl
+    bool nbl_valid = false;   // ... and nbl is folded for it
     uint32_t *n1_owner = nullptr;  // scratch of the n2 build (one u32 per n1 cell, 512 MiB), kept: hipMalloc / hipFree of that size cost ~100 ms per set load
     bool nb_valid = false;
     uint64_t *nt = nullptr;   // grown on demand: 1.6 slots of 8 bytes per (barcode, step) pair, 7.8 GB for the 3.6 M list
@@ -246,7 +250,8 @@ int launch_extract_windows(smi_ctx *ctx, const uint8_t *d_reads, const uint64_t 
 int launch_build_pyramid(smi_ctx *ctx, const uint32_t *d_keys, size_t n, hipStream_t s, bool membership_only = false);
 int launch_hist(smi_ctx *ctx, const uint32_t *d_keys, const uint8_t *d_pass, size_t n, uint32_t *d_hist,
                 hipStream_t s);
-int launch_set_digests(smi_ctx *ctx, uint64_t *out5, hipStream_t s);  // bits of nb / nb5, digest of nb5, slots / entries of nt
+int ensure_nbl(smi_ctx *ctx, hipStream_t s);  // folds nbl for the loaded set where it is wanted and not folded yet (a lane: for its owner), and waits for it
+int launch_set_digests(smi_ctx *ctx, uint64_t *out7, hipStream_t s);  // bits of nb / nb5, digest of nb5, slots / entries of nt, bits / digest of nbl
 int launch_bc_counts(smi_ctx *ctx, const smi_bc_result *d_res, size_t n, uint32_t *d_counts, hipStream_t s);
 int launch_hist_windows(smi_ctx *ctx, const smi_bc_window *d_win, const smi_scan_result *d_scan, size_t n,
                         uint32_t *d_hist, hipStream_t s);

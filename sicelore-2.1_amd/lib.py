@@ -2124,12 +2124,14 @@ class Context:
         self.n_keys = int(np.unique(k).size)
 
     def set_stats(self, digests=False):
-        """smi_set_stats: what the last set_barcode_set built -> dict(keys, hbm_bytes, build_ms[, nb_bits, nb5_bits, nb5_digest, nt_slots, nt_entries])"""
-        out = np.zeros(8, dtype=np.uint64)
-        self._check(self._lib.smi_set_stats(self._h, out.ctypes.data, int(bool(digests))))
+        """smi_set_stats: what the last set_barcode_set built -> dict(keys, hbm_bytes, build_ms[, nb_bits, nb5_bits, nb5_digest, nt_slots, nt_entries,
+        nbl_bits, nbl_digest])"""
+        out = np.zeros(10, dtype=np.uint64)
+        self._check(self._lib.smi_set_stats(self._h, out.ctypes.data, 3 if digests else 0))  # (bit 1: ten entries, with the line filter's two)
         d = dict(keys=int(out[0]), hbm_bytes=int(out[1]), build_ms=float(out[2]) / 1e3)
         if digests:
-            d.update(nb_bits=int(out[3]), nb5_bits=int(out[4]), nb5_digest=int(out[5]), nt_slots=int(out[6]), nt_entries=int(out[7]))
+            d.update(nb_bits=int(out[3]), nb5_bits=int(out[4]), nb5_digest=int(out[5]), nt_slots=int(out[6]), nt_entries=int(out[7]),
+                     nbl_bits=int(out[8]), nbl_digest=int(out[9]))
         return d
 
     def set_barcode_set_device(self, d_keys_u32, mode=SET_USED_LIST, stream=None):

@@ -1689,6 +1689,47 @@ int smi_bamsort_error_read(const smi_bamsort *h, char *name, size_t cap, int64_t
 int smi_bamsort_free(smi_bamsort *h);
 int smi_bamsort_host_loop(smi_bamsort *h, double *seconds, int64_t *mismatches);
 
+/* ---- SamView (K-SAM-SIZE, K-SAM-WRITE, smi_samview.hip) ------------------------------------------------------------------------------------
+ * SAM text to BAM records, in the place of `samtools view -bS`: this build's own canonical conversion.
+ * smi_samview_create: header_text is the leading @ lines of the SAM text as they stand (n_text 0: no header, every RNAME must then be *).
+ *   Returns 2 at an @SQ line without SN or LN: *out is then a handle that only smi_samview_error_line and smi_samview_free take.
+ * smi_samview_header: the BAM header (magic, l_text, the text unchanged, n_ref, one reference per @SQ line in text order), with the size
+ *   protocol of the text getters (out == NULL: the size alone; 1 = cap is too small).
+ * smi_samview_add_segment: n_bytes of alignment lines that begin at a line's start; bytes behind the last LF are a line.  Builds the line
+ *   table, checks and sizes every line and sums the sizes: *n_records_bytes = the bytes of the segment's records, *n_bgzf = the room their
+ *   BGZF blocks need.  Returns 2 at a line that breaks a rule: smi_last_error and smi_samview_error_line name the first such line (1-based
+ *   in the file, the header's lines counted) and the rule, and the handle takes nothing further.
+ * smi_samview_convert: writes the records of the segment taken last and deflates them into BGZF blocks on the device
+ *   (smi_bgzf_deflate_device; no end-of-file block): *n_out bytes at out_bgzf.  1 = cap or cap_records is too small (*n_out = the room
+ *   needed).  out_records (may be NULL): the records as they stand in the blocks.
+ * smi_samview_counts: SMI_SAMVIEW_N_COUNT entries.  smi_samview_stage_ms: SMI_SAMVIEW_N_STAGE device times of the last add_segment (index,
+ *   size, scan) and convert (write, deflate: the latter with its copy to the host).
+ * smi_samview_host_loop (measurement and tests, after convert): the same conversion of the segment taken last on one host thread: its
+ *   seconds, the copies from the device not counted, and the number of records whose bytes differ from the device's (0). */
+#define SMI_SAMVIEW_RECORDS 0      /* records written */
+#define SMI_SAMVIEW_SEGMENTS 1     /* segments with at least one line */
+#define SMI_SAMVIEW_TEXT_BYTES 2   /* bytes of alignment lines taken */
+#define SMI_SAMVIEW_RECORD_BYTES 3 /* bytes of records written */
+#define SMI_SAMVIEW_REFERENCES 4   /* @SQ lines of the header */
+#define SMI_SAMVIEW_N_COUNT 5
+#define SMI_SAMVIEW_MS_INDEX 0
+#define SMI_SAMVIEW_MS_SIZE 1
+#define SMI_SAMVIEW_MS_SCAN 2
+#define SMI_SAMVIEW_MS_WRITE 3
+#define SMI_SAMVIEW_MS_DEFLATE 4
+#define SMI_SAMVIEW_N_STAGE 5
+typedef struct smi_samview smi_samview;
+int smi_samview_create(smi_ctx *ctx, const uint8_t *header_text, size_t n_text, smi_samview **out);
+int smi_samview_header(const smi_samview *h, uint8_t *out, size_t cap, size_t *n_out);
+int smi_samview_add_segment(smi_samview *h, const uint8_t *text, size_t n_bytes, size_t *n_bgzf, size_t *n_records_bytes);
+int smi_samview_convert(smi_samview *h, uint8_t *out_bgzf, size_t cap, size_t *n_out, uint8_t *out_records, size_t cap_records);
+int smi_samview_counts(const smi_samview *h, int64_t *counts);
+int smi_samview_stage_ms(const smi_samview *h, float *ms);
+/* the line that ended the run (a call returned 2): its 1-based number in the file and the rule it breaks (cut to cap - 1 bytes); 0 = none */
+int smi_samview_error_line(const smi_samview *h, int64_t *line, char *reason, size_t cap);
+int smi_samview_free(smi_samview *h);
+int smi_samview_host_loop(smi_samview *h, double *seconds, int64_t *mismatches);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

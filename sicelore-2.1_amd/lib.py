@@ -87,6 +87,8 @@ EXPORTS = [
     "smi_bamindex_counts", "smi_bamindex_error_read", "smi_bamindex_stage_ms", "smi_bamindex_free",
     "smi_bamsort_create", "smi_bamsort_add_segment", "smi_bamsort_finish", "smi_bamsort_window", "smi_bamsort_counts", "smi_bamsort_stage_ms",
     "smi_bamsort_error_read", "smi_bamsort_free", "smi_bamsort_host_loop",
+    "smi_samview_create", "smi_samview_header", "smi_samview_add_segment", "smi_samview_convert", "smi_samview_counts", "smi_samview_stage_ms",
+    "smi_samview_error_line", "smi_samview_free", "smi_samview_host_loop",
     "smi_select_valid_cells",
 ]
 
@@ -351,6 +353,15 @@ def load_library():
     lib.smi_bamsort_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
     lib.smi_bamsort_free.argtypes = [vp]
     lib.smi_bamsort_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_samview_create.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+    lib.smi_samview_header.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_samview_add_segment.argtypes = [vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    lib.smi_samview_convert.argtypes = [vp, vp, sz, ctypes.POINTER(sz), vp, sz]
+    lib.smi_samview_counts.argtypes = [vp, vp]
+    lib.smi_samview_stage_ms.argtypes = [vp, vp]
+    lib.smi_samview_error_line.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), vp, sz]
+    lib.smi_samview_free.argtypes = [vp]
+    lib.smi_samview_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     lib.smi_poa_batch_ex.argtypes = lib.smi_poa_batch.argtypes + [vp]
@@ -1344,6 +1355,79 @@ class BamSort(_Handle):
         """-> (seconds of the same sort on one host thread, records whose bytes differ from the device's windows)"""
         sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
         self._check(self._lib.smi_bamsort_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)))
+        return sec.value, bad.value
+
+
+# smi_samview_counts, in SMI_SAMVIEW_* order (SMI_SAMVIEW_N_COUNT entries); smi_samview_stage_ms (SMI_SAMVIEW_N_STAGE entries)
+SAMVIEW_COUNTS = ("records", "segments", "text_bytes", "record_bytes", "references")
+SAMVIEW_STAGES = ("index", "size", "scan", "write", "deflate")
+
+
+class SamViewError(SmiError):
+    """a line the conversion stops at (smi_samview_create or smi_samview_add_segment returned 2); .line: its 1-based number in the file,
+    .reason: the rule it breaks"""
+
+    def __init__(self, msg, line, reason):
+        super().__init__(msg)
+        self.line, self.reason = line, reason
+
+
+class SamView(_Handle):
+    """SAM text to BAM records on the device (smi_samview_*).  header_text: the leading @ lines of the text as they stand; header():
+    the BAM header they make; add_segment() / convert(): alignment lines in, their records out as BGZF blocks."""
+    _NAME, _COUNTS = "samview", SAMVIEW_COUNTS
+
+    def __init__(self, ctx, header_text=b""):
+        self._lib = load_library()
+        self._z = self._data = None
+        args, _keep = self._text(header_text)
+        h = ctypes.c_void_p()
+        rc = self._lib.smi_samview_create(ctx._h, *args, ctypes.byref(h))
+        self._h, self._ctx = h, ctx
+        self._stop_or_check(rc)
+
+    def _stop_or_check(self, rc):
+        if rc == 2:
+            msg = self._lib.smi_last_error().decode(errors="replace")
+            reason, line = ctypes.create_string_buffer(256), ctypes.c_int64(0)
+            self._lib.smi_samview_error_line(self._h, ctypes.byref(line), reason, 256)
+            self.close()
+            raise SamViewError(msg, line.value, reason.value.decode("latin-1"))
+        self._check(rc)
+
+    def header(self):
+        return self._fetch(self._lib.smi_samview_header, self._h).tobytes()
+
+    def add_segment(self, text):
+        """text: alignment lines from a line's start on (a contiguous uint8 array); bytes behind the last LF are a line
+        -> (room the BGZF blocks need, bytes of the records)"""
+        if not isinstance(text, np.ndarray) or text.dtype != np.uint8 or text.ndim != 1 or not text.flags.c_contiguous:
+            raise ValueError("text: a contiguous 1-D uint8 array")
+        nz, nd = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self._stop_or_check(self._lib.smi_samview_add_segment(self._h, _ptr(text) if text.size else None, text.size, ctypes.byref(nz), ctypes.byref(nd)))
+        self._sizes = nz.value, nd.value
+        return self._sizes
+
+    def convert(self, inflated=False):
+        """the segment taken last -> (its BGZF blocks without an end-of-file block, its records or None), uint8 views of buffers that
+        the next call writes again"""
+        nz, nd = self._sizes
+        if self._z is None or self._z.size < nz:
+            self._z = np.empty(nz, dtype=np.uint8)
+        if inflated and (self._data is None or self._data.size < nd):
+            self._data = np.empty(max(nd, 1), dtype=np.uint8)
+        n = ctypes.c_size_t(0)
+        self._check(self._lib.smi_samview_convert(self._h, _ptr(self._z), self._z.size, ctypes.byref(n), _ptr(self._data) if inflated else None,
+                                                  self._data.size if inflated else 0))
+        return self._z[:n.value], self._data[:nd] if inflated else None
+
+    def stage_ms(self):
+        return self._named("stage_ms", SAMVIEW_STAGES, np.float32)
+
+    def host_loop(self):
+        """-> (seconds of the same conversion of the last segment on one host thread, records whose bytes differ from the device's)"""
+        sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
+        self._check(self._lib.smi_samview_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)))
         return sec.value, bad.value
 
 

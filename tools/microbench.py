@@ -38,9 +38,9 @@ def main():
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
             "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse, "fusion": leg_fusion, "validator": leg_validator,
-            "fusionprep": leg_fusionprep, "bamindex": leg_bamindex, "bamsort": leg_bamsort}
+            "fusionprep": leg_fusionprep, "bamindex": leg_bamindex, "bamsort": leg_bamsort, "samview": leg_samview}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep", "bamindex", "bamsort")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep", "bamindex", "bamsort", "samview")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -1190,6 +1190,99 @@ def leg_bamsort(pkg, synth, ctx, dev, wl, used, res):
         finally:
             shutil.rmtree(d, ignore_errors=True)
         res["bamsort"][case] = out
+
+
+def _samview_fixture(path, n_recs, with_seq, seed=111, n_ref=25, n_ops=8, chunk=1000):
+    """the record mix of _bamsort_fixture as SAM text at `path`: names of the molecule form, a CIGAR of n_ops operations (M and N in turn),
+    random strand, one line in 500 unmapped (flag 4, placed on a reference as mappers place a mate); with_seq: SEQ and QUAL of L bases, L seeded in 400 .. 800 and one L per run of
+    `chunk` lines (the rows of a run are built as one array; numbers stand zero-padded in fixed columns), else * and * -> bytes written"""
+    rng = np.random.default_rng(seed)
+    tab = np.uint8(9)
+    written = 0
+
+    def digits(col, v, n):
+        for j in range(n):
+            col[:, n - 1 - j] = 48 + (v // 10 ** j) % 10
+
+    with open(path, "wb") as f:
+        written += f.write(b"@HD\tVN:1.6\tSO:unsorted\n" + b"".join(b"@SQ\tSN:chr%02d\tLN:%d\n" % (r + 1, 1 << 28) for r in range(n_ref)))
+        for at in range(0, n_recs, chunk):
+            m = min(chunk, n_recs - at)
+            L = int(rng.integers(400, 801)) if with_seq else 1
+            fields = [("name", "u1", (37,)), ("t0", "u1"), ("flag", "u1", (2,)), ("t1", "u1"), ("ref", "u1", (5,)), ("t2", "u1"), ("pos", "u1", (9,)), ("t3", "u1"),
+                      ("mapq", "u1", (2,)), ("t4", "u1"), ("cigar", "u1", (n_ops, 4)), ("t5", "u1"), ("mate", "u1", (6,)), ("seq", "u1", (L,)), ("t9", "u1"),
+                      ("qual", "u1", (L,)), ("lf", "u1")]
+            row = np.zeros(m, dtype=fields)
+            for t in ("t0", "t1", "t2", "t3", "t4", "t5", "t9"):
+                row[t] = tab
+            row["lf"] = 10
+            row["name"][:, :30] = np.frombuffer(b"ACGTACGTACGTACGT-TTTTGGGGCCCC-", dtype=np.uint8)
+            digits(row["name"][:, 30:], np.arange(at, at + m, dtype=np.int64), 7)
+            un = rng.integers(0, 500, m) == 0
+            digits(row["flag"], np.where(un, 4, 16 * rng.integers(0, 2, m)), 2)
+            row["ref"][:, :3] = np.frombuffer(b"chr", dtype=np.uint8)
+            digits(row["ref"][:, 3:], rng.integers(1, n_ref + 1, m), 2)
+            digits(row["pos"], rng.integers(1, 1 << 27, m), 9)
+            row["mapq"] = np.frombuffer(b"60", dtype=np.uint8)
+            for k in range(n_ops):
+                digits(row["cigar"][:, k, :3], rng.integers(20, 201, m), 3)
+                row["cigar"][:, k, 3] = ord("N") if k % 2 else ord("M")
+            row["mate"] = np.frombuffer(b"*\t0\t0\t", dtype=np.uint8)
+            if with_seq:
+                row["seq"] = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, (m, L))]
+                row["qual"] = rng.integers(35, 75, (m, L), dtype=np.uint8)
+            else:
+                row["seq"] = row["qual"] = ord("*")
+            written += f.write(row.view(np.uint8).tobytes())
+    return written
+
+
+def leg_samview(pkg, synth, ctx, dev, wl, used, res):
+    """K-SAM (`samview.py`, in the place of `samtools view -bS`), file to file: a seeded SAM text of SMI_MB_VIEW_LINES lines (2,000,000), once
+    without sequence and once with SEQ and QUAL of 400 .. 800 bases, in segments of SMI_MB_VIEW_SEGMENT bytes (256 MiB); sam_to_bam after a
+    run that loads the code objects: device ms per stage (HIP events), the seconds in the read, in the device calls and in the write, wall
+    seconds; the text bytes per second through the size and the write pass from their stage times; then smi_samview_host_loop per segment:
+    the seconds of the same conversion on one host thread and its mismatch count."""
+    import shutil
+    import tempfile
+
+    sv = importlib.import_module(graft.PKG_NAME + ".samview")
+    lib = importlib.import_module(graft.PKG_NAME + ".lib")
+    n_lines = int(os.environ.get("SMI_MB_VIEW_LINES", "2000000"))
+    seg = int(os.environ.get("SMI_MB_VIEW_SEGMENT", str(256 << 20)))
+    res["samview"] = {}
+    for case, with_seq in (("no_sequence", False), ("seq_qual_400_800", True)):
+        d = tempfile.mkdtemp(prefix="samview_")
+        try:
+            src, dst = os.path.join(d, "in.sam"), os.path.join(d, "out.bam")
+            t0 = time.perf_counter()
+            n_bytes = _samview_fixture(src, n_lines, with_seq)
+            out = {"lines": n_lines, "sam_bytes": n_bytes, "segment_bytes": seg, "fixture_s": time.perf_counter() - t0}
+            sv.sam_to_bam(ctx, src, dst, segment_bytes=seg)                                     # the first run loads the code objects
+            info = sv.sam_to_bam(ctx, src, dst, segment_bytes=seg)
+            ms = info["stage_ms"]
+            out["sam_to_bam"] = dict({k: info[k] for k in ("records", "segments", "text_bytes", "record_bytes")}, stage_ms=ms, seconds=info["seconds"],
+                                     wall_s=info["wall_s"], bytes_written=info["bytes_written"],
+                                     size_text_bytes_per_s=info["text_bytes"] / max(ms["size"], 1e-6) * 1e3,
+                                     write_text_bytes_per_s=info["text_bytes"] / max(ms["write"], 1e-6) * 1e3)
+            h = None
+            try:
+                sec = bad = 0
+                with open(src, "rb") as f:
+                    pieces = sv.text_segments(f, seg)
+                    h = lib.SamView(ctx, next(pieces))
+                    for piece in pieces:
+                        h.add_segment(piece)
+                        h.convert()
+                        s, b = h.host_loop()
+                        sec, bad = sec + s, bad + b
+                out["host_loop"] = dict(seconds=sec, mismatches=bad)
+            finally:
+                if h is not None:
+                    h.close()
+        finally:
+            shutil.rmtree(d, ignore_errors=True)
+        res["samview"][case] = out
 
 
 def _snp_fixture(n_recs, n_lines, n_cells, seed=51):

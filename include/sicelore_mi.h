@@ -1661,7 +1661,25 @@ int smi_bamindex_free(smi_bamindex *h);
  *   (key), finish (sort) or window (gather, deflate: the latter with its copy to the host).
  * smi_bamsort_host_loop (measurement and tests, after finish): the same sort on one host thread over the bytes the device holds (the
  *   keys rebuilt from the records, std::stable_sort, one memcpy per record): its seconds, the copies from the device not counted, and
- *   the number of records whose bytes in the device's windows differ from it (0). */
+ *   the number of records whose bytes in the device's windows differ from it (0).  It needs the arena: SMI_ERR_STATE in run mode.
+ *
+ * Run mode (K-MERGE-RANK, K-MERGE-SLICES, K-MERGE-GATHER): a file beyond resident_bytes goes through sorted runs that the caller keeps in
+ * files, one per arena-full, and a merge in which every output window draws one contiguous slice from each run.  The output is the same.
+ * smi_bamsort_run_mode: before the first segment.  smi_bamsort_add_segment then returns 3 for a segment that does not fit beside what the
+ *   arena holds (arena bytes + segment bytes + SMI_BAMSORT_PER_RECORD * all records taken so far, spilled ones included, > resident_bytes):
+ *   nothing was taken; the caller spills and hands the segment in again.  A segment that does not fit the empty arena is refused by name
+ *   (SMI_ERR_INVALID; the text names segment_bytes and resident_bytes).  The bound of 2^31 - 1 records holds over all runs.
+ * smi_bamsort_spill_begin: sorts what the arena holds: *n_windows windows of at most window_bytes, *n_records records, *n_bytes bytes.
+ * smi_bamsort_spill_window: window k of the run as raw record bytes (out == NULL: *n_out = its size; 1 = cap is too small).  The caller
+ *   appends the windows in order to the run's file, so a record's offset in the file is its offset in the run.
+ * smi_bamsort_spill_end: the arena is empty again.  Of every spilled record the device keeps key, length and run-file offset (20 bytes).
+ * smi_bamsort_finish: without a run as ever.  With runs, what the arena holds has to be spilled first (SMI_ERR_STATE otherwise); it
+ *   sorts the keys of all runs and finds the windows and their slices.
+ * smi_bamsort_window_slices: *n_runs, and for window k and every run j the slice [first_byte[j], first_byte[j] + n_bytes[j]) of run j's
+ *   file (n_bytes[j] may be 0) and, if first_ordinal is given, the ordinal of the slice's first record (records numbered run after run in
+ *   sorted order).  first_byte == NULL: *n_runs alone; 1 = cap (entries per array) is too small.
+ * smi_bamsort_merge_window: smi_bamsort_window for a sort with runs: slices / n_slices are the window's slices one behind the other in
+ *   run order (n_slices == the window's inflated bytes).  smi_bamsort_window answers SMI_ERR_STATE once a run was written. */
 #define SMI_BAMSORT_RECORDS 0        /* records taken */
 #define SMI_BAMSORT_SEGMENTS 1       /* segments taken */
 #define SMI_BAMSORT_WINDOWS 2        /* output windows (after finish) */
@@ -1669,12 +1687,19 @@ int smi_bamindex_free(smi_bamindex *h);
 #define SMI_BAMSORT_ARENA_HELD 4     /* bytes the arena holds room for */
 #define SMI_BAMSORT_LARGEST_WINDOW 5 /* bytes of the largest window (after finish) */
 #define SMI_BAMSORT_BYTES_OUT 6      /* inflated bytes that left through smi_bamsort_window */
-#define SMI_BAMSORT_N_COUNT 7
+#define SMI_BAMSORT_RUNS 7           /* runs spilled */
+#define SMI_BAMSORT_RUN_BYTES 8      /* record bytes that left through smi_bamsort_spill_window's runs */
+#define SMI_BAMSORT_LARGEST_RUN 9    /* bytes of the largest run */
+#define SMI_BAMSORT_N_COUNT 10
 #define SMI_BAMSORT_MS_KEY 0
 #define SMI_BAMSORT_MS_SORT 1
 #define SMI_BAMSORT_MS_GATHER 2
 #define SMI_BAMSORT_MS_DEFLATE 3
-#define SMI_BAMSORT_N_STAGE 4
+#define SMI_BAMSORT_MS_SPILL_GATHER 4 /* K-SORT-GATHER of a run's window (smi_bamsort_spill_window) */
+#define SMI_BAMSORT_MS_MERGE_SORT 5   /* the sort of all runs' keys, the offsets and the windows (finish with runs) */
+#define SMI_BAMSORT_MS_SLICES 6       /* K-MERGE-RANK and K-MERGE-SLICES */
+#define SMI_BAMSORT_MS_STAGE_UPLOAD 7 /* a window's slices to the staging buffer */
+#define SMI_BAMSORT_N_STAGE 8
 #define SMI_BAMSORT_PER_RECORD 48
 typedef struct smi_bamsort smi_bamsort;
 int smi_bamsort_create(smi_ctx *ctx, int32_t n_ref, uint64_t resident_bytes, uint64_t window_bytes, smi_bamsort **out);
@@ -1688,6 +1713,13 @@ int smi_bamsort_stage_ms(const smi_bamsort *h, float *ms);
 int smi_bamsort_error_read(const smi_bamsort *h, char *name, size_t cap, int64_t *record);
 int smi_bamsort_free(smi_bamsort *h);
 int smi_bamsort_host_loop(smi_bamsort *h, double *seconds, int64_t *mismatches);
+int smi_bamsort_run_mode(smi_bamsort *h);
+int smi_bamsort_spill_begin(smi_bamsort *h, int64_t *n_windows, int64_t *n_records, uint64_t *n_bytes);
+int smi_bamsort_spill_window(smi_bamsort *h, int64_t k, uint8_t *out, size_t cap, size_t *n_out);
+int smi_bamsort_spill_end(smi_bamsort *h);
+int smi_bamsort_window_slices(const smi_bamsort *h, int64_t k, int64_t *n_runs, uint64_t *first_byte, uint64_t *n_bytes, uint32_t *first_ordinal, size_t cap);
+int smi_bamsort_merge_window(smi_bamsort *h, int64_t k, const uint8_t *slices, size_t n_slices, uint8_t *out_bgzf, size_t cap, size_t *n_out,
+                             uint8_t *out_inflated, size_t cap_inflated, size_t *n_inflated);
 
 /* ---- SamView (K-SAM-SIZE, K-SAM-WRITE, smi_samview.hip) ------------------------------------------------------------------------------------
  * SAM text to BAM records, in the place of `samtools view -bS`: this build's own canonical conversion.

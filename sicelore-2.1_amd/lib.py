@@ -87,6 +87,8 @@ EXPORTS = [
     "smi_bamindex_counts", "smi_bamindex_error_read", "smi_bamindex_stage_ms", "smi_bamindex_free",
     "smi_bamsort_create", "smi_bamsort_add_segment", "smi_bamsort_finish", "smi_bamsort_window", "smi_bamsort_counts", "smi_bamsort_stage_ms",
     "smi_bamsort_error_read", "smi_bamsort_free", "smi_bamsort_host_loop",
+    "smi_bamsort_run_mode", "smi_bamsort_spill_begin", "smi_bamsort_spill_window", "smi_bamsort_spill_end", "smi_bamsort_window_slices",
+    "smi_bamsort_merge_window",
     "smi_samview_create", "smi_samview_header", "smi_samview_add_segment", "smi_samview_convert", "smi_samview_counts", "smi_samview_stage_ms",
     "smi_samview_error_line", "smi_samview_free", "smi_samview_host_loop",
     "smi_select_valid_cells",
@@ -353,6 +355,12 @@ def load_library():
     lib.smi_bamsort_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
     lib.smi_bamsort_free.argtypes = [vp]
     lib.smi_bamsort_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_bamsort_run_mode.argtypes = [vp]
+    lib.smi_bamsort_spill_begin.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64)]
+    lib.smi_bamsort_spill_window.argtypes = [vp, ctypes.c_int64, vp, sz, ctypes.POINTER(sz)]
+    lib.smi_bamsort_spill_end.argtypes = [vp]
+    lib.smi_bamsort_window_slices.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), vp, vp, vp, sz]
+    lib.smi_bamsort_merge_window.argtypes = [vp, ctypes.c_int64, vp, sz, vp, sz, ctypes.POINTER(sz), vp, sz, ctypes.POINTER(sz)]
     lib.smi_samview_create.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
     lib.smi_samview_header.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
     lib.smi_samview_add_segment.argtypes = [vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
@@ -1295,8 +1303,9 @@ class BamIndex(_Handle):
 
 
 # smi_bamsort_counts, in SMI_BAMSORT_* order (SMI_BAMSORT_N_COUNT entries); smi_bamsort_stage_ms (SMI_BAMSORT_N_STAGE entries)
-BAMSORT_COUNTS = ("records", "segments", "windows", "arena_bytes", "arena_held", "largest_window", "bytes_out")
-BAMSORT_STAGES = ("key", "sort", "gather", "deflate")
+BAMSORT_COUNTS = ("records", "segments", "windows", "arena_bytes", "arena_held", "largest_window", "bytes_out", "runs", "run_bytes", "largest_run")
+BAMSORT_STAGES = ("key", "sort", "gather", "deflate", "spill_gather", "merge_sort", "slices", "stage_upload")
+BAMSORT_RUN_STAGES = BAMSORT_STAGES[4:]               # what only a sort through runs spends time in
 
 
 class BamSortError(SmiError):
@@ -1310,7 +1319,9 @@ class BamSortError(SmiError):
 
 class BamSort(_Handle):
     """The coordinate sort of a BAM that is resident in device memory (smi_bamsort_*): the inflated stream in segments in, after finish()
-    the sorted records out in windows of BGZF blocks.  n_ref: the number of the header's references; resident_bytes: the bound on the
+    the sorted records out in windows of BGZF blocks.  After run_mode() a file beyond resident_bytes goes through sorted runs: the caller
+    keeps each run's windows (spill_begin, spill_window, spill_end) in a file and hands every output window its slices (window_slices,
+    merge_window).  n_ref: the number of the header's references; resident_bytes: the bound on the
     record bytes and the per-record arrays on the device (None: two fifths of the free device memory)."""
     _NAME, _COUNTS = "bamsort", BAMSORT_COUNTS
 
@@ -1319,15 +1330,41 @@ class BamSort(_Handle):
         self._z = self._data = None
         self._create(ctx, int(n_ref), int(resident_bytes or 0), int(window_bytes))
 
+    def run_mode(self):
+        """before the first segment: a segment that does not fit makes add_segment return False instead of refusing the file"""
+        self._check(self._lib.smi_bamsort_run_mode(self._h))
+
     def add_segment(self, bam, recs):
-        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it"""
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it -> True; in run mode False where the
+        segment does not fit beside what the arena holds: nothing was taken, spill() and hand it in again"""
         args, recs = self._segment_args(bam, recs)
         rc = self._lib.smi_bamsort_add_segment(self._h, *args)
         if rc == 2:
             msg = self._lib.smi_last_error().decode(errors="replace")
             name, rec = self._error_read()
             raise BamSortError(msg, name.decode("latin-1"), rec)
+        if rc == 3:
+            return False
         self._check(rc)
+        return True
+
+    def spill_begin(self):
+        """sorts what the arena holds -> (windows of the run, its records, its bytes)"""
+        nw, nr, nb = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_uint64(0)
+        self._check(self._lib.smi_bamsort_spill_begin(self._h, ctypes.byref(nw), ctypes.byref(nr), ctypes.byref(nb)))
+        return nw.value, nr.value, nb.value
+
+    def spill_window(self, k):
+        """window k of the open run: its record bytes in sorted order, a uint8 view of a buffer that the next call writes again"""
+        n = ctypes.c_size_t(0)
+        self._check(self._lib.smi_bamsort_spill_window(self._h, int(k), None, 0, ctypes.byref(n)))
+        if self._data is None or self._data.size < n.value:
+            self._data = np.empty(max(n.value, 1), dtype=np.uint8)
+        self._check(self._lib.smi_bamsort_spill_window(self._h, int(k), _ptr(self._data), self._data.size, ctypes.byref(n)))
+        return self._data[:n.value]
+
+    def spill_end(self):
+        self._check(self._lib.smi_bamsort_spill_end(self._h))
 
     def finish(self):
         """sorts -> (number of output windows, number of records)"""
@@ -1335,18 +1372,36 @@ class BamSort(_Handle):
         self._check(self._lib.smi_bamsort_finish(self._h, ctypes.byref(nw), ctypes.byref(nr)))
         return nw.value, nr.value
 
-    def window(self, k, inflated=False):
-        """window k -> (its BGZF blocks without an end-of-file block, its inflated records or None), uint8 views of buffers that the next
-        call writes again"""
+    def _window(self, fn, args, inflated):
+        """smi_bamsort_window and smi_bamsort_merge_window: called for the sizes, then for the bytes"""
         nz, nd = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        self._check(self._lib.smi_bamsort_window(self._h, int(k), None, 0, ctypes.byref(nz), None, 0, ctypes.byref(nd)))
+        self._check(fn(self._h, *args, None, 0, ctypes.byref(nz), None, 0, ctypes.byref(nd)))
         if self._z is None or self._z.size < nz.value:
             self._z = np.empty(nz.value, dtype=np.uint8)
         if inflated and (self._data is None or self._data.size < nd.value):
             self._data = np.empty(max(nd.value, 1), dtype=np.uint8)
-        self._check(self._lib.smi_bamsort_window(self._h, int(k), _ptr(self._z), self._z.size, ctypes.byref(nz), _ptr(self._data) if inflated else None,
-                                                 self._data.size if inflated else 0, ctypes.byref(nd)))
+        self._check(fn(self._h, *args, _ptr(self._z), self._z.size, ctypes.byref(nz), _ptr(self._data) if inflated else None,
+                       self._data.size if inflated else 0, ctypes.byref(nd)))
         return self._z[:nz.value], self._data[:nd.value] if inflated else None
+
+    def window(self, k, inflated=False):
+        """window k -> (its BGZF blocks without an end-of-file block, its inflated records or None), uint8 views of buffers that the next
+        call writes again"""
+        return self._window(self._lib.smi_bamsort_window, (int(k),), inflated)
+
+    def window_slices(self, k):
+        """after finish over runs -> (first_byte, n_bytes, first_ordinal), one entry per run: the slice of every run file window k draws"""
+        n = ctypes.c_int64(0)
+        self._check(self._lib.smi_bamsort_window_slices(self._h, int(k), ctypes.byref(n), None, None, None, 0))
+        first, size, ordinal = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
+        self._check(self._lib.smi_bamsort_window_slices(self._h, int(k), ctypes.byref(n), _ptr(first), _ptr(size), _ptr(ordinal), n.value))
+        return first, size, ordinal
+
+    def merge_window(self, k, slices, inflated=False):
+        """window k of a sort with runs, from its slices one behind the other in run order (uint8) -> as window()"""
+        if not isinstance(slices, np.ndarray) or slices.dtype != np.uint8 or slices.ndim != 1 or not slices.flags.c_contiguous:
+            raise ValueError("slices: a contiguous 1-D uint8 array")
+        return self._window(self._lib.smi_bamsort_merge_window, (int(k), _ptr(slices) if slices.size else None, slices.size), inflated)
 
     def stage_ms(self):
         return self._named("stage_ms", BAMSORT_STAGES, np.float32)

@@ -38,9 +38,9 @@ def main():
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
             "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse, "fusion": leg_fusion, "validator": leg_validator,
-            "fusionprep": leg_fusionprep, "bamindex": leg_bamindex, "bamsort": leg_bamsort, "samview": leg_samview}
+            "fusionprep": leg_fusionprep, "bamindex": leg_bamindex, "bamsort": leg_bamsort, "bamsort_runs": leg_bamsort_runs, "samview": leg_samview}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep", "bamindex", "bamsort", "samview")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep", "bamindex", "bamsort", "bamsort_runs", "samview")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -1138,7 +1138,8 @@ def leg_bamsort(pkg, synth, ctx, dev, wl, used, res):
     compressed bytes (64 MiB) and windows of 64 MiB; sort_bam after a run that loads the code objects, without and with index=True: device
     ms per stage (HIP events), the seconds in read and inflate, in the device calls and in the write, wall seconds; the gather's bytes per
     second from its stage time, and the same run with the gather's 4-byte stores (SMI_BAMSORT_STORE_BYTES=4); then
-    smi_bamsort_host_loop: the seconds of the same sort on one host thread and its mismatch count."""
+    smi_bamsort_host_loop: the seconds of the same sort on one host thread and its mismatch count.  The file with US / QS is sorted once
+    more through runs (_bamsort_runs; `microbench.py bamsort_runs` does that part alone)."""
     import shutil
     import tempfile
 
@@ -1174,6 +1175,8 @@ def leg_bamsort(pkg, synth, ctx, dev, wl, used, res):
                 del os.environ["SMI_BAMSORT_STORE_BYTES"]
             out["gather_4_byte_stores"] = dict(gather_ms=info["stage_ms"]["gather"],
                                                gather_bytes_per_s=info["arena_bytes"] / max(info["stage_ms"]["gather"], 1e-6) * 1e3)
+            if with_seq:
+                out["sort_bam_runs"] = _bamsort_runs(bs, ctx, d, src, seg, n_rec, inflated, out["sort_bam"]["wall_s"])
             h = None
             try:
                 for bam, recs, hdr in segs.segments(src, seg, 16):
@@ -1190,6 +1193,47 @@ def leg_bamsort(pkg, synth, ctx, dev, wl, used, res):
         finally:
             shutil.rmtree(d, ignore_errors=True)
         res["bamsort"][case] = out
+
+
+def _bamsort_runs(bs, ctx, d, src, seg, n_rec, inflated, resident_wall_s):
+    """the file at `src` sorted through runs (runs_prefix) with resident_bytes a quarter of what the resident sort needs (the record bytes
+    and SMI_BAMSORT_PER_RECORD per record), so four runs or more: device ms per stage, the seconds of the run files' writes and reads among
+    the others, wall seconds, their ratio to the resident sort's of the same file in the same process, and whether the two files are equal"""
+    need = inflated + 48 * n_rec
+    dst, ref = os.path.join(d, "runs.bam"), os.path.join(d, "out.bam")
+    info = bs.sort_bam(ctx, src, dst, segment_bytes=seg, n_threads=16, resident_bytes=need // 4, runs_prefix=os.path.join(d, "spill"))
+    with open(dst, "rb") as a, open(ref, "rb") as b:
+        same = all(x == y for x, y in iter(lambda: (a.read(1 << 24), b.read(1 << 24)), (b"", b"")))
+    return dict({k: info[k] for k in ("records", "segments", "windows", "runs", "run_bytes", "largest_run", "largest_window")}, resident_bytes=need // 4,
+                stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"], bytes_written=info["bytes_written"],
+                wall_over_resident=info["wall_s"] / resident_wall_s, equal_to_resident=same, left_behind=sorted(f for f in os.listdir(d) if ".run" in f))
+
+
+def leg_bamsort_runs(pkg, synth, ctx, dev, wl, used, res):
+    """the runs part of leg_bamsort alone: the seeded BAM with US / QS, the resident sort_bam (after a run that loads the code objects) and
+    the sort through runs beside it"""
+    import shutil
+    import tempfile
+
+    bs = importlib.import_module(graft.PKG_NAME + ".bamsort")
+    n_recs = int(os.environ.get("SMI_MB_SORT_RECS", "2000000"))
+    seg = int(os.environ.get("SMI_MB_SORT_SEGMENT", str(64 << 20)))
+    t0 = time.perf_counter()
+    z, n_rec, inflated = _bamsort_fixture(n_recs, True)
+    out = {"records": n_rec, "bam_bytes": int(z.size), "inflated_bytes": inflated, "segment_bytes": seg, "fixture_s": time.perf_counter() - t0}
+    d = tempfile.mkdtemp(prefix="bamsort_runs_")
+    try:
+        src, dst = os.path.join(d, "in.bam"), os.path.join(d, "out.bam")
+        z.tofile(src)
+        del z
+        bs.sort_bam(ctx, src, dst, segment_bytes=seg, n_threads=16)                             # the first run loads the code objects
+        info = bs.sort_bam(ctx, src, dst, segment_bytes=seg, n_threads=16)
+        out["sort_bam"] = dict({k: info[k] for k in ("records", "segments", "windows", "arena_bytes", "largest_window")}, stage_ms=info["stage_ms"],
+                               seconds=info["seconds"], wall_s=info["wall_s"], bytes_written=info["bytes_written"])
+        out["sort_bam_runs"] = _bamsort_runs(bs, ctx, d, src, seg, n_rec, inflated, info["wall_s"])
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    res["bamsort_runs"] = out
 
 
 def _samview_fixture(path, n_recs, with_seq, seed=111, n_ref=25, n_ops=8, chunk=1000):

@@ -491,6 +491,74 @@ __device__ __forceinline__ float nw_errors(const uint32_t (&col)[N]) {
     return __fsub_rn((float)nx, __fmul_rn(0.9f, (float)lead));
 }
 
+#if !SMI_NW_CELL7
+// The four counts every statistic of the TSO fold is made of, no moves kept and no walk: nw_errors' cell with two further fields.
+//   cell = (4*score + 36*r + 20*c) << 17 | q << 11 | up << 6 | trail << 3 | lead          (from the top: tagged score, q, up, trail, lead)
+//   q      as in nw_errors: 2N - #mismatch - 2 * #match on the best path, #x at (N, N)
+//   up     up moves on the best path, the `lead` ones of column 0 included: the up predecessor's constant adds 1 to it, column 0 starts at r
+//   trail  left moves that end the path in row N (read gaps at the end of the read, which countNeedlemanErrorsInRead L68-86 does not take for
+//          deletions): written in row N only, where the left predecessor enters as U[c-1] + (1 << 3) -- one more add for the cells of the last
+//          row that have a left neighbour in the band.  The diagonal and up predecessors come from row N - 1, whose field is zero: the field
+//          resets itself.
+//   lead   as in nw_errors: column 0 starts at r
+// On an N x N alignment #up = #left, so what the walk counts is (nw_walk_bits: I = up steps, D = left steps, S = mismatches)
+//   ins = up      del = (int8_t)(up - trail)      nmis = ins + del + S = #x - trail      ne = (float)#x - 0.9f * (float)lead
+// No field borrows from or carries into its neighbour: q >= 2N - 2 * min(r, c) >= 0 in every cell (a path to (r, c) has at most min(r, c)
+// diagonal steps), up <= r <= N < 32 (an up move takes a row), trail <= the W left neighbours row N has in the band < 8, and lead is never
+// added to (<= W < 8: column 0 lies in the band for the rows up to W only).  The three candidates of a cell differ in (score, tag), so no
+// field decides a maximum.  4*score + 36*r + 20*c stays within 0 .. 56 N + 78 (1,294 for N = 16); with the bias (as in nw_full: the
+// compiler must not prove the cells non-negative, or the maximum splits in two) it fits the 13 signed bits above the tag.
+struct NwCounts {
+    int nx, lead, up, trail;
+};
+template <int N, int W>
+__device__ __forceinline__ NwCounts nw_counts(const uint32_t (&col)[N]) {
+    constexpr int kLeadBits = 3, kTrailBits = 3, kUpBits = 5, kQBits = 6;
+    constexpr int kTrailPos = kLeadBits, kUpPos = kTrailPos + kTrailBits, kQPos = kUpPos + kUpBits, SH = kQPos + kQBits;
+    static_assert(W >= 1 && W < N, "a band: column 0 and row N are reached through W cells only");
+    static_assert(W < (1 << kLeadBits), "lead: column 0 lies in the band for the rows up to W");
+    static_assert(W < (1 << kTrailBits), "trail: row N has W left neighbours in the band");
+    static_assert(N < (1 << kUpBits), "up: at most N up moves");
+    static_assert(2 * N < (1 << kQBits), "q starts at 2N");
+    static_assert(SH + 2 + 13 == 32 && 56 * N + 78 < (1 << 12), "4*score + 36*r + 20*c + bias in the 13 signed bits above the tag");
+    const uint32_t kmatch = (39u << SH) - (1u << kQPos);  // diag: +39 and q - 1 on a mismatch, twice that on a match
+    constexpr int kBias = -(1 << (12 + SH)), kUp = (17 << SH) + (1 << kUpPos), kTrail = 1 << kTrailPos;
+    int U[N + 1];
+#pragma unroll
+    for (int c = 0; c <= N; c++) U[c] = kBias + ((2 * N) << kQPos);
+#pragma unroll
+    for (int r = 1; r <= N; r++) {
+        const int clo = r - W > 1 ? r - W : 1, chi = r + W < N ? r + W : N;  // the band of nw_full
+        int diag = U[clo - 1];
+        if (r <= W) U[0] = kBias + ((20 * r) << SH) + ((2 * N) << kQPos) + (r << kUpPos) + r;
+#pragma unroll
+        for (int c = clo; c <= chi; c++) {
+            int m, d;
+            asm("v_bfe_u32 %0, %1, %2, 1" : "=v"(m) : "v"(col[c - 1]), "n"(r - 1));
+            asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(d) : "s"(kmatch), "v"(m), "v"(diag));
+            const int left = r == N ? U[c - 1] + kTrail : U[c - 1];
+            int v;
+            if (c - r == W) {
+                v = max(d, left);
+            } else if (r - c == W) {
+                v = max(d, U[c] + kUp);
+            } else {
+                v = max(max(d, U[c] + kUp), left);
+            }
+            diag = U[c];
+            U[c] = v & ~(3 << SH);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    NwCounts out;
+    out.lead = U[N] & ((1 << kLeadBits) - 1);
+    out.trail = (U[N] >> kTrailPos) & ((1 << kTrailBits) - 1);
+    out.up = (U[N] >> kUpPos) & ((1 << kUpBits) - 1);
+    out.nx = (U[N] >> kQPos) & ((1 << kQBits) - 1);
+    return out;
+}
+#endif
+
 // ---- Myers / Hyyro bit-vector step shared by the exact pre-filters of K-CHIM-A and K-SCAN (derivation: smi_chimera.hip "Exact
 // pre-filter of the Needleman-Wunsch acceptance tests").  Sixteen two-cycle VALU operations per pattern base in one asm block.
 #define SMI_MYERS_STEP(EQ)                                                                                          \

@@ -511,7 +511,8 @@ __device__ __forceinline__ int kth_bit(uint64_t m, int k) {
 
 // result of one aligned candidate, as the owner lane needs it (5 words per entry in LDS, odd stride)
 // Words 1, 2 and the low half of word 4 depend on the path (see SMI_SCAN_EAGER_* below).  Lazy: word 1 = Mt of a TSO candidate, words 1 and 2 = X
-// and ND of an adapter candidate (smi_nw.h kLazy), and the low half of b is unused.
+// and ND of an adapter candidate (smi_nw.h kLazy), and the low half of b is unused.  A TSO candidate of the shipped 3' kernels (kTsoCounts) writes ne, a
+// and b only: nothing of its path is kept.
 struct Entry {
     float ne, end5, endn;
     uint32_t a;  // nmis | ins << 8 | del(+128) << 16 | term6 << 24
@@ -520,7 +521,8 @@ struct Entry {
 
 // The statistics few rules read are computed where a rule reads them, from the step masks the alignment leaves in the entry (smi_nw.h kLazy):
 //   TSO      consec and best_two are read by the rescue rules of scanReadForTSOs only, for the winner of an end that is present and did not pass
-//            by nmis: phase C computes them there, behind one ballot
+//            by nmis: phase C computes them there, behind one ballot (the generic kernels, the 5' kernels and -DSMI_SCAN_TSO_WALK=1; the shipped 3'
+//            kernels keep no Mt either, see SMI_SCAN_TSO_WALK below)
 //   adapter  end5 orders two acceptable candidates of one end that tie on the best ne, endn is tested against zero by the pass-1 filter on the
 //            chosen lane: the fold keeps the incumbent's masks and computes keys on a tie.  Where both masks fit one word each (2 * AD <= 32: the
 //            10-mer); the 22-mer keeps the eager path.
@@ -535,6 +537,20 @@ struct Entry {
 #endif
 #ifndef SMI_SCAN_EAGER_ENDS
 #define SMI_SCAN_EAGER_ENDS 0
+#endif
+// The TSO round of the shipped 3' kernels keeps no path at all.  Its fold reads ne, nmis, ins, del and the position of every candidate and nothing else,
+// and those four are sums of counts a cell can carry (smi_nw.h nw_counts: five operations per cell, no tags, no walk).  The match steps Mt were kept for
+// the rescue rules alone; the few ends a rescue rule really reads the runs of (present, not passed by nmis, the partner end not found: 0.05 % of the ends
+// of the bench generator's reads, one wave in thirty) align their winner again in phase C, with the walk.  The generic kernels keep nw_full and the walk
+// for every candidate: the parity suite compares the two.
+// -DSMI_SCAN_TSO_WALK=1 (make VARIANT=tsowalk EXTRA=-DSMI_SCAN_TSO_WALK=1) compiles the walk for every TSO candidate of the shipped kernels again, Mt in
+// the entry and nw_runs behind the ballot "present and not passed", for counter runs -- same results; there is no run-time switch.
+#if SMI_NW_CELL7  // (nw_counts is written for the cell of six operations)
+#undef SMI_SCAN_TSO_WALK
+#define SMI_SCAN_TSO_WALK 1
+#endif
+#ifndef SMI_SCAN_TSO_WALK
+#define SMI_SCAN_TSO_WALK 0
 #endif
 
 // Two variant switches for counter runs and cross-checks (make VARIANT=... EXTRA=-D...=1), never set in the shipped library:
@@ -700,10 +716,12 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
         // ---- phases B + C(fold): adapter candidates, then TSO candidates -----------------------------------------
         // adapter fold state (AdapterScanRslt best key + getMatchList L275-319)
         // The fold state rides through the alignment loops in few registers: a_pack / t_pack = pos | nmis << 8 | ins << 16 | (del + 128) << 24
-        // (positions are <= 192), t_aux = consec | best_two << 8 | skip << 16 (lazy: the skip position alone; the winner's Mt rides in t_mt)
+        // (positions are <= 192), t_aux = consec | best_two << 8 | skip << 16 (lazy: the skip position alone; the winner's Mt rides in t_mt, and nowhere under kTsoCounts)
         // a_w1, a_w2: the incumbent's words 1 and 2 of its entry -- end5 (not kept: a_key has it) and endn, or X and ND on the lazy path, where a_key
         // caches the incumbent's end5 once a tie has asked for it (< 0: not computed; the keys are >= 0)
         constexpr bool kLazyAd = 2 * AD <= 32 && !SMI_SCAN_EAGER_ENDS, kLazyTso = !SMI_SCAN_EAGER_RUNS;
+        // kTsoCounts: the TSO round counts and keeps no path (see SMI_SCAN_TSO_WALK above); t_mt is dead then, and phase C aligns again where a rule reads the runs
+        constexpr bool kTsoCounts = SHIP && !FP && kLazyTso && !SMI_SCAN_TSO_WALK;
         float a_best = 3.4028234663852886e+38f, a_key = kLazyAd ? -1.0f : 0.0f;
         bool a_have = false;
         uint32_t a_pack = 0;
@@ -908,14 +926,28 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                         uint32_t col[16];
 #pragma unroll
                         for (int c = 0; c < 16; c++) col[c] = col_of(SHIP ? tso4(c) : P.t4(c)) & 0xFFFFu;
-                        // the TSO rules read ne, nmis, ins, del of every candidate; consec and best_two in the rescue rules (lazy: off Mt)
-                        nw_full<16, false, true, kBandTso, kLazyTso>(col, 0, st);
+#if !SMI_SCAN_TSO_WALK
+                        if constexpr (kTsoCounts) {
+                            // the TSO fold reads ne, nmis, ins, del of every candidate and nothing else: the counts, as the walk forms them of its masks
+                            const NwCounts k = nw_counts<16, kBandTso>(col);
+                            st.ne = __fsub_rn((float)k.nx, __fmul_rn(0.9f, (float)k.lead));  // Match.countErrorsInNeedleman: two roundings
+                            st.ins = k.up;
+                            st.del = (int)(int8_t)(k.up - k.trail);  // (byte arithmetic, L84)
+                            st.nmis = k.nx - k.trail;                // ins + del + mismatches, with #x = mismatches + 2 * up
+                        } else
+#endif
+                        {
+                            // the TSO rules read ne, nmis, ins, del of every candidate; consec and best_two in the rescue rules (lazy: off Mt)
+                            nw_full<16, false, true, kBandTso, kLazyTso>(col, 0, st);
+                        }
                     }
                     uint32_t *o = ent + tid * 5;
                     o[0] = __float_as_uint(st.ne);
-                    const bool lazy = kind == 0 ? kLazyAd : kLazyTso;
-                    o[1] = lazy ? (uint32_t)st.mask_a : __float_as_uint(st.end5);
-                    o[2] = lazy ? (uint32_t)st.mask_b : __float_as_uint(st.endn);
+                    if (!(kTsoCounts && kind == 1)) {  // (the counts leave nothing for words 1 and 2, and the TSO fold reads neither)
+                        const bool lazy = kind == 0 ? kLazyAd : kLazyTso;
+                        o[1] = lazy ? (uint32_t)st.mask_a : __float_as_uint(st.end5);
+                        o[2] = lazy ? (uint32_t)st.mask_b : __float_as_uint(st.endn);
+                    }
                     o[3] = (uint32_t)(st.nmis & 0xFF) | ((uint32_t)(st.ins & 0xFF) << 8) | ((uint32_t)((st.del + 128) & 0xFF) << 16) |
                            ((uint32_t)st.term6 << 24);
                     o[4] = (uint32_t)(st.consec & 0xFF) | ((uint32_t)(st.best_two & 0xFF) << 8) | ((uint32_t)pos << 16);
@@ -960,9 +992,9 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                         if (!((float)(int)floorf(__fadd_rn(ne, 0.5f)) > t_max) && ne < t_best) {  // Math.round(ne) <= maxErrors
                             t_best = ne;
                             t_pack = packed;
-                            if (kLazyTso)
-                                t_mt = o[1];
-                            else
+                            if (kLazyTso) {
+                                if (!kTsoCounts) t_mt = o[1];
+                            } else
                                 t_aux = (t_aux & 0xFFFF0000u) | (o[4] & 0xFFFFu);
                         }
                         if (t_max < ne) {
@@ -974,6 +1006,98 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                 wave_sync();
             }
         }
+
+        // ---- TSO rules on both ends (PolyATadapterAnalyzer_3pBCUMI.scanReadForTSOs L122-190) ----------------------
+        // -> the end of the forward end's match | the end of the reverse end's << 16, in scan coordinates; 0 where the end has no TSO
+        // kTsoCounts: evaluated here, before the strand decision and the record are built, where little is live -- the few waves that align a winner
+        // again need the registers of an alignment with its walk, and one word leaves this block.  Otherwise: behind the record, as before.
+        auto tso_rules = [&]() -> uint32_t {
+            const int t_pos = (int)(t_pack & 0xFF), t_nmis = (int)((t_pack >> 8) & 0xFF), t_ins = (int)((t_pack >> 16) & 0xFF),
+                      t_del = (int)(t_pack >> 24) - 128;
+            struct Tm {
+                int present, passed, nmis, end_scan, consec, two;
+            };
+            Tm mine;
+            mine.present = t_pos != 0;
+            mine.nmis = t_nmis;
+            mine.passed = mine.present && t_nmis <= (SHIP ? 5 : P.tso_max_mm);  // scanForTSO L350
+            mine.end_scan = t_pos + 15 + t_ins - t_del;
+            mine.consec = mine.two = 0;
+            Tm o;
+            if (kLazyTso) {
+                // present, passed, nmis (8 bits) and end_scan (16 bits) in one word: one exchange
+                const uint32_t w = (uint32_t)mine.present | ((uint32_t)mine.passed << 1) | ((uint32_t)mine.nmis << 2) | ((uint32_t)(mine.end_scan & 0xFFFF) << 16);
+                const uint32_t ow = (uint32_t)__shfl_xor((int)w, 1);
+                o.present = (int)(ow & 1u);
+                o.passed = (int)((ow >> 1) & 1u);
+                o.nmis = (int)((ow >> 2) & 0xFFu);
+                o.end_scan = (int)(int16_t)(ow >> 16);
+                o.consec = o.two = 0;
+            } else {
+                mine.consec = (int)(t_aux & 0xFF);
+                mine.two = (int)((t_aux >> 8) & 0xFF);
+                o.present = __shfl_xor(mine.present, 1);
+                o.passed = __shfl_xor(mine.passed, 1);
+                o.nmis = __shfl_xor(mine.nmis, 1);
+                o.end_scan = __shfl_xor(mine.end_scan, 1);
+                o.consec = __shfl_xor(mine.consec, 1);
+                o.two = __shfl_xor(mine.two, 1);
+            }
+            // The rescue rules below apply when NEITHER end of the read is found (found = present && passed), and read consec / two of an end that is
+            // present.  So a lane's runs are read only when its end is present and did not pass by nmis and its partner end is not found -- by its own
+            // lane and by the partner lane, which receives them through the exchange below; an end that is absent, passed, or beside a found partner
+            // contributes runs to no rule, and no rule reads the runs of any third lane.
+            //   kTsoCounts  nothing of the winner's path was kept: those lanes align their own winner again, with the walk (one wave in thirty on the
+            //               bench generator's reads: NOTES R6.34)
+            //   lazy        the runs of the winner's match mask are counted for every end that is present and did not pass, when the wave has one (one
+            //               wave in four: NOTES R6.26)
+            const bool need = mine.present && !mine.passed && !(kTsoCounts && o.present && o.passed);
+            const bool rescue = !kLazyTso || __ballot(need) != 0;  // wave-uniform
+            if (kLazyTso && rescue) {
+                if constexpr (kTsoCounts) {
+                    // (the empty asm keeps the plane loads and the front of the alignment INSIDE this branch: a wave that does not take it pays nothing for it)
+                    asm volatile("" ::: "memory");
+                    if (need) {
+                        uint32_t W[4], col[16];
+#pragma unroll
+                        for (int c = 0; c < 4; c++) W[c] = get32(planes + c * kLdsWords * kBlock, tid, t_pos - 1);
+#pragma unroll
+                        for (int c = 0; c < 16; c++) {
+                            const uint32_t a4 = tso4(c);
+                            col[c] = (((a4 & 1u) ? W[0] : 0u) | ((a4 & 2u) ? W[1] : 0u) | ((a4 & 4u) ? W[2] : 0u) | ((a4 & 8u) ? W[3] : 0u)) & 0xFFFFu;
+                        }
+                        AlnStats st;
+                        nw_full<16, false, true, kBandTso, false>(col, 0, st);
+                        mine.consec = st.consec;
+                        mine.two = st.best_two;
+                    }
+                } else {
+                    if (need) nw_runs(t_mt, mine.consec, mine.two);
+                }
+                o.consec = __shfl_xor(mine.consec, 1);
+                o.two = __shfl_xor(mine.two, 1);
+            }
+            Tm f = side == 0 ? mine : o, r = side == 0 ? o : mine;
+            auto found = [](const Tm &x) { return x.present && x.passed; };
+            if (rescue && !found(f) && !found(r)) {  // L146-153: rescue by >= 8 consecutive matches (config.xml:161)
+                const int min_consec = SHIP ? 8 : P.tso_min_consec, min_two = SHIP ? 12 : P.tso_min_two;
+                if (f.present) f.passed = f.consec >= min_consec;
+                if (r.present) r.passed = r.consec >= min_consec;
+                if (!found(f) && !found(r)) {  // L155-162: rescue by the two stretches >= 12 (config.xml:164)
+                    if (f.present) f.passed = f.two >= min_two;
+                    if (r.present) r.passed = r.two >= min_two;
+                }
+            }
+            if (found(f) && found(r) && abs(f.nmis - r.nmis) > 3) {  // L167-172
+                if (f.nmis > r.nmis)
+                    f.present = 0;
+                else
+                    r.present = 0;
+            }
+            return (found(f) ? (uint32_t)(f.end_scan & 0xFFFF) : 0u) | ((found(r) ? (uint32_t)(r.end_scan & 0xFFFF) : 0u) << 16);
+        };
+        uint32_t tso_se = 0;
+        if constexpr (kTsoCounts) tso_se = tso_rules();
 
         // ---- phase C: strand decision (PolyATadapterAnalyzerBase.analyze L145-163): lanes 2i and 2i+1 exchange ----
         const int o_has_t = __shfl_xor((int)has_t, 1);
@@ -1011,8 +1135,6 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
         const bool chosen = active && use_fwd >= 0 && side == (use_fwd ? 0 : 1);
         const int a_pos = (int)(a_pack & 0xFF), a_nmis = (int)((a_pack >> 8) & 0xFF), a_ins = (int)((a_pack >> 16) & 0xFF),
                   a_del = (int)(a_pack >> 24) - 128;
-        const int t_pos = (int)(t_pack & 0xFF), t_nmis = (int)((t_pack >> 8) & 0xFF), t_ins = (int)((t_pack >> 16) & 0xFF),
-                  t_del = (int)(t_pack >> 24) - 128;
 
         smi_scan_result res;
         res.flags = flags;
@@ -1134,66 +1256,11 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                 }
             }
         }
-        // ---- TSO rules on both ends (PolyATadapterAnalyzer_3pBCUMI.scanReadForTSOs L122-190) ----------------------
+        if constexpr (!kTsoCounts) tso_se = tso_rules();
+        res.tso_start = (int16_t)(tso_se & 0xFFFFu);  // TSOresult.start/.end = end of the match in scan coordinates (L177-181): 0 = not found,
+        res.tso_end = (int16_t)(tso_se >> 16);        // a match ends at position 16 at the earliest
         {
-            struct Tm {
-                int present, passed, nmis, end_scan, consec, two;
-            };
-            Tm mine;
-            mine.present = t_pos != 0;
-            mine.nmis = t_nmis;
-            mine.passed = mine.present && t_nmis <= (SHIP ? 5 : P.tso_max_mm);  // scanForTSO L350
-            mine.end_scan = t_pos + 15 + t_ins - t_del;
-            mine.consec = mine.two = 0;
-            Tm o;
-            if (kLazyTso) {
-                // present, passed, nmis (8 bits) and end_scan (16 bits) in one word: one exchange
-                const uint32_t w = (uint32_t)mine.present | ((uint32_t)mine.passed << 1) | ((uint32_t)mine.nmis << 2) | ((uint32_t)(mine.end_scan & 0xFFFF) << 16);
-                const uint32_t ow = (uint32_t)__shfl_xor((int)w, 1);
-                o.present = (int)(ow & 1u);
-                o.passed = (int)((ow >> 1) & 1u);
-                o.nmis = (int)((ow >> 2) & 0xFFu);
-                o.end_scan = (int)(int16_t)(ow >> 16);
-                o.consec = o.two = 0;
-            } else {
-                mine.consec = (int)(t_aux & 0xFF);
-                mine.two = (int)((t_aux >> 8) & 0xFF);
-                o.present = __shfl_xor(mine.present, 1);
-                o.passed = __shfl_xor(mine.passed, 1);
-                o.nmis = __shfl_xor(mine.nmis, 1);
-                o.end_scan = __shfl_xor(mine.end_scan, 1);
-                o.consec = __shfl_xor(mine.consec, 1);
-                o.two = __shfl_xor(mine.two, 1);
-            }
-            // The rescue rules read consec / two of an end that is present and did not pass by nmis, and of no other (found = present && passed).  Lazy:
-            // the runs of the winner's match mask are counted here, for those ends, when the wave has one (one wave in four on the bench's reads: NOTES R6.26)
-            const bool need = mine.present && !mine.passed;
-            const bool rescue = !kLazyTso || __ballot(need) != 0;  // wave-uniform
-            if (kLazyTso && rescue) {
-                if (need) nw_runs(t_mt, mine.consec, mine.two);
-                o.consec = __shfl_xor(mine.consec, 1);
-                o.two = __shfl_xor(mine.two, 1);
-            }
-            Tm f = side == 0 ? mine : o, r = side == 0 ? o : mine;
-            auto found = [](const Tm &x) { return x.present && x.passed; };
-            if (rescue && !found(f) && !found(r)) {  // L146-153: rescue by >= 8 consecutive matches (config.xml:161)
-                const int min_consec = SHIP ? 8 : P.tso_min_consec, min_two = SHIP ? 12 : P.tso_min_two;
-                if (f.present) f.passed = f.consec >= min_consec;
-                if (r.present) r.passed = r.consec >= min_consec;
-                if (!found(f) && !found(r)) {  // L155-162: rescue by the two stretches >= 12 (config.xml:164)
-                    if (f.present) f.passed = f.two >= min_two;
-                    if (r.present) r.passed = r.two >= min_two;
-                }
-            }
-            if (found(f) && found(r) && abs(f.nmis - r.nmis) > 3) {  // L167-172
-                if (f.nmis > r.nmis)
-                    f.present = 0;
-                else
-                    r.present = 0;
-            }
-            const bool ff = found(f), rf = found(r);
-            res.tso_start = ff ? (int16_t)f.end_scan : (int16_t)0;  // TSOresult.start/.end = end of the match in scan
-            res.tso_end = rf ? (int16_t)r.end_scan : (int16_t)0;    // coordinates (L177-181)
+            const bool ff = (tso_se & 0xFFFFu) != 0, rf = (tso_se >> 16) != 0;
             if (long_enough) res.flags |= (ff && !rf) ? SMI_F_TSO_5P : (!ff && rf) ? SMI_F_TSO_3P : (ff && rf) ? SMI_F_TSO_5P_AND_3P : 0u;
         }
         // one record per read: written by the chosen lane, else by the even lane

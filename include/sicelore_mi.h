@@ -538,6 +538,14 @@ int smi_pack_reads_device(smi_ctx *ctx, const uint8_t *d_reads, const uint64_t *
 int smi_chimera_device(smi_ctx *ctx, const uint32_t *d_planes, const uint64_t *d_offsets, size_t n, uint64_t total_bases,
                        const smi_chimera_config *cfg, smi_chimera_result *d_out, void *stream);
 
+/* Which way the reads of the last smi_chimera_device of this context went (nothing in the reference): waits for the device (that call's stream included) and copies
+ * its sixteen counters.  out[0] reads the filter queued for the exact kernels, [1] reads redone by the serial kernel, [2] queued TSO positions
+ * (SMI_CHIM_A1 only: the default keeps them per region), [3] polyA / polyT stretches, [4] adapter positions queued for alignment, [5] reads
+ * handed to the first-generation kernels (second chance), [6] [7] unused, [8 .. 15] reads over a cap, by cap: stretches per read, stretch
+ * queue, adapter-alignment queue, matches per read, TSO slot, gated positions per read, position queue, accepted positions.
+ * SMI_ERR_INVALID before the first smi_chimera_device with n > 0 that returned SMI_OK, and after one that failed. */
+int smi_chimera_last_counts(smi_ctx *ctx, uint32_t out[16]);
+
 /* The records after the split (L288-326) are consecutive slices of the same byte buffer, so splitting is a new offset
  * array: d_frag_offsets [n_frag + 1] (capacity 3n + 1), d_frag_src [n_frag] (capacity 3n, may be NULL) =
  * (source read << 2 | fragment index), *d_n_frag = number of records.  d_scratch: (n + 1023) / 1024 + 1 u32 words. */

@@ -2779,6 +2779,7 @@ int launch_chimera(smi_ctx *ctx, const uint32_t *d_planes, const uint64_t *d_off
         ctx->chim_list_bytes = list_bytes;
     }
     uint32_t *d_count = ctx->chim_list, *d_list = ctx->chim_list + 16;
+    ctx->chim_counts_valid = false;  // until this call has queued all its kernels
     SMI_HIP(hipMemsetAsync(d_count, 0, 64, s));
     if (int rc = time_begin(ctx, SMI_K_CHIMERA, s)) return rc;
     FilterParams F;
@@ -3061,6 +3062,7 @@ int launch_chimera(smi_ctx *ctx, const uint32_t *d_planes, const uint64_t *d_off
         }
     }
     if (int rc = time_end(ctx, SMI_K_CHIMERA, s)) return rc;
+    ctx->chim_counts_valid = true;
     return SMI_OK;
 }
 

@@ -750,6 +750,23 @@ int smi_chimera_device(smi_ctx *ctx, const uint32_t *d_planes, const uint64_t *d
     return launch_chimera(ctx, d_planes, d_offsets, n, total_bases, cfg, d_out, (hipStream_t)stream);
 }
 
+// the queue counters of the last smi_chimera_device of this context: which kernels its reads went through is otherwise invisible to the caller
+int smi_chimera_last_counts(smi_ctx *ctx, uint32_t out[16]) {
+    if (!ctx || !out) {
+        set_error("smi_chimera_last_counts: null argument");
+        return SMI_ERR_INVALID;
+    }
+    if (int rc = bind(ctx)) return rc;
+    if (!ctx->chim_counts_valid || !ctx->chim_list) {
+        set_error("smi_chimera_last_counts: no smi_chimera_device call on this context has succeeded yet");
+        return SMI_ERR_INVALID;
+    }
+    // the call's stream may be the caller's and gone by now: wait for the device, which includes it (this is a diagnostic call, not a hot one)
+    SMI_HIP(hipDeviceSynchronize());
+    SMI_HIP(hipMemcpy(out, ctx->chim_list, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SMI_OK;
+}
+
 int smi_split_offsets_device(smi_ctx *ctx, const smi_chimera_result *d_chim, const uint64_t *d_offsets, size_t n,
                              uint32_t *d_scratch, uint64_t *d_n_frag, uint64_t *d_frag_offsets, uint32_t *d_frag_src,
                              void *stream) {

@@ -191,6 +191,7 @@ struct smi_ctx {
     const smi_ctx *set_owner = nullptr;  // worker lane (smi_ctx_create_lane): the pyramid pointers above belong to this context
     uint32_t *chim_list = nullptr; // K-CHIM: queue of the reads the filter pass could not clear (+ its counter), grow-only
     size_t chim_list_bytes = 0;
+    bool chim_counts_valid = false;  // the sixteen counters at chim_list are those of a smi_chimera_device that returned SMI_OK (smi_chimera_last_counts)
     void *chim_slots = nullptr;    // K-CHIM: matches handed from the exact TSO scan to the rules kernel
     size_t chim_slot_bytes = 0;
     void *chim_work = nullptr;     // K-CHIM second generation: per-read heads, the global queue of positions to align, their error counts (grow-only)

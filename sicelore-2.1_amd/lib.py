@@ -41,6 +41,10 @@ FLAG_BITS = {"FAILED": 5, "PASSED_FWD": 8, "PASSED_REV": 9, "POLY_T_5P": 11, "PO
 assert BC_WINDOW_DTYPE.itemsize == 16 and BC_RESULT_DTYPE.itemsize == 16 and SCAN_RESULT_DTYPE.itemsize == 32
 assert CHIMERA_RESULT_DTYPE.itemsize == 16
 
+# the reasons a read leaves the lane-per-read kernels of the splitter, in the order of the counters (Context.chimera_last_counts()["caps"])
+CHIM_CAP_REASONS = ("stretches_per_read", "stretch_queue", "ad_queue", "matches_per_read", "tso_slot", "gated_per_read", "position_queue",
+                    "accepted_positions")
+
 SET_USED_LIST = 0
 SET_WHITELIST = 1
 SET_MEMBERSHIP = 2   # the list of all possible barcodes for pass 1 only: membership pyramid, no matcher structures (smi_set_mode)
@@ -51,7 +55,7 @@ EXPORTS = [
     "smi_set_barcode_set_device", "smi_bc_match_batch", "smi_bc_match_device", "smi_extract_windows_device",
     "smi_hist_device", "smi_last_kernel_ms", "smi_set_timing", "smi_scan_default_config", "smi_pack_ends_device",
     "smi_ctx_set_polya", "smi_scan_device", "smi_hist_windows_device", "smi_pass1_keys_device", "smi_count_keys_device", "smi_scanfastq_pass1_chunk_keys", "smi_kernel_ms", "smi_finalize_used_list", "smi_umi_dist_device", "smi_format_read_name",
-    "smi_chimera_default_config", "smi_read_planes_words", "smi_pack_reads_device", "smi_chimera_device",
+    "smi_chimera_default_config", "smi_read_planes_words", "smi_pack_reads_device", "smi_chimera_device", "smi_chimera_last_counts",
     "smi_split_offsets_device", "smi_chimera_fragment_name", "smi_umi_cluster_default_config", "smi_umi_cluster_groups",
     "smi_region_group", "smi_ref_position_at_read_position", "smi_scan_default_config_5p", "smi_chimera_default_config_5p", "smi_fastq_index_device", "smi_fastq_gather_device",
     "smi_fastq_write_device", "smi_bgzf_uncompressed_size", "smi_bgzf_inflate", "smi_bam_header", "smi_bam_index_records", "smi_gz_inflate", "smi_bgzf_deflate", "smi_pass2_default_config", "smi_scanfastq_pass2_chunk", "smi_scanfastq_pass1_chunk", "smi_host_alloc", "smi_host_free", "smi_assignumis_default_config", "smi_assignumis_chunk", "smi_assignumis_last_path", "smi_bc_counts_device", "smi_assigned_tsv", "smi_barcode_list_tsv", "smi_hist_allreduce", "smi_hist_allreduce_after", "smi_hist_allreduce_release", "smi_ctx_create_lane", "smi_ctx_lane_refresh", "smi_scan_batch", "smi_umi_dist_batch",
@@ -218,6 +222,7 @@ def load_library():
     lib.smi_read_planes_words.restype = sz
     lib.smi_pack_reads_device.argtypes = [vp, vp, vp, sz, ctypes.c_uint64, vp, vp]
     lib.smi_chimera_device.argtypes = [vp, vp, vp, sz, ctypes.c_uint64, vp, vp, vp]
+    lib.smi_chimera_last_counts.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
     lib.smi_split_offsets_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp]
     lib.smi_chimera_fragment_name.argtypes = [ctypes.c_char_p, vp, ci, ctypes.c_char_p, sz]
     lib.smi_umi_cluster_default_config.argtypes = [vp]
@@ -2663,6 +2668,13 @@ class Context:
         """d_out: int32 [n, 4] (16-B smi_chimera_result records)"""
         self._check(self._lib.smi_chimera_device(self._h, _ptr(d_planes), _ptr(d_offsets), int(n), int(total_bases),
                                                  ctypes.addressof(cfg), _ptr(d_out), _stream_ptr(stream)))
+
+    def chimera_last_counts(self):
+        """which way the reads of the last chimera_device of this context went: the queue counters and, in `caps`, how many reads were over each cap"""
+        h = (ctypes.c_uint32 * 16)()
+        self._check(self._lib.smi_chimera_last_counts(self._h, h))
+        return {"queued": h[0], "serial": h[1], "positions": h[2], "stretches": h[3], "ad_entries": h[4], "second_chance": h[5],
+                "caps": dict(zip(CHIM_CAP_REASONS, h[8:16]))}
 
     def split_offsets_device(self, d_chim, d_offsets, n, d_scratch, d_n_frag, d_frag_offsets, d_frag_src=None, stream=None):
         self._check(self._lib.smi_split_offsets_device(self._h, _ptr(d_chim), _ptr(d_offsets), int(n), _ptr(d_scratch),

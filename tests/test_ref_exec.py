@@ -559,6 +559,46 @@ def test_chimera_split_equals_reference_bytecode(sor):
     assert n_split >= 8 and n_multi >= 1
 
 
+@pytest.mark.parametrize("five_prime", [False, True])
+def test_chimera_thresholds_equal_reference_bytecode(sor, five_prime):
+    """the reads of tests/chimcases.py that sit AT a threshold of findSplitPositions' rules and one base past it (families T, S4, S5, K3), both configurations"""
+    import chimcases
+
+    sec = load("chimera_edges_5p" if five_prime else "chimera_edges_3p")["sections"][0]
+    fv = sec["flag_values"]
+    par = chimcases.oracle_params(sor, five_prime)
+    today = chimcases.ref_exec_reads(five_prime)
+    assert [(c["name"].split(" ")[0], c["seq"]) for c in sec["cases"]] == today  # the fixture's reads are the ones chimcases builds today
+    outcomes = {}
+    for c in sec["cases"]:
+        assert c["hash_orders_agree"] and isinstance(c["records"], list), c["name"]
+        rc, splits, multi, _n, raw = sor.chimera_split(c["seq"], par)
+        assert rc == 0
+        cuts = [0] + [p for _, p in splits] + [len(c["seq"])]
+        want = c["records"]
+        assert len(want) == len(cuts) - 1, (c["name"], splits, [w["name"] for w in want])
+        for k, w in enumerate(want):
+            name = sor.chimera_fragment_name(c["name"], raw, k) if splits else c["name"]
+            assert name == w["name"] and cuts[k + 1] - cuts[k] == w["length"], (c["name"], k, name, w)
+            assert c["seq"][cuts[k]:cuts[k] + 24] == w["bases_head"]
+            expect = fv["READS_AFTER_SPLIT"] if splits else ((fv["MULTI_CHIMERIC_READS_DISCARDED"] | fv["FAILED"]) if multi else 0)
+            assert w["flag"] == expect, (c["name"], hex(w["flag"]), hex(expect))
+        outcomes[c["name"].split(" ")[0]] = [(w["name"], w["length"], w["flag"]) for w in want]
+    # the reference's own records separate every pair whose threshold shows in the records (a dropped TSO match leaves no trace there: those pairs
+    # are held by the oracle's n_matches in tests/test_chim_cases_cpu.py)
+    by = chimcases.by_name()
+    n_pairs = 0
+    for name in outcomes:
+        twin = by[name]["intent"].get("twin")
+        if not twin or name[:3] + twin not in outcomes:
+            continue
+        exp = [chimcases.expected(sor, by[k]["reads"][by[k]["target"]], five_prime)[1:3] for k in (name, name[:3] + twin)]
+        if exp[0] != exp[1]:
+            assert [x[1:] for x in outcomes[name]] != [x[1:] for x in outcomes[name[:3] + twin]], name
+            n_pairs += 1
+    assert n_pairs >= 8
+
+
 # ---- GE / GS / XF (GennameTagger over picard's refFlat genes): model and product against the reference's bytecode ---------------
 def _gene_expectation(case):
     """(GE, GS, XF) as lib.GeneTagger reports them, from the setAttribute calls the reference made"""

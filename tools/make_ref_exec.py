@@ -1406,6 +1406,29 @@ NPSET = "com/rw/nanopore/analyzers/parameters/NeedlemanParameters$OneSet"
 RFLAGS = "com/rw/nanoporereadscanner/stats/ReadFlags"
 
 
+def chimera_case(j, p2, name, seq, qual, shuffle_seed):
+    """findSplitPositions on one record under three iteration orders of the JDK hash containers -> the case as the fixtures keep it"""
+    results = []
+    for order in ("insertion", "reverse", ("shuffle", shuffle_seed)):
+        j.hash_order = order
+        fq = p2.record(name, seq, qual)
+        cf = j.new(CHIM, f"(L{PAR};L{NPSET};)V", p2.par, j.new(NPSET))
+        rf = j.new_object(RFLAGS)   # statistics object: its counters are not outputs of this path; atomics created, the rest left null
+        jc = j.load(RFLAGS)
+        for fname, fdesc in jc.instance_fields:
+            if fdesc in ("Ljava/util/concurrent/atomic/AtomicLong;", "Ljava/util/concurrent/atomic/AtomicInteger;"):
+                rf.f[fname] = j.natives[fdesc[1:-1] + ".<new>"](j)
+        try:
+            coll = j.call_virtual(cf, "findSplitPositions", f"(L{FQX};L{RFLAGS};Z)Ljava/util/Collection;", fq, rf, 0)  # skip = !doSplitChimericReads (Parser.java:L180)
+            recs = [{"name": r.f["readName"], "length": len(r.f["readString"]), "bases_head": r.f["readString"][:24],
+                     "flag": u64(r.f["scanResult"].f["flag"])} for r in coll.native]
+            results.append(recs)
+        except JavaThrow as e:
+            results.append({"throws": e.obj.cls, "message": e.obj.f.get("message"), "in": e.trace[:6]})
+    j.hash_order = None
+    return {"name": name, "seq": seq, "hash_orders_agree": all(r == results[0] for r in results[1:]), "records": results[0]}
+
+
 def gen_chimera(g, five_prime=False, seed=909, n_reads=26):
     j = g.j
     rng = random.Random(seed)
@@ -1439,25 +1462,7 @@ def gen_chimera(g, five_prime=False, seed=909, n_reads=26):
             seq = rnd_seq(rng, rng.randrange(150, 260))           # below 2 * 70 + 100
         qual = "".join(chr(33 + rng.randrange(3, 35)) for _ in seq)
         name = f"read{idx:04d} runid=abc ch={idx}"
-        results = []
-        for order in ("insertion", "reverse", ("shuffle", idx + 1)):
-            j.hash_order = order
-            fq = p2.record(name, seq, qual)
-            cf = j.new(CHIM, f"(L{PAR};L{NPSET};)V", p2.par, j.new(NPSET))
-            rf = j.new_object(RFLAGS)   # statistics object: its counters are not outputs of this path; atomics created, the rest left null
-            jc = j.load(RFLAGS)
-            for fname, fdesc in jc.instance_fields:
-                if fdesc in ("Ljava/util/concurrent/atomic/AtomicLong;", "Ljava/util/concurrent/atomic/AtomicInteger;"):
-                    rf.f[fname] = j.natives[fdesc[1:-1] + ".<new>"](j)
-            try:
-                coll = j.call_virtual(cf, "findSplitPositions", f"(L{FQX};L{RFLAGS};Z)Ljava/util/Collection;", fq, rf, 0)  # skip = !doSplitChimericReads (Parser.java:L180)
-                recs = [{"name": r.f["readName"], "length": len(r.f["readString"]), "bases_head": r.f["readString"][:24],
-                         "flag": u64(r.f["scanResult"].f["flag"])} for r in coll.native]
-                results.append(recs)
-            except JavaThrow as e:
-                results.append({"throws": e.obj.cls, "message": e.obj.f.get("message"), "in": e.trace[:6]})
-        j.hash_order = None
-        s["cases"].append({"name": name, "seq": seq, "hash_orders_agree": all(r == results[0] for r in results[1:]), "records": results[0]})
+        s["cases"].append(chimera_case(j, p2, name, seq, qual, idx + 1))
         if idx % 5 == 0:
             print(f"  chimera {idx + 1}/{n_reads}  {time.time() - g.t0:.0f}s", flush=True)
     vals = j.call_static(FLAGS, "values", f"()[L{FLAGS};")
@@ -1468,6 +1473,48 @@ def gen_chimera(g, five_prime=False, seed=909, n_reads=26):
 
 def gen_chimera_3p(g):
     return gen_chimera(g, False, 909)
+
+
+def _chimera_edges_worker(args):
+    five_prime, reads = args
+    g = Gen()
+    p2 = Pass2(g, five_prime, 1, dont_search_polya=False)
+    cases = []
+    for k, name, seq in reads:
+        cases.append((k, chimera_case(g.j, p2, f"{name} runid=abc ch={k}", seq, "5" * len(seq), k + 1)))
+        print(f"  chimera edge {name} done  {time.time() - g.t0:.0f}s", flush=True)
+    vals = g.j.call_static(FLAGS, "values", f"()[L{FLAGS};")
+    flag_values = {v.f["$name"]: u64(g.j.call_virtual(v, "getValue", "()J")) for v in vals.a}
+    return cases, sorted(g.j.natives_used), g.hits(), g.j.steps, flag_values
+
+
+def gen_chimera_edges(g, five_prime):
+    """gen_chimera's driver on the threshold reads of tests/chimcases.py (families T, S4, S5, K3: chimcases.ref_exec_reads), spread over --jobs processes"""
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import chimcases
+
+    reads = [(k, name, seq) for k, (name, seq) in enumerate(chimcases.ref_exec_reads(five_prime))]
+    assert len(reads) <= 40
+    jobs = max(1, int(os.environ.get("WIDE_JOBS", "1")))
+    args = [(five_prime, reads[k::jobs]) for k in range(jobs) if reads[k::jobs]]
+    if len(args) == 1:
+        parts = [_chimera_edges_worker(args[0])]
+    else:
+        import multiprocessing as mp
+
+        with mp.get_context("fork").Pool(len(args)) as pool:
+            parts = pool.map(_chimera_edges_worker, args)
+    hits = {}
+    for p in parts:
+        merge_hits(hits, p[2])
+    natives = sorted(set(n for p in parts for n in p[1]))
+    s = {"reference_class": CHIM, "reference_method": "findSplitPositions:(L...FastqRecordExt;L...ReadFlags;Z)Ljava/util/Collection;",
+         "title": ("5-prime" if five_prime else "3-prime") + " barcoding: findSplitPositions as in ref_exec_chimera_3p.json, on reads built AT the thresholds of its rules "
+                  "and one base past them (tests/chimcases.py); each case under three iteration orders of the JDK hash containers",
+         "cases": [c for _, c in sorted((kc for p in parts for kc in p[0]), key=lambda kc: kc[0])], "five_prime": five_prime, "flag_values": parts[0][4],
+         "natives": [{"native": k, "tier": jvm_natives.tier_of(k)} for k in natives]}
+    s["max_tier"] = max([n["tier"] for n in s["natives"]] or ["A"])
+    return {"jar": "NanoporeBC_UMI_finder-2.1.jar", "sections": [s], "_steps": sum(p[3] for p in parts), "_hits": hits}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -3090,6 +3137,7 @@ SECTIONS = {"pass2t": gen_pass2t, "pass2k": gen_pass2k, "umi_3p_len10": gen_umi_
             "umi_3p": gen_umi_3p, "umi_5p": gen_umi_5p, "umi_odd_names": gen_umi_odd_names, "chimera_3p": gen_chimera_3p, "stats_print": gen_stats_print,
             "pass2w_3p": gen_pass2w_3p, "pass2w_3p_ed2": gen_pass2w_3p_ed2, "pass2w_5p": gen_pass2w_5p, "pass2w_5p_polya": gen_pass2w_5p_polya,
             "pass2x_3p": gen_pass2x_3p, "pass2x_5p": gen_pass2x_5p, "pass2p": gen_pass2p, "group2": gen_group2, "cluster_own2": gen_cluster_own2,
+            "chimera_edges_3p": lambda g: gen_chimera_edges(g, False), "chimera_edges_5p": lambda g: gen_chimera_edges(g, True),
             "pass1_5p": lambda g: gen_pass1(g, 32, 1626, five_prime=True),
             "pass1_nowl": lambda g: gen_pass1(g, 60, 1636, no_whitelist=True), "pass1_nowl_5p": lambda g: gen_pass1(g, 66, 1646, five_prime=True, no_whitelist=True)}
 

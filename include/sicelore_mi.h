@@ -1770,6 +1770,52 @@ int smi_samview_error_line(const smi_samview *h, int64_t *line, char *reason, si
 int smi_samview_free(smi_samview *h);
 int smi_samview_host_loop(smi_samview *h, double *seconds, int64_t *mismatches);
 
+/* ---- BamView (K-VIEW-TEST, K-VIEW-GATHER, smi_bamview.hip) ----------------------------------------------------------------------------------
+ * The records of a BAM that pass the flag and quality filters and overlap one of the regions, in the order they come in, in the place of
+ * `samtools view -b in.bam [region ...]`.  A record's extent is BamIndex's: pos and pos + the M D N = X lengths of
+ * the stored CIGAR (one base where that sum is 0, where there is no CIGAR and where flag 0x4 is set); it overlaps (ref, beg, end) when
+ * ref_id == ref, its begin < end and its end > beg, in 64 bits.  A record without a reference overlaps nothing.
+ * smi_bamview_create: n_ref references of the header; a record stays when every bit of `require` and no bit of `exclude` is set in its
+ *   flag and its mapq >= min_mapq (samtools' -f, -F, -q).  The n_regions regions (0: the filters alone decide) are half-open, 0-based,
+ *   already merged and sorted by the caller: ascending by reference, inside a reference ascending and neither overlapping nor touching;
+ *   anything else is SMI_ERR_INVALID.
+ * smi_bamview_add_segment: bam / n_bam / recs / n as smi_tagbam_segment takes them; the caller decides which bytes of the file these are
+ *   (the whole stream in segments, or the bytes under the ranges an index gave).  Tests every record and sums the sizes of the kept ones:
+ *   *n_record_bytes = their bytes, *n_bgzf = the room their BGZF blocks need.  Returns 2 at a ref_id >= n_ref: smi_last_error and
+ *   smi_bamview_error_read name the first such read and its 0-based number among the records handed in, and the handle takes nothing
+ *   further.
+ * smi_bamview_convert: gathers the kept records of the segment taken last and deflates them into BGZF blocks on the device
+ *   (smi_bgzf_deflate_device; no end-of-file block): *n_out bytes at out_bgzf.  1 = cap or cap_records is too small (*n_out = the room
+ *   needed).  out_records (may be NULL): the records as they stand in the blocks.
+ * smi_bamview_counts: SMI_BAMVIEW_N_COUNT entries.  smi_bamview_stage_ms: SMI_BAMVIEW_N_STAGE device times of the last add_segment (test,
+ *   scan) and convert (gather, deflate: the latter with its copy to the host).
+ * smi_bamview_host_loop (measurement and tests, after convert): the same test and copy of the segment taken last on one host thread: its
+ *   seconds, the copies from the device not counted, and the number of records whose keep decision or bytes differ from the device's (0). */
+#define SMI_BAMVIEW_RECORDS 0    /* records seen */
+#define SMI_BAMVIEW_KEPT 1       /* records kept */
+#define SMI_BAMVIEW_BYTES 2      /* bytes of the records seen */
+#define SMI_BAMVIEW_BYTES_KEPT 3 /* bytes of the records kept */
+#define SMI_BAMVIEW_REGIONS 4    /* merged regions */
+#define SMI_BAMVIEW_SEGMENTS 5   /* segments with at least one record */
+#define SMI_BAMVIEW_N_COUNT 6
+#define SMI_BAMVIEW_MS_TEST 0
+#define SMI_BAMVIEW_MS_SCAN 1
+#define SMI_BAMVIEW_MS_GATHER 2
+#define SMI_BAMVIEW_MS_DEFLATE 3
+#define SMI_BAMVIEW_N_STAGE 4
+typedef struct smi_bamview smi_bamview;
+int smi_bamview_create(smi_ctx *ctx, int32_t n_ref, uint32_t require, uint32_t exclude, uint32_t min_mapq, const int32_t *region_ref,
+                       const int64_t *region_beg, const int64_t *region_end, size_t n_regions, smi_bamview **out);
+int smi_bamview_add_segment(smi_bamview *h, const uint8_t *bam, size_t n_bam, const smi_bam_record *recs, int32_t n, size_t *n_bgzf,
+                            size_t *n_record_bytes);
+int smi_bamview_convert(smi_bamview *h, uint8_t *out_bgzf, size_t cap, size_t *n_out, uint8_t *out_records, size_t cap_records);
+int smi_bamview_counts(const smi_bamview *h, int64_t *counts);
+int smi_bamview_stage_ms(const smi_bamview *h, float *ms);
+/* the read that ended the run (smi_bamview_add_segment returned 2): its name (cut to cap - 1 bytes) and its 0-based number; -1 = none */
+int smi_bamview_error_read(const smi_bamview *h, char *name, size_t cap, int64_t *record);
+int smi_bamview_free(smi_bamview *h);
+int smi_bamview_host_loop(smi_bamview *h, double *seconds, int64_t *mismatches);
+
 /* device-time of the dominant kernel of the last *_device call on this context, measured with HIP events on the
  * stream the kernel was launched on; valid after the stream has been synchronised.  ms <= 0: not available. */
 int smi_last_kernel_ms(smi_ctx *ctx, float *ms);

@@ -161,6 +161,37 @@ __device__ __forceinline__ void wave_copy(uint8_t *__restrict__ dst, const uint8
     if (done + lane < n) dst[done + lane] = src[done + lane];
 }
 
+// The copy K-SORT-GATHER, K-MERGE-GATHER (smi_bamsort.hip) and K-VIEW-GATHER (smi_bamview.hip) share: the L bytes at s to dst + d0, where
+// dst is aligned to 256 bytes, by the kCopyLanes lanes of a group (sub: the lane's number in it).  The bytes in front of the first
+// W-aligned destination address and those behind the last one go one byte per lane (fewer than W <= kCopyLanes of either), the body in
+// W-byte words: a store aligned to W, a load of any alignment.  Every load and store lies inside the record.
+constexpr int kCopyLanes = 16;
+template <int W>
+struct Word;
+template <>
+struct Word<16> {
+    using type = uint4;
+};
+template <>
+struct Word<4> {
+    using type = uint32_t;
+};
+template <int W>
+__device__ __forceinline__ void copy_record(const uint8_t *__restrict__ s, uint32_t L, uint64_t d0, uint8_t *__restrict__ dst, uint32_t sub) {
+    using T = typename Word<W>::type;
+    static_assert(W <= kCopyLanes, "head and tail go one byte per lane");
+    uint8_t *__restrict__ d = dst + d0;
+    const uint32_t want = (uint32_t)(-(int64_t)d0) & (W - 1), head = want < L ? want : L;
+    const uint32_t words = (L - head) / W, tail = (L - head) % W, tail_at = head + words * W;
+    if (sub < head) d[sub] = s[sub];
+    for (uint32_t w = sub; w < words; w += kCopyLanes) {
+        T v;
+        __builtin_memcpy(&v, s + head + (size_t)w * W, W);
+        *reinterpret_cast<T *>(__builtin_assume_aligned(d + head + (size_t)w * W, W)) = v;
+    }
+    if (sub < tail) d[tail_at + sub] = s[tail_at + sub];
+}
+
 // inclusive prefix sum across the wave
 template <class T>
 __device__ __forceinline__ T wave_incl_sum(T v, int lane) {

@@ -95,6 +95,8 @@ EXPORTS = [
     "smi_bamsort_merge_window",
     "smi_samview_create", "smi_samview_header", "smi_samview_add_segment", "smi_samview_convert", "smi_samview_counts", "smi_samview_stage_ms",
     "smi_samview_error_line", "smi_samview_free", "smi_samview_host_loop",
+    "smi_bamview_create", "smi_bamview_add_segment", "smi_bamview_convert", "smi_bamview_counts", "smi_bamview_stage_ms",
+    "smi_bamview_error_read", "smi_bamview_free", "smi_bamview_host_loop",
     "smi_select_valid_cells",
 ]
 
@@ -375,6 +377,14 @@ def load_library():
     lib.smi_samview_error_line.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), vp, sz]
     lib.smi_samview_free.argtypes = [vp]
     lib.smi_samview_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_bamview_create.argtypes = [vp, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, sz, ctypes.POINTER(vp)]
+    lib.smi_bamview_add_segment.argtypes = [vp, vp, sz, vp, ctypes.c_int32, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    lib.smi_bamview_convert.argtypes = [vp, vp, sz, ctypes.POINTER(sz), vp, sz]
+    lib.smi_bamview_counts.argtypes = [vp, vp]
+    lib.smi_bamview_stage_ms.argtypes = [vp, vp]
+    lib.smi_bamview_error_read.argtypes = [vp, vp, sz, ctypes.POINTER(ctypes.c_int64)]
+    lib.smi_bamview_free.argtypes = [vp]
+    lib.smi_bamview_host_loop.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
     lib.smi_poa_batch.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_int32)]
     lib.smi_poa_batch_ex.argtypes = lib.smi_poa_batch.argtypes + [vp]
@@ -1488,6 +1498,78 @@ class SamView(_Handle):
         """-> (seconds of the same conversion of the last segment on one host thread, records whose bytes differ from the device's)"""
         sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
         self._check(self._lib.smi_samview_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)))
+        return sec.value, bad.value
+
+
+# smi_bamview_counts, in SMI_BAMVIEW_* order (SMI_BAMVIEW_N_COUNT entries); smi_bamview_stage_ms (SMI_BAMVIEW_N_STAGE entries)
+BAMVIEW_COUNTS = ("records", "kept", "bytes", "bytes_kept", "regions", "segments")
+BAMVIEW_STAGES = ("test", "scan", "gather", "deflate")
+
+
+class BamViewError(SmiError):
+    """a record the view stops at (smi_bamview_add_segment returned 2: a ref_id outside the header); .read: its name, .record: its 0-based
+    number among the records handed in"""
+
+    def __init__(self, msg, read, record):
+        super().__init__(msg)
+        self.read, self.record = read, record
+
+
+class BamView(_Handle):
+    """The records that pass the flag and quality filters and overlap a region, on the device (smi_bamview_*).  n_ref: the number of the
+    header's references; regions: (ref_id, beg, end) half-open and 0-based, already merged and sorted (bamview.merge_regions); none: the
+    filters alone decide.  add_segment() / convert(): inflated bytes and their record index in, the kept records out as BGZF blocks."""
+    _NAME, _COUNTS = "bamview", BAMVIEW_COUNTS
+
+    def __init__(self, ctx, n_ref, regions=(), require=0, exclude=0, min_mapq=0):
+        self._lib = load_library()
+        self._z = self._data = None
+        for name, v, top in (("require", require, 0xFFFF), ("exclude", exclude, 0xFFFF), ("min_mapq", min_mapq, 255)):
+            if not 0 <= int(v) <= top:
+                raise SmiError(f"BamView: {name} = {v} is not in 0 .. {top}")
+        regions = list(regions)
+        ref = np.array([r[0] for r in regions], dtype=np.int32)
+        beg = np.array([r[1] for r in regions], dtype=np.int64)
+        end = np.array([r[2] for r in regions], dtype=np.int64)
+        n = len(regions)
+        self._create(ctx, int(n_ref), int(require), int(exclude), int(min_mapq), _ptr(ref) if n else None, _ptr(beg) if n else None,
+                     _ptr(end) if n else None, n)
+
+    def add_segment(self, bam, recs):
+        """bam: inflated BAM bytes (uint8), recs: BAM_RECORD_DTYPE entries of the records in it
+        -> (room the BGZF blocks of the kept records need, their bytes)"""
+        args, recs = self._segment_args(bam, recs)
+        nz, nd = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        rc = self._lib.smi_bamview_add_segment(self._h, *args, ctypes.byref(nz), ctypes.byref(nd))
+        if rc == 2:
+            msg = self._lib.smi_last_error().decode(errors="replace")
+            name, rec = self._error_read()
+            raise BamViewError(msg, name.decode("latin-1"), rec)
+        self._check(rc)
+        self._sizes = nz.value, nd.value
+        return self._sizes
+
+    def convert(self, inflated=False):
+        """the segment taken last -> (the BGZF blocks of its kept records without an end-of-file block, those records or None), uint8
+        views of buffers that the next call writes again"""
+        nz, nd = self._sizes
+        if self._z is None or self._z.size < nz:
+            self._z = np.empty(nz, dtype=np.uint8)
+        if inflated and (self._data is None or self._data.size < nd):
+            self._data = np.empty(max(nd, 1), dtype=np.uint8)
+        n = ctypes.c_size_t(0)
+        self._check(self._lib.smi_bamview_convert(self._h, _ptr(self._z), self._z.size, ctypes.byref(n), _ptr(self._data) if inflated else None,
+                                                  self._data.size if inflated else 0))
+        return self._z[:n.value], self._data[:nd] if inflated else None
+
+    def stage_ms(self):
+        return self._named("stage_ms", BAMVIEW_STAGES, np.float32)
+
+    def host_loop(self):
+        """-> (seconds of the same test and copy of the last segment on one host thread, records whose keep decision or bytes differ from
+        the device's)"""
+        sec, bad = ctypes.c_double(0), ctypes.c_int64(-1)
+        self._check(self._lib.smi_bamview_host_loop(self._h, ctypes.byref(sec), ctypes.byref(bad)))
         return sec.value, bad.value
 
 

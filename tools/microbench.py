@@ -38,9 +38,9 @@ def main():
     legs = {"bc2": leg_bc2, "bc": leg_bc, "pass1": leg_pass1, "umi": leg_umi, "chimera": leg_chimera, "fastq": leg_fastq, "assignumis": leg_assignumis,
             "packed": leg_packed, "deflate": leg_deflate, "inflate": leg_inflate, "tagbam": leg_tagbam,
             "consensus": leg_consensus, "isoform": leg_isoform, "snp": leg_snp, "dedup": leg_dedup, "moltag": leg_moltag, "collapse": leg_collapse, "fusion": leg_fusion, "validator": leg_validator,
-            "fusionprep": leg_fusionprep, "bamindex": leg_bamindex, "bamsort": leg_bamsort, "bamsort_runs": leg_bamsort_runs, "samview": leg_samview}
+            "fusionprep": leg_fusionprep, "bamindex": leg_bamindex, "bamsort": leg_bamsort, "bamsort_runs": leg_bamsort_runs, "samview": leg_samview, "bamview": leg_bamview}
     for name, fn in legs.items():
-        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep", "bamindex", "bamsort", "bamsort_runs", "samview")):
+        if only == name or (only is None and name not in ("bc2", "tagbam", "consensus", "isoform", "snp", "dedup", "moltag", "collapse", "fusion", "validator", "fusionprep", "bamindex", "bamsort", "bamsort_runs", "samview", "bamview")):
             fn(pkg, synth, ctx, dev, wl, used, res)
     print(json.dumps(res))
 
@@ -1384,6 +1384,75 @@ def _snp_fixture(n_recs, n_lines, n_cells, seed=51):
     bam = np.concatenate([np.frombuffer(head, dtype=np.uint8), rec.reshape(-1)])
     csv = "".join(f"CELL{c:05d}-1\n" for c in range(n_cells))
     return "".join(lines), csv, lib.bgzf_deflate(bam, level=1, n_threads=16), int(bam.size)
+
+
+def leg_bamview(pkg, synth, ctx, dev, wl, used, res):
+    """K-VIEW (`bamview.py`, in the place of `samtools view in.bam [region ...]`), file to file: _bamsort_fixture's seeded BAMs of
+    SMI_MB_VIEW_RECS records (2,000,000) over 25 references, once without sequence and once with US / QS of 400 .. 800 bytes, sorted with
+    sort_bam and indexed with index_bam; view_bam after a run that loads the code objects, three ways: one reference of the 25, 1,000
+    seeded regions, and no region with -F 4: device ms per stage (HIP events), the ranges, blocks and compressed bytes read against the
+    file's, the seconds in read and inflate, in the record index, in the device calls and in the write, wall seconds, and wall seconds
+    with index=True; then smi_bamview_host_loop on every segment of the 1,000-region query: the seconds of the same test and copy on one
+    host thread and its mismatch count."""
+    import shutil
+    import tempfile
+
+    bs = importlib.import_module(graft.PKG_NAME + ".bamsort")
+    bi = importlib.import_module(graft.PKG_NAME + ".bamindex")
+    bv = importlib.import_module(graft.PKG_NAME + ".bamview")
+    segs = importlib.import_module(graft.PKG_NAME + ".bamsegments")
+    lib = importlib.import_module(graft.PKG_NAME + ".lib")
+    n_recs = int(os.environ.get("SMI_MB_VIEW_RECS", "2000000"))
+    seg = int(os.environ.get("SMI_MB_VIEW_SEGMENT", str(64 << 20)))
+    rng = np.random.default_rng(211)
+    regions = []
+    for _ in range(1000):
+        beg = int(rng.integers(0, 1 << 27))
+        regions.append((int(rng.integers(0, 25)), beg, beg + 1 + int(rng.integers(0, 1 << int(rng.integers(1, 18))))))
+    queries = (("one_reference", ["chr13"], {}), ("regions_1000", regions, {}), ("no_region_F4", [], dict(exclude=4)))
+    res["bamview"] = {}
+    for case, with_seq in (("no_sequence", False), ("us_qs_400_800", True)):
+        t0 = time.perf_counter()
+        z, n_rec, inflated = _bamsort_fixture(n_recs, with_seq)
+        d = tempfile.mkdtemp(prefix="bamview_")
+        try:
+            unsorted, src, dst = os.path.join(d, "unsorted.bam"), os.path.join(d, "in.bam"), os.path.join(d, "out.bam")
+            z.tofile(unsorted)
+            del z
+            bs.sort_bam(ctx, unsorted, src, segment_bytes=seg, n_threads=16)
+            os.remove(unsorted)
+            bi.index_bam(ctx, src, segment_bytes=seg, n_threads=16)
+            out = {"records": n_rec, "bam_bytes": os.path.getsize(src), "bai_bytes": os.path.getsize(src + ".bai"), "inflated_bytes": inflated,
+                   "segment_bytes": seg, "fixture_s": time.perf_counter() - t0}
+            bv.view_bam(ctx, src, dst, ["chr1:1-100000"], segment_bytes=seg, n_threads=16)          # the first run loads the code objects
+            for name, asked, filters in queries:
+                for flag in (False, True):
+                    info = bv.view_bam(ctx, src, dst, asked, segment_bytes=seg, n_threads=16, index=flag, **filters)
+                    if not flag:
+                        out[name] = dict({k: info[k] for k in lib.BAMVIEW_COUNTS + ("ranges", "blocks_read", "compressed_bytes_read")},
+                                         stage_ms=info["stage_ms"], seconds=info["seconds"], wall_s=info["wall_s"], bytes_written=info["bytes_written"],
+                                         read_fraction=info["compressed_bytes_read"] / out["bam_bytes"],
+                                         gather_bytes_per_s=info["bytes_kept"] / max(info["stage_ms"]["gather"], 1e-6) * 1e3)
+                    else:
+                        out[name]["wall_s_with_index"] = info["wall_s"]
+                        out[name]["index_error"] = info["index_error"]
+            merged = bv.merge_regions(regions)
+            with open(src + ".bai", "rb") as f:
+                spans = bv.query_ranges(bv.read_bai(f.read()), merged)
+            h = lib.BamView(ctx, 25, merged)
+            try:
+                sec = bad = n = 0
+                for bam, recs in segs.ranges(src, spans, seg, 16):
+                    h.add_segment(bam, recs)
+                    h.convert()
+                    s1, b1 = h.host_loop()
+                    sec, bad, n = sec + s1, bad + b1, n + 1
+                out["host_loop"] = dict(seconds=sec, mismatches=bad, segments=n, records=h.counts()["records"])
+            finally:
+                h.close()
+        finally:
+            shutil.rmtree(d, ignore_errors=True)
+        res["bamview"][case] = out
 
 
 def leg_snp(pkg, synth, ctx, dev, wl, used, res):

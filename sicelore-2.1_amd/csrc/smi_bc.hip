@@ -18,6 +18,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "smi_internal.h"
+#include "smi_wave.h"
 
 namespace smi {
 
@@ -1257,7 +1258,8 @@ __global__ __launch_bounds__(256) void k_bc_match_ed1f(const smi_bc_window *__re
     }
 }
 
-// K-BC1 from the neighbourhood table (P.nt), two kernels.
+// K-BC1 from the neighbourhood table (P.nt), two kernels: the table path as it shipped before k_bc_match_ed1w (below), kept behind
+// SMI_BC1_TWO_KERNELS as its cross-check.  The look-up and the pick are the same functions in both.
 // k_bc_codes_ed1t: one lane = one (read, offset) pair, so that every look-up of the batch is in flight at once (with a lane per read the
 // five windows of a read were looked up one behind the other and a wave waited for its slowest lane: 2.5 ms, 1.5 of them waiting).  The
 // window's filter bit (P.nb) first; a window whose bit is set reads the 64-byte bucket of its sequence and every entry with that sequence
@@ -1273,6 +1275,95 @@ __global__ __launch_bounds__(256) void k_bc_match_ed1f(const smi_bc_window *__re
 // the free-slot test over all eight slots, as they were (the counter runs' "before").
 // The offset of pair q (0, -1, 1, -2, 2: the reference's order, Parser.java:L203) by arithmetic: as a chain of selects on a lane-varying q the compiler
 // built it from divergent branches.  -DSMI_BC1_OFFSET_SELECTS=1: the chain of selects, as it was.
+// The window record as ONE 16-byte load.  The values pass through an empty asm statement: without it the compiler, which knows the record
+// read-only, loaded it a second time (global_load_dwordx4 and, right behind it, global_load_dwordx2 of the same address) rather than keep
+// the bases live across the bucket loop -- one of a lane's three or four memory requests for nothing.
+__device__ __forceinline__ smi_bc_window load_window16(const smi_bc_window *__restrict__ w) {
+    uint4 raw = *reinterpret_cast<const uint4 *>(w);
+    asm volatile("" : "+v"(raw.x), "+v"(raw.y), "+v"(raw.z), "+v"(raw.w));
+    smi_bc_window my;
+    my.bases = ((uint64_t)raw.y << 32) | raw.x;
+    my.nmask = raw.z;
+    my.flags = raw.w;
+    return my;
+}
+
+// the filter the loaded set is probed through, in the finest layout it has (wave-uniform), and the index (-> bit through wbit) of the word of key K
+// at offset `off` in it
+__device__ __forceinline__ const uint32_t *bc1_filter_table(const Pyramid &P) { return P.nbl ? P.nbl : (P.nb5 ? P.nb5 : P.nb); }
+__device__ __forceinline__ uint32_t bc1_filter_index(const Pyramid &P, uint32_t K, int off, bool fp, uint32_t &wbit) {
+    uint32_t wi;
+    if (P.nbl)  // the five words of a read lie in ONE 128-byte line; a superset of nb5's bits, and the bucket compare decides
+        wbit = nbl_bit_index(K, fp ? -off : off, wi);
+    else if (P.nb5)  // the five words of a read are neighbours: 160 consecutive bytes, two 128-byte lines
+        wbit = nb5_bit_index(K, fp ? -off : off, wi);
+    else
+        wbit = K & 31u, wi = K >> 5;
+    return wi;
+}
+
+// One slot of a bucket against sequence K (k_lo = K << 8, k_hi = K >> 24 | 0x100: the compare in 32-bit halves): an entry of K names one mutation of
+// the reference's enumeration that turns the window into a barcode -> exact |= 0x80, or best = min(best, its enumeration index) where it is valid.
+__device__ __forceinline__ void bc1_slot(uint32_t e_lo, uint32_t e_hi, uint32_t K, uint32_t k_lo, uint32_t k_hi, uint32_t del_base, uint32_t &best, uint32_t &exact) {
+    const uint32_t step = e_lo ^ k_lo;
+    if (step < 256u && e_hi == k_hi) {
+        const uint32_t kind = step & 3u, pos = (step >> 2) & 15u, base = (step >> 6) & 3u;
+        if (kind == 0u) {
+            exact |= 0x80u;  // exact match (BarcodeMatchTester.java:L204-206)
+        } else if (kind == 1u) {
+            const uint32_t cur = (K >> (30 - 2 * pos)) & 3u;
+            best = min(best, 8u * pos + base - (base > cur ? 1u : 0u));  // substitutions by ascending base, the current one skipped
+        } else if (kind == 2u) {
+            if (!(pos == 14u && (K & 3u) != 0u)) best = min(best, 8u * pos + 3u + base);
+        } else {
+            if (base == del_base) best = min(best, 8u * pos + 7u);
+        }
+    }
+}
+
+// What stands behind the filter bit: the bucket(s) of sequence K -> exact << 7 | (smallest valid enumeration index + 1).
+__device__ __forceinline__ uint32_t bc1_lookup(uint32_t K, uint32_t del_base, const Pyramid &P) {
+    uint32_t code = 0;
+    uint32_t best = 255u;
+    uint32_t idx = nt_slot(K, P.nt_cap);
+    const uint32_t k_lo = K << 8, k_hi = (K >> 24) | 0x100u;
+    for (;;) {
+        uint64_t e[8];
+        __builtin_memcpy(e, P.nt + idx, 64);  // one bucket = one line
+#if SMI_BC1_BUCKET_COMPARE64
+        bool open = false;
+#else
+        const bool open = (uint32_t)(e[7] >> 32) == 0u;
+#endif
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+#if SMI_BC1_BUCKET_COMPARE64
+            open = open || e[t] == 0ull;
+            const uint32_t step = (uint32_t)e[t];
+            if ((uint32_t)(e[t] >> 8) == K && (e[t] >> 40)) {
+                const uint32_t kind = step & 3u, pos = (step >> 2) & 15u, base = (step >> 6) & 3u;
+                if (kind == 0u) {
+                    code |= 0x80u;
+                } else if (kind == 1u) {
+                    const uint32_t cur = (K >> (30 - 2 * pos)) & 3u;
+                    best = min(best, 8u * pos + base - (base > cur ? 1u : 0u));
+                } else if (kind == 2u) {
+                    if (!(pos == 14u && (K & 3u) != 0u)) best = min(best, 8u * pos + 3u + base);
+                } else {
+                    if (base == del_base) best = min(best, 8u * pos + 7u);
+                }
+            }
+#else
+            bc1_slot((uint32_t)e[t], (uint32_t)(e[t] >> 32), K, k_lo, k_hi, del_base, best, code);
+#endif
+        }
+        if (open) break;  // a bucket with a free slot has never overflowed into the next one
+        idx = idx + 8 == P.nt_cap ? 0u : idx + 8;
+    }
+    if (best != 255u) code |= best + 1u;
+    return code;
+}
+
 __device__ __forceinline__ uint32_t bc1_code(const smi_bc_window *__restrict__ w, int q, bool fp, const Pyramid &P) {
 #if SMI_BC1_OFFSET_SELECTS
     const int off = q == 0 ? 0 : (q == 1 ? -1 : (q == 2 ? 1 : (q == 3 ? -2 : 2)));
@@ -1281,72 +1372,14 @@ __device__ __forceinline__ uint32_t bc1_code(const smi_bc_window *__restrict__ w
 #endif
     // the window as ONE 16-byte load (as `win[i]` the flags word was fetched and tested first, the bases behind that wait: a fourth
     // dependent round trip in front of the filter bit, the bucket and the store)
-    smi_bc_window my;
-    {
-        const uint4 raw = *reinterpret_cast<const uint4 *>(w);
-        my.bases = ((uint64_t)raw.y << 32) | raw.x;
-        my.nmask = raw.z;
-        my.flags = raw.w;
-    }
-    uint32_t code = 0;
+    const smi_bc_window my = load_window16(w);
     // key and filter word for every lane, valid window or not (any 32-bit key lies inside the 512 MiB bitmap): nothing but the window's
     // own load stands in front of the probe
     const OffsetKey k = make_key(my.bases, my.nmask, off, fp);
-    const uint32_t K = k.key;
-    uint32_t word, wbit = K & 31u;
-    if (P.nbl) {  // (wave-uniform) the five lanes of a read ask for words of ONE 128-byte line; a superset of nb5's bits, and the bucket compare decides
-        uint32_t wi;
-        wbit = nbl_bit_index(K, fp ? -off : off, wi);
-        word = P.nbl[wi];
-    } else if (P.nb5) {  // (wave-uniform) the five lanes of a read ask for neighbouring words: 160 consecutive bytes, two 128-byte lines
-        uint32_t wi;
-        wbit = nb5_bit_index(K, fp ? -off : off, wi);
-        word = P.nb5[wi];
-    } else
-        word = P.nb[K >> 5];
-    if ((my.flags & SMI_WIN_VALID) && k.usable && ((word >> wbit) & 1u)) {
-        uint32_t best = 255u;
-        uint32_t idx = nt_slot(K, P.nt_cap);
-#if !SMI_BC1_BUCKET_COMPARE64
-        const uint32_t k_lo = K << 8, k_hi = (K >> 24) | 0x100u;
-#endif
-        for (;;) {
-            uint64_t e[8];
-            __builtin_memcpy(e, P.nt + idx, 64);  // one bucket = one line
-#if SMI_BC1_BUCKET_COMPARE64
-            bool open = false;
-#else
-            const bool open = (uint32_t)(e[7] >> 32) == 0u;
-#endif
-#pragma unroll
-            for (int t = 0; t < 8; t++) {
-#if SMI_BC1_BUCKET_COMPARE64
-                open = open || e[t] == 0ull;
-                const uint32_t step = (uint32_t)e[t];
-                if ((uint32_t)(e[t] >> 8) == K && (e[t] >> 40)) {
-#else
-                const uint32_t step = (uint32_t)e[t] ^ k_lo;
-                if (step < 256u && (uint32_t)(e[t] >> 32) == k_hi) {
-#endif
-                    const uint32_t kind = step & 3u, pos = (step >> 2) & 15u, base = (step >> 6) & 3u;
-                    if (kind == 0u) {
-                        code |= 0x80u;  // exact match (BarcodeMatchTester.java:L204-206)
-                    } else if (kind == 1u) {
-                        const uint32_t cur = (K >> (30 - 2 * pos)) & 3u;
-                        best = min(best, 8u * pos + base - (base > cur ? 1u : 0u));  // substitutions by ascending base, the current one skipped
-                    } else if (kind == 2u) {
-                        if (!(pos == 14u && (K & 3u) != 0u)) best = min(best, 8u * pos + 3u + base);
-                    } else {
-                        if (base == k.del_base) best = min(best, 8u * pos + 7u);
-                    }
-                }
-            }
-            if (open) break;  // a bucket with a free slot has never overflowed into the next one
-            idx = idx + 8 == P.nt_cap ? 0u : idx + 8;
-        }
-        if (best != 255u) code |= best + 1u;
-    }
-    return code;
+    uint32_t wbit;
+    const uint32_t word = bc1_filter_table(P)[bc1_filter_index(P, k.key, off, fp, wbit)];
+    if ((my.flags & SMI_WIN_VALID) && k.usable && ((word >> wbit) & 1u)) return bc1_lookup(k.key, k.del_base, P);
+    return 0u;
 }
 
 // (read, offset) = (j / 5, j mod 5) in 32 bits where every index of the grid-stride loop fits them -- as size_t the quotient and the remainder are 64-bit
@@ -1371,38 +1404,174 @@ __global__ __launch_bounds__(256) void k_bc_codes_ed1t(const smi_bc_window *__re
     }
 }
 
+// The reference's rule over the five bytes of a read (keys / del_base of offsets 0, -1, 1, -2, 2) -> its record.
+__device__ __forceinline__ smi_bc_result bc1_pick(const uint32_t (&key)[5], const uint32_t (&del_base)[5], const uint32_t (&code)[5], bool valid) {
+    smi_bc_result res;
+    uint32_t c_bc[10], c_rs[10];
+    int c_imd[10];
+    uint32_t present = 0;
+#pragma unroll
+    for (int q = 0; q < 5; q++) {
+        c_rs[2 * q] = c_rs[2 * q + 1] = key[q];
+        c_bc[2 * q] = key[q];
+        c_imd[2 * q] = 0;
+        present |= (code[q] >> 7) << (2 * q);
+        const int e = (int)(code[q] & 0x7Fu) - 1;
+        bool dummy;
+        c_bc[2 * q + 1] = mutate(make_lane(e < 0 ? 0 : e), key[q], del_base[q], dummy);
+        c_imd[2 * q + 1] = ins_minus_del_of(e < 0 ? 0 : e);
+        present |= (e >= 0 ? 1u : 0u) << (2 * q + 1);
+    }
+    pick_best(c_bc, c_rs, c_imd, present, 1, res);
+    if (!valid) {
+        res.found = -1;
+        res.n_matches = 0;
+    }
+    return res;
+}
+
 __global__ __launch_bounds__(256) void k_bc_pick_ed1t(const smi_bc_window *__restrict__ win, size_t n, int five_prime,
                                                       const uint8_t *__restrict__ codes, smi_bc_result *__restrict__ out) {
     const bool fp = five_prime != 0;
     constexpr int OFFS[5] = {0, -1, 1, -2, 2};
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const smi_bc_window my = win[i];
-        const bool valid = my.flags & SMI_WIN_VALID;
-        smi_bc_result res;
-        uint32_t c_bc[10], c_rs[10];
-        int c_imd[10];
-        uint32_t present = 0;
+        uint32_t key[5], db[5], code[5];
 #pragma unroll
         for (int q = 0; q < 5; q++) {
             const OffsetKey k = make_key(my.bases, my.nmask, OFFS[q], fp);
-            const uint32_t code = codes[5 * i + q];
-            c_rs[2 * q] = c_rs[2 * q + 1] = k.key;
-            c_bc[2 * q] = k.key;
-            c_imd[2 * q] = 0;
-            present |= (code >> 7) << (2 * q);
-            const int e = (int)(code & 0x7Fu) - 1;
-            bool dummy;
-            c_bc[2 * q + 1] = mutate(make_lane(e < 0 ? 0 : e), k.key, k.del_base, dummy);
-            c_imd[2 * q + 1] = ins_minus_del_of(e < 0 ? 0 : e);
-            present |= (e >= 0 ? 1u : 0u) << (2 * q + 1);
+            key[q] = k.key;
+            db[q] = k.del_base;
+            code[q] = codes[5 * i + q];
         }
-        pick_best(c_bc, c_rs, c_imd, present, 1, res);
-        if (!valid) {
-            res.found = -1;
-            res.n_matches = 0;
-        }
-        out[i] = res;
+        out[i] = bc1_pick(key, db, code, my.flags & SMI_WIN_VALID);
     }
+}
+
+// K-BC1 from the neighbourhood table in ONE kernel (the shipped table path; SMI_BC1_TWO_KERNELS=1 keeps the pair above as its cross-check).
+// One wavefront owns 64 consecutive reads from the window load to the store of the record; the four waves of a block are independent (no
+// block barrier, wave_sync() between the phases):
+//   1 (lane = read)            one 16-byte load of the window, the five keys, the five filter words (each offset indexed on its own: a window
+//                              with an N has an unrelated key whose word lies in another line) -> a 5-bit mask `pass`; keys and del_base go
+//                              to the wave's LDS for phases 2 and 3 (held in registers across phase 2 they cost the eighth wave of a SIMD)
+//   2 (lane = a quarter of a (read, offset) pair)  the pairs that passed are numbered by a prefix sum in the reference's order (read, then
+//                              offsets 0, -1, 1, -2, 2) and looked up 64 to a round (smi_wave.h), so the bucket branch -- which with a lane per
+//                              pair ran for the whole wave with ~ 20 of 64 lanes live -- runs with full waves: ~ 102 pairs per wave on the
+//                              bench's reads = two rounds.  A round is four steps of 16 pairs, four lanes to a bucket (see there).  The byte of a
+//                              pair goes to its owner's place in LDS; a pair that did not pass keeps byte 0
+//   3 (lane = read)            the five bytes, mutate / pick_best on the keys of phase 1, the record
+// LDS per wave: 64 slots (256 B) + 5 x 64 keys (1,280 B) + 64 packed del_base words (256 B) + 64 x 8 code bytes (512 B) = 2,304 B.
+constexpr int kBc1wWaves = 4;
+__global__ __launch_bounds__(64 * kBc1wWaves) void k_bc_match_ed1w(const smi_bc_window *__restrict__ win, size_t n, int five_prime, Pyramid P,
+                                                                  smi_bc_result *__restrict__ out) {
+    __shared__ uint32_t s_slot[kBc1wWaves][64];
+    __shared__ uint32_t s_key[kBc1wWaves][5 * 64];
+    __shared__ uint32_t s_db[kBc1wWaves][64];
+    __shared__ uint2 s_code[kBc1wWaves][64];
+    const bool fp = five_prime != 0;
+    constexpr int OFFS[5] = {0, -1, 1, -2, 2};
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t i = (blockIdx.x * (size_t)kBc1wWaves + wv) * 64 + lane;
+    uint32_t *slots = s_slot[wv], *keys = s_key[wv], *dbs = s_db[wv];
+    uint8_t *codes = reinterpret_cast<uint8_t *>(s_code[wv]);
+
+    // phase 1.  A lane behind the batch's end holds an empty record: its key lies inside every filter like any other, nothing passes.
+    smi_bc_window my;
+    my.bases = 0, my.nmask = 0, my.flags = 0;
+    if (i < n) my = load_window16(win + i);
+    const bool valid = my.flags & SMI_WIN_VALID;
+    uint32_t key[5], db[5], wi[5], word[5], wbit[5];
+    bool usable[5];
+#pragma unroll
+    for (int q = 0; q < 5; q++) {
+        const OffsetKey k = make_key(my.bases, my.nmask, OFFS[q], fp);
+        key[q] = k.key, db[q] = k.del_base, usable[q] = k.usable;
+        wi[q] = bc1_filter_index(P, k.key, OFFS[q], fp, wbit[q]);
+    }
+    // The five loads of a lane go out back to back, behind all five indices (the empty asm holds them together): they ask for one 128-byte line where
+    // the read is valid, and issued each behind its own key they found it gone from the L1 again (64 lines per instruction, 32 waves per CU).
+    asm volatile("" : "+v"(wi[0]), "+v"(wi[1]), "+v"(wi[2]), "+v"(wi[3]), "+v"(wi[4]));
+    const uint32_t *__restrict__ filter = bc1_filter_table(P);
+#pragma unroll
+    for (int q = 0; q < 5; q++) word[q] = filter[wi[q]];
+    uint32_t db_packed = 0;
+#pragma unroll
+    for (int q = 0; q < 5; q++) {
+        keys[q * 64 + lane] = key[q];
+        db_packed |= db[q] << (2 * q);
+    }
+    dbs[lane] = db_packed;
+    s_code[wv][lane] = make_uint2(0u, 0u);
+    uint32_t pass = 0;
+#pragma unroll
+    for (int q = 0; q < 5; q++) pass |= (valid && usable[q] && ((word[q] >> wbit[q]) & 1u)) ? 1u << q : 0u;
+
+    // phase 2
+    const int cnt = __popc(pass);
+    int total;
+    const int off = wave_exscan(cnt, lane, total);
+    wave_sync();  // keys, del_base and the zeroed bytes are in LDS
+    const int sub = lane & 3, quad = lane >> 2;
+    for (int base = 0; base < total; base += 64) {
+        queue_push<1>(slots, lane, off, cnt, base, [&](int) { return (uint64_t)pass; }, [](int, int bit) { return bit; });
+        wave_sync();
+        // Four lanes to a bucket, 16 bytes (two slots) each: step t of a round looks up its pairs 16 t .. 16 t + 15, so one load instruction asks for
+        // 16 whole buckets.  With a lane to a bucket (64 bytes in four loads, each instruction 64 lanes in 64 different lines and pages) the kernel
+        // took 1.18 ms, with such rounds of 32 pairs 0.60 and of 16 pairs 0.73: NOTES R6.35.  The four loads of a round go out before the first is read.
+        uint32_t K[4], dbq[4], at[4], idx[4];
+        uint4 e[4];
+        bool on[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int p = 16 * t + quad;
+            on[t] = base + p < total;
+            const uint32_t s = on[t] ? slots[p] : 0u;
+            const uint32_t owner = s & 0xFFu, q = s >> 8;
+            at[t] = owner * 8u + q;
+            K[t] = keys[q * 64u + owner];
+            dbq[t] = (dbs[owner] >> (2u * q)) & 3u;
+            idx[t] = nt_slot(K[t], P.nt_cap);
+            e[t] = make_uint4(0u, 0u, 0u, 0u);
+            if (on[t]) e[t] = *reinterpret_cast<const uint4 *>(P.nt + idx[t] + 2 * sub);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            uint32_t best = 255u, exact = 0u;
+            const uint32_t k_lo = K[t] << 8, k_hi = (K[t] >> 24) | 0x100u;
+            bool walk = on[t];
+            for (;;) {
+                bc1_slot(e[t].x, e[t].y, K[t], k_lo, k_hi, dbq[t], best, exact);
+                bc1_slot(e[t].z, e[t].w, K[t], k_lo, k_hi, dbq[t], best, exact);
+                // the bucket has a free slot exactly when its last slot (the fourth lane's second) is free: quad_perm [3, 3, 3, 3]
+                const uint32_t last_hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)e[t].w, 0xFF, 0xf, 0xf, false);
+                walk = walk && last_hi != 0u;
+                if (!walk) break;  // (whole quads leave together)
+                idx[t] = idx[t] + 8 == P.nt_cap ? 0u : idx[t] + 8;
+                e[t] = *reinterpret_cast<const uint4 *>(P.nt + idx[t] + 2 * sub);
+            }
+            // over the quad: the smallest index, any exact match (quad_perm [1, 0, 3, 2] and [2, 3, 0, 1])
+            uint32_t v = (exact << 8) | (255u - best);  // larger = better in both bytes
+            uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);
+            v = ((v | o) & 0x8000u) | max(v & 0xFFu, o & 0xFFu);
+            o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false);
+            v = ((v | o) & 0x8000u) | max(v & 0xFFu, o & 0xFFu);
+            best = 255u - (v & 0xFFu);
+            if (on[t] && sub == 0) codes[at[t]] = (uint8_t)((v >> 8) | (best != 255u ? best + 1u : 0u));
+        }
+        wave_sync();  // the next round writes the slots again; after the last one the owners read their bytes
+    }
+
+    // phase 3
+    const uint2 c8 = s_code[wv][lane];
+    uint32_t code[5];
+#pragma unroll
+    for (int q = 0; q < 5; q++) code[q] = q < 4 ? (c8.x >> (8 * q)) & 0xFFu : c8.y & 0xFFu;
+    // (keys and del_base come back from LDS: held in registers across phase 2 they cost the eighth wave of a SIMD)
+    const uint32_t db_mine = dbs[lane];
+#pragma unroll
+    for (int q = 0; q < 5; q++) key[q] = keys[q * 64 + lane], db[q] = (db_mine >> (2 * q)) & 3u;
+    const smi_bc_result res = bc1_pick(key, db, code, valid);
+    if (i < n) out[i] = res;
 }
 
 int launch_bc_match(smi_ctx *ctx, const smi_bc_window *d_win, size_t n, int max_ed, int five_prime,
@@ -1414,7 +1583,10 @@ int launch_bc_match(smi_ctx *ctx, const smi_bc_window *d_win, size_t n, int max_
     Pyramid P = pyramid_of(ctx);
     const size_t n_waves = (n + 63) / 64;
     const unsigned grid = (unsigned)((n_waves + 3) / 4);  // one batch of 64 reads per wave: measured 3 % faster than a capped grid
-    if (max_ed != 0 && P.nt && ctx->bc_codes_bytes < 5 * n) {  // one byte per (read, offset) between the two kernels of the table path
+    // SMI_BC1_TWO_KERNELS (read per launch): the table path as the pair k_bc_codes_ed1t + k_bc_pick_ed1t with its byte per (read, offset)
+    // between them -- cross-checks and same-session comparisons; the one-kernel path allocates no such buffer
+    const bool two_kernels = max_ed != 0 && P.nt && std::getenv("SMI_BC1_TWO_KERNELS");
+    if (two_kernels && ctx->bc_codes_bytes < 5 * n) {
         SMI_HIP(hipStreamSynchronize(s));
         if (ctx->bc_codes) SMI_HIP(hipFree(ctx->bc_codes));
         ctx->bc_codes = nullptr;
@@ -1425,12 +1597,13 @@ int launch_bc_match(smi_ctx *ctx, const smi_bc_window *d_win, size_t n, int max_
     if (int rc = time_begin(ctx, SMI_K_BC_MATCH, s)) return rc;
     if (max_ed == 0)
         hipLaunchKernelGGL(k_bc_match_ed1<0>, dim3(grid), dim3(256), 0, s, d_win, n, five_prime, P, d_out);
-    else if (P.nt) {
+    else if (two_kernels) {
         hipLaunchKernelGGL(k_bc_codes_ed1t, dim3((unsigned)std::min<size_t>((5 * n + 255) / 256, 256 * 256)), dim3(256), 0, s, d_win, n, five_prime, P,
                            ctx->bc_codes);
         hipLaunchKernelGGL(k_bc_pick_ed1t, dim3((unsigned)std::min<size_t>((n + 255) / 256, 256 * 64)), dim3(256), 0, s, d_win, n, five_prime,
                            ctx->bc_codes, d_out);
-    }
+    } else if (P.nt)
+        hipLaunchKernelGGL(k_bc_match_ed1w, dim3((unsigned)((n_waves + kBc1wWaves - 1) / kBc1wWaves)), dim3(64 * kBc1wWaves), 0, s, d_win, n, five_prime, P, d_out);
     else if (P.nb)
         hipLaunchKernelGGL(k_bc_match_ed1f, dim3(grid), dim3(256), 0, s, d_win, n, five_prime, P, d_out);
     else

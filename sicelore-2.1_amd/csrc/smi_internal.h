@@ -166,7 +166,7 @@ struct smi_ctx {
     size_t nt_alloc = 0;      // slots allocated
     bool nt_small_only = false;  // the 3-slot table did not fit this device: lists of that size keep the 1.6-slot one (no retry per load)
     uint32_t nt_cap = 0;      // slots in use by the set that is loaded now (0: no table)
-    uint8_t *bc_codes = nullptr;  // K-BC1, table path: one byte per (read, offset) between its two kernels (grow-only, private to a context or lane)
+    uint8_t *bc_codes = nullptr;  // K-BC1, table path under SMI_BC1_TWO_KERNELS only: one byte per (read, offset) between the two kernels (grow-only, private to a context or lane)
     size_t bc_codes_bytes = 0;
     uint32_t *fine = nullptr;
     uint32_t *rank = nullptr;

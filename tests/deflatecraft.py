@@ -348,11 +348,12 @@ class Case:
     """one file of the catalogue.  text: what it must inflate to (None: it must be refused); raw: its bare DEFLATE stream when it is one
     member (for zlib.decompress(raw, -15)); n_members where the case fixes it; device_refuses: legal, but more than K-INFLATE takes (the
     host decoder reads it); room: for an illegal file, an output capacity that is more than the text in front of what makes it illegal, so
-    that a decoder given that much is not stopped by the capacity first; big: the file is of about 1 MB or more"""
+    that a decoder given that much is not stopped by the capacity first; big: the file is of about 1 MB or more; blocks: the writer's
+    blocks `raw` was made of, where the case kept them (a reader's view of the stream is held against them)"""
 
-    def __init__(self, name, file, text, raw=None, n_members=None, device_refuses=False, big=False, room=4096):
+    def __init__(self, name, file, text, raw=None, n_members=None, device_refuses=False, big=False, room=4096, blocks=None):
         self.name, self.file, self.text, self.raw, self.n_members, self.device_refuses, self.big = name, file, text, raw, n_members, device_refuses, big
-        self.room = room
+        self.room, self.blocks = room, blocks
 
     def __repr__(self):
         return f"Case({self.name})"
@@ -360,7 +361,7 @@ class Case:
 
 def _single(name, blocks, **header):
     raw, text = deflate(blocks)
-    return Case(name, gzip_member(raw, text, **header), text, raw=raw, n_members=1)
+    return Case(name, gzip_member(raw, text, **header), text, raw=raw, n_members=1, blocks=list(blocks))
 
 
 def _literals(rng, n, alphabet=None):
@@ -561,7 +562,8 @@ def soup_cases():
 
 def headers_cases():
     toks = soup_tokens(77, 2000)
-    raw, text = deflate([dynamic_for(toks)])
+    blocks = [dynamic_for(toks)]
+    raw, text = deflate(blocks)
     pattern = b"\x1f\x8b\x08\x01\x02"
     extras = [b"", b"extra", (pattern * 13107)[:65535]]
     out, k = [], 0
@@ -574,7 +576,8 @@ def headers_cases():
             kw["name"] = b"reads\x1f\x8b\x08_0001.fastq"
         if bits & 16:
             kw["comment"] = b"a comment \x1f\x8b and more"
-        out.append(Case(f"headers/flg{bits:02x}" + (f"_x{len(kw['extra'])}" if bits & 4 else ""), gzip_member(raw, text, **kw), text, raw=raw, n_members=1))
+        out.append(Case(f"headers/flg{bits:02x}" + (f"_x{len(kw['extra'])}" if bits & 4 else ""), gzip_member(raw, text, **kw), text, raw=raw, n_members=1,
+                        blocks=blocks))
     return out
 
 

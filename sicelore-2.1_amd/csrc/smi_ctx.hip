@@ -150,6 +150,7 @@ int smi_ctx_create(int device, smi_ctx **out) {
     SMI_TRY(hipMalloc((void **)&ctx->rank, kRankEntries * 4));
     SMI_TRY(hipMalloc((void **)&ctx->block_counts, kRankEntries * 4));
     SMI_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+    SMI_TRY(hipMalloc((void **)&ctx->claim_ring, (size_t)kClaimSlots * kClaimWords * 4));
     for (int k = 0; k < SMI_K_COUNT; k++) {
         SMI_TRY(hipEventCreate(&ctx->kev[k][0]));
         SMI_TRY(hipEventCreate(&ctx->kev[k][1]));
@@ -178,6 +179,7 @@ int smi_ctx_create_lane(smi_ctx *owner, smi_ctx **out) {
     ctx->device = owner->device;
     ctx->set_owner = owner;
     hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&ctx->claim_ring, (size_t)kClaimSlots * kClaimWords * 4);
     for (int k = 0; k < SMI_K_COUNT && e == hipSuccess; k++) {
         e = hipEventCreate(&ctx->kev[k][0]);
         if (e == hipSuccess) e = hipEventCreate(&ctx->kev[k][1]);
@@ -247,6 +249,9 @@ int smi_ctx_destroy(smi_ctx *ctx) {
         (void)hipFree(ctx->block_counts);
     }
     (void)hipFree(ctx->bc_codes);
+    (void)hipFree(ctx->claim_ring);
+    for (hipEvent_t ev : ctx->claim_done)
+        if (ev) (void)hipEventDestroy(ev);
     (void)hipFree(ctx->stage_in);
     (void)hipFree(ctx->scan_tmp);
     (void)hipFree(ctx->arena);
@@ -969,6 +974,38 @@ int worker_scan_config(const smi_ctx *ctx, int pass, int five_prime, int dont_se
 int worker_chimera_config(const smi_ctx *ctx, int five_prime, smi_chimera_config *cc) {
     if (int rc = smi_chimera_config_from_knobs(ctx->knobs_set ? &ctx->knobs : nullptr, five_prime, cc)) return rc;
     if (ctx->polya_window) cc->window_polya = ctx->polya_window;  // (the splitter keeps away from the read ends by windowSearchForPolyA + 70)
+    return SMI_OK;
+}
+}  // namespace smi
+
+namespace smi {
+int claim_counters(smi_ctx *ctx, hipStream_t s, uint32_t **out, uint32_t *slot) {
+    static_assert(kClaimSlots == sizeof(smi_ctx::claim_done) / sizeof(hipEvent_t), "one event per slot");
+    const uint32_t k = ctx->claim_next.fetch_add(1u) % kClaimSlots;
+    if (!ctx->claim_done[k])
+        SMI_HIP(hipEventCreateWithFlags(&ctx->claim_done[k], hipEventDisableTiming));
+    else
+        SMI_HIP(hipStreamWaitEvent(s, ctx->claim_done[k], 0));
+    uint32_t *heads = ctx->claim_ring + (size_t)k * kClaimWords;
+    SMI_HIP(hipMemsetAsync(heads, 0, (size_t)kClaimWords * 4, s));
+    *out = heads;
+    *slot = k;
+    return SMI_OK;
+}
+
+int claim_release(smi_ctx *ctx, uint32_t slot, hipStream_t s) {
+    SMI_HIP(hipEventRecord(ctx->claim_done[slot], s));
+    return SMI_OK;
+}
+
+int resident_blocks(smi_ctx *ctx, const void *kernel, int block, size_t lds, int *cache, unsigned *out) {
+    if (!ctx->n_cus) SMI_HIP(hipDeviceGetAttribute(&ctx->n_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    if (!*cache) {
+        int per_cu = 0;
+        SMI_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds));
+        *cache = std::max(per_cu, 1);
+    }
+    *out = (unsigned)*cache * (unsigned)ctx->n_cus;
     return SMI_OK;
 }
 }  // namespace smi

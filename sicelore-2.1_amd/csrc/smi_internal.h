@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -166,6 +167,13 @@ struct smi_ctx {
     size_t nt_alloc = 0;      // slots allocated
     bool nt_small_only = false;  // the 3-slot table did not fit this device: lists of that size keep the 1.6-slot one (no retry per load)
     uint32_t nt_cap = 0;      // slots in use by the set that is loaded now (0: no table)
+    // K-SCAN: the counters its waves take work from (claim_counters() in smi_ctx.hip).  A ring, one slot per launch, zeroed on the launch's
+    // stream: launches of one context or lane in flight on different streams never share a slot, and a slot needs no particular value left in it.
+    uint32_t *claim_ring = nullptr;
+    std::atomic<uint32_t> claim_next{0};
+    hipEvent_t claim_done[64] = {};  // per slot (kClaimSlots): recorded behind the launch that used it; the slot's next user waits for it on its own stream
+    int scan_resident[8] = {};  // blocks of each k_scan instantiation a CU holds at once (0: not asked yet)
+    int n_cus = 0;
     uint8_t *bc_codes = nullptr;  // K-BC1, table path under SMI_BC1_TWO_KERNELS only: one byte per (read, offset) between the two kernels (grow-only, private to a context or lane)
     size_t bc_codes_bytes = 0;
     uint32_t *fine = nullptr;
@@ -241,6 +249,15 @@ int worker_chimera_config(const smi_ctx *ctx, int five_prime, smi_chimera_config
 // ClusterOne_MyClustering of one group above 100 reads on the matrix in HBM (smi_cluster.hip)
 int umi_cluster_own_device(smi_ctx *ctx, const uint8_t *d_mat, int n, const float *d_qv, const smi_umi_cluster_config &cfg, smi_umi_assignment *d_out,
                            uint8_t *d_skipped, hipStream_t s, int ld = 0);  // ld: row stride of d_mat (0: n)
+// the next slot of the context's ring of work counters (kClaimWords words: the heads of smi_wave.h's WaveClaim, a 128-byte line each), zeroed on s;
+// the kernel launched behind it on s adds to them, and claim_release() behind that launch records the slot's event.  A slot is handed out again
+// kClaimSlots launches later: its new user first waits, on s, for the event of the launch that used it last, so two launches never share a slot
+// whatever streams they run on (on one stream, or with fewer than kClaimSlots launches in flight, the event has long been reached)
+constexpr uint32_t kClaimSlots = 64, kClaimStride = 32, kClaimWords = 16 * kClaimStride;
+int claim_counters(smi_ctx *ctx, hipStream_t s, uint32_t **out, uint32_t *slot);
+int claim_release(smi_ctx *ctx, uint32_t slot, hipStream_t s);
+// blocks of `kernel` (block size, dynamic LDS) that the device holds at once, asked once per context (*cache, 0 = not asked yet)
+int resident_blocks(smi_ctx *ctx, const void *kernel, int block, size_t lds, int *cache, unsigned *out);
 int time_begin(smi_ctx *ctx, int kid, hipStream_t s);
 int time_end(smi_ctx *ctx, int kid, hipStream_t s);
 Pyramid pyramid_of(const smi_ctx *ctx);

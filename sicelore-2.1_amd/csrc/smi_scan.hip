@@ -55,6 +55,16 @@ constexpr int scan_waves() {
     return SHIP ? (AD == 10 ? SMI_SCAN_WAVES : 3) : (AD == 10 ? SMI_SCAN_GENERIC_WAVES : 2);
 }
 
+// Which instantiations take their tiles by the wave from the launch's counters (below: "How the tiles of 64 ends reach the waves").  The generic
+// 22-mer 3' kernel keeps the loop by the block: the claim took its scratch from 16 to 20 bytes per lane (162 registers at three waves).
+template <int AD, bool FP, bool SHIP>
+constexpr bool scan_claims() {
+#if defined(SMI_SCAN_BLOCK_TILES) && SMI_SCAN_BLOCK_TILES
+    return false;
+#else
+    return !(AD == 22 && !FP && !SHIP);
+#endif
+}
 // SMI_SCAN_ABLATE's switches are compiled into measurement builds only.  (They used to be run-time tests of a field that is 0 in the shipped
 // library; two more of them -- uniform, never taken -- made the 22-mer kernel lose the records of reads with no side chosen: a kernel at 128
 // VGPRs with spilled SGPRs is not the place for code that does nothing.)
@@ -561,6 +571,21 @@ struct Entry {
 #ifndef SMI_SCAN_QUEUE_SEARCH
 #define SMI_SCAN_QUEUE_SEARCH 0
 #endif
+// How the tiles of 64 ends reach the waves.  Shipped: as many blocks as are resident at once, and every wave takes its next tile from a counter
+// (launch_scan "Grid"), so a wave slot is never held for the slowest of a block's four waves and the launch ends within one tile.  Variant switches,
+// for same-session comparisons -- same results; there is no run-time switch:
+//   SMI_SCAN_BLOCK_TILES   (make VARIANT=blocktiles EXTRA=-DSMI_SCAN_BLOCK_TILES=1) a block strides over tiles of 256 ends on a grid of 64 blocks per CU
+//   SMI_SCAN_CLAIM_LATE    the next tile is asked for at the end of a tile, its round trip on the wave's critical path
+//   SMI_SCAN_OVERSUB=k     k times the resident blocks: the hardware hands out the surplus blocks as the first ones run out of tiles
+#ifndef SMI_SCAN_BLOCK_TILES
+#define SMI_SCAN_BLOCK_TILES 0
+#endif
+#ifndef SMI_SCAN_CLAIM_LATE
+#define SMI_SCAN_CLAIM_LATE 0
+#endif
+#ifndef SMI_SCAN_OVERSUB
+#define SMI_SCAN_OVERSUB 1
+#endif
 
 // wave_exscan and queue_push: smi_wave.h (K-BC1 numbers its bucket look-ups the same way)
 
@@ -578,7 +603,7 @@ template <int AD, bool FP, bool SHIP>
 __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const uint32_t *__restrict__ ends, const int32_t *__restrict__ read_len,
                                                  const uint8_t *__restrict__ qtail, const uint32_t *__restrict__ qsum,
                                                  size_t n_reads, ScanParams P, smi_scan_result *__restrict__ out,
-                                                 smi_bc_window *__restrict__ windows) {
+                                                 smi_bc_window *__restrict__ windows, uint32_t *__restrict__ claim) {
     // Every aligned candidate passed gate64 on the slice that is aligned (>= 2 matching 4-mers = >= 5 matching bases on the main diagonal),
     // which bounds how far an optimal path can leave the diagonal (smi_nw.h "Band"): 3 cells for the 10-mer, 12 for the 22-mer, 7 for the
     // TSO.  The kernels of the shipped adapters fill the band only; the generic kernels fill the whole matrix, and the parity tests run both.
@@ -590,8 +615,17 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
     uint32_t *ent = coff + kBlock;                                                    // [kBlock][5]
     const int tid = threadIdx.x;
     const size_t n_ends = 2 * n_reads;
-    for (size_t e0 = (size_t)blockIdx.x * kBlock; e0 < n_ends; e0 += (size_t)gridDim.x * kBlock) {
-        const size_t e = e0 + tid;
+    constexpr bool kClaim = scan_claims<AD, FP, SHIP>();
+    WaveClaim wc = wave_claim_init(claim, (uint32_t)((n_ends + 63) >> 6));
+    uint32_t tile = 0;
+    size_t e0 = (size_t)blockIdx.x * kBlock;
+    if constexpr (kClaim) tile = wc.take(wc.ask(tid & 63), tid & 63);
+    for (;;) {
+        if (kClaim ? tile >= wc.n : e0 >= n_ends) break;  // wave-uniform / block-uniform
+        const size_t e = kClaim ? (size_t)tile * 64 + (tid & 63) : e0 + tid;
+        // the next tile is asked for now and read at the end of this one: the atomic's round trip runs beside the plane loads
+        uint32_t next_tile = 0;
+        if constexpr (kClaim && !SMI_SCAN_CLAIM_LATE) next_tile = wc.ask(tid & 63);
         const bool active = e < n_ends;
         const size_t read = e >> 1;
         const int side = (int)(e & 1);  // 0 = head (forward scan), 1 = reverse-complemented tail
@@ -602,6 +636,8 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
             for (int w = 0; w < kLdsWords; w++)
                 planes[(c * kLdsWords + w) * kBlock + tid] = active ? ends[(size_t)(c * kPlaneWords + w) * n_ends + e] : 0u;
         const int len = active ? read_len[read] : 0;
+        if constexpr (kClaim && !SMI_SCAN_CLAIM_LATE)
+            next_tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)next_tile);  // an SGPR from here on: the kernel has no VGPR to spare
         const bool long_enough = len >= P.min_read_length;  // testReadLength L131-137
         int pb = 0, pe = 0;
         bool has_t = false;
@@ -1222,6 +1258,11 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
             if (windows) windows[read] = win;
         }
         wave_sync();  // the next iteration overwrites this wave's columns
+        if constexpr (kClaim) {
+            if constexpr (SMI_SCAN_CLAIM_LATE) next_tile = wc.ask(tid & 63);
+            tile = wc.take(next_tile, tid & 63);
+        } else
+            e0 += (size_t)gridDim.x * kBlock;
     }
 }
 
@@ -1285,30 +1326,45 @@ int launch_scan(smi_ctx *ctx, const uint32_t *d_ends, const int32_t *d_len, cons
     }
 #endif
     const size_t n_ends = 2 * n;
-    const unsigned grid = (unsigned)std::min<size_t>((n_ends + kBlock - 1) / kBlock, 256 * 64);  // measured: x4 8.2, x16 7.5, x64 7.2, uncapped 7.7 ms
-    if (int rc = time_begin(ctx, SMI_K_SCAN, s)) return rc;
-    // the dynamic LDS size (40 KiB) is below the 64 KiB that needs an opt-in
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), scan_lds_bytes(), s, d_ends, d_len, d_qtail, d_qsum, n, P, d_out,
-                           d_win);
-    };
     bool ship = (ad == 10 || ad == 22) && P.finder_bits;
     for (int i = 0; ship && i < ad; i++) ship = P.a4(i) == (ad == 10 ? shipped_a4<10>(i) : shipped_a4<22>(i));
     // (the shipped kernels carry the TSO, its window and its limits as constants, and the isolated-candidate pre-filter is derived for them)
     ship = ship && P.tso_window == 90 && P.tso_max_mm == 5 && P.tso_min_consec == 8 && P.tso_min_two == 12;
     for (int i = 0; ship && i < 16; i++) ship = P.t4(i) == tso4(i);
     if (std::getenv("SMI_SCAN_GENERIC")) ship = false;  // tests run both builds against the oracle
+    // the dynamic LDS size (40 KiB) is below the 64 KiB that needs an opt-in
+    auto launch = [&](auto kernel, int inst, bool claims) -> int {
+        const size_t n_blocks = (n_ends + kBlock - 1) / kBlock;
+        uint32_t *claim = nullptr;
+        uint32_t slot = 0;
+        unsigned grid = (unsigned)std::min<size_t>(n_blocks, 256 * 64);  // tiles by the block: 64 blocks per CU
+        if (claims) {
+            // Grid: the blocks the device holds at once (occupancy of this instantiation x CUs), never more than there are tiles of 256 ends.  Every
+            // wave takes its tiles of 64 ends from the launch's counters (smi_wave.h WaveClaim), which a 2-KiB fill on the launch's stream zeroes.
+            // Measured on the bench's 10 M reads (profiles/wave_sched/compare.json): by the block on 64 blocks per CU 1.91 ms, this 1.86, on twice the
+            // resident blocks 1.875, with the claim at the end of a tile 1.896, with one counter for the whole launch 3.79.
+            unsigned resident = 0;
+            if (int rc = resident_blocks(ctx, reinterpret_cast<const void *>(kernel), kBlock, scan_lds_bytes(), &ctx->scan_resident[inst], &resident)) return rc;
+            grid = (unsigned)std::min<size_t>(n_blocks, (size_t)resident * SMI_SCAN_OVERSUB);
+            if (int rc = claim_counters(ctx, s, &claim, &slot)) return rc;
+        }
+        if (int rc = time_begin(ctx, SMI_K_SCAN, s)) return rc;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), scan_lds_bytes(), s, d_ends, d_len, d_qtail, d_qsum, n, P, d_out, d_win, claim);
+        return claims ? claim_release(ctx, slot, s) : SMI_OK;
+    };
+    int rc;
     if (ad == 10) {
         if (cfg->five_prime)
-            ship ? launch(k_scan<10, true, true>) : launch(k_scan<10, true, false>);
+            rc = ship ? launch(k_scan<10, true, true>, 0, scan_claims<10, true, true>()) : launch(k_scan<10, true, false>, 1, scan_claims<10, true, false>());
         else
-            ship ? launch(k_scan<10, false, true>) : launch(k_scan<10, false, false>);
+            rc = ship ? launch(k_scan<10, false, true>, 2, scan_claims<10, false, true>()) : launch(k_scan<10, false, false>, 3, scan_claims<10, false, false>());
     } else {
         if (cfg->five_prime)
-            ship ? launch(k_scan<22, true, true>) : launch(k_scan<22, true, false>);
+            rc = ship ? launch(k_scan<22, true, true>, 4, scan_claims<22, true, true>()) : launch(k_scan<22, true, false>, 5, scan_claims<22, true, false>());
         else
-            ship ? launch(k_scan<22, false, true>) : launch(k_scan<22, false, false>);
+            rc = ship ? launch(k_scan<22, false, true>, 6, scan_claims<22, false, true>()) : launch(k_scan<22, false, false>, 7, scan_claims<22, false, false>());
     }
+    if (rc) return rc;
     SMI_HIP(hipGetLastError());
     if (int rc = time_end(ctx, SMI_K_SCAN, s)) return rc;
     return SMI_OK;

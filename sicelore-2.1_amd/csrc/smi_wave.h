@@ -12,6 +12,47 @@
 
 namespace smi {
 
+// ---- work units taken by the wave (K-SCAN: tiles of 64 read ends) ---------------------------------------------------------------------------------
+// The units 0 .. n - 1 of a launch are cut into kClaimShards consecutive ranges with a head counter each (heads[s * kClaimStride], set to 0 on the
+// launch's stream: claim_counters() in smi_ctx.hip).  A wave takes units from the range of its block's shard with one returning atomicAdd by lane 0
+// and, when that range has run out, from the next range that has units left (one load of all heads by the first lanes finds it).  One head for the
+// whole launch was measured first: a device-scope atomic on ONE word is served every ~ 12 ns, the device finishes a tile every 6 ns, and the
+// kernel ran at the atomic's rate (K-SCAN 1.90 -> 3.79 ms; K-BC1, whose claim loop was not kept, 0.59 -> 1.86 ms: NOTES R6.36).
+constexpr int kClaimShards = 16;
+struct WaveClaim {
+    uint32_t *heads;
+    uint32_t n, per;  // units of the launch, units per shard (the last shards may hold fewer, or none)
+    uint32_t shard;   // the range this wave takes from now (wave-uniform)
+    __device__ __forceinline__ uint32_t len(uint32_t s) const { return s * per >= n ? 0u : min(per, n - s * per); }
+    // lane 0 asks for the next unit of the wave's shard; the answer is read by take()
+    __device__ __forceinline__ uint32_t ask(int lane) const {
+        uint32_t v = 0;
+        if (lane == 0) v = atomicAdd(heads + shard * kClaimStride, 1u);
+        return v;
+    }
+    // the unit an answer stands for, or n when no range has a unit left (every lane of the wave calls this; the result is wave-uniform)
+    __device__ __forceinline__ uint32_t take(uint32_t answer, int lane) {
+        uint32_t rel = (uint32_t)__builtin_amdgcn_readfirstlane((int)answer);
+        while (rel >= len(shard)) {
+            uint32_t head = 0xFFFFFFFFu;
+            if (lane < kClaimShards) head = __hip_atomic_load(heads + lane * kClaimStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint64_t open = __ballot(lane < kClaimShards && head < len((uint32_t)lane));
+            if (!open) return n;
+            // the first open range behind this one, cyclically
+            const uint64_t behind = open & ~((2ull << shard) - 1ull);
+            shard = (uint32_t)__builtin_ctzll(behind ? behind : open);
+            rel = (uint32_t)__builtin_amdgcn_readfirstlane((int)ask(lane));
+        }
+        return shard * per + rel;
+    }
+};
+__device__ __forceinline__ WaveClaim wave_claim_init(uint32_t *heads, uint32_t n_units) {
+    WaveClaim c;
+    c.heads = heads, c.n = n_units, c.per = (n_units + kClaimShards - 1) / kClaimShards;
+    c.shard = blockIdx.x % kClaimShards;
+    return c;
+}
+
 // wave-wide exclusive prefix sum of one int per lane; returns the wave total (wave-uniform) through `total`.  Called with all 64 lanes active.
 __device__ __forceinline__ int wave_exscan(int v, int lane, int &total) {
     int inc = v;

@@ -215,9 +215,61 @@ __device__ __forceinline__ bool find_polyt(const uint32_t *planes, int tid, cons
 // (back: with T[e] and T[e - 1] set, ">= 3 T's in the last four" is "one of T[e-2], T[e-3]", ">= 4 in the last five" is "two of T[e-2 .. e-4]",
 // which implies it.)  For polya_len = 15 with the thresholds 12 and 10 the shipped fractions give; anything else takes the loop above.
 // The generic kernels keep the loop, so the parity suite (shipped against generic against the oracle) compares the two finders as well.
+//
+// Three-input forms (R6.37).  gfx950's v_bitop3_b32 computes any boolean function of three registers in one instruction: bit (a << 2 | b << 1 | c)
+// of its 8-bit immediate is the result for the inputs a, b, c.  The compiler picks it where an intermediate has one use, and not where a ^ b
+// feeds both the sum and the carry of a full adder (xor, and, xor, and_or: four instructions where two do), so the finder's front, the walk back's
+// mask and the smear of the isolated TSO candidates name it.  -DSMI_SCAN_LOGIC2=1 (make VARIANT=logic2 EXTRA=-DSMI_SCAN_LOGIC2=1) compiles the
+// two-input expressions those places had before -- same results, more instructions; there is no run-time switch.
+// (For counter runs of one place alone: -DSMI_SCAN_LOGIC2_FRONT=1 the finder's adders and entry mask, -DSMI_SCAN_LOGIC2_BACK=1 the walk back's mask,
+// -DSMI_SCAN_LOGIC2_SMEAR=1 the smear on two 64-bit words; SMI_SCAN_LOGIC2 sets all three.)
+#ifndef SMI_SCAN_LOGIC2
+#define SMI_SCAN_LOGIC2 0
+#endif
+#ifndef SMI_SCAN_LOGIC2_FRONT
+#define SMI_SCAN_LOGIC2_FRONT SMI_SCAN_LOGIC2
+#endif
+#ifndef SMI_SCAN_LOGIC2_BACK
+#define SMI_SCAN_LOGIC2_BACK SMI_SCAN_LOGIC2
+#endif
+#ifndef SMI_SCAN_LOGIC2_SMEAR
+#define SMI_SCAN_LOGIC2_SMEAR SMI_SCAN_LOGIC2
+#endif
+constexpr uint32_t bit3_ref(uint32_t imm, uint32_t a, uint32_t b, uint32_t c) {  // the truth table, bit by bit
+    uint32_t r = 0;
+    for (int i = 0; i < 32; i++) r |= ((imm >> ((((a >> i) & 1u) << 2) | (((b >> i) & 1u) << 1) | ((c >> i) & 1u))) & 1u) << i;
+    return r;
+}
+// the eight input combinations side by side in the low byte of a word: over (0xF0, 0xCC, 0xAA) a function's result byte is its immediate
+constexpr uint32_t kBit3A = 0xF0u, kBit3B = 0xCCu, kBit3C = 0xAAu;
+constexpr bool bit3_is(uint32_t imm, uint32_t expr_of_abc) { return (bit3_ref(imm, kBit3A, kBit3B, kBit3C) & 0xFFu) == (expr_of_abc & 0xFFu); }
+constexpr uint32_t kSum3 = 0x96u, kMaj3 = 0xE8u, kAnd3 = 0x80u, kOrAnd3 = 0xF8u, kAndOr3 = 0xE0u;
+static_assert(bit3_is(kSum3, kBit3A ^ kBit3B ^ kBit3C), "a ^ b ^ c: the sum of a full adder");
+static_assert(bit3_is(kMaj3, (kBit3A & kBit3B) | (kBit3C & (kBit3A ^ kBit3B))), "majority: the carry of a full adder");
+static_assert(bit3_is(kAnd3, kBit3A & kBit3B & kBit3C), "a & b & c");
+static_assert(bit3_is(kOrAnd3, kBit3A | (kBit3B & kBit3C)), "a | (b & c)");
+static_assert(bit3_is(kAndOr3, kBit3A & (kBit3B | kBit3C)), "a & (b | c)");
+static_assert(bit3_ref(kSum3, 0x0F0F3355u, 0x33CC5A5Au, 0x55AA0FF0u) == (0x0F0F3355u ^ 0x33CC5A5Au ^ 0x55AA0FF0u) &&
+                  bit3_ref(kMaj3, 0x0F0F3355u, 0x33CC5A5Au, 0x55AA0FF0u) ==
+                      ((0x0F0F3355u & 0x33CC5A5Au) | (0x55AA0FF0u & (0x0F0F3355u ^ 0x33CC5A5Au))),
+              "the reference evaluates every bit position alike");
+template <uint32_t IMM>
+__device__ __forceinline__ uint32_t bit3(uint32_t a, uint32_t b, uint32_t c) {
+    static_assert(IMM < 256u, "eight inputs, eight bits");
+    return __builtin_amdgcn_bitop3_b32(a, b, c, IMM);
+}
+template <uint32_t IMM>
+__device__ __forceinline__ uint64_t bit3_64(uint64_t a, uint64_t b, uint64_t c) {  // the same function on both halves of a 64-bit mask
+    return ((uint64_t)bit3<IMM>((uint32_t)(a >> 32), (uint32_t)(b >> 32), (uint32_t)(c >> 32)) << 32) | bit3<IMM>((uint32_t)a, (uint32_t)b, (uint32_t)c);
+}
 __device__ __forceinline__ void full_add(uint32_t a, uint32_t b, uint32_t c, uint32_t &sum, uint32_t &carry) {
+#if SMI_SCAN_LOGIC2_FRONT
     sum = a ^ b ^ c;
     carry = (a & b) | (c & (a ^ b));
+#else
+    sum = bit3<kSum3>(a, b, c);
+    carry = bit3<kMaj3>(a, b, c);
+#endif
 }
 // 64 bits from bit position p of a 192-bit mask kept in the lane's own three 64-bit slots of the candidate-mask area ([slot][lane]: the four
 // waves of a block run independently, so a lane may only touch the columns of its own wave); bits past the mask read as 0
@@ -275,16 +327,25 @@ __device__ __forceinline__ bool find_polyt_bits(const uint32_t *planes, uint64_t
             b[j] = __builtin_amdgcn_alignbit(c5[j][k + 1], c5[j][k], 5);
             c[j] = __builtin_amdgcn_alignbit(c5[j][k + 1], c5[j][k], 10);
         }
-        uint32_t r0, k0, t1, k1a, t2, k2a, r2, k2b;
+        uint32_t k0, t1, k1a, t2, k2a, r2, k2b;
+#if SMI_SCAN_LOGIC2_FRONT
+        uint32_t r0;
         full_add(c5[0][k], b[0], c[0], r0, k0);
+        (void)r0;
+#else
+        k0 = bit3<kMaj3>(c5[0][k], b[0], c[0]);  // the lowest plane of the sum is read by nobody: its carry alone
+#endif
         full_add(c5[1][k], b[1], c[1], t1, k1a);
         const uint32_t r1 = t1 ^ k0, k1b = t1 & k0;
         full_add(c5[2][k], b[2], c[2], t2, k2a);
         full_add(t2, k1a, k1b, r2, k2b);
         const uint32_t r3 = k2a | k2b;  // (the count is at most 15: the two carries never come together)
-        (void)r0;
         ge12[k] = r3 & r2;
+#if SMI_SCAN_LOGIC2_FRONT
         ge10[k] = r3 & (r2 | r1);
+#else
+        ge10[k] = bit3<kAndOr3>(r3, r2, r1);
+#endif
     }
     {
         const int top = __popc(tw[kFinderPosWords] & ((1u << ML) - 1u));  // position kFinderMaxWindow: T's in its fifteen bases
@@ -300,7 +361,12 @@ __device__ __forceinline__ bool find_polyt_bits(const uint32_t *planes, uint64_t
     for (int k = kFinderPosWords - 1; k >= 0; k--) {
         const int keep = P.window - 32 * k;  // positions below `window` (uniform)
         const uint32_t below = keep >= 32 ? 0xFFFFFFFFu : (keep <= 0 ? 0u : ((1u << keep) - 1u));
+#if SMI_SCAN_LOGIC2_FRONT
         const uint32_t entry = __builtin_amdgcn_alignbit(ge12[k + 1], ge12[k], 1) & tw[k] & (c5[2][k] | (c5[1][k] & c5[0][k])) & below;
+#else
+        // ">= 3 of 5" = c5[2] | (c5[1] & c5[0]) in one operation, the three conditions in another
+        const uint32_t entry = bit3<kAnd3>(__builtin_amdgcn_alignbit(ge12[k + 1], ge12[k], 1), tw[k], bit3<kOrAnd3>(c5[2][k], c5[1][k], c5[0][k])) & below;
+#endif
         gom[k] = __builtin_amdgcn_alignbit(ge10[k + 1], ge10[k], 1) & below;
         if (entry) first = 32 * k + __builtin_ctz(entry);
     }
@@ -374,7 +440,11 @@ __device__ __forceinline__ bool find_polyt_bits(const uint32_t *planes, uint64_t
     {
         // lambda$findpolyAT$3 L122-142: the last position <= endpos (and > 4) that passes; 4 when there is none
         const uint64_t l1 = wbits << 1, l2 = wbits << 2, l3 = wbits << 3, l4 = wbits << 4;
+#if SMI_SCAN_LOGIC2_BACK
         uint64_t back = wbits & l1 & ((l2 & l3) | (l4 & (l2 ^ l3)));
+#else
+        uint64_t back = bit3_64<kAnd3>(wbits, l1, bit3_64<kMaj3>(l2, l3, l4));  // two operations per word
+#endif
         back &= ((2ull << (endpos - wbase)) - 1ull) & (wbase ? ~15ull : ~31ull);
         if (back) {
             endpos = wbase + 63 - __builtin_clzll(back);
@@ -752,6 +822,7 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                     // pattern base instead of a 184-cell fill and a walk.  About a third of the TSO candidates go this way (the
                     // chance hits on the end that has no TSO, and behind the true site on the end that has one); the generic
                     // kernels align every candidate, and the parity suite runs both.
+#if SMI_SCAN_LOGIC2_SMEAR
                     auto shr128 = [](uint64_t &lo, uint64_t &hi, int k) {
                         lo = (lo >> k) | (hi << (64 - k));
                         hi >>= k;
@@ -772,6 +843,24 @@ __global__ __launch_bounds__(kBlock, (scan_waves<AD, SHIP>())) void k_scan(const
                         shi |= b;
                     }
                     const uint64_t iso0 = tm[0] & ~slo, iso1 = tm[1] & ~shi;
+#else
+                    // The 90 candidate bits on three 32-bit words (the third holds 26).  s = "a candidate 1 position further on"; each step ORs
+                    // two shifted copies into it (v_alignbit, v_alignbit, v_or3 per word), and the distances covered grow 1 -> 1..3 -> 1..9 ->
+                    // 1..26: {1..9} | {1..9} + 9 | {1..9} + 17.
+                    const uint32_t t0 = (uint32_t)tm[0], t1 = (uint32_t)(tm[0] >> 32), t2 = (uint32_t)tm[1];
+                    uint32_t s0 = __builtin_amdgcn_alignbit(t1, t0, 1), s1 = __builtin_amdgcn_alignbit(t2, t1, 1), s2 = t2 >> 1;
+                    auto widen = [&](int k1, int k2) {
+                        const uint32_t n0 = s0 | __builtin_amdgcn_alignbit(s1, s0, k1) | __builtin_amdgcn_alignbit(s1, s0, k2),
+                                       n1 = s1 | __builtin_amdgcn_alignbit(s2, s1, k1) | __builtin_amdgcn_alignbit(s2, s1, k2), n2 = s2 | (s2 >> k1) | (s2 >> k2);
+                        s0 = n0;
+                        s1 = n1;
+                        s2 = n2;
+                    };
+                    widen(1, 2);   // 1..3
+                    widen(3, 6);   // 1..9
+                    widen(9, 17);  // 1..26
+                    const uint64_t iso0 = tm[0] & ~(((uint64_t)s1 << 32) | s0), iso1 = tm[1] & ~(uint64_t)s2;
+#endif
                     // The pre-filter is there so that a wave's candidates fit fewer alignment rounds, and it drops isolated candidates only: when
                     // even without all of them the wave needs as many rounds of 64 as with them (in a quarter of the waves everything gated
                     // fits one round as it is), it is ~ 500 instructions for nothing, and the wave aligns every gated candidate as the generic

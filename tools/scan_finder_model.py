@@ -51,6 +51,69 @@ def masks_of(codes, window=150):
     return T, G, first
 
 
+M32 = (1 << 32) - 1
+SUM3, MAJ3, AND3, ORAND3, ANDOR3 = 0x96, 0xE8, 0x80, 0xF8, 0xE0   # smi_scan.hip kSum3 .. kAndOr3
+
+
+def bit3(imm, a, b, c):
+    """v_bitop3_b32 on 32-bit words: bit (a << 2 | b << 1 | c) of the immediate, position by position"""
+    r = 0
+    for idx in range(8):
+        if (imm >> idx) & 1:
+            r |= (a if idx & 4 else ~a) & (b if idx & 2 else ~b) & (c if idx & 1 else ~c)
+    return r & M32
+
+
+def alignbit(hi, lo, s):
+    return (((hi << 32) | lo) >> s) & M32
+
+
+def front_words(T, window=150):
+    """the finder's branch-free front operation for operation (find_polyt_bits up to `first`: the bit-sliced five-counts and fifteen-counts on 32-bit
+    words in their three-input forms, the entry mask, the probe mask) -> (G, first); masks_of says the same with a loop over the positions"""
+    tw = [(T >> (32 * k)) & M32 for k in range(6)]
+    c5 = [[0] * 6 for _ in range(3)]
+    for k in range(6):
+        up = tw[k + 1] if k + 1 < 6 else 0
+        s1, s2, s3, s4 = (alignbit(up, tw[k], s) for s in (1, 2, 3, 4))
+        x, k1 = bit3(SUM3, tw[k], s1, s2), bit3(MAJ3, tw[k], s1, s2)
+        c5[0][k], k2 = bit3(SUM3, x, s3, s4), bit3(MAJ3, x, s3, s4)
+        c5[1][k], c5[2][k] = k1 ^ k2, k1 & k2
+    ge12, ge10 = [0] * 6, [0] * 6
+    for k in range(5):
+        b = [alignbit(c5[j][k + 1], c5[j][k], 5) for j in range(3)]
+        c = [alignbit(c5[j][k + 1], c5[j][k], 10) for j in range(3)]
+        k0 = bit3(MAJ3, c5[0][k], b[0], c[0])
+        t1, k1a = bit3(SUM3, c5[1][k], b[1], c[1]), bit3(MAJ3, c5[1][k], b[1], c[1])
+        r1, k1b = t1 ^ k0, t1 & k0
+        t2, k2a = bit3(SUM3, c5[2][k], b[2], c[2]), bit3(MAJ3, c5[2][k], b[2], c[2])
+        r2, k2b = bit3(SUM3, t2, k1a, k1b), bit3(MAJ3, t2, k1a, k1b)
+        r3 = k2a | k2b
+        ge12[k], ge10[k] = r3 & r2, bit3(ANDOR3, r3, r2, r1)
+    top = popc(tw[5] & 0x7FFF)
+    ge12[5], ge10[5] = int(top >= 12), int(top >= 10)
+    G, first = 0, -1
+    for k in range(4, -1, -1):
+        keep = window - 32 * k
+        below = M32 if keep >= 32 else (0 if keep <= 0 else (1 << keep) - 1)
+        entry = bit3(AND3, alignbit(ge12[k + 1], ge12[k], 1), tw[k], bit3(ORAND3, c5[2][k], c5[1][k], c5[0][k])) & below
+        G |= (alignbit(ge10[k + 1], ge10[k], 1) & below) << (32 * k)
+        if entry:
+            first = 32 * k + ctz(entry)
+    return G, first
+
+
+def back_mask_words(w):
+    """the walk back's mask over a 64-bit window of exact-T bits as the kernel computes it: two three-input operations per 32-bit half"""
+    w &= M64
+    l1, l2, l3, l4 = ((w << s) & M64 for s in (1, 2, 3, 4))
+    out = 0
+    for h in (0, 32):
+        half = lambda x: (x >> h) & M32   # noqa: E731
+        out |= bit3(AND3, half(w), half(l1), bit3(MAJ3, half(l2), half(l3), half(l4))) << h
+    return out
+
+
 def back_ok(T, e):
     """lambda$findpolyAT$3 L122-142 at position e: T at e, >= 2 T in the last 2, >= 3 in the last 4, >= 4 in the last 5"""
     x = (T >> (e - 4)) & 31

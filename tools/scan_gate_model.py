@@ -44,6 +44,31 @@ def isolated(mask):
     return mask & ~later
 
 
+def isolated_words(mask):
+    """`isolated` as the shipped kernels compute it for the TSO window of 90 positions: the candidate bits on three 32-bit words, s = the mask one
+    position down, then three steps that OR two shifted copies into s (distances 1 -> 1..3 -> 1..9 -> 1..26)"""
+    n, P = mask.shape
+    assert P == TSO_WINDOW
+    m32 = (1 << 32) - 1
+    out = np.zeros_like(mask)
+
+    def align(hi, lo, s):
+        return (((hi << 32) | lo) >> s) & m32
+
+    for i in range(n):
+        m = 0
+        for p in np.nonzero(mask[i])[0].tolist():
+            m |= 1 << p
+        t = [(m >> (32 * k)) & m32 for k in range(3)]
+        s = [align(t[1], t[0], 1), align(t[2], t[1], 1), t[2] >> 1]
+        for k1, k2 in ((1, 2), (3, 6), (9, 17)):
+            s = [s[0] | align(s[1], s[0], k1) | align(s[1], s[0], k2), s[1] | align(s[2], s[1], k1) | align(s[2], s[1], k2), s[2] | (s[2] >> k1) | (s[2] >> k2)]
+        iso = m & ~(s[0] | (s[1] << 32) | (s[2] << 64))
+        for p in range(P):
+            out[i, p] = bool((iso >> p) & 1)
+    return out
+
+
 def scan_ends(rd):
     """both ends of every read in scan orientation as 4-bit codes: [2 n, 208], end 2 i = head, 2 i + 1 = reverse complement of the tail"""
     lut = np.array([1, 2, 4, 8, 15], dtype=np.int64)

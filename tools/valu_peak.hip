@@ -233,6 +233,53 @@ DEF_KERNEL(cmp_cnd, "r5: v_cmp vcc .. v_cndmask vcc + 6 v_max3 per row (rate cou
 DEF_KERNEL(cmp64_cnd64, "r5: v_cmp s[] .. v_cndmask_e64 s[] + 6 v_max3 per row (rate counts all 8)", ROW_CMP64_CND64, 8, 0)
 DEF_KERNEL(max8, "r5: 8 v_max3 per row (reference for the rows above)", ROW_MAX8, 8, 0)
 
+// ---- K-SCAN's phase A (profiles/scan_bits): the three-input boolean form and the 64-bit forms the compiler picks for uint64_t masks.
+// The 64-bit rows run eight chains of register PAIRS (%k = v[n:n+1]); %8 = a pair, %9 = a 32-bit VGPR (the shift), as above.
+// Run these alone with `valu_peak 8000 bits:` -> profiles/scan_bits/valu_rates.json.
+#define DEF_KERNEL64(ID, NAME, ROW)                                                                                    \
+    __global__ __launch_bounds__(256) void k_##ID(uint32_t *out, uint64_t *stamps, int iters, uint32_t seed) {         \
+        extern __shared__ uint32_t lds_pin[]; /* only pins occupancy */                                                \
+        uint64_t a0 = ((uint64_t)seed << 32) | threadIdx.x, a1 = a0 * 3 + 1, a2 = a0 * 5 + 2, a3 = a0 * 7 + 3,          \
+                 a4 = a0 * 9 + 4, a5 = a0 * 11 + 5, a6 = a0 * 13 + 6, a7 = a0 * 15 + 7;                                  \
+        uint64_t b = (0x5a5a5a5b12345678ull ^ seed) + threadIdx.x;                                                      \
+        uint32_t c = 3u + (seed & 1);                                                                                  \
+        const uint64_t t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();                         \
+        for (int i = 0; i < iters; ++i)                                                                                \
+            asm volatile(REP8(ROW)                                                                                     \
+                         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)               \
+                         : "v"(b), "v"(c));                                                                            \
+        const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();                         \
+        const uint64_t x = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7;                                                       \
+        out[blockIdx.x * 256 + threadIdx.x] = (uint32_t)x ^ (uint32_t)(x >> 32);                                        \
+        if (threadIdx.x == 0) {                                                                                        \
+            stamps[2 * blockIdx.x] = t1 - t0;                                                                          \
+            stamps[2 * blockIdx.x + 1] = r1 - r0;                                                                      \
+        }                                                                                                              \
+        if (iters < 0) lds_pin[threadIdx.x] = (uint32_t)a0;                                                            \
+    }                                                                                                                  \
+    static const bool reg_##ID = (registry().push_back({NAME, k_##ID, 8, 0}), true);
+#define T_BITOP3(k) "v_bitop3_b32 %" #k ", %" #k ", %8, %9 bitop3:0x96\n\t"
+#define T_BITOP3_MAJ(k) "v_bitop3_b32 %" #k ", %" #k ", %8, %9 bitop3:0xe8\n\t"
+#define T_BITOP3_XOR(k) "v_bitop3_b32 %" #k ", %" #k ", %8, %9 bitop3:0x96\n\tv_xor_b32 %" #k ", %" #k ", %8\n\t"
+#define T_LSHR64V(k) "v_lshrrev_b64 %" #k ", %9, %" #k "\n\t"
+#define T_LSHR64I(k) "v_lshrrev_b64 %" #k ", 3, %" #k "\n\t"
+#define T_LSHL64V(k) "v_lshlrev_b64 %" #k ", %9, %" #k "\n\t"
+#define T_LSHL64I(k) "v_lshlrev_b64 %" #k ", 3, %" #k "\n\t"
+#define T_LSHLADD64(k) "v_lshl_add_u64 %" #k ", %" #k ", 2, %8\n\t"
+#define T_MOV64(k) "v_mov_b64 %" #k ", %8\n\t"
+DEF_KERNEL(bits_and, "bits: v_and_b32 v,v,v (the 2-cycle form, same session)", ROWOF(T_AND), 8, 0)
+DEF_KERNEL(bits_or3, "bits: v_or3_b32 v,v,v,v (the 4-cycle form, same session)", ROWOF(T_OR3), 8, 0)
+DEF_KERNEL(bits_alignbit, "bits: v_alignbit_b32 v,v,v,2 (same session)", ROWOF(T_ALIGNBITI), 8, 0)
+DEF_KERNEL(bits_bitop3, "bits: v_bitop3_b32 v,v,v,v (0x96, a ^ b ^ c)", ROWOF(T_BITOP3), 8, 0)
+DEF_KERNEL(bits_bitop3_maj, "bits: v_bitop3_b32 v,v,v,v (0xe8, majority)", ROWOF(T_BITOP3_MAJ), 8, 0)
+DEF_KERNEL(bits_bitop3_xor, "bits: v_bitop3_b32 + v_xor_b32 (1:1, rate counts both)", ROWOF(T_BITOP3_XOR), 16, 0)
+DEF_KERNEL64(bits_lshr64_v, "bits: v_lshrrev_b64 v[],v,v[]", ROWOF(T_LSHR64V))
+DEF_KERNEL64(bits_lshr64_i, "bits: v_lshrrev_b64 v[],3,v[] (inline)", ROWOF(T_LSHR64I))
+DEF_KERNEL64(bits_lshl64_v, "bits: v_lshlrev_b64 v[],v,v[]", ROWOF(T_LSHL64V))
+DEF_KERNEL64(bits_lshl64_i, "bits: v_lshlrev_b64 v[],3,v[] (inline)", ROWOF(T_LSHL64I))
+DEF_KERNEL64(bits_lshl_add64, "bits: v_lshl_add_u64 v[],v[],2,v[]", ROWOF(T_LSHLADD64))
+DEF_KERNEL64(bits_mov64, "bits: v_mov_b64 v[],v[]", ROWOF(T_MOV64))
+
 int main(int argc, char **argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 8000;
     hipDeviceProp_t prop;

@@ -486,43 +486,18 @@ int launch_build_pyramid(smi_ctx *ctx, const uint32_t *d_keys, size_t n, hipStre
         }
         // Round 6: the bitmap chain (nb, then nb5 from it) and the table are independent and bound by different things (atomics on 512 MiB against
         // atomics / stores over gigabytes): the chain runs on the context's side stream beside the table's kernel.  SMI_SET_ONE_STREAM: one after the other.
-        hipStream_t sb = s;
-        const bool two_streams = !std::getenv("SMI_SET_ONE_STREAM") && !std::getenv("SMI_BC1_NO_TABLE");
-        if (two_streams) {
-            if (!ctx->side_stream) {
-                SMI_HIP(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
-                SMI_HIP(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
-                SMI_HIP(hipEventCreateWithFlags(&ctx->side_join, hipEventDisableTiming));
-            }
-            SMI_HIP(hipEventRecord(ctx->side_fork, s));
-            SMI_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0));
-            sb = ctx->side_stream;
-        }
-        // from here to the join an error must not leave the side stream running on buffers the caller may free: every exit waits for it
-        auto join = [&]() -> int {
-            if (!two_streams) return SMI_OK;
-            if (hipEventRecord(ctx->side_join, ctx->side_stream) != hipSuccess || hipStreamWaitEvent(s, ctx->side_join, 0) != hipSuccess) {
-                (void)hipStreamSynchronize(ctx->side_stream);
-                return hip_fail(hipGetLastError(), "smi_set_barcode_set (side stream)");
-            }
-            return SMI_OK;
-        };
-#define SMI_SET_HIP(call)                                \
-    do {                                                 \
-        const hipError_t e_ = (call);                    \
-        if (e_ != hipSuccess) {                          \
-            (void)hipStreamSynchronize(ctx->side_stream ? ctx->side_stream : s); \
-            return hip_fail(e_, #call);                  \
-        }                                                \
-    } while (0)
-        SMI_SET_HIP(fill_zero(ctx->nb, kFineWords * 4, sb));
+        // (from the fork to the join an error return waits for the side stream: SideFork)
+        SideFork fork;
+        if (int rc = side_fork(ctx, s, &fork, std::getenv("SMI_SET_ONE_STREAM") || std::getenv("SMI_BC1_NO_TABLE"))) return rc;
+        const hipStream_t sb = fork.side;
+        SMI_HIP(fill_zero(ctx->nb, kFineWords * 4, sb));
         // nb5 by scattered atomics (round 5's way) instead of the transposition: the cross-check switch, and the way of SHORT lists -- the transposition streams
         // the whole 512 MiB bitmap into 2.5 GiB whatever the list holds (3.7 ms), five atomics per neighbour of a used list are a few microseconds behind a
         // 0.6 ms zero fill.  SMI_BC1_NB5_TRANSPOSE keeps the transposition for every list.
         const bool nb5_atomic = std::getenv("SMI_BC1_NB5_ATOMIC") != nullptr || (n <= kN1MaxKeys && !std::getenv("SMI_BC1_NB5_TRANSPOSE"));
-        if (want_nb5 && ctx->nb5 && nb5_atomic) SMI_SET_HIP(fill_zero(ctx->nb5, kNb5Words * 4, sb));
+        if (want_nb5 && ctx->nb5 && nb5_atomic) SMI_HIP(fill_zero(ctx->nb5, kNb5Words * 4, sb));
         hipLaunchKernelGGL(k_set_nb, dim3(gb), dim3(256), 0, sb, d_keys, n, ctx->nb, want_nb5 && nb5_atomic ? ctx->nb5 : nullptr);
-        SMI_SET_HIP(hipGetLastError());
+        SMI_HIP(hipGetLastError());
         if (want_nb5 && ctx->nb5 && !nb5_atomic) {
             static const bool lds_ok = [] { return hipFuncSetAttribute(reinterpret_cast<const void *>(k_nb5_from_nb), hipFuncAttributeMaxDynamicSharedMemorySize, kNb5TileWords * 4) == hipSuccess; }();
             if (!lds_ok) {
@@ -531,7 +506,7 @@ int launch_build_pyramid(smi_ctx *ctx, const uint32_t *d_keys, size_t n, hipStre
                 return SMI_ERR_HIP;
             }
             hipLaunchKernelGGL(k_nb5_from_nb, dim3((unsigned)(((size_t)1 << 24) / kNb5TileCores)), dim3(256), kNb5TileWords * 4, sb, ctx->nb, ctx->nb5);  // (every word of nb5 is written: no memset)
-            SMI_SET_HIP(hipGetLastError());
+            SMI_HIP(hipGetLastError());
         }
         ctx->nb_valid = true;
         ctx->nb5_valid = want_nb5 && ctx->nb5 != nullptr;
@@ -553,7 +528,7 @@ int launch_build_pyramid(smi_ctx *ctx, const uint32_t *d_keys, size_t n, hipStre
                 if (ctx->nt_alloc < cap && ctx->nt_alloc >= cap_at(16) && ctx->nt_small_only) cap = cap_at(16);
                 if (ctx->nt_alloc < cap) {
                     (void)hipStreamSynchronize(sb);  // (hipFree synchronises the device anyway)
-                    if (ctx->nt) SMI_SET_HIP(hipFree(ctx->nt));
+                    if (ctx->nt) SMI_HIP(hipFree(ctx->nt));
                     ctx->nt = nullptr;
                     ctx->nt_alloc = 0;
                     ctx->nt_small_only = false;
@@ -574,24 +549,23 @@ int launch_build_pyramid(smi_ctx *ctx, const uint32_t *d_keys, size_t n, hipStre
                     }
                 }
                 if (ctx->nt_alloc >= cap) {
-                    SMI_SET_HIP(fill_zero(ctx->nt, cap * sizeof(uint64_t), s));
+                    SMI_HIP(fill_zero(ctx->nt, cap * sizeof(uint64_t), s));
                     // distinct barcodes (the usual case): slots by per-bucket counters; else the compare-and-swap build, which drops repeated entries
-                    SMI_SET_HIP(hipStreamSynchronize(s));  // (`last` has arrived: the number of distinct keys)
+                    SMI_HIP(hipStreamSynchronize(s));  // (`last` has arrived: the number of distinct keys)
                     const bool distinct = (size_t)last[0] + last[1] == n;
                     // (the counters live behind the table's nt_alloc slots: allocated with it, idle between builds)
                     uint32_t *cnt = distinct && !std::getenv("SMI_SET_NT_CAS") ? reinterpret_cast<uint32_t *>(ctx->nt + ctx->nt_alloc) : nullptr;
                     if (cnt) {
-                        SMI_SET_HIP(fill_zero(cnt, (cap >> 3) * sizeof(uint32_t), s));
+                        SMI_HIP(fill_zero(cnt, (cap >> 3) * sizeof(uint32_t), s));
                         hipLaunchKernelGGL(k_set_nt_counted, dim3(gb), dim3(256), 0, s, d_keys, n, reinterpret_cast<unsigned long long *>(ctx->nt), cnt, (uint32_t)cap);
                     } else
                         hipLaunchKernelGGL(k_set_nt, dim3(gb), dim3(256), 0, s, d_keys, n, reinterpret_cast<unsigned long long *>(ctx->nt), (uint32_t)cap);
-                    SMI_SET_HIP(hipGetLastError());
+                    SMI_HIP(hipGetLastError());
                     ctx->nt_cap = (uint32_t)cap;
                 }
             }
         }
-        if (int rc = join()) return rc;
-#undef SMI_SET_HIP
+        if (int rc = fork.join(s)) return rc;
     }
     mark("nb / nb5 / nt");
     ctx->n1_valid = false;
@@ -1586,22 +1560,17 @@ int launch_bc_match(smi_ctx *ctx, const smi_bc_window *d_win, size_t n, int max_
     // SMI_BC1_TWO_KERNELS (read per launch): the table path as the pair k_bc_codes_ed1t + k_bc_pick_ed1t with its byte per (read, offset)
     // between them -- cross-checks and same-session comparisons; the one-kernel path allocates no such buffer
     const bool two_kernels = max_ed != 0 && P.nt && std::getenv("SMI_BC1_TWO_KERNELS");
-    if (two_kernels && ctx->bc_codes_bytes < 5 * n) {
-        SMI_HIP(hipStreamSynchronize(s));
-        if (ctx->bc_codes) SMI_HIP(hipFree(ctx->bc_codes));
-        ctx->bc_codes = nullptr;
-        ctx->bc_codes_bytes = 0;
-        SMI_HIP(hipMalloc((void **)&ctx->bc_codes, 5 * n + 5 * n / 4));
-        ctx->bc_codes_bytes = 5 * n + 5 * n / 4;
-    }
+    if (two_kernels)
+        if (int rc = ctx->bc_codes.need(5 * n, s)) return rc;
+    uint8_t *d_codes = ctx->bc_codes.as<uint8_t>();
     if (int rc = time_begin(ctx, SMI_K_BC_MATCH, s)) return rc;
     if (max_ed == 0)
         hipLaunchKernelGGL(k_bc_match_ed1<0>, dim3(grid), dim3(256), 0, s, d_win, n, five_prime, P, d_out);
     else if (two_kernels) {
         hipLaunchKernelGGL(k_bc_codes_ed1t, dim3((unsigned)std::min<size_t>((5 * n + 255) / 256, 256 * 256)), dim3(256), 0, s, d_win, n, five_prime, P,
-                           ctx->bc_codes);
+                           d_codes);
         hipLaunchKernelGGL(k_bc_pick_ed1t, dim3((unsigned)std::min<size_t>((n + 255) / 256, 256 * 64)), dim3(256), 0, s, d_win, n, five_prime,
-                           ctx->bc_codes, d_out);
+                           d_codes, d_out);
     } else if (P.nt)
         hipLaunchKernelGGL(k_bc_match_ed1w, dim3((unsigned)((n_waves + kBc1wWaves - 1) / kBc1wWaves)), dim3(64 * kBc1wWaves), 0, s, d_win, n, five_prime, P, d_out);
     else if (P.nb)

@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "smi_internal.h"
@@ -2718,16 +2719,50 @@ static bool chim_sync_on() {
         }                                                                                                      \
     } while (0)
 
-int launch_chimera(smi_ctx *ctx, const uint32_t *d_planes, const uint64_t *d_offsets, size_t n, uint64_t total_bases,
-                   const smi_chimera_config *cfg, smi_chimera_result *d_out, hipStream_t s, const uint32_t *d_pstart, size_t stride_override) {
-    if (!n) return SMI_OK;
-    const int tl = (int)std::strlen(cfg->tso_complete), al = (int)std::strlen(cfg->adapter_complete);
-    if (!((tl == 27 && al == 22) || (tl == 22 && al == 25))) {
-        set_error("smi_chimera_device: this build handles pattern lengths 27 + 22 (3' barcoding) and 22 + 25 (5' barcoding), "
-                  "the shipped config.xml values");
-        return SMI_ERR_INVALID;
-    }
+// ---- the launcher, stage by stage ------------------------------------------------------------------------------------------------------
+// launch a kernel of the splitter on STREAM and, under SMI_CHIM_SYNC, wait for it and name it when it failed
+#define CHIM_LAUNCH(NAME, KERNEL, GRID, BLOCK, STREAM, ...)                   \
+    do {                                                                      \
+        hipLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, STREAM, __VA_ARGS__);      \
+        SMI_CHIM_CHECK(NAME);                                                 \
+    } while (0)
+
+namespace {
+
+int plane_of(uint32_t code) { return code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : -1; }
+
+// what one launch_chimera carries from stage to stage
+struct ChimRun {
+    smi_ctx *ctx;
+    hipStream_t s;
+    const uint32_t *d_planes, *d_pstart;
+    const uint64_t *d_offsets;
+    size_t n, st;  // reads, plane stride
+    smi_chimera_result *d_out;
+    int tl;  // TSO length: 27 (with the adapter of 22) or 22 (with the adapter of 25)
     ChimParams P;
+    FilterParams F;
+    // the generations: v1 = the first-generation kernels throughout (one wave per read), a1 = first-generation filter + the wave-per-read
+    // select / trigger kernels (both cross-check switches); shipped3 / shipped5 = the TSO is the shipped 3' / 5' one (kernels with the pattern built in)
+    bool v1, a1, shipped3, shipped5;
+    uint32_t *d_count, *d_list;  // the sixteen counters and the queue behind them (chim_list)
+    uint32_t *d_cand_w = nullptr, *d_hot_w = nullptr, *d_trig_w = nullptr;  // the second-generation filter's gate / bound / trigger words (chim_flat)
+    TsoSlot *d_slots = nullptr;
+};
+
+// The run-time pattern choice as template arguments: f(TSO length, the adapter length that goes with it, pattern built in: 1 = shipped 3',
+// 2 = shipped 5', 0 = from the parameters), each a std::integral_constant.  Every kernel of the splitter is launched from inside such an f.
+template <int V> using Int = std::integral_constant<int, V>;
+template <class Fn>
+int with_pattern(const ChimRun &R, const Fn &f) {
+    if (R.shipped3) return f(Int<27>(), Int<22>(), Int<1>());
+    if (R.shipped5) return f(Int<22>(), Int<25>(), Int<2>());
+    if (R.tl == 27) return f(Int<27>(), Int<22>(), Int<0>());
+    return f(Int<22>(), Int<25>(), Int<0>());
+}
+
+// 1. the kernels' parameters from the configuration
+int chim_params(const smi_chimera_config *cfg, int tl, int al, ChimParams &P, FilterParams &F) {
     for (int i = 0; i < tl; i++) {
         P.tso4[0][i] = code_of(cfg->tso_complete[i]);
         const uint32_t b = code_of(cfg->tso_complete[tl - 1 - i]);
@@ -2740,7 +2775,6 @@ int launch_chimera(smi_ctx *ctx, const uint32_t *d_planes, const uint64_t *d_off
     P.pat_thr = thr_count(cfg->internal_pat_len, cfg->internal_pat_frac);
     P.off = cfg->window_polya + 70;
     P.bc_umi = cfg->bc_umi_len;
-    auto plane_of = [](uint32_t code) { return code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : -1; };
     P.prefilter = 1;
     P.myers_ok = 1;
     for (int j = 0; j < tl; j++) {
@@ -2769,20 +2803,6 @@ int launch_chimera(smi_ctx *ctx, const uint32_t *d_planes, const uint64_t *d_off
     // lead <= nErrors / 1.1 (see myers_bound); one more for safety -- a larger range only weakens the filter
     P.tso_lead_max = std::min(tl, (int)(((float)P.tso_max + 0.5f) / 1.1f) + 1);
     P.ad_lead_max = std::min(al, (int)(((float)P.ad_max + 0.5f) / 1.1f) + 1);
-    // queue of the reads K-CHIM-A could not clear, and the hand-over slots of K-CHIM-B: device scratch of the context, grow-only
-    const size_t list_bytes = (2 * n + 64) * sizeof(uint32_t);
-    if (ctx->chim_list_bytes < list_bytes) {
-        if (ctx->chim_list) (void)hipFree(ctx->chim_list);
-        ctx->chim_list = nullptr;
-        ctx->chim_list_bytes = 0;
-        SMI_HIP(hipMalloc(&ctx->chim_list, list_bytes));
-        ctx->chim_list_bytes = list_bytes;
-    }
-    uint32_t *d_count = ctx->chim_list, *d_list = ctx->chim_list + 16;
-    ctx->chim_counts_valid = false;  // until this call has queued all its kernels
-    SMI_HIP(hipMemsetAsync(d_count, 0, 64, s));
-    if (int rc = time_begin(ctx, SMI_K_CHIMERA, s)) return rc;
-    FilterParams F;
     std::memset(&F, 0, sizeof F);
     for (int j = 0; j < tl; j++) {
         F.gate_idx[0][j] = (uint8_t)std::max(0, plane_of(P.tso4[0][j]));
@@ -2799,266 +2819,279 @@ int launch_chimera(smi_ctx *ctx, const uint32_t *d_planes, const uint64_t *d_off
     F.pat_len = P.pat_len;
     F.pat_thr = P.pat_thr;
     F.off = P.off;
-    const size_t st = stride_override ? stride_override : read_planes_stride(total_bases, n);
-    const bool v1 = getenv("SMI_CHIM_V1") != nullptr;        // cross-check switch: the first-generation kernels throughout (one wave per read)
-    const bool a1 = v1 || getenv("SMI_CHIM_A1") != nullptr;  // cross-check switch: first-generation filter + the wave-per-read select / trigger kernels
-    const bool generic = getenv("SMI_CHIM_GENERIC") != nullptr || !P.myers_ok;
-    const bool shipped3 = tl == 27 && !std::strcmp(cfg->tso_complete, PatSeq<1>::s) && !generic;
-    const bool shipped5 = tl == 22 && !std::strcmp(cfg->tso_complete, PatSeq<2>::s) && !generic;
-    uint32_t *d_cand_w = nullptr, *d_hot_w = nullptr, *d_trig_w = nullptr;
-    if (!a1) {
-        // flat scratch: own[st] | cand[2 st] | hot[2 st] | trig[2 st] | verd[n]
-        const size_t flat_bytes = (7 * st + n + 64) * sizeof(uint32_t);
-        if (ctx->chim_flat_bytes < flat_bytes) {
-            if (ctx->chim_flat) (void)hipFree(ctx->chim_flat);
-            ctx->chim_flat = nullptr;
-            ctx->chim_flat_bytes = 0;
-            const size_t want = flat_bytes + flat_bytes / 8;
-            SMI_HIP(hipMalloc(&ctx->chim_flat, want));
-            ctx->chim_flat_bytes = want;
-        }
-        uint32_t *d_own = static_cast<uint32_t *>(ctx->chim_flat);
-        d_cand_w = d_own + st;
-        d_hot_w = d_cand_w + 2 * st;
-        d_trig_w = d_hot_w + 2 * st;
-        uint32_t *d_verd = d_trig_w + 2 * st;
-        if (d_pstart || n == 0) SMI_HIP(hipMemsetAsync(d_own, 0xFF, st * sizeof(uint32_t), s));
-        SMI_HIP(hipMemsetAsync(d_verd, 0, n * sizeof(uint32_t), s));
-        { hipLaunchKernelGGL(k_chim_owner, dim3((unsigned)std::min<size_t>((n + 3) / 4, 256 * 32)), dim3(256), 0, s, d_pstart, d_offsets, n, st, d_own); SMI_CHIM_CHECK("k_chim_owner"); }
-        const size_t n_tiles = (st + 255) / 256;
-        const unsigned gridF = (unsigned)std::min<size_t>(n_tiles, 256 * 8);
-        if (shipped3)
-            { hipLaunchKernelGGL((k_chima_flat<27, 1>), dim3(gridF), dim3(256), 0, s, d_planes, st, n_tiles, d_own, d_pstart, d_offsets, F, d_cand_w, d_hot_w, d_trig_w, d_verd); SMI_CHIM_CHECK("k_chima_flat"); }
-        else if (shipped5)
-            { hipLaunchKernelGGL((k_chima_flat<22, 2>), dim3(gridF), dim3(256), 0, s, d_planes, st, n_tiles, d_own, d_pstart, d_offsets, F, d_cand_w, d_hot_w, d_trig_w, d_verd); SMI_CHIM_CHECK("k_chima_flat"); }
-        else if (tl == 27)
-            { hipLaunchKernelGGL((k_chima_flat<27, 0>), dim3(gridF), dim3(256), 0, s, d_planes, st, n_tiles, d_own, d_pstart, d_offsets, F, d_cand_w, d_hot_w, d_trig_w, d_verd); SMI_CHIM_CHECK("k_chima_flat"); }
-        else
-            { hipLaunchKernelGGL((k_chima_flat<22, 0>), dim3(gridF), dim3(256), 0, s, d_planes, st, n_tiles, d_own, d_pstart, d_offsets, F, d_cand_w, d_hot_w, d_trig_w, d_verd); SMI_CHIM_CHECK("k_chima_flat"); }
-        { hipLaunchKernelGGL(k_chima_finish, dim3((unsigned)std::min<size_t>((n + 1023) / 1024, 256 * 8)), dim3(1024), 0, s, d_verd, n, d_out, d_list, d_count); SMI_CHIM_CHECK("k_chima_finish"); }
-        SMI_HIP(hipGetLastError());
-    } else {
+    return SMI_OK;
+}
+
+// 2. the filter pass: verdicts into d_out, the reads it could not clear into the queue.  Second generation: owner of every plane word, the
+// flat filter over the plane words, verdicts per read; under a1 the first generation's one kernel, a wave per read.
+int chim_filter(ChimRun &R) {
+    const hipStream_t s = R.s;
+    const size_t n = R.n, st = R.st;
+    if (R.a1) {
         const unsigned gridA = (unsigned)std::min<size_t>((n + 3) / 4, 256 * 32);
-        if (shipped3)
-            { hipLaunchKernelGGL((k_chim_tso_filter<27, 1>), dim3(gridA), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, n, F, d_out, d_list, d_count); SMI_CHIM_CHECK("k_chim_tso_filter"); }
-        else if (shipped5)
-            { hipLaunchKernelGGL((k_chim_tso_filter<22, 2>), dim3(gridA), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, n, F, d_out, d_list, d_count); SMI_CHIM_CHECK("k_chim_tso_filter"); }
-        else if (tl == 27)
-            { hipLaunchKernelGGL((k_chim_tso_filter<27, 0>), dim3(gridA), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, n, F, d_out, d_list, d_count); SMI_CHIM_CHECK("k_chim_tso_filter"); }
-        else
-            { hipLaunchKernelGGL((k_chim_tso_filter<22, 0>), dim3(gridA), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, n, F, d_out, d_list, d_count); SMI_CHIM_CHECK("k_chim_tso_filter"); }
-        SMI_HIP(hipGetLastError());
+        return with_pattern(R, [&](auto tl_, auto, auto pat_) -> int {
+            constexpr int TL = decltype(tl_)::value, PAT = decltype(pat_)::value;
+            CHIM_LAUNCH("k_chim_tso_filter", (k_chim_tso_filter<TL, PAT>), dim3(gridA), dim3(256), s, R.d_planes, st, R.d_pstart, R.d_offsets, n, R.F, R.d_out, R.d_list, R.d_count);
+            SMI_HIP(hipGetLastError());
+            return SMI_OK;
+        });
     }
-    // the queue length decides the size of the hand-over slots (one small copy + sync per launch)
-    uint32_t n_list = 0;
-    {
-        uint32_t *pw = static_cast<uint32_t *>(pin_words(ctx));
-        SMI_HIP(hipMemcpyAsync(pw ? pw : &n_list, d_count, 4, hipMemcpyDeviceToHost, s));
-        SMI_HIP(hipStreamSynchronize(s));
-        if (pw) n_list = *pw;
-    }
+    // flat scratch: own[st] | cand[2 st] | hot[2 st] | trig[2 st] | verd[n]
+    if (int rc = R.ctx->chim_flat.need((7 * st + n + 64) * sizeof(uint32_t))) return rc;
+    uint32_t *d_own = R.ctx->chim_flat.as<uint32_t>();
+    R.d_cand_w = d_own + st;
+    R.d_hot_w = R.d_cand_w + 2 * st;
+    R.d_trig_w = R.d_hot_w + 2 * st;
+    uint32_t *d_verd = R.d_trig_w + 2 * st;
+    if (R.d_pstart || n == 0) SMI_HIP(hipMemsetAsync(d_own, 0xFF, st * sizeof(uint32_t), s));
+    SMI_HIP(hipMemsetAsync(d_verd, 0, n * sizeof(uint32_t), s));
+    CHIM_LAUNCH("k_chim_owner", k_chim_owner, dim3((unsigned)std::min<size_t>((n + 3) / 4, 256 * 32)), dim3(256), s, R.d_pstart, R.d_offsets, n, st, d_own);
+    const size_t n_tiles = (st + 255) / 256;
+    const unsigned gridF = (unsigned)std::min<size_t>(n_tiles, 256 * 8);
+    if (int rc = with_pattern(R, [&](auto tl_, auto, auto pat_) -> int {
+            constexpr int TL = decltype(tl_)::value, PAT = decltype(pat_)::value;
+            CHIM_LAUNCH("k_chima_flat", (k_chima_flat<TL, PAT>), dim3(gridF), dim3(256), s, R.d_planes, st, n_tiles, d_own, R.d_pstart, R.d_offsets, R.F, R.d_cand_w, R.d_hot_w, R.d_trig_w, d_verd);
+            return SMI_OK;
+        }))
+        return rc;
+    CHIM_LAUNCH("k_chima_finish", k_chima_finish, dim3((unsigned)std::min<size_t>((n + 1023) / 1024, 256 * 8)), dim3(1024), s, d_verd, n, R.d_out, R.d_list, R.d_count);
+    SMI_HIP(hipGetLastError());
+    return SMI_OK;
+}
+
+// 3. the queue length: it decides the size of the hand-over slots (one small copy + sync per launch)
+int chim_queue_length(ChimRun &R, uint32_t *n_list) {
+    *n_list = 0;
+    if (int rc = read_words(R.ctx, R.s, n_list, R.d_count, 4)) return rc;
 #ifdef SMI_MEASURE
     if (getenv("SMI_CHIM_STATS")) {  // how many reads K-CHIM-A queues, and for what
-        std::vector<smi_chimera_result> h(n);
-        SMI_HIP(hipMemcpy(h.data(), d_out, n * sizeof(smi_chimera_result), hipMemcpyDeviceToHost));
+        std::vector<smi_chimera_result> h(R.n);
+        SMI_HIP(hipMemcpy(h.data(), R.d_out, R.n * sizeof(smi_chimera_result), hipMemcpyDeviceToHost));
         size_t n_tso = 0, n_pat = 0, n_both = 0;
-        for (size_t i = 0; i < n; i++) {
+        for (size_t i = 0; i < R.n; i++) {
             const int v = h[i].n_matches;
             n_tso += (v & SMI_CHIMA_TSO) != 0;
             n_pat += (v & SMI_CHIMA_PAT) != 0;
             n_both += v == (SMI_CHIMA_TSO | SMI_CHIMA_PAT);
         }
-        fprintf(stderr, "[chim stats] reads %zu queued %u tso %zu pat %zu both %zu\n", n, n_list, n_tso, n_pat, n_both);
+        fprintf(stderr, "[chim stats] reads %zu queued %u tso %zu pat %zu both %zu\n", R.n, *n_list, n_tso, n_pat, n_both);
     }
 #endif
+    return SMI_OK;
+}
+
+// chim_work, the scratch of the second-generation pipelines: one grow-only buffer, every section aligned to 256 bytes
+struct ChimWork {
+    size_t cap, st_cap, e_cap;  // entries of the position queue, of the stretch queue, of the alignment queue
+    size_t bcnt, heads, cand, ne, trig, st, sres, rst, rn, ent, ene, enm, total;  // byte offsets of the sections, in this order
+};
+ChimWork chim_work_layout(size_t n_list, size_t stride, bool a1) {
+    ChimWork W;
+    W.cap = (std::max<size_t>(n_list * 48, (size_t)1 << 16) + kSubQ - 1) / kSubQ * kSubQ;
+    W.st_cap = std::max<size_t>(n_list * 4, (size_t)1 << 12);
+    W.e_cap = std::max<size_t>(n_list * 8, (size_t)1 << 12);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    W.bcnt = take(kSubQ * 4);                      // B: the kSubQ counters of the position queue (second-generation select)
+    W.heads = take(n_list * sizeof(BHead));        // B: per-read heads
+    W.cand = take(W.cap * 8);                      // B: queue of positions (u64)
+    W.ne = take(W.cap * 4);                        // B: their error counts (f32)
+    W.trig = take(a1 ? 2 * stride * 4 : 0);        // C: trigger words (2 x stride) where the first-generation filter left none
+    W.st = take(W.st_cap * sizeof(Stretch));       // C: stretches
+    W.sres = take(W.st_cap * sizeof(StretchRes));  // C: their results
+    W.rst = take(n_list * kStPerRead * 4);         // C: per-read stretch lists
+    W.rn = take(n_list);                           // C: their lengths
+    W.ent = take(W.e_cap * sizeof(AdEntry));       // C: alignment queue
+    W.ene = take(W.e_cap * 4);                     // C: its error counts
+    W.enm = take(W.e_cap * 4);                     // C: its match counts
+    W.total = off;
+    return W;
+}
+
+// 4. the exact pass, second generation: chain B (select -> align -> fold) on s, chain C (triggers -> walk -> gate -> align) on the side
+// stream, the rules kernel behind both, then a second chance for the reads over a cap of the lane-per-read kernels
+int chim_exact(ChimRun &R, uint32_t n_list) {
+    const hipStream_t s = R.s;
+    const size_t n = R.n, st = R.st;
+    const bool a1 = R.a1;
+    const ChimParams &P = R.P;
+    const uint32_t *d_planes = R.d_planes, *d_pstart = R.d_pstart;
+    const uint64_t *d_offsets = R.d_offsets;
+    smi_chimera_result *d_out = R.d_out;
+    uint32_t *d_count = R.d_count, *d_list = R.d_list;
+    TsoSlot *d_slots = R.d_slots;
+    const ChimWork W = chim_work_layout(n_list, st, a1);
+    if (int rc = R.ctx->chim_work.need(W.total)) return rc;
+    char *wk = R.ctx->chim_work.as<char>();
+    BHead *d_heads = reinterpret_cast<BHead *>(wk + W.heads);
+    uint64_t *d_cand = reinterpret_cast<uint64_t *>(wk + W.cand);
+    float *d_ne = reinterpret_cast<float *>(wk + W.ne);
+    uint32_t *d_trig = a1 ? reinterpret_cast<uint32_t *>(wk + W.trig) : R.d_trig_w;
+    Stretch *d_st = reinterpret_cast<Stretch *>(wk + W.st);
+    StretchRes *d_sres = reinterpret_cast<StretchRes *>(wk + W.sres);
+    uint32_t *d_rst = reinterpret_cast<uint32_t *>(wk + W.rst);
+    uint8_t *d_rn = reinterpret_cast<uint8_t *>(wk + W.rn);
+    AdEntry *d_ent = reinterpret_cast<AdEntry *>(wk + W.ent);
+    float *d_ene = reinterpret_cast<float *>(wk + W.ene);
+    int *d_enm = reinterpret_cast<int *>(wk + W.enm);
+    uint32_t *d_gcount = a1 ? d_count + 2 : reinterpret_cast<uint32_t *>(wk + W.bcnt);  // (second generation: kSubQ counters)
+    if (!a1) SMI_HIP(hipMemsetAsync(d_gcount, 0, kSubQ * 4, s));
+    uint32_t *d_stcount = d_count + 3, *d_ecount = d_count + 4;  // zeroed with the queue counters
+    uint32_t *d_dbg = d_count + 8;  // why reads went to the serial kernel: 0 stretches per read, 1 stretch queue, 2 alignment queue, 3 matches per read, 4 TSO slot, 5 gated positions per read, 6 position queue, 7 accepted positions
+    const uint32_t cap = (uint32_t)W.cap, st_cap = (uint32_t)W.st_cap, e_cap = (uint32_t)W.e_cap;
+    const unsigned grid = (unsigned)std::min<size_t>(((size_t)n_list + 3) / 4, 256 * 16);
+    const unsigned grid_flat = 256 * 8;
+    const unsigned grid_lane = (unsigned)(((size_t)n_list + 63) / 64);
+    // B and C share nothing but the filter's words and the queue: C runs on the context's side stream beside B -- both are chains of short
+    // kernels that leave most of the chip idle (C's walk is a lane per queued read: under one wave per SIMD) -- and the rules kernel waits for
+    // both.  SMI_CHIM_SYNC keeps everything on one stream.  (An error return between the fork and the join waits for chain C, which runs
+    // on arena buffers the caller reuses or frees: SideFork.)
+    SideFork fork;
+    if (int rc = side_fork(R.ctx, s, &fork, chim_sync_on())) return rc;
+    const hipStream_t sc = fork.side;
+    if (int rc = with_pattern(R, [&](auto tl_, auto al_, auto pat_) -> int {
+            constexpr int TL = decltype(tl_)::value, AL = decltype(al_)::value, PAT = decltype(pat_)::value;
+            // ---- B: select
+            if (!a1)
+                CHIM_LAUNCH("k_chimb_select2", k_chimb_select2, dim3((unsigned)(((size_t)n_list + 15) / 16)), dim3(1024), s, st, d_pstart, d_offsets, d_list, d_count, d_out, R.d_cand_w, R.d_hot_w, d_heads, d_cand, d_gcount, cap, d_dbg);
+            else
+                CHIM_LAUNCH("k_chimb_select", (k_chimb_select<TL, PAT>), dim3(grid), dim3(256), s, d_planes, st, d_pstart, d_offsets, d_list, d_count, R.F, d_out, d_heads, d_cand, d_gcount, cap, d_dbg);
+            // ---- C: triggers -> walk
+            if (a1) CHIM_LAUNCH("k_chimc_trig", k_chimc_trig, dim3(grid), dim3(256), sc, d_planes, st, d_pstart, d_offsets, d_list, d_count, P, d_out, d_trig);
+            CHIM_LAUNCH("k_chimc_walk", k_chimc_walk, dim3(grid_lane), dim3(64), sc, d_planes, st, d_pstart, d_offsets, d_list, d_count, P, d_out, d_trig, d_st, d_stcount, st_cap, d_rst, d_rn, d_dbg);
+            // ---- B: align -> fold;  C: gate -> align
+            CHIM_LAUNCH("k_chimb_align", (k_chimb_align<TL>), a1 ? dim3(grid_flat) : dim3(32, kSubQ), dim3(256), s, d_planes, st, d_cand, d_gcount, cap, P, d_ne);
+            CHIM_LAUNCH("k_chimb_fold", (k_chimb_fold<TL>), dim3(grid), dim3(256), s, d_pstart, d_offsets, d_list, d_count, P.tso_max, d_out, d_heads, d_cand, d_ne, d_slots, d_dbg);
+            CHIM_LAUNCH("k_chimc_gate", (k_chimc_gate<AL>), dim3(grid_flat), dim3(256), sc, d_planes, st, d_pstart, d_offsets, d_list, P, d_st, d_stcount, st_cap, d_sres, d_ent, d_ecount, e_cap, d_dbg);
+            CHIM_LAUNCH("k_chimc_align", (k_chimc_align<AL>), dim3(grid_flat), dim3(256), sc, d_planes, st, d_pstart, d_offsets, d_list, P, d_st, d_ent, d_ecount, e_cap, d_ene, d_enm);
+            return SMI_OK;
+        }))
+        return rc;
+    if (fork.armed) SMI_HIP(hipGetLastError());
+    if (int rc = fork.join(s)) return rc;
+    CHIM_LAUNCH("k_chimc_rules", k_chimc_rules, dim3(grid_lane), dim3(64), s, d_pstart, d_offsets, d_list, d_count, P, d_slots, d_st, d_sres, d_rst, d_rn, d_ene, d_enm, d_out, d_dbg);
+    // second chance for the reads over a cap of the lane-per-read kernels (one in 10^5): the first-generation kernels, one wave per read,
+    // with their caps of 64; what is over those too goes to the serial kernel.  The usual chunk has none: the two kernels then
+    // find an empty list (they take its length from the device, 64 workgroups each: ~ 10 us together) -- reading the length back
+    // first, to skip them, cost a round trip to the host of ~ 45 us per chunk
+    uint32_t *d_over2_count = d_count + 5, *d_over2 = d_list + n;
+    CHIM_LAUNCH("k_collect_overflow", k_collect_overflow, dim3(64), dim3(256), s, d_out, d_list, d_count, d_over2, d_over2_count);
+#ifdef SMI_MEASURE
+    if (getenv("SMI_CHIM_STATS")) {
+        uint32_t h[16];
+        SMI_HIP(hipMemcpy(h, d_count, 64, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[chim stats] queue %u second chance %u stretches %u ad-entries %u | caps hit: st/read %u st-queue %u ad-queue %u matches %u slot %u gated %u pos-queue %u accepted %u\n",
+                h[0], h[5], h[3], h[4], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15]);
+    }
+#endif
+    return with_pattern(R, [&](auto tl_, auto al_, auto) -> int {
+        constexpr int TL = decltype(tl_)::value, AL = decltype(al_)::value;
+        CHIM_LAUNCH("k_chimera", (k_chimera<TL, AL, 1>), dim3(64), dim3(256), s, d_planes, st, d_pstart, d_offsets, d_over2, d_over2_count, P, d_slots, d_out);
+        CHIM_LAUNCH("k_chimera", (k_chimera<TL, AL, 2>), dim3(64), dim3(256), s, d_planes, st, d_pstart, d_offsets, d_over2, d_over2_count, P, d_slots, d_out);
+        return SMI_OK;
+    });
+}
+
+// 4, under v1: the first-generation kernels over the whole queue, one wave per read
+int chim_exact_v1(ChimRun &R, uint32_t n_list) {
+    const hipStream_t s = R.s;
+    const unsigned grid = (unsigned)std::min<size_t>(((size_t)n_list + 3) / 4, 256 * 16);
+    return with_pattern(R, [&](auto tl_, auto al_, auto) -> int {
+        constexpr int TL = decltype(tl_)::value, AL = decltype(al_)::value;
+        CHIM_LAUNCH("k_chimera", (k_chimera<TL, AL, 1>), dim3(grid), dim3(256), s, R.d_planes, R.st, R.d_pstart, R.d_offsets, R.d_list, R.d_count, R.P, R.d_slots, R.d_out);
+        CHIM_LAUNCH("k_chimera", (k_chimera<TL, AL, 2>), dim3(grid), dim3(256), s, R.d_planes, R.st, R.d_pstart, R.d_offsets, R.d_list, R.d_count, R.P, R.d_slots, R.d_out);
+        return SMI_OK;
+    });
+}
+
+// 5. reads with more than kCap accepted positions / matches are collected for one more pass without the cap.  The overflow queue sits
+// behind the main queue in the same buffer (the main queue never uses more than n entries, the buffer holds 2 n + 64)
+int chim_collect_overflow(ChimRun &R, uint32_t *n_over) {
+    const hipStream_t s = R.s;
+    uint32_t *d_over_count = R.d_count + 1, *d_over = R.d_list + R.n;
+    CHIM_LAUNCH("k_collect_overflow", k_collect_overflow, dim3(64), dim3(256), s, R.d_out, R.d_list, R.d_count, d_over, d_over_count);
+    *n_over = 0;
+    if (int rc = read_words(R.ctx, s, n_over, d_over_count, 4)) return rc;
+#ifdef SMI_MEASURE
+    if (getenv("SMI_CHIM_STATS")) {
+        uint32_t h[16];
+        SMI_HIP(hipMemcpy(h, R.d_count, 64, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[chim stats] queue %u over %u positions %u stretches %u ad-entries %u | caps hit: st/read %u st-queue %u ad-queue %u matches %u slot %u gated %u pos-queue %u accepted %u\n",
+                h[0], h[1], h[2], h[3], h[4], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15]);
+    }
+#endif
+    return SMI_OK;
+}
+
+// 6. K-CHIM-S: the collected reads once more, serially and without a cap, on scratch sized by their lengths
+int chim_serial(ChimRun &R, uint32_t n_over) {
+    const hipStream_t s = R.s;
+    const size_t n = R.n;
+    const uint32_t *d_over = R.d_list + n;
+    std::vector<uint32_t> over(n_over);
+    std::vector<uint64_t> offs(n + 1);
+    SMI_HIP(hipMemcpyAsync(over.data(), d_over, (size_t)n_over * 4, hipMemcpyDeviceToHost, s));
+    SMI_HIP(hipMemcpyAsync(offs.data(), R.d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    SMI_HIP(hipStreamSynchronize(s));
+    std::sort(over.begin(), over.end());  // the collection order is not deterministic; the results do not depend on it
+    std::vector<uint64_t> scr_off(n_over + 1, 0);
+    for (uint32_t i = 0; i < n_over; i++) scr_off[i + 1] = scr_off[i] + 7 * (offs[over[i] + 1] - offs[over[i]] + 8);
+    DevBuf<uint64_t> d_scr_off("K-CHIM-S");
+    DevBuf<int32_t> d_scr("K-CHIM-S");
+    DevBuf<uint32_t> d_over_sorted("K-CHIM-S");
+    if (int rc = d_scr_off.put(scr_off, s)) return rc;
+    if (int rc = d_scr.alloc(scr_off[n_over])) return rc;
+    if (int rc = d_over_sorted.put(over, s)) return rc;
+    const unsigned gs = (unsigned)std::min<uint32_t>(n_over, 4096);
+    if (int rc = with_pattern(R, [&](auto tl_, auto al_, auto) -> int {
+            constexpr int TL = decltype(tl_)::value, AL = decltype(al_)::value;
+            CHIM_LAUNCH("k_chimera_serial", (k_chimera_serial<TL, AL>), dim3(gs), dim3(64), s, R.d_planes, R.st, R.d_pstart, R.d_offsets, d_over_sorted.p, n_over, d_scr_off.p, d_scr.p, R.P, R.d_out);
+            return SMI_OK;
+        }))
+        return rc;
+    const hipError_t e = hipStreamSynchronize(s);  // (the scratch is freed behind the kernel, on every way out)
+    if (e != hipSuccess) return hip_fail(e, "k_chimera_serial");
+    return SMI_OK;
+}
+
+}  // namespace
+
+int launch_chimera(smi_ctx *ctx, const uint32_t *d_planes, const uint64_t *d_offsets, size_t n, uint64_t total_bases,
+                   const smi_chimera_config *cfg, smi_chimera_result *d_out, hipStream_t s, const uint32_t *d_pstart, size_t stride_override) {
+    if (!n) return SMI_OK;
+    const int tl = (int)std::strlen(cfg->tso_complete), al = (int)std::strlen(cfg->adapter_complete);
+    if (!((tl == 27 && al == 22) || (tl == 22 && al == 25))) {
+        set_error("smi_chimera_device: this build handles pattern lengths 27 + 22 (3' barcoding) and 22 + 25 (5' barcoding), "
+                  "the shipped config.xml values");
+        return SMI_ERR_INVALID;
+    }
+    ChimRun R{};
+    R.ctx = ctx, R.s = s, R.d_planes = d_planes, R.d_pstart = d_pstart, R.d_offsets = d_offsets, R.n = n, R.d_out = d_out, R.tl = tl;
+    R.st = stride_override ? stride_override : read_planes_stride(total_bases, n);
+    if (int rc = chim_params(cfg, tl, al, R.P, R.F)) return rc;  // 1
+    R.v1 = getenv("SMI_CHIM_V1") != nullptr;
+    R.a1 = R.v1 || getenv("SMI_CHIM_A1") != nullptr;
+    const bool generic = getenv("SMI_CHIM_GENERIC") != nullptr || !R.P.myers_ok;
+    R.shipped3 = tl == 27 && !std::strcmp(cfg->tso_complete, PatSeq<1>::s) && !generic;
+    R.shipped5 = tl == 22 && !std::strcmp(cfg->tso_complete, PatSeq<2>::s) && !generic;
+    // queue of the reads K-CHIM-A could not clear behind the sixteen counters: device scratch of the context, grow-only
+    ctx->chim_counts_valid = false;  // until this call has queued all its kernels
+    if (int rc = ctx->chim_list.need((2 * n + 64) * sizeof(uint32_t))) return rc;
+    R.d_count = ctx->chim_list.as<uint32_t>(), R.d_list = R.d_count + 16;
+    SMI_HIP(hipMemsetAsync(R.d_count, 0, 64, s));
+    if (int rc = time_begin(ctx, SMI_K_CHIMERA, s)) return rc;
+    if (int rc = chim_filter(R)) return rc;  // 2
+    uint32_t n_list = 0, n_over = 0;
+    if (int rc = chim_queue_length(R, &n_list)) return rc;  // 3
     if (n_list) {
-        const size_t slot_bytes = (size_t)n_list * sizeof(TsoSlot);
-        if (ctx->chim_slot_bytes < slot_bytes) {
-            if (ctx->chim_slots) (void)hipFree(ctx->chim_slots);
-            ctx->chim_slots = nullptr;
-            ctx->chim_slot_bytes = 0;
-            const size_t want = slot_bytes + slot_bytes / 4;
-            SMI_HIP(hipMalloc(&ctx->chim_slots, want));
-            ctx->chim_slot_bytes = want;
-        }
-        TsoSlot *d_slots = static_cast<TsoSlot *>(ctx->chim_slots);
-        const unsigned grid = (unsigned)std::min<size_t>(((size_t)n_list + 3) / 4, 256 * 16);
-        if (!(P.ablate & 16)) {
-            if (!v1) {
-                // scratch of the second-generation pipelines, one grow-only buffer:
-                //   B: heads | queue of positions (u64) | error counts (f32)
-                //   C: trigger words (2 x stride) | stretches | their results | per-read stretch lists | alignment queue | its results
-                auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-                const size_t cap = (std::max<size_t>((size_t)n_list * 48, (size_t)1 << 16) + kSubQ - 1) / kSubQ * kSubQ;
-                const size_t st_cap = std::max<size_t>((size_t)n_list * 4, (size_t)1 << 12);
-                const size_t e_cap = std::max<size_t>((size_t)n_list * 8, (size_t)1 << 12);
-                size_t off = 0;
-                auto take = [&](size_t bytes) { const size_t o = off; off += up(bytes); return o; };
-                const size_t o_bcnt = take(kSubQ * 4);
-                const size_t o_heads = take((size_t)n_list * sizeof(BHead)), o_cand = take(cap * 8), o_ne = take(cap * 4);
-                const size_t o_trig = take(a1 ? 2 * st * 4 : 0), o_st = take(st_cap * sizeof(Stretch)), o_sres = take(st_cap * sizeof(StretchRes));
-                const size_t o_rst = take((size_t)n_list * kStPerRead * 4), o_rn = take(n_list), o_ent = take(e_cap * sizeof(AdEntry));
-                const size_t o_ene = take(e_cap * 4), o_enm = take(e_cap * 4);
-                if (ctx->chim_work_bytes < off) {
-                    if (ctx->chim_work) (void)hipFree(ctx->chim_work);
-                    ctx->chim_work = nullptr;
-                    ctx->chim_work_bytes = 0;
-                    const size_t want = off + off / 4;
-                    SMI_HIP(hipMalloc(&ctx->chim_work, want));
-                    ctx->chim_work_bytes = want;
-                }
-                char *wk = static_cast<char *>(ctx->chim_work);
-                BHead *d_heads = reinterpret_cast<BHead *>(wk + o_heads);
-                uint64_t *d_cand = reinterpret_cast<uint64_t *>(wk + o_cand);
-                float *d_ne = reinterpret_cast<float *>(wk + o_ne);
-                uint32_t *d_trig = a1 ? reinterpret_cast<uint32_t *>(wk + o_trig) : d_trig_w;
-                Stretch *d_st = reinterpret_cast<Stretch *>(wk + o_st);
-                StretchRes *d_sres = reinterpret_cast<StretchRes *>(wk + o_sres);
-                uint32_t *d_rst = reinterpret_cast<uint32_t *>(wk + o_rst);
-                uint8_t *d_rn = reinterpret_cast<uint8_t *>(wk + o_rn);
-                AdEntry *d_ent = reinterpret_cast<AdEntry *>(wk + o_ent);
-                float *d_ene = reinterpret_cast<float *>(wk + o_ene);
-                int *d_enm = reinterpret_cast<int *>(wk + o_enm);
-                uint32_t *d_gcount = a1 ? d_count + 2 : reinterpret_cast<uint32_t *>(wk + o_bcnt);  // (second generation: kSubQ counters)
-                if (!a1) SMI_HIP(hipMemsetAsync(d_gcount, 0, kSubQ * 4, s));
-                uint32_t *d_stcount = d_count + 3, *d_ecount = d_count + 4;  // zeroed with the queue counters above
-                uint32_t *d_dbg = d_count + 8;  // why reads went to the serial kernel: 0 stretches per read, 1 stretch queue, 2 alignment queue, 3 matches per read, 4 TSO slot, 5 gated positions per read, 6 position queue, 7 accepted positions
-                const unsigned grid_flat = 256 * 8;
-                const unsigned grid_lane = (unsigned)(((size_t)n_list + 63) / 64);
-                // B (select -> align -> fold) and C (walk -> gate -> align) share nothing but the filter's words and the queue: C runs on the
-                // context's side stream beside B -- both are chains of short kernels that leave most of the chip idle (C's walk is a lane per
-                // queued read: under one wave per SIMD) -- and the rules kernel waits for both.  SMI_CHIM_SYNC keeps everything on one stream.
-                const bool use_side = !chim_sync_on();
-                if (use_side && !ctx->side_stream) {
-                    SMI_HIP(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
-                    SMI_HIP(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
-                    SMI_HIP(hipEventCreateWithFlags(&ctx->side_join, hipEventDisableTiming));
-                }
-                hipStream_t sc = use_side ? ctx->side_stream : s;
-                if (use_side) {
-                    SMI_HIP(hipEventRecord(ctx->side_fork, s));
-                    SMI_HIP(hipStreamWaitEvent(sc, ctx->side_fork, 0));
-                }
-                // (advisor, round 5) an error return between here and the join must not leave chain C running on arena buffers the caller reuses or
-                // frees: every such exit drains the side stream first
-                SideStreamGuard side_guard{sc, use_side};
-                // ---- B: select -> align -> fold
-                if (!a1)
-                    { hipLaunchKernelGGL(k_chimb_select2, dim3((unsigned)(((size_t)n_list + 15) / 16)), dim3(1024), 0, s, st, d_pstart, d_offsets, d_list, d_count, d_out, d_cand_w, d_hot_w, d_heads, d_cand, d_gcount,
-                                       (uint32_t)cap, d_dbg); SMI_CHIM_CHECK("k_chimb_select2"); }
-                else if (shipped3)
-                    { hipLaunchKernelGGL((k_chimb_select<27, 1>), dim3(grid), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_list, d_count, F, d_out, d_heads, d_cand, d_gcount, (uint32_t)cap, d_dbg); SMI_CHIM_CHECK("k_chimb_select"); }
-                else if (shipped5)
-                    { hipLaunchKernelGGL((k_chimb_select<22, 2>), dim3(grid), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_list, d_count, F, d_out, d_heads, d_cand, d_gcount, (uint32_t)cap, d_dbg); SMI_CHIM_CHECK("k_chimb_select"); }
-                else if (tl == 27)
-                    { hipLaunchKernelGGL((k_chimb_select<27, 0>), dim3(grid), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_list, d_count, F, d_out, d_heads, d_cand, d_gcount, (uint32_t)cap, d_dbg); SMI_CHIM_CHECK("k_chimb_select"); }
-                else
-                    { hipLaunchKernelGGL((k_chimb_select<22, 0>), dim3(grid), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_list, d_count, F, d_out, d_heads, d_cand, d_gcount, (uint32_t)cap, d_dbg); SMI_CHIM_CHECK("k_chimb_select"); }
-                // ---- C: triggers -> walk
-                if (a1) { hipLaunchKernelGGL(k_chimc_trig, dim3(grid), dim3(256), 0, sc, d_planes, st, d_pstart, d_offsets, d_list, d_count, P, d_out, d_trig); SMI_CHIM_CHECK("k_chimc_trig"); }
-                { hipLaunchKernelGGL(k_chimc_walk, dim3(grid_lane), dim3(64), 0, sc, d_planes, st, d_pstart, d_offsets, d_list, d_count, P, d_out, d_trig, d_st, d_stcount,
-                                   (uint32_t)st_cap, d_rst, d_rn, d_dbg); SMI_CHIM_CHECK("k_chimc_walk"); }
-                if (tl == 27) {
-                    { hipLaunchKernelGGL((k_chimb_align<27>), a1 ? dim3(grid_flat) : dim3(32, kSubQ), dim3(256), 0, s, d_planes, st, d_cand, d_gcount, (uint32_t)cap, P, d_ne); SMI_CHIM_CHECK("k_chimb_align"); }
-                    { hipLaunchKernelGGL((k_chimb_fold<27>), dim3(grid), dim3(256), 0, s, d_pstart, d_offsets, d_list, d_count, P.tso_max, d_out, d_heads, d_cand, d_ne, d_slots, d_dbg); SMI_CHIM_CHECK("k_chimb_fold"); }
-                    { hipLaunchKernelGGL((k_chimc_gate<22>), dim3(grid_flat), dim3(256), 0, sc, d_planes, st, d_pstart, d_offsets, d_list, P, d_st, d_stcount, (uint32_t)st_cap, d_sres,
-                                       d_ent, d_ecount, (uint32_t)e_cap, d_dbg); SMI_CHIM_CHECK("k_chimc_gate"); }
-                    { hipLaunchKernelGGL((k_chimc_align<22>), dim3(grid_flat), dim3(256), 0, sc, d_planes, st, d_pstart, d_offsets, d_list, P, d_st, d_ent, d_ecount, (uint32_t)e_cap, d_ene, d_enm); SMI_CHIM_CHECK("k_chimc_align"); }
-                } else {
-                    { hipLaunchKernelGGL((k_chimb_align<22>), a1 ? dim3(grid_flat) : dim3(32, kSubQ), dim3(256), 0, s, d_planes, st, d_cand, d_gcount, (uint32_t)cap, P, d_ne); SMI_CHIM_CHECK("k_chimb_align"); }
-                    { hipLaunchKernelGGL((k_chimb_fold<22>), dim3(grid), dim3(256), 0, s, d_pstart, d_offsets, d_list, d_count, P.tso_max, d_out, d_heads, d_cand, d_ne, d_slots, d_dbg); SMI_CHIM_CHECK("k_chimb_fold"); }
-                    { hipLaunchKernelGGL((k_chimc_gate<25>), dim3(grid_flat), dim3(256), 0, sc, d_planes, st, d_pstart, d_offsets, d_list, P, d_st, d_stcount, (uint32_t)st_cap, d_sres,
-                                       d_ent, d_ecount, (uint32_t)e_cap, d_dbg); SMI_CHIM_CHECK("k_chimc_gate"); }
-                    { hipLaunchKernelGGL((k_chimc_align<25>), dim3(grid_flat), dim3(256), 0, sc, d_planes, st, d_pstart, d_offsets, d_list, P, d_st, d_ent, d_ecount, (uint32_t)e_cap, d_ene, d_enm); SMI_CHIM_CHECK("k_chimc_align"); }
-                }
-                if (use_side) {
-                    SMI_HIP(hipGetLastError());
-                    SMI_HIP(hipEventRecord(ctx->side_join, sc));
-                    SMI_HIP(hipStreamWaitEvent(s, ctx->side_join, 0));
-                    side_guard.armed = false;  // s is ordered behind the side stream from here on
-                }
-                { hipLaunchKernelGGL(k_chimc_rules, dim3(grid_lane), dim3(64), 0, s, d_pstart, d_offsets, d_list, d_count, P, d_slots, d_st, d_sres, d_rst, d_rn, d_ene, d_enm, d_out, d_dbg); SMI_CHIM_CHECK("k_chimc_rules"); }
-                // second chance for the reads over a cap of the lane-per-read kernels (one in 10^5): the first-generation kernels, one wave per read,
-                // with their caps of 64; what is over those too goes to the serial kernel below.  The usual chunk has none: the two kernels then
-                // find an empty list (they take its length from the device, 64 workgroups each: ~ 10 us together) -- reading the length back
-                // first, to skip them, cost a round trip to the host of ~ 45 us per chunk
-                uint32_t *d_over2_count = d_count + 5, *d_over2 = d_list + n;
-                { hipLaunchKernelGGL(k_collect_overflow, dim3(64), dim3(256), 0, s, d_out, d_list, d_count, d_over2, d_over2_count); SMI_CHIM_CHECK("k_collect_overflow"); }
-#ifdef SMI_MEASURE
-                if (getenv("SMI_CHIM_STATS")) {
-                    uint32_t h[16];
-                    SMI_HIP(hipMemcpy(h, d_count, 64, hipMemcpyDeviceToHost));
-                    fprintf(stderr, "[chim stats] queue %u second chance %u stretches %u ad-entries %u | caps hit: st/read %u st-queue %u ad-queue %u matches %u slot %u gated %u pos-queue %u accepted %u\n",
-                            h[0], h[5], h[3], h[4], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15]);
-                }
-#endif
-                if (tl == 27) {
-                    { hipLaunchKernelGGL((k_chimera<27, 22, 1>), dim3(64), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_over2, d_over2_count, P, d_slots, d_out); SMI_CHIM_CHECK("k_chimera"); }
-                    { hipLaunchKernelGGL((k_chimera<27, 22, 2>), dim3(64), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_over2, d_over2_count, P, d_slots, d_out); SMI_CHIM_CHECK("k_chimera"); }
-                } else {
-                    { hipLaunchKernelGGL((k_chimera<22, 25, 1>), dim3(64), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_over2, d_over2_count, P, d_slots, d_out); SMI_CHIM_CHECK("k_chimera"); }
-                    { hipLaunchKernelGGL((k_chimera<22, 25, 2>), dim3(64), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_over2, d_over2_count, P, d_slots, d_out); SMI_CHIM_CHECK("k_chimera"); }
-                }
-            } else if (tl == 27) {
-                { hipLaunchKernelGGL((k_chimera<27, 22, 1>), dim3(grid), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_list, d_count, P, d_slots, d_out); SMI_CHIM_CHECK("k_chimera"); }
-                { hipLaunchKernelGGL((k_chimera<27, 22, 2>), dim3(grid), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_list, d_count, P, d_slots, d_out); SMI_CHIM_CHECK("k_chimera"); }
-            } else {
-                { hipLaunchKernelGGL((k_chimera<22, 25, 1>), dim3(grid), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_list, d_count, P, d_slots, d_out); SMI_CHIM_CHECK("k_chimera"); }
-                { hipLaunchKernelGGL((k_chimera<22, 25, 2>), dim3(grid), dim3(256), 0, s, d_planes, st, d_pstart, d_offsets, d_list, d_count, P, d_slots, d_out); SMI_CHIM_CHECK("k_chimera"); }
-            }
+        if (int rc = ctx->chim_slots.need((size_t)n_list * sizeof(TsoSlot))) return rc;
+        R.d_slots = ctx->chim_slots.as<TsoSlot>();
+        if (!(R.P.ablate & 16)) {
+            if (int rc = R.v1 ? chim_exact_v1(R, n_list) : chim_exact(R, n_list)) return rc;  // 4
             SMI_HIP(hipGetLastError());
-            // reads with more than kCap accepted positions / matches: once more without the cap (K-CHIM-S).  The overflow queue sits
-            // behind the main queue in the same buffer (the main queue never uses more than n entries, the buffer holds 2 n + 64)
-            uint32_t *d_over_count = d_count + 1, *d_over = d_list + n;
-            { hipLaunchKernelGGL(k_collect_overflow, dim3(64), dim3(256), 0, s, d_out, d_list, d_count, d_over, d_over_count); SMI_CHIM_CHECK("k_collect_overflow"); }
-            uint32_t n_over = 0;
-            {
-                uint32_t *pw = static_cast<uint32_t *>(pin_words(ctx));
-                SMI_HIP(hipMemcpyAsync(pw ? pw : &n_over, d_over_count, 4, hipMemcpyDeviceToHost, s));
-                SMI_HIP(hipStreamSynchronize(s));
-                if (pw) n_over = *pw;
-            }
-#ifdef SMI_MEASURE
-            if (getenv("SMI_CHIM_STATS")) {
-                uint32_t h[16];
-                SMI_HIP(hipMemcpy(h, d_count, 64, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[chim stats] queue %u over %u positions %u stretches %u ad-entries %u | caps hit: st/read %u st-queue %u ad-queue %u matches %u slot %u gated %u pos-queue %u accepted %u\n",
-                        h[0], h[1], h[2], h[3], h[4], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15]);
-            }
-#endif
-            if (n_over) {
-                std::vector<uint32_t> over(n_over);
-                std::vector<uint64_t> offs(n + 1);
-                SMI_HIP(hipMemcpyAsync(over.data(), d_over, (size_t)n_over * 4, hipMemcpyDeviceToHost, s));
-                SMI_HIP(hipMemcpyAsync(offs.data(), d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-                SMI_HIP(hipStreamSynchronize(s));
-                std::sort(over.begin(), over.end());  // the collection order is not deterministic; the results do not depend on it
-                std::vector<uint64_t> scr_off(n_over + 1, 0);
-                for (uint32_t i = 0; i < n_over; i++) scr_off[i + 1] = scr_off[i] + 7 * (offs[over[i] + 1] - offs[over[i]] + 8);
-                uint64_t *d_scr_off = nullptr;
-                int32_t *d_scr = nullptr;
-                uint32_t *d_over_sorted = nullptr;
-                SMI_HIP(hipMalloc(&d_scr_off, (n_over + 1) * 8));
-                hipError_t e = hipMalloc(&d_scr, scr_off[n_over] * 4);
-                if (e == hipSuccess) e = hipMalloc(&d_over_sorted, (size_t)n_over * 4);
-                if (e != hipSuccess) {
-                    (void)hipFree(d_scr_off);
-                    (void)hipFree(d_scr);
-                    return hip_fail(e, "hipMalloc (K-CHIM-S scratch)");
-                }
-                SMI_HIP(hipMemcpyAsync(d_scr_off, scr_off.data(), (n_over + 1) * 8, hipMemcpyHostToDevice, s));
-                SMI_HIP(hipMemcpyAsync(d_over_sorted, over.data(), (size_t)n_over * 4, hipMemcpyHostToDevice, s));
-                const unsigned gs = (unsigned)std::min<uint32_t>(n_over, 4096);
-                if (tl == 27)
-                    { hipLaunchKernelGGL((k_chimera_serial<27, 22>), dim3(gs), dim3(64), 0, s, d_planes, st, d_pstart, d_offsets, d_over_sorted, n_over, d_scr_off, d_scr, P, d_out); SMI_CHIM_CHECK("k_chimera_serial"); }
-                else
-                    { hipLaunchKernelGGL((k_chimera_serial<22, 25>), dim3(gs), dim3(64), 0, s, d_planes, st, d_pstart, d_offsets, d_over_sorted, n_over, d_scr_off, d_scr, P, d_out); SMI_CHIM_CHECK("k_chimera_serial"); }
-                hipError_t e2 = hipStreamSynchronize(s);
-                (void)hipFree(d_scr_off);
-                (void)hipFree(d_scr);
-                (void)hipFree(d_over_sorted);
-                if (e2 != hipSuccess) return hip_fail(e2, "k_chimera_serial");
-            }
+            if (int rc = chim_collect_overflow(R, &n_over)) return rc;  // 5
+            if (n_over)
+                if (int rc = chim_serial(R, n_over)) return rc;  // 6
         }
     }
     if (int rc = time_end(ctx, SMI_K_CHIMERA, s)) return rc;

@@ -709,15 +709,9 @@ int umi_cluster_own_device(smi_ctx *ctx, const uint8_t *d_mat, int n, const floa
     const int ced = cfg.complete_link_ed;
     // Room: every array of a step has at most n + 2 entries of at most 8 bytes, and a call takes fewer than 48 of them on either side.
     const size_t room = 48 * ((size_t)n + 64) * 8;
-    if (ctx->umi_own_bytes < room) {
-        if (ctx->umi_own) (void)hipFree(ctx->umi_own);
-        ctx->umi_own = nullptr;
-        ctx->umi_own_bytes = 0;
-        SMI_HIP(hipMalloc(&ctx->umi_own, room + room / 4));
-        ctx->umi_own_bytes = room + room / 4;
-    }
+    SMI_OWN_RC(ctx->umi_own.need(room));
     SMI_OWN_RC(ensure_host_buf(ctx, smi_ctx::HB_OWN, room));
-    Arena D{static_cast<char *>(ctx->umi_own), room, 0}, H{static_cast<char *>(ctx->host_buf[smi_ctx::HB_OWN]), room, 0};
+    Arena D{ctx->umi_own.as<char>(), room, 0}, H{ctx->host_buf[smi_ctx::HB_OWN].as<char>(), room, 0};
     bool short_of_room = false;
     auto up = [](size_t x) { return (x + 63) & ~(size_t)63; };
     auto block = [&](size_t bytes) {

@@ -55,37 +55,57 @@ Pyramid pyramid_of(const smi_ctx *ctx) {
     return p;
 }
 
-void *pin_words(smi_ctx *ctx) {
-    if (!ctx->pin_words && hipHostMalloc(&ctx->pin_words, 4096, hipHostMallocDefault) != hipSuccess) ctx->pin_words = nullptr;
-    return ctx->pin_words;
-}
-
-int ensure_host_buf(smi_ctx *ctx, int which, size_t bytes) {
-    if (ctx->host_buf_bytes[which] >= bytes) return SMI_OK;
-    if (ctx->host_buf[which]) SMI_HIP(hipHostFree(ctx->host_buf[which]));
-    ctx->host_buf[which] = nullptr;
-    ctx->host_buf_bytes[which] = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    SMI_HIP(hipHostMalloc(&ctx->host_buf[which], want, hipHostMallocDefault));
-    ctx->host_buf_bytes[which] = want;
+int side_fork(smi_ctx *ctx, hipStream_t s, SideFork *f, bool one_stream) {
+    f->ctx = ctx;
+    f->side = s;
+    if (one_stream) return SMI_OK;
+    if (!ctx->side_stream) {
+        SMI_HIP(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
+        SMI_HIP(hipEventCreateWithFlags(&ctx->side_fork_ev, hipEventDisableTiming));
+        SMI_HIP(hipEventCreateWithFlags(&ctx->side_join_ev, hipEventDisableTiming));
+    }
+    SMI_HIP(hipEventRecord(ctx->side_fork_ev, s));
+    SMI_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->side_fork_ev, 0));
+    f->side = ctx->side_stream;
+    f->armed = true;
     return SMI_OK;
 }
 
-static int ensure_stage(smi_ctx *ctx, size_t in_bytes, size_t out_bytes) {
-    if (in_bytes > ctx->stage_in_bytes) {
-        if (ctx->stage_in) SMI_HIP(hipFree(ctx->stage_in));
-        ctx->stage_in = nullptr;
-        ctx->stage_in_bytes = 0;
-        SMI_HIP(hipMalloc(&ctx->stage_in, in_bytes));
-        ctx->stage_in_bytes = in_bytes;
+int SideFork::join(hipStream_t s) {
+    if (!armed) return SMI_OK;
+    SMI_HIP(hipEventRecord(ctx->side_join_ev, side));  // (a failure here or below leaves the guard armed: the destructor waits)
+    SMI_HIP(hipStreamWaitEvent(s, ctx->side_join_ev, 0));
+    armed = false;  // s is ordered behind the side stream from here on
+    return SMI_OK;
+}
+
+int take_scan_tmp(smi_ctx *ctx, size_t bytes, hipStream_t s) {
+    ctx->fq_swept_text = nullptr;
+    return ctx->scan_tmp.need(bytes, s);
+}
+
+WordRead::WordRead(smi_ctx *ctx, hipStream_t s_) : s(s_) {
+    auto &b = ctx->pin_words;  // (not through need(): a call that succeeds without the words must leave no error text behind)
+    if (!b.p && hipHostMalloc(&b.p, 4096, hipHostMallocDefault) == hipSuccess) b.cap = 4096;
+    if (!b.cap) b.p = nullptr, (void)hipGetLastError();
+    pw = b.as<uint8_t>();
+}
+
+int WordRead::add(void *dst, const void *d_src, size_t bytes) {
+    if (n == 4 || used + bytes > 4096) {
+        set_error("WordRead: more than four items or 4 KiB");
+        return SMI_ERR_INVALID;
     }
-    if (out_bytes > ctx->stage_out_bytes) {
-        if (ctx->stage_out) SMI_HIP(hipFree(ctx->stage_out));
-        ctx->stage_out = nullptr;
-        ctx->stage_out_bytes = 0;
-        SMI_HIP(hipMalloc(&ctx->stage_out, out_bytes));
-        ctx->stage_out_bytes = out_bytes;
-    }
+    SMI_HIP(hipMemcpyAsync(pw ? static_cast<void *>(pw + used) : dst, d_src, bytes, hipMemcpyDeviceToHost, s));
+    item[n++] = {dst, used, bytes};
+    used += (bytes + 7) & ~(size_t)7;
+    return SMI_OK;
+}
+
+int WordRead::wait() {
+    SMI_HIP(hipStreamSynchronize(s));
+    if (pw)
+        for (int k = 0; k < n; k++) std::memcpy(item[k].dst, pw + item[k].off, item[k].bytes);
     return SMI_OK;
 }
 
@@ -248,35 +268,20 @@ int smi_ctx_destroy(smi_ctx *ctx) {
         (void)hipFree(ctx->rank);
         (void)hipFree(ctx->block_counts);
     }
-    (void)hipFree(ctx->bc_codes);
     (void)hipFree(ctx->claim_ring);
     for (hipEvent_t ev : ctx->claim_done)
         if (ev) (void)hipEventDestroy(ev);
-    (void)hipFree(ctx->stage_in);
-    (void)hipFree(ctx->scan_tmp);
-    (void)hipFree(ctx->arena);
-    (void)hipFree(ctx->umi_dist);
-    (void)hipFree(ctx->deflate_scratch);
     region_work_free(ctx->region_work);
-    (void)hipFree(ctx->chim_list);
-    (void)hipFree(ctx->chim_slots);
-    (void)hipFree(ctx->chim_work);
-    (void)hipFree(ctx->chim_flat);
-    (void)hipFree(ctx->umi_own);
-    (void)hipFree(ctx->umi_plan);
-    if (ctx->pin_words) (void)hipHostFree(ctx->pin_words);
-    (void)hipHostFree(ctx->host_out[0]);
-    (void)hipHostFree(ctx->host_out[1]);
-    for (void *hb : ctx->host_buf) (void)hipHostFree(hb);
-    (void)hipFree(ctx->stage_out);
     for (int k = 0; k < SMI_K_COUNT; k++) {
         if (ctx->kev[k][0]) (void)hipEventDestroy(ctx->kev[k][0]);
         if (ctx->kev[k][1]) (void)hipEventDestroy(ctx->kev[k][1]);
     }
-    if (ctx->side_fork) (void)hipEventDestroy(ctx->side_fork);
-    if (ctx->side_join) (void)hipEventDestroy(ctx->side_join);
+    if (ctx->side_fork_ev) (void)hipEventDestroy(ctx->side_fork_ev);
+    if (ctx->side_join_ev) (void)hipEventDestroy(ctx->side_join_ev);
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    // the scratch buffers free themselves in `delete`, behind the destruction of the events and streams (they used to be freed in front of
+    // it): the device is set and the stream drained above, and hipFree waits for the device, which is what makes that safe
     delete ctx;
     return SMI_OK;
 }
@@ -398,10 +403,10 @@ int smi_set_barcode_set(smi_ctx *ctx, const uint64_t *keys, size_t n, int mode) 
         }
         k32[i] = (uint32_t)keys[i];
     }
-    if (int rc = ensure_stage(ctx, std::max<size_t>(n * 4, 16), 0)) return rc;
-    if (n) SMI_HIP(hipMemcpyAsync(ctx->stage_in, k32.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = ctx->stage_in.need(std::max<size_t>(n * 4, 16))) return rc;
+    if (n) SMI_HIP(hipMemcpyAsync(ctx->stage_in.p, k32.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
     SMI_HIP(hipStreamSynchronize(ctx->stream));
-    return smi_set_barcode_set_device(ctx, (const uint32_t *)ctx->stage_in, n, mode, ctx->stream);
+    return smi_set_barcode_set_device(ctx, ctx->stage_in.as<const uint32_t>(), n, mode, ctx->stream);
 }
 
 static int check_match_args(smi_ctx *ctx, const void *in, const void *out, size_t n, int max_ed) {
@@ -431,12 +436,13 @@ int smi_bc_match_batch(smi_ctx *ctx, const smi_bc_window *windows, size_t n, int
                        smi_bc_result *out) {
     if (int rc = check_match_args(ctx, windows, out, n, max_ed)) return rc;
     if (!n) return SMI_OK;
-    if (int rc = ensure_stage(ctx, n * sizeof(smi_bc_window), n * sizeof(smi_bc_result))) return rc;
-    SMI_HIP(hipMemcpyAsync(ctx->stage_in, windows, n * sizeof(smi_bc_window), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = launch_bc_match(ctx, (const smi_bc_window *)ctx->stage_in, n, max_ed, five_prime,
-                                 (smi_bc_result *)ctx->stage_out, ctx->stream))
+    if (int rc = ctx->stage_in.need(n * sizeof(smi_bc_window))) return rc;
+    if (int rc = ctx->stage_out.need(n * sizeof(smi_bc_result))) return rc;
+    SMI_HIP(hipMemcpyAsync(ctx->stage_in.p, windows, n * sizeof(smi_bc_window), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = launch_bc_match(ctx, ctx->stage_in.as<const smi_bc_window>(), n, max_ed, five_prime,
+                                 ctx->stage_out.as<smi_bc_result>(), ctx->stream))
         return rc;
-    SMI_HIP(hipMemcpyAsync(out, ctx->stage_out, n * sizeof(smi_bc_result), hipMemcpyDeviceToHost, ctx->stream));
+    SMI_HIP(hipMemcpyAsync(out, ctx->stage_out.p, n * sizeof(smi_bc_result), hipMemcpyDeviceToHost, ctx->stream));
     SMI_HIP(hipStreamSynchronize(ctx->stream));
     return SMI_OK;
 }
@@ -762,13 +768,13 @@ int smi_chimera_last_counts(smi_ctx *ctx, uint32_t out[16]) {
         return SMI_ERR_INVALID;
     }
     if (int rc = bind(ctx)) return rc;
-    if (!ctx->chim_counts_valid || !ctx->chim_list) {
+    if (!ctx->chim_counts_valid || !ctx->chim_list.p) {
         set_error("smi_chimera_last_counts: no smi_chimera_device call on this context has succeeded yet");
         return SMI_ERR_INVALID;
     }
     // the call's stream may be the caller's and gone by now: wait for the device, which includes it (this is a diagnostic call, not a hot one)
     SMI_HIP(hipDeviceSynchronize());
-    SMI_HIP(hipMemcpy(out, ctx->chim_list, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SMI_HIP(hipMemcpy(out, ctx->chim_list.p, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return SMI_OK;
 }
 

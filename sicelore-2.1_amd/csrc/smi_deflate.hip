@@ -661,15 +661,7 @@ int launch_deflate(smi_ctx *ctx, const uint8_t *d_in, size_t n_bytes, uint8_t *d
 }
 
 int ensure_deflate_scratch(smi_ctx *ctx, size_t n_bytes, size_t extra_bytes) {
-    const size_t want = deflate_scratch_bytes(n_bytes) + extra_bytes;
-    if (ctx->deflate_scratch_bytes >= want) return SMI_OK;
-    if (ctx->deflate_scratch) SMI_HIP(hipFree(ctx->deflate_scratch));
-    ctx->deflate_scratch = nullptr;
-    ctx->deflate_scratch_bytes = 0;
-    const size_t grown = want + want / 4;
-    SMI_HIP(hipMalloc(&ctx->deflate_scratch, grown));
-    ctx->deflate_scratch_bytes = grown;
-    return SMI_OK;
+    return ctx->deflate_scratch.need(deflate_scratch_bytes(n_bytes) + extra_bytes);
 }
 
 int deflate_pair(smi_ctx *ctx, const uint8_t *d_a, size_t na, const uint8_t *d_b, size_t nb, uint8_t **d_za, uint8_t **d_zb, uint64_t **d_totals,
@@ -677,7 +669,7 @@ int deflate_pair(smi_ctx *ctx, const uint8_t *d_a, size_t na, const uint8_t *d_b
     const size_t ca = (deflate_bound(na) + 255) & ~(size_t)255, cb = (deflate_bound(nb) + 255) & ~(size_t)255;
     const size_t work = (deflate_scratch_bytes(std::max(na, nb)) + 255) & ~(size_t)255;
     if (int rc = ensure_deflate_scratch(ctx, std::max(na, nb), ca + cb + 1024)) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->deflate_scratch);
+    uint8_t *base = ctx->deflate_scratch.as<uint8_t>();
     *d_za = base + work;
     *d_zb = base + work + ca;
     *d_totals = reinterpret_cast<uint64_t *>(base + work + ca + cb);
@@ -726,14 +718,8 @@ extern "C" int smi_bgzf_deflate_device(smi_ctx *ctx, const uint8_t *in, size_t n
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t o_bb = al(n_blocks * (size_t)kSlotBytes), o_offs = o_bb + al(n_blocks * 4), o_tmp = o_offs + al((n_blocks + 1) * 8), o_state = o_tmp + al(scan_tmp),
                  o_crc = o_state + 256, o_in = o_crc + al(n_blocks * 4), o_out = o_in + al(n_in + 64), end = o_out + al(bound);
-    if (ctx->deflate_scratch_bytes < end) {
-        if (ctx->deflate_scratch) SMI_HIP(hipFree(ctx->deflate_scratch));
-        ctx->deflate_scratch = nullptr;
-        ctx->deflate_scratch_bytes = 0;
-        SMI_HIP(hipMalloc(&ctx->deflate_scratch, end + end / 4));
-        ctx->deflate_scratch_bytes = end + end / 4;
-    }
-    uint8_t *base = static_cast<uint8_t *>(ctx->deflate_scratch);
+    if (int rc = ctx->deflate_scratch.need(end)) return rc;
+    uint8_t *base = ctx->deflate_scratch.as<uint8_t>();
     uint32_t *d_bb = reinterpret_cast<uint32_t *>(base + o_bb), *d_state = reinterpret_cast<uint32_t *>(base + o_state), *d_crc = reinterpret_cast<uint32_t *>(base + o_crc);
     uint64_t *d_offs = reinterpret_cast<uint64_t *>(base + o_offs);
     uint8_t *d_in = base + o_in, *d_out = base + o_out;
@@ -769,6 +755,6 @@ extern "C" int smi_gzip_device(smi_ctx *ctx, const uint8_t *d_in, size_t n_bytes
     }
     SMI_HIP(hipSetDevice(ctx->device));
     if (int rc = ensure_deflate_scratch(ctx, n_bytes, 0)) return rc;
-    return launch_deflate(ctx, d_in, n_bytes, d_out, out_cap, static_cast<uint8_t *>(ctx->deflate_scratch), d_total, raw_deflate ? 0 : 1,
+    return launch_deflate(ctx, d_in, n_bytes, d_out, out_cap, ctx->deflate_scratch.as<uint8_t>(), d_total, raw_deflate ? 0 : 1,
                           (hipStream_t)stream);
 }

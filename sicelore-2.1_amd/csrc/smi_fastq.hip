@@ -189,17 +189,6 @@ __global__ __launch_bounds__(256) void k_fq_gather(const uint8_t *__restrict__ t
     }
 }
 
-static int ensure_scan_tmp(smi_ctx *ctx, size_t bytes) {
-    if (bytes > ctx->scan_tmp_bytes) {
-        if (ctx->scan_tmp) SMI_HIP(hipFree(ctx->scan_tmp));
-        ctx->scan_tmp = nullptr;
-        ctx->scan_tmp_bytes = 0;
-        SMI_HIP(hipMalloc(&ctx->scan_tmp, bytes));
-        ctx->scan_tmp_bytes = bytes;
-    }
-    return SMI_OK;
-}
-
 // number of lines of a text in device memory (a last line without newline counts): what the chunk workers size their buffers by --
 // a host-side memchr pass over a 1.2 GB chunk costs 50-130 ms, this 0.25 ms
 __global__ __launch_bounds__(kFqBlock) void k_fq_count_total(const uint8_t *__restrict__ text, size_t n, unsigned long long *__restrict__ total) {
@@ -214,8 +203,8 @@ __global__ __launch_bounds__(kFqBlock) void k_fq_count_total(const uint8_t *__re
 int launch_count_lines(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, size_t *n_lines, hipStream_t s) {
     *n_lines = 0;
     if (!n_bytes) return SMI_OK;
-    if (int rc = ensure_scan_tmp(ctx, 256)) return rc;
-    unsigned long long *d_total = (unsigned long long *)ctx->scan_tmp;
+    if (int rc = take_scan_tmp(ctx, 256, s)) return rc;
+    unsigned long long *d_total = ctx->scan_tmp.as<unsigned long long>();
     SMI_HIP(hipMemsetAsync(d_total, 0, 8, s));
     const unsigned grid = (unsigned)std::min<size_t>((n_bytes + kFqTile - 1) / kFqTile, 256 * 16);
     hipLaunchKernelGGL(k_fq_count_total, dim3(grid), dim3(kFqBlock), 0, s, d_text, n_bytes, d_total);
@@ -255,7 +244,7 @@ __global__ void k_fq_sweep_lines(const uint8_t *__restrict__ text, size_t n_byte
 // full read of the chunk).
 int launch_fastq_sweep(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, size_t *n_lines, hipStream_t s) {
     *n_lines = 0;
-    ctx->fq_swept_text = nullptr;
+    ctx->fq_swept_text = nullptr;  // (also where nothing is swept below)
     if (!n_bytes) return SMI_OK;
     if (getenv("SMI_FQ_TWO_SWEEPS") != nullptr) return launch_count_lines(ctx, d_text, n_bytes, n_lines, s);
     const size_t n_blocks = (n_bytes + kFqTile - 1) / kFqTile;
@@ -265,8 +254,8 @@ int launch_fastq_sweep(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, size
     SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_a, (uint32_t *)nullptr, (uint64_t *)nullptr, (int)n_blocks, s));
     SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_b, (uint32_t *)nullptr, (uint64_t *)nullptr, (int)max_rec + 1, s));
     const FqScratch L = fq_scratch(n_bytes, false, std::max(cub_a, cub_b));
-    if (int rc = ensure_scan_tmp(ctx, L.total)) return rc;
-    uint8_t *tmp = (uint8_t *)ctx->scan_tmp;
+    if (int rc = take_scan_tmp(ctx, L.total, s)) return rc;
+    uint8_t *tmp = ctx->scan_tmp.as<uint8_t>();
     uint32_t *counts = (uint32_t *)tmp;
     uint64_t *bases = (uint64_t *)(tmp + L.off_base);
     uint64_t *d_lines = (uint64_t *)(tmp + L.off_scal + 128);
@@ -276,12 +265,9 @@ int launch_fastq_sweep(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, size
     hipLaunchKernelGGL(k_fq_sweep_lines, dim3(1), dim3(1), 0, s, d_text, n_bytes, n_blocks, (const uint64_t *)bases, (const uint32_t *)counts, d_lines);
     SMI_HIP(hipGetLastError());
     uint64_t h = 0;
-    uint64_t *pw = static_cast<uint64_t *>(pin_words(ctx));
-    SMI_HIP(hipMemcpyAsync(pw ? pw : &h, d_lines, 8, hipMemcpyDeviceToHost, s));
-    SMI_HIP(hipStreamSynchronize(s));
-    if (pw) h = *pw;
+    if (int rc = read_words(ctx, s, &h, d_lines, 8)) return rc;
     *n_lines = (size_t)h;
-    ctx->fq_swept_text = d_text;
+    ctx->fq_swept_text = d_text;  // the flags are in scan_tmp until its next taker
     ctx->fq_swept_bytes = n_bytes;
     return SMI_OK;
 }
@@ -294,10 +280,9 @@ int launch_fastq_line_starts(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes
     size_t cub_a = 0;
     SMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, cub_a, (uint32_t *)nullptr, (uint64_t *)nullptr, (int)((n_bytes + kFqTile - 1) / kFqTile), s));
     const FqScratch L = fq_scratch(n_bytes, false, cub_a);
-    const bool swept = ctx->fq_swept_text == d_text && ctx->fq_swept_bytes == n_bytes && L.total <= ctx->scan_tmp_bytes;
-    ctx->fq_swept_text = nullptr;
-    if (int rc = ensure_scan_tmp(ctx, L.total)) return rc;
-    uint8_t *tmp = (uint8_t *)ctx->scan_tmp;
+    const bool swept = ctx->fq_swept_text == d_text && ctx->fq_swept_bytes == n_bytes && L.total <= ctx->scan_tmp.cap;  // (read before the buffer is taken)
+    if (int rc = take_scan_tmp(ctx, L.total, s)) return rc;
+    uint8_t *tmp = ctx->scan_tmp.as<uint8_t>();
     uint32_t *counts = (uint32_t *)tmp;
     uint64_t *bases = (uint64_t *)(tmp + L.off_base);
     uint64_t *masks = (uint64_t *)(tmp + L.off_masks);
@@ -329,10 +314,9 @@ int launch_fastq_index(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, uint
     const FqScratch L = fq_scratch(n_bytes, two_sweeps, std::max(cub_a, cub_b));
     const size_t n_blocks = L.n_blocks, off_base = L.off_base, off_scal = L.off_scal, off_masks = L.off_masks, off_cub = L.off_cub;
     // launch_fastq_sweep ran over this very text just before: its flags, counts and bases are in the scratch (unless the scratch has to grow now)
-    const bool swept = !two_sweeps && ctx->fq_swept_text == d_text && ctx->fq_swept_bytes == n_bytes && L.total <= ctx->scan_tmp_bytes;
-    ctx->fq_swept_text = nullptr;
-    if (int rc = ensure_scan_tmp(ctx, L.total)) return rc;
-    uint8_t *tmp = (uint8_t *)ctx->scan_tmp;
+    const bool swept = !two_sweeps && ctx->fq_swept_text == d_text && ctx->fq_swept_bytes == n_bytes && L.total <= ctx->scan_tmp.cap;  // (read before the buffer is taken)
+    if (int rc = take_scan_tmp(ctx, L.total, s)) return rc;
+    uint8_t *tmp = ctx->scan_tmp.as<uint8_t>();
     uint32_t *counts = (uint32_t *)tmp;
     uint64_t *bases = (uint64_t *)(tmp + off_base);
     FqTotals *d_tot = (FqTotals *)(tmp + off_scal);
@@ -360,18 +344,11 @@ int launch_fastq_index(smi_ctx *ctx, const uint8_t *d_text, size_t n_bytes, uint
     {
         // the sum of all sequence lengths rides on the same wait: lengths behind the last record are 0, so the last offset of the buffer is
         // the total whatever the record count turns out to be (a text that fills the buffer to its last entry is refused below)
-        static_assert(sizeof(FqTotals) % 8 == 0 && sizeof(FqTotals) + 8 <= 256, "the total sits behind the scalars in the pinned words");
-        uint8_t *pw = static_cast<uint8_t *>(pin_words(ctx));
-        uint64_t tot = 0;
-        SMI_HIP(hipMemcpyAsync(pw ? (void *)pw : (void *)&h, d_tot, sizeof h, hipMemcpyDeviceToHost, s));
+        WordRead r(ctx, s);
+        if (int rc = r.add(&h, d_tot, sizeof h)) return rc;
         if (total_bases)
-            SMI_HIP(hipMemcpyAsync(pw ? (void *)(pw + sizeof h) : (void *)&tot, d_offsets + (cap_records - 1), 8, hipMemcpyDeviceToHost, s));
-        SMI_HIP(hipStreamSynchronize(s));
-        if (pw) {
-            std::memcpy(&h, pw, sizeof h);
-            std::memcpy(&tot, pw + sizeof h, 8);
-        }
-        if (total_bases) *total_bases = tot;
+            if (int rc = r.add(total_bases, d_offsets + (cap_records - 1), 8)) return rc;
+        if (int rc = r.wait()) return rc;
     }
     if (h.overflow & 1u) {
         set_error("smi_fastq_index_device: line buffer too small");

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "sicelore_mi.h"
+#include "smi_growbuf.h"
 
 namespace smi {
 
@@ -138,6 +139,25 @@ struct Pyramid {
     uint32_t nt_cap;     // its slots
 };
 
+// The two places a context's grow-only scratch lives (smi_growbuf.h): device memory and page-locked host memory.  Failures are reported
+// through hip_fail, as everywhere.
+struct DeviceMem {
+    static int alloc(void **p, size_t bytes) { SMI_HIP(hipMalloc(p, bytes)); return SMI_OK; }
+    static int release(void *p) { SMI_HIP(hipFree(p)); return SMI_OK; }
+    static int wait(hipStream_t s) { SMI_HIP(hipStreamSynchronize(s)); return SMI_OK; }
+    static int copy_front(void *dst, const void *src, size_t bytes, hipStream_t s) {
+        if (bytes) SMI_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+        return wait(s);
+    }
+};
+struct PinnedMem {
+    static int alloc(void **p, size_t bytes) { SMI_HIP(hipHostMalloc(p, bytes, hipHostMallocDefault)); return SMI_OK; }
+    static int release(void *p) { SMI_HIP(hipHostFree(p)); return SMI_OK; }
+};
+template <unsigned DIV = 0, size_t ADD = 0>
+using DevScratch = GrowBuf<DeviceMem, DIV, ADD>;
+using PinScratch = GrowBuf<PinnedMem, 4, 4096>;  // downloads of one run are of similar size; a page more spares the regrow by a few bytes
+
 }  // namespace smi
 
 struct smi_ctx {
@@ -174,8 +194,6 @@ struct smi_ctx {
     hipEvent_t claim_done[64] = {};  // per slot (kClaimSlots): recorded behind the launch that used it; the slot's next user waits for it on its own stream
     int scan_resident[8] = {};  // blocks of each k_scan instantiation a CU holds at once (0: not asked yet)
     int n_cus = 0;
-    uint8_t *bc_codes = nullptr;  // K-BC1, table path under SMI_BC1_TWO_KERNELS only: one byte per (read, offset) between the two kernels (grow-only, private to a context or lane)
-    size_t bc_codes_bytes = 0;
     uint32_t *fine = nullptr;
     uint32_t *rank = nullptr;
     uint32_t *block_counts = nullptr;  // scratch for the rank scan
@@ -187,61 +205,81 @@ struct smi_ctx {
     bool ev_valid = false;
     hipEvent_t kev[SMI_K_COUNT][2] = {};       // per kernel id (smi_kernel_ms)
     bool kev_valid[SMI_K_COUNT] = {};
-    // staging buffers of the *_batch entry points (grown on demand)
-    void *stage_in = nullptr;
-    void *stage_out = nullptr;
-    size_t stage_in_bytes = 0, stage_out_bytes = 0;
     hipStream_t stream = nullptr;  // private stream of the *_batch entry points
     hipStream_t side_stream = nullptr;  // created on first use: independent kernels of one call run beside the caller's stream (K-WNAME || K-WRITE)
-    hipEvent_t side_fork = nullptr, side_join = nullptr;
-    void *scan_tmp = nullptr;      // scratch of the FASTQ indexer (block counts + hipcub temp storage)
-    size_t scan_tmp_bytes = 0;
+    hipEvent_t side_fork_ev = nullptr, side_join_ev = nullptr;  // smi::side_fork / SideFork::join
     const smi_ctx *set_owner = nullptr;  // worker lane (smi_ctx_create_lane): the pyramid pointers above belong to this context
-    uint32_t *chim_list = nullptr; // K-CHIM: queue of the reads the filter pass could not clear (+ its counter), grow-only
-    size_t chim_list_bytes = 0;
     bool chim_counts_valid = false;  // the sixteen counters at chim_list are those of a smi_chimera_device that returned SMI_OK (smi_chimera_last_counts)
-    void *chim_slots = nullptr;    // K-CHIM: matches handed from the exact TSO scan to the rules kernel
-    size_t chim_slot_bytes = 0;
-    void *chim_work = nullptr;     // K-CHIM second generation: per-read heads, the global queue of positions to align, their error counts (grow-only)
-    size_t chim_work_bytes = 0;
-    void *umi_own = nullptr;       // ClusterOne_MyClustering on the device: index / count / sum scratch of one large group (grow-only)
-    size_t umi_own_bytes = 0;
-    const uint8_t *fq_swept_text = nullptr;  // launch_fastq_sweep's text while its flags are valid in scan_tmp (consumed by the next launch_fastq_index)
+    const uint8_t *fq_swept_text = nullptr;  // launch_fastq_sweep's text while its flags are valid in scan_tmp: cleared by whoever takes scan_tmp (smi::take_scan_tmp)
     size_t fq_swept_bytes = 0;
-    void *pin_words = nullptr;     // 4 KiB of page-locked host memory for read-backs of a few words (pin_words() in smi_ctx.hip)
-    void *umi_plan = nullptr;      // K-UMI: per group its pairs in the flat kernel / tiles in the tiled one, and their prefix sums (grow-only)
-    size_t umi_plan_bytes = 0;
-    void *chim_flat = nullptr;     // K-CHIM-A second generation: owner of every plane word, gate / bound / trigger words, verdicts (grow-only)
-    size_t chim_flat_bytes = 0;
-    void *arena = nullptr;         // device memory of the chunk workers (smi_worker.hip), grow-only
-    size_t arena_bytes = 0;
-    uint8_t *host_out[2] = {nullptr, nullptr};  // pinned: passed / failed text of the last smi_scanfastq_pass2_chunk
-    size_t host_out_bytes[2] = {0, 0};
     std::vector<smi_scan_result> host_scan;  // its per-record results when asked for
     std::vector<smi_bc_result> host_bc;
     // packed chunk workers: page-locked, grow-only host buffers (index, offsets, planes, quality tails / sums, decisions)
     enum { HB_RECS = 0, HB_OFFS, HB_PSTART, HB_PLANES, HB_QTAIL, HB_QSUM, HB_CHIM, HB_FOFFS, HB_FSRC, HB_SCAN, HB_BC, HB_RANK, HB_RKEYS, HB_RBITS, HB_REGION, HB_OWN, HB_COUNT };
     smi_scan_stats host_stats = {};  // scan statistics of the last packed pass-2 chunk (want_results)
-    void *umi_dist = nullptr;      // K-UMI matrices of the device UMI stage (smi_assignumis_chunk), grow-only
-    size_t umi_dist_bytes = 0;
+    // ---- Grow-only scratch (smi_growbuf.h), private to a context or lane.  Each buffer owns its block: need(bytes) is a compare while the block
+    // suffices, a grown block carries the head-room named here, and the destructor frees (smi_ctx_destroy has set the device and drained the
+    // stream by then).  Per buffer: who writes it.  Contents are dead when the call that wrote them returns, with three exceptions: scan_tmp's
+    // sweep flags (until the next taker), the sixteen counters at the head of chim_list (smi_chimera_last_counts), and host_out / host_scan /
+    // host_bc / host_buf (what the last chunk call handed its caller).
+    smi::DevScratch<> stage_in, stage_out;  // the *_batch entry points (smi_ctx.hip): their arguments and results on the device
+    smi::DevScratch<> scan_tmp;             // the FASTQ indexer (block counts, newline flags, hipcub storage) and K-WRITE (lengths, plan rows, hipcub storage), through take_scan_tmp() only
+    smi::DevScratch<> chim_list;            // K-CHIM: sixteen counters, then the queue of the reads the filter pass could not clear and the overflow queues behind it (sized by the batch)
+    smi::DevScratch<8> chim_flat;           // K-CHIM-A second generation: owner of every plane word, gate / bound / trigger words, verdicts (sized by the planes: chunks of one run are of similar size)
+    smi::DevScratch<4> chim_slots;          // K-CHIM: matches handed from the exact TSO scan to the rules kernel (sized by the queue length, which varies from chunk to chunk)
+    smi::DevScratch<4> chim_work;           // K-CHIM second generation: per-read heads, the queue of positions to align, their error counts, chain C's stretches and entries (chim_work_layout)
+    smi::DevScratch<4> umi_own;             // ClusterOne_MyClustering on the device (smi_cluster.hip): index / count / sum scratch of one large group
+    smi::DevScratch<4> umi_plan;            // K-UMI (smi_umi.hip): per group its pairs in the flat kernel / tiles in the tiled one, and their prefix sums
+    smi::DevScratch<4, 4096> umi_dist;      // K-UMI matrices of the device UMI stage (smi_assignumis_chunk)
+    smi::DevScratch<4> arena;               // device memory of the chunk workers (smi_worker.hip): chunks of one run are of similar size
+    smi::DevScratch<4> deflate_scratch;     // K-DEFLATE: block slots, sizes, offsets, scan storage; deflate_pair's two members behind them
+    smi::DevScratch<4> bc_codes;            // K-BC1, table path under SMI_BC1_TWO_KERNELS only: one byte per (read, offset) between the two kernels
+    smi::GrowBuf<smi::PinnedMem> pin_words; // 4 KiB for read-backs of a few words (smi::WordRead), allocated on first use; valid until the next read-back
+    smi::PinScratch host_out[2];            // passed / failed text of the last smi_scanfastq_pass2_chunk[_packed]
+    smi::PinScratch host_buf[HB_COUNT];     // packed chunk workers and the UMI stage: index, offsets, planes, decisions, keys (ensure_host_buf)
     void *region_work = nullptr;      // host scratch of the region grouping (smi_cluster.hip), kept between calls
     int32_t au_last_path = 0;         // SMI_AU_PATH_* of the last smi_assignumis_chunk of this context or lane (smi_assignumis_last_path)
-    void *deflate_scratch = nullptr;  // K-DEFLATE: block slots, sizes, offsets, scan storage (grow-only)
-    size_t deflate_scratch_bytes = 0;
-    void *host_buf[HB_COUNT] = {};
-    size_t host_buf_bytes[HB_COUNT] = {};
 };
 
 namespace smi {
-// work forked onto a context's side stream: unless disarmed (the join is in place), leaving the scope waits for the side stream -- an error return between a
-// fork and its join does not leave kernels running on buffers the caller is about to reuse
-struct SideStreamGuard {
-    hipStream_t side;
-    bool armed;
-    ~SideStreamGuard() {
-        if (armed) (void)hipStreamSynchronize(side);
-    }
+// Work forked onto a context's side stream (created on first use): independent kernels of one call run beside the caller's stream.
+//   SideFork f;  side_fork(ctx, s, &f);  launch on f.side and on s;  f.join(s);
+// side_fork orders f.side behind what is queued on s, join orders s behind what is queued on f.side.  Leaving the scope between the two (an
+// error return) waits for the side stream, so no kernel is left running on buffers the caller is about to reuse.  one_stream (a site's
+// switch): f.side == s, nothing is forked and join does nothing.
+struct SideFork {
+    smi_ctx *ctx = nullptr;
+    hipStream_t side = nullptr;
+    bool armed = false;
+    SideFork() = default;
+    SideFork(const SideFork &) = delete;
+    ~SideFork() { if (armed) (void)hipStreamSynchronize(side); }
+    int join(hipStream_t s);
 };
+int side_fork(smi_ctx *ctx, hipStream_t s, SideFork *f, bool one_stream = false);
+// scan_tmp with room for `bytes`, for a caller that is about to write it: the sweep's flags are no longer valid (fq_swept_text is cleared;
+// launch_fastq_sweep sets it again behind its own flags).  A reader of the flags tests fq_swept_text BEFORE it takes the buffer.  Where the
+// block has to grow, work queued on s is waited for first.
+int take_scan_tmp(smi_ctx *ctx, size_t bytes, hipStream_t s);
+// A few small items read back from the device on one wait: add() queues the copy of each on s into the context's page-locked words (a copy
+// into pageable memory is staged by the runtime and blocks for about twice as long; without page-locked words, straight into dst), wait()
+// waits for s once and stores the values.  Other copies queued on s between the two share that wait.
+struct WordRead {
+    hipStream_t s;
+    struct { void *dst; size_t off, bytes; } item[4] = {};
+    int n = 0;
+    size_t used = 0;
+    uint8_t *pw;  // the page-locked words, or null where they could not be had
+    WordRead(smi_ctx *ctx, hipStream_t s_);
+    int add(void *dst, const void *d_src, size_t bytes);
+    int wait();
+};
+// the usual case: one item, one wait
+inline int read_words(smi_ctx *ctx, hipStream_t s, void *dst, const void *d_src, size_t bytes) {
+    WordRead r(ctx, s);
+    if (int rc = r.add(dst, d_src, bytes)) return rc;
+    return r.wait();
+}
 // the configurations a chunk worker of `ctx` runs with: its knobs (smi_ctx_set_knobs), then -p / -f / -w (smi_ctx_set_polya); the splitter's
 // strings point into the context (smi_ctx.hip)
 int worker_scan_config(const smi_ctx *ctx, int pass, int five_prime, int dont_search_polya, smi_scan_config *sc);
@@ -314,10 +352,7 @@ constexpr int kReadPadWords = 5;
 __host__ __device__ inline size_t plane_start(uint64_t base_offset, size_t r) { return (size_t)(base_offset >> 5) + kReadPadWords * r; }
 int launch_ends_from_planes(smi_ctx *ctx, const uint32_t *d_planes, size_t stride, const uint64_t *d_read_offsets, const uint64_t *d_rec_offsets,
                             const uint32_t *d_frag_src, size_t m, uint32_t *d_ends, int32_t *d_len, hipStream_t s, const uint32_t *d_pstart = nullptr);
-int ensure_host_buf(smi_ctx *ctx, int which, size_t bytes);
-// 4 KiB of page-locked host memory of the context for reading a few words back (a copy into pageable memory is staged by the runtime and
-// blocks for about twice as long); valid until the next call that uses it, i.e. read it before calling on -- nullptr if the allocation failed
-void *pin_words(smi_ctx *ctx);
+inline int ensure_host_buf(smi_ctx *ctx, int which, size_t bytes) { return ctx->host_buf[which].need(bytes); }
 // smi_region_group from keys sorted on the device (smi_cluster.hip)
 int region_group_from_sorted(void **work, const uint64_t *keys, size_t n_pos, int32_t n, const uint64_t *has_bits, int32_t max_dist, int keep_data_end,
                              int32_t *region, int32_t *n_done);  // *work: scratch kept between calls (ctx->region_work)

@@ -410,14 +410,8 @@ int launch_umi_dist(smi_ctx *ctx, const uint64_t *d_windows, const uint32_t *d_g
     SMI_HIP(hipcub::DeviceScan::ExclusiveScan(nullptr, cub_bytes, (UmiPlan *)nullptr, (UmiPlan *)nullptr, UmiPlanAdd(), UmiPlan{0, 0}, (int)n_groups + 1, s));
     const size_t arr = (((size_t)n_groups + 1) * sizeof(UmiPlan) + 255) & ~(size_t)255;
     const size_t need = 2 * arr + 256 + cub_bytes;
-    if (ctx->umi_plan_bytes < need) {
-        if (ctx->umi_plan) (void)hipFree(ctx->umi_plan);
-        ctx->umi_plan = nullptr;
-        ctx->umi_plan_bytes = 0;
-        SMI_HIP(hipMalloc(&ctx->umi_plan, need + need / 4));
-        ctx->umi_plan_bytes = need + need / 4;
-    }
-    char *base = static_cast<char *>(ctx->umi_plan);
+    if (int rc = ctx->umi_plan.need(need)) return rc;
+    char *base = ctx->umi_plan.as<char>();
     UmiPlan *d_cnt = reinterpret_cast<UmiPlan *>(base), *d_plan = reinterpret_cast<UmiPlan *>(base + arr);
     uint32_t *d_next = reinterpret_cast<uint32_t *>(base + 2 * arr);
     if (int rc = time_begin(ctx, SMI_K_UMI, s)) return rc;

@@ -85,24 +85,13 @@ struct Arena {
     template <class T>
     T *take(size_t count) {
         const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-        T *p = reinterpret_cast<T *>(static_cast<uint8_t *>(ctx->arena) + used);
+        T *p = reinterpret_cast<T *>(ctx->arena.as<uint8_t>() + used);
         used += bytes;
         return p;
     }
 };
 
 inline size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-int ensure_arena(smi_ctx *ctx, size_t bytes) {
-    if (ctx->arena_bytes >= bytes) return SMI_OK;
-    if (ctx->arena) SMI_HIP(hipFree(ctx->arena));
-    ctx->arena = nullptr;
-    ctx->arena_bytes = 0;
-    const size_t want = bytes + bytes / 4;  // head-room: chunks of one run are of similar size
-    SMI_HIP(hipMalloc(&ctx->arena, want));
-    ctx->arena_bytes = want;
-    return SMI_OK;
-}
 
 // The chunk's text goes to the front of the arena first and its lines are counted THERE: the buffers behind it are sized by the record
 // count, and counting on the host (memchr over ~1.2 GB) took longer than the upload.  *d_text stays valid when the arena grows afterwards.
@@ -118,23 +107,16 @@ bool is_device_text(const uint8_t *text) {
 int upload_and_count(smi_ctx *ctx, const uint8_t *text, size_t n_bytes, hipStream_t s, size_t *n_lines) {
     // the count is the first half of the record index (its one sweep over the text): launch_fastq_index continues from what it left
     if (is_device_text(text)) return launch_fastq_sweep(ctx, text, n_bytes, n_lines, s);
-    if (int rc = ensure_arena(ctx, pad(n_bytes) + 4096)) return rc;
-    SMI_HIP(hipMemcpyAsync(ctx->arena, text, n_bytes, hipMemcpyDefault, s));
-    return launch_fastq_sweep(ctx, static_cast<const uint8_t *>(ctx->arena), n_bytes, n_lines, s);
+    if (int rc = ctx->arena.need(pad(n_bytes) + 4096)) return rc;
+    SMI_HIP(hipMemcpyAsync(ctx->arena.p, text, n_bytes, hipMemcpyDefault, s));
+    return launch_fastq_sweep(ctx, ctx->arena.as<const uint8_t>(), n_bytes, n_lines, s);
 }
 // grow the arena to `bytes`, keeping its first keep_bytes (the uploaded text)
 int grow_arena_keep(smi_ctx *ctx, size_t bytes, size_t keep_bytes, hipStream_t s) {
-    if (ctx->arena_bytes >= bytes) return SMI_OK;
-    const size_t want = bytes + bytes / 4;
-    void *fresh = nullptr;
-    SMI_HIP(hipMalloc(&fresh, want));
-    if (keep_bytes) SMI_HIP(hipMemcpyAsync(fresh, ctx->arena, keep_bytes, hipMemcpyDeviceToDevice, s));
-    SMI_HIP(hipStreamSynchronize(s));
-    if (keep_bytes && ctx->fq_swept_text == ctx->arena) ctx->fq_swept_text = static_cast<const uint8_t *>(fresh);  // the swept text moved with the arena
-    SMI_HIP(hipFree(ctx->arena));
-    ctx->arena = fresh;
-    ctx->arena_bytes = want;
-    return SMI_OK;
+    const bool swept_here = keep_bytes && ctx->fq_swept_text == ctx->arena.p;
+    const int rc = ctx->arena.need_keep(bytes, keep_bytes, s);
+    if (swept_here) ctx->fq_swept_text = ctx->arena.as<const uint8_t>();  // the swept text moved with the arena
+    return rc;
 }
 
 
@@ -237,14 +219,13 @@ extern "C" int smi_scanfastq_pass2_chunk(smi_ctx *ctx, const uint8_t *text, size
         hipLaunchKernelGGL(k_chim_refused, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_chim, n, d_nfrag + 1);
         SMI_HIP(hipGetLastError());
         uint64_t nf[2] = {0, 0};
-        uint64_t *pw = static_cast<uint64_t *>(pin_words(ctx));
-        SMI_HIP(hipMemcpyAsync(pw ? pw : nf, d_nfrag, 16, hipMemcpyDeviceToHost, s));
+        WordRead r(ctx, s);
+        SMI_RC(r.add(nf, d_nfrag, 16));
         if (cfg->want_results) {  // the statistics count the split decisions; nothing else on the host reads them
             h_chim.resize(n);
             SMI_HIP(hipMemcpyAsync(h_chim.data(), d_chim, n * sizeof(smi_chimera_result), hipMemcpyDeviceToHost, s));
         }
-        SMI_HIP(hipStreamSynchronize(s));
-        if (pw) std::memcpy(nf, pw, 16);
+        SMI_RC(r.wait());
         if (nf[1]) {
             set_error("smi_scanfastq_pass2_chunk: a read outside what the splitter supports (SMI_CHIM_RANGE: longer than the plane offsets can address)");
             return SMI_ERR_INVALID;
@@ -333,17 +314,9 @@ extern "C" int smi_scanfastq_pass2_chunk(smi_ctx *ctx, const uint8_t *text, size
             std::fprintf(stderr, "pass2_chunk: sweep+count %.3f  index %.3f  split %.3f  ends..write %.3f ms (%zu records)\n", t_ph[0], t_ph[1], t_ph[2], t_ph[3], n);
         return SMI_OK;
     }
-    for (int k = 0; k < 2; k++)  // pinned, grow-only: the download runs at link speed and nothing is zero-filled
-        if (ctx->host_out_bytes[k] < down[k]) {
-            if (ctx->host_out[k]) SMI_HIP(hipHostFree(ctx->host_out[k]));
-            ctx->host_out[k] = nullptr;
-            ctx->host_out_bytes[k] = 0;
-            const size_t want = down[k] + down[k] / 4 + 4096;
-            SMI_HIP(hipHostMalloc((void **)&ctx->host_out[k], want, hipHostMallocDefault));
-            ctx->host_out_bytes[k] = want;
-        }
-    if (down[0]) SMI_HIP(hipMemcpyAsync(ctx->host_out[0], d_src[0], down[0], hipMemcpyDeviceToHost, s));
-    if (down[1]) SMI_HIP(hipMemcpyAsync(ctx->host_out[1], d_src[1], down[1], hipMemcpyDeviceToHost, s));
+    for (int k = 0; k < 2; k++) SMI_RC(ctx->host_out[k].need(down[k]));  // pinned, grow-only: the download runs at link speed and nothing is zero-filled
+    for (int k = 0; k < 2; k++)
+        if (down[k]) SMI_HIP(hipMemcpyAsync(ctx->host_out[k].p, d_src[k], down[k], hipMemcpyDeviceToHost, s));
     if (cfg->want_results) {
         ctx->host_scan.resize(m);
         ctx->host_bc.resize(m);
@@ -377,8 +350,8 @@ extern "C" int smi_scanfastq_pass2_chunk(smi_ctx *ctx, const uint8_t *text, size
         SMI_RC(smi_scan_stats_add(&ctx->host_stats, &dec));
         out->stats = &ctx->host_stats;
     }
-    out->passed = ctx->host_out[0];
-    out->failed = ctx->host_out[1];
+    out->passed = ctx->host_out[0].as<uint8_t>();
+    out->failed = ctx->host_out[1].as<uint8_t>();
     out->passed_bytes = down[0];
     out->failed_bytes = down[1];
     out->n_passed = totals[2];
@@ -525,7 +498,7 @@ int pass2_packed_core(smi_ctx *ctx, const smi_packed_reads *pk, const uint64_t *
                         pad((3 * n + 1) * 8) + pad(3 * n * 4) + pad((size_t)SMI_ENDS_ROWS * 2 * m_cap * 4) + pad(m_cap * 4) +
                         pad(m_cap * sizeof(smi_scan_result)) + pad(m_cap * sizeof(smi_bc_window)) + pad(m_cap * sizeof(smi_bc_result)) +
                         pad(m_cap * 4) + pad(cfg->n_ranks * 8) + pad(cfg->n_ranks * 4) + 4096;
-    SMI_RC(ensure_arena(ctx, need));
+    SMI_RC(ctx->arena.need(need));
     Arena A(ctx);
     uint32_t *d_planes = A.take<uint32_t>(planes_words);
     uint32_t *d_pstart = A.take<uint32_t>(n);
@@ -549,7 +522,7 @@ int pass2_packed_core(smi_ctx *ctx, const smi_packed_reads *pk, const uint64_t *
         SMI_RC(launch_chimera(ctx, d_planes, d_offs, n, total, &cc, d_chim, s, d_pstart, pstride));
         SMI_RC(smi_split_offsets_device(ctx, d_chim, d_offs, n, d_scr, d_nfrag, d_foffs, d_fsrc, s));
         SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_CHIM, n * sizeof(smi_chimera_result)));
-        smi_chimera_result *h_chim = static_cast<smi_chimera_result *>(ctx->host_buf[smi_ctx::HB_CHIM]);
+        smi_chimera_result *h_chim = ctx->host_buf[smi_ctx::HB_CHIM].as<smi_chimera_result>();
         uint64_t nf = 0;
         SMI_HIP(hipMemcpyAsync(&nf, d_nfrag, 8, hipMemcpyDeviceToHost, s));
         SMI_HIP(hipMemcpyAsync(h_chim, d_chim, n * sizeof(smi_chimera_result), hipMemcpyDeviceToHost, s));
@@ -596,25 +569,25 @@ int pass2_packed_core(smi_ctx *ctx, const smi_packed_reads *pk, const uint64_t *
     // decisions down: ~80 bytes per record
     SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_SCAN, m * sizeof(smi_scan_result)));
     SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_BC, m * sizeof(smi_bc_result)));
-    SMI_HIP(hipMemcpyAsync(ctx->host_buf[smi_ctx::HB_SCAN], d_scan, m * sizeof(smi_scan_result), hipMemcpyDeviceToHost, s));
-    SMI_HIP(hipMemcpyAsync(ctx->host_buf[smi_ctx::HB_BC], d_bc, m * sizeof(smi_bc_result), hipMemcpyDeviceToHost, s));
+    SMI_HIP(hipMemcpyAsync(ctx->host_buf[smi_ctx::HB_SCAN].p, d_scan, m * sizeof(smi_scan_result), hipMemcpyDeviceToHost, s));
+    SMI_HIP(hipMemcpyAsync(ctx->host_buf[smi_ctx::HB_BC].p, d_bc, m * sizeof(smi_bc_result), hipMemcpyDeviceToHost, s));
     if (d_rank) {
         SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_RANK, m * 4));
-        SMI_HIP(hipMemcpyAsync(ctx->host_buf[smi_ctx::HB_RANK], d_rank, m * 4, hipMemcpyDeviceToHost, s));
-        out->rank = static_cast<const int32_t *>(ctx->host_buf[smi_ctx::HB_RANK]);
+        SMI_HIP(hipMemcpyAsync(ctx->host_buf[smi_ctx::HB_RANK].p, d_rank, m * 4, hipMemcpyDeviceToHost, s));
+        out->rank = ctx->host_buf[smi_ctx::HB_RANK].as<const int32_t>();
     }
     if (split) {
         SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_FOFFS, (m + 1) * 8));
         SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_FSRC, m * 4));
-        SMI_HIP(hipMemcpyAsync(ctx->host_buf[smi_ctx::HB_FOFFS], d_foffs, (m + 1) * 8, hipMemcpyDeviceToHost, s));
-        SMI_HIP(hipMemcpyAsync(ctx->host_buf[smi_ctx::HB_FSRC], d_fsrc, m * 4, hipMemcpyDeviceToHost, s));
-        out->frag_offsets = static_cast<const uint64_t *>(ctx->host_buf[smi_ctx::HB_FOFFS]);
-        out->frag_src = static_cast<const uint32_t *>(ctx->host_buf[smi_ctx::HB_FSRC]);
+        SMI_HIP(hipMemcpyAsync(ctx->host_buf[smi_ctx::HB_FOFFS].p, d_foffs, (m + 1) * 8, hipMemcpyDeviceToHost, s));
+        SMI_HIP(hipMemcpyAsync(ctx->host_buf[smi_ctx::HB_FSRC].p, d_fsrc, m * 4, hipMemcpyDeviceToHost, s));
+        out->frag_offsets = ctx->host_buf[smi_ctx::HB_FOFFS].as<const uint64_t>();
+        out->frag_src = ctx->host_buf[smi_ctx::HB_FSRC].as<const uint32_t>();
     } else
         out->frag_offsets = offsets;  // the caller's array: output records = input records
     SMI_HIP(hipStreamSynchronize(s));
-    out->scan = static_cast<const smi_scan_result *>(ctx->host_buf[smi_ctx::HB_SCAN]);
-    out->bc = static_cast<const smi_bc_result *>(ctx->host_buf[smi_ctx::HB_BC]);
+    out->scan = ctx->host_buf[smi_ctx::HB_SCAN].as<const smi_scan_result>();
+    out->bc = ctx->host_buf[smi_ctx::HB_BC].as<const smi_bc_result>();
     return SMI_OK;
 }
 }  // namespace
@@ -634,10 +607,10 @@ int index_and_pack(smi_ctx *ctx, const char *who, const uint8_t *text, size_t n_
         SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_OFFS, (cap_try + 1) * 8));
         SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_PSTART, cap_try * 4));
         SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_PLANES, planes_words * 4));
-        const int rc = smi_fastq_index_pack_host(text, n_bytes, static_cast<smi_fastq_record *>(ctx->host_buf[smi_ctx::HB_RECS]),
-                                                 static_cast<uint64_t *>(ctx->host_buf[smi_ctx::HB_OFFS]),
-                                                 static_cast<uint32_t *>(ctx->host_buf[smi_ctx::HB_PSTART]), cap_try,
-                                                 static_cast<uint32_t *>(ctx->host_buf[smi_ctx::HB_PLANES]), planes_words, pk, n_out, fq_err, n_threads);
+        const int rc = smi_fastq_index_pack_host(text, n_bytes, ctx->host_buf[smi_ctx::HB_RECS].as<smi_fastq_record>(),
+                                                 ctx->host_buf[smi_ctx::HB_OFFS].as<uint64_t>(),
+                                                 ctx->host_buf[smi_ctx::HB_PSTART].as<uint32_t>(), cap_try,
+                                                 ctx->host_buf[smi_ctx::HB_PLANES].as<uint32_t>(), planes_words, pk, n_out, fq_err, n_threads);
         if (rc == SMI_OK) break;
         if (cap_try >= cap_worst) return rc;
         cap_try = cap_worst;  // tiny records: once more with the worst-case capacities
@@ -674,8 +647,8 @@ extern "C" int smi_scanfastq_pass2_chunk_packed(smi_ctx *ctx, const uint8_t *tex
     out->fastq_errors = fq_err;
     if (rc_ix != SMI_OK) return rc_ix;
     if (n == 0) return SMI_OK;
-    const smi_fastq_record *recs = static_cast<const smi_fastq_record *>(ctx->host_buf[smi_ctx::HB_RECS]);
-    const uint64_t *offs = static_cast<const uint64_t *>(ctx->host_buf[smi_ctx::HB_OFFS]);
+    const smi_fastq_record *recs = ctx->host_buf[smi_ctx::HB_RECS].as<const smi_fastq_record>();
+    const uint64_t *offs = ctx->host_buf[smi_ctx::HB_OFFS].as<const uint64_t>();
     const auto t0 = std::chrono::steady_clock::now();
     smi_pass2_decisions dec;
     SMI_RC(pass2_packed_core(ctx, &pk, offs, n, cfg, &dec));
@@ -684,20 +657,12 @@ extern "C" int smi_scanfastq_pass2_chunk_packed(smi_ctx *ctx, const uint8_t *tex
     // the records: never longer than the text they are cut from + a name suffix each
     // (bases and qualities once; the name token and the '+' line once per fragment, at most three fragments per record)
     const size_t out_cap = n_bytes + 320 * dec.n_records_out + (dec.frag_src ? 2 * (n_bytes - std::min<size_t>(n_bytes, 2 * (size_t)offs[n])) : 0) + 64;
-    for (int k = 0; k < 2; k++)
-        if (ctx->host_out_bytes[k] < out_cap) {
-            if (ctx->host_out[k]) SMI_HIP(hipHostFree(ctx->host_out[k]));
-            ctx->host_out[k] = nullptr;
-            ctx->host_out_bytes[k] = 0;
-            const size_t want = out_cap + out_cap / 4 + 4096;
-            SMI_HIP(hipHostMalloc((void **)&ctx->host_out[k], want, hipHostMallocDefault));
-            ctx->host_out_bytes[k] = want;
-        }
+    for (int k = 0; k < 2; k++) SMI_RC(ctx->host_out[k].need(out_cap));
     smi_write_config wc{cfg->five_prime, cfg->trim_fastq};
     uint64_t totals[3] = {0, 0, 0};
     uint32_t werr = 0;
-    const int rc_w = smi_fastq_write_host(text, recs, offs, &dec, cfg->first_read_id, &wc, ctx->host_out[0], ctx->host_out_bytes[0], ctx->host_out[1],
-                                          ctx->host_out_bytes[1], totals, &werr, n_threads);
+    const int rc_w = smi_fastq_write_host(text, recs, offs, &dec, cfg->first_read_id, &wc, ctx->host_out[0].as<uint8_t>(), ctx->host_out[0].cap, ctx->host_out[1].as<uint8_t>(),
+                                          ctx->host_out[1].cap, totals, &werr, n_threads);
     if (rc_w != SMI_OK) {
         if (werr & SMI_WR_QUAL_NEWLINE) {  // a line end inside a quality line that the one-pass index stepped over: what the exact index reports
             out->fastq_errors = SMI_FQ_LENGTH_MISMATCH;
@@ -719,8 +684,8 @@ extern "C" int smi_scanfastq_pass2_chunk_packed(smi_ctx *ctx, const uint8_t *tex
         SMI_RC(smi_scan_stats_add(&ctx->host_stats, &dec));
         out->stats = &ctx->host_stats;
     }
-    out->passed = ctx->host_out[0];
-    out->failed = ctx->host_out[1];
+    out->passed = ctx->host_out[0].as<uint8_t>();
+    out->failed = ctx->host_out[1].as<uint8_t>();
     out->passed_bytes = out->passed_text_bytes = totals[0];
     out->failed_bytes = out->failed_text_bytes = totals[1];
     out->n_passed = totals[2];
@@ -745,12 +710,12 @@ extern "C" int smi_scanfastq_pass1_chunk_packed(smi_ctx *ctx, const uint8_t *tex
     if (fastq_errors) *fastq_errors = fq_err;
     if (rc_ix != SMI_OK) return rc_ix;
     if (n == 0) return SMI_OK;
-    const smi_fastq_record *recs = static_cast<const smi_fastq_record *>(ctx->host_buf[smi_ctx::HB_RECS]);
-    const uint64_t *offs = static_cast<const uint64_t *>(ctx->host_buf[smi_ctx::HB_OFFS]);
+    const smi_fastq_record *recs = ctx->host_buf[smi_ctx::HB_RECS].as<const smi_fastq_record>();
+    const uint64_t *offs = ctx->host_buf[smi_ctx::HB_OFFS].as<const uint64_t>();
     SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_QTAIL, n * (size_t)SMI_END_BASES));
     SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_QSUM, n * 4));
-    uint8_t *h_qtail = static_cast<uint8_t *>(ctx->host_buf[smi_ctx::HB_QTAIL]);
-    uint32_t *h_qsum = static_cast<uint32_t *>(ctx->host_buf[smi_ctx::HB_QSUM]);
+    uint8_t *h_qtail = ctx->host_buf[smi_ctx::HB_QTAIL].as<uint8_t>();
+    uint32_t *h_qsum = ctx->host_buf[smi_ctx::HB_QSUM].as<uint32_t>();
     if (int rc = smi_pack_quals_host(text, recs, n, five_prime, h_qtail, h_qsum, n_threads)) {
         if (fastq_errors && std::strstr(smi_last_error(), "line end inside")) *fastq_errors = SMI_FQ_LENGTH_MISMATCH;
         return rc;
@@ -760,7 +725,7 @@ extern "C" int smi_scanfastq_pass1_chunk_packed(smi_ctx *ctx, const uint8_t *tex
     const size_t pstride = pk.total_words, planes_words = 4 * pstride;
     const size_t need = pad(planes_words * 4) + pad(n * 4) + pad((n + 1) * 8) + pad((size_t)SMI_ENDS_ROWS * 2 * n * 4) + 2 * pad(n * 4) + pad(n * (size_t)SMI_END_BASES) +
                         pad(n * sizeof(smi_scan_result)) + pad(n * sizeof(smi_bc_window)) + 4096;
-    SMI_RC(ensure_arena(ctx, need));
+    SMI_RC(ctx->arena.need(need));
     Arena A(ctx);
     uint32_t *d_planes = A.take<uint32_t>(planes_words);
     uint32_t *d_pstart = A.take<uint32_t>(n);
@@ -1135,7 +1100,7 @@ int assignumis_chunk_host(smi_ctx *ctx, const char *names, const uint32_t *name_
     // ---- K-UMI ------------------------------------------------------------------------------------------------------------
     SMI_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    SMI_RC(ensure_arena(ctx, pad(m * 8) + pad(goff.size() * 4) + 2 * pad(goff.size() * 8) + pad(moff.back()) + 1024));
+    SMI_RC(ctx->arena.need(pad(m * 8) + pad(goff.size() * 4) + 2 * pad(goff.size() * 8) + pad(moff.back()) + 1024));
     Arena A(ctx);
     uint64_t *d_w = A.take<uint64_t>(m);
     uint32_t *d_go = A.take<uint32_t>(goff.size());
@@ -1242,7 +1207,7 @@ extern "C" int smi_assignumis_chunk(smi_ctx *ctx, const char *names, const uint3
     const size_t fixed = pad(name_bytes + 16) + 2 * pad((N + 1) * 4) + pad(N * 2) + pad(N * 4) + pad((n_cig + 1) * 4) + pad(N * sizeof(UmiParsed)) + pad(N * 4) +
                          3 * pad((N + 2) * 8) + 4 * pad((N + 2) * 4) + pad(16) + pad(16) + pad((N / 64 + 2) * 8) + 4 * pad((N + 2) * 4) + 4 * pad((N + 2) * 8) + pad(G * 4) + pad(N * 4) + 2 * pad(G * 8) +
                          pad(N * 8) + pad(N * 4) + pad(tmp_bytes) + pad(N * sizeof(smi_umi_assignment)) + pad(N) + pad(N * sizeof(smi_umi_tag)) + 8192;
-    SMI_RC(ensure_arena(ctx, fixed));
+    SMI_RC(ctx->arena.need(fixed));
     Arena A(ctx);
     char *d_names = A.take<char>(name_bytes + 16);
     uint32_t *d_noff = A.take<uint32_t>(N + 1), *d_coff = A.take<uint32_t>(N + 1);
@@ -1295,9 +1260,9 @@ extern "C" int smi_assignumis_chunk(smi_ctx *ctx, const char *names, const uint3
     SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_RKEYS, N * 8 + 16));
     SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_RBITS, n_words * 8 + 16));
     SMI_RC(ensure_host_buf(ctx, smi_ctx::HB_REGION, N * 4));
-    uint64_t *h_keys = static_cast<uint64_t *>(ctx->host_buf[smi_ctx::HB_RKEYS]);
-    uint64_t *h_bits = static_cast<uint64_t *>(ctx->host_buf[smi_ctx::HB_RBITS]);
-    int32_t *h_region = static_cast<int32_t *>(ctx->host_buf[smi_ctx::HB_REGION]);
+    uint64_t *h_keys = ctx->host_buf[smi_ctx::HB_RKEYS].as<uint64_t>();
+    uint64_t *h_bits = ctx->host_buf[smi_ctx::HB_RBITS].as<uint64_t>();
+    int32_t *h_region = ctx->host_buf[smi_ctx::HB_REGION].as<int32_t>();
     uint32_t *h_rcount = reinterpret_cast<uint32_t *>(h_bits + n_words);
     SMI_HIP(hipMemcpyAsync(h_rcount, d_rcount, 8, hipMemcpyDeviceToHost, s));
     SMI_HIP(hipMemcpyAsync(h_keys, B.keys_sorted, N * 8, hipMemcpyDeviceToHost, s));
@@ -1318,16 +1283,8 @@ extern "C" int smi_assignumis_chunk(smi_ctx *ctx, const char *names, const uint3
     lap("groups");
     if (n_groups) {
         // the matrices: a grow-only buffer of the context beside the arena
-        if (ctx->umi_dist_bytes < totals[3]) {
-            SMI_HIP(hipStreamSynchronize(s));
-            if (ctx->umi_dist) SMI_HIP(hipFree(ctx->umi_dist));
-            ctx->umi_dist = nullptr;
-            ctx->umi_dist_bytes = 0;
-            const size_t want = (size_t)totals[3] + (size_t)totals[3] / 4 + 4096;
-            SMI_HIP(hipMalloc(&ctx->umi_dist, want));
-            ctx->umi_dist_bytes = want;
-        }
-        uint8_t *d_dist = static_cast<uint8_t *>(ctx->umi_dist);
+        SMI_RC(ctx->umi_dist.need((size_t)totals[3], s));
+        uint8_t *d_dist = ctx->umi_dist.as<uint8_t>();
         SMI_RC(launch_umi_dist(ctx, B.wpk, B.group_off, B.pair_off, B.mat_off, n_groups, totals[2], d_dist, s, UL, true));  // rows padded to whole lines (smi_umi_stage.h)
         int dev_max = std::min(cc.own_clusterer_above, kUmiClusterDeviceMax);
         if (cc.single_link_switch < dev_max) dev_max = cc.single_link_switch;  // (never with the shipped values: the switch sits at 3000)

@@ -545,15 +545,8 @@ static int write_core(smi_ctx *ctx, const uint8_t *d_text, const uint64_t *d_lin
     const size_t plan_bytes = n_out * sizeof(RecPlan);
     const size_t tmp_off = ((6 * arr + sfx_bytes + 256 + 255) / 256) * 256 + plan_bytes;
     const size_t need = tmp_off + tmp_bytes;
-    if (ctx->scan_tmp_bytes < need) {
-        SMI_HIP(hipStreamSynchronize(s));
-        if (ctx->scan_tmp) SMI_HIP(hipFree(ctx->scan_tmp));
-        ctx->scan_tmp = nullptr;
-        ctx->scan_tmp_bytes = 0;
-        SMI_HIP(hipMalloc(&ctx->scan_tmp, need));
-        ctx->scan_tmp_bytes = need;
-    }
-    uint8_t *base = static_cast<uint8_t *>(ctx->scan_tmp);
+    if (int rc = take_scan_tmp(ctx, need, s)) return rc;  // (the indexer's sweep flags end here)
+    uint8_t *base = ctx->scan_tmp.as<uint8_t>();
     uint64_t *lenp = (uint64_t *)base, *lenf = (uint64_t *)(base + arr), *cntp = (uint64_t *)(base + 2 * arr);
     uint64_t *offp = (uint64_t *)(base + 3 * arr), *offf = (uint64_t *)(base + 4 * arr), *ordp = (uint64_t *)(base + 5 * arr);
     uint32_t *sfx = (uint32_t *)(base + 6 * arr);
@@ -577,35 +570,21 @@ static int write_core(smi_ctx *ctx, const uint8_t *d_text, const uint64_t *d_lin
     SMI_HIP(hipcub::DeviceScan::ExclusiveSum(cub_tmp, tmp_bytes, lenf, offf, (int)(n_out + 1), s));
     // K-WNAME (serial per record, latency-bound) and K-WRITE (wave per record, bandwidth-bound) write disjoint bytes and only read what is
     // finished by now: they run side by side, K-WNAME on the context's side stream
-    if (!ctx->side_stream) {
-        SMI_HIP(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
-        SMI_HIP(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
-        SMI_HIP(hipEventCreateWithFlags(&ctx->side_join, hipEventDisableTiming));
-    }
-    SMI_HIP(hipEventRecord(ctx->side_fork, s));
-    SMI_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0));
-    SideStreamGuard side_guard{ctx->side_stream, true};  // (an error return before the join drains the side stream: smi_internal.h)
-    hipLaunchKernelGGL(k_write_name, dim3((unsigned)((n_out + kNameBlock - 1) / kNameBlock)), dim3(kNameBlock), 0, ctx->side_stream, A, plan, offp, offf, ordp, sfx, d_passed, cap_passed, d_failed,
+    SideFork fork;
+    if (int rc = side_fork(ctx, s, &fork)) return rc;
+    hipLaunchKernelGGL(k_write_name, dim3((unsigned)((n_out + kNameBlock - 1) / kNameBlock)), dim3(kNameBlock), 0, fork.side, A, plan, offp, offf, ordp, sfx, d_passed, cap_passed, d_failed,
                        cap_failed);
     SMI_HIP(hipGetLastError());
-    SMI_HIP(hipEventRecord(ctx->side_join, ctx->side_stream));
     hipLaunchKernelGGL(k_write, dim3((unsigned)((n_out + 3) / 4)), dim3(256), 0, s, A, plan, offp, offf, sfx, d_passed, cap_passed,
                        d_failed, cap_failed, d_rec_off, d_err);
     SMI_HIP(hipGetLastError());
-    SMI_HIP(hipStreamWaitEvent(s, ctx->side_join, 0));
-    side_guard.armed = false;
-    uint64_t h_stack[4];
-    uint64_t *h = static_cast<uint64_t *>(pin_words(ctx));  // (four words: page-locked, or the stack if there is none)
-    if (!h) h = h_stack;
-    SMI_HIP(hipMemcpyAsync(&h[0], offp + n_out, 8, hipMemcpyDeviceToHost, s));
-    SMI_HIP(hipMemcpyAsync(&h[1], offf + n_out, 8, hipMemcpyDeviceToHost, s));
-    SMI_HIP(hipMemcpyAsync(&h[2], ordp + n_out, 8, hipMemcpyDeviceToHost, s));
-    SMI_HIP(hipMemcpyAsync(&h[3], d_err, 4, hipMemcpyDeviceToHost, s));
-    SMI_HIP(hipStreamSynchronize(s));
-    totals[0] = h[0];
-    totals[1] = h[1];
-    totals[2] = h[2];
-    *errors = (uint32_t)h[3];
+    if (int rc = fork.join(s)) return rc;
+    WordRead r(ctx, s);
+    if (int rc = r.add(&totals[0], offp + n_out, 8)) return rc;
+    if (int rc = r.add(&totals[1], offf + n_out, 8)) return rc;
+    if (int rc = r.add(&totals[2], ordp + n_out, 8)) return rc;
+    if (int rc = r.add(errors, d_err, 4)) return rc;
+    if (int rc = r.wait()) return rc;
     if (*errors) {
         set_error("smi_fastq_write_device: see *errors (SMI_WR_*)");
         return SMI_ERR_INVALID;

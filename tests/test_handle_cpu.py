@@ -171,3 +171,13 @@ def test_error_read_cuts_the_name_to_cap(tool):
                     ["64", "0", "41", "read_12345", "1"]]
     out = subprocess.run([tool, "error_read", "", "-1"], check=True, capture_output=True).stdout.decode()
     assert [line.split("\t") for line in out.split("\n")[:-1]][2] == ["4", "0", "-1", "", "1"]
+
+
+def test_grow_only_buffer_under_the_sanitizers(tmp_path):
+    """csrc/smi_growbuf.h against a counting allocator (tools/asan/growbuf_host.cpp): a stand-alone host program, built with
+    AddressSanitizer and UBSan and run directly"""
+    exe = tmp_path / "growbuf_host"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", f"-I{ROOT}/sicelore-2.1_amd/csrc",
+                    f"{ROOT}/tools/asan/growbuf_host.cpp", "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True)
+    assert out.returncode == 0 and out.stdout.decode().strip() == "growbuf_host: ok", out.stderr.decode()
